@@ -127,6 +127,8 @@ def spmv_stream(args, ctx, rank, world, torch, dist, synth_mod):
     y, ms, by = ctx.spmv_bench(rp32, colidx, val, x, reps=args.steps)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs({"y": y}, args.dump_outputs)
     gbs = by / (ms * 1e-3) / 1e9
     tm = torch.tensor([gbs, ms], dtype=torch.float64, device="cuda")
     mx = tm.clone()
@@ -198,6 +200,37 @@ def e2e_cli(maps, mono):
         shutil.rmtree(d, ignore_errors=True)
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+NPY_HEADER_BYTES = 128
+
+
+def dump_outputs(result, out_dir, budget=DUMP_BUDGET_BYTES, seed=0):
+    """The final map a caller of the timed path receives (lsfm_tree_download) as out_dir/<name>.npy, every field in float64 (the
+    integer fields exactly), `budget` bytes on disk at most.  The state vector (stno, stVal) comes first and is written whole
+    unless it alone takes more than half the budget; the other arrays share what is left, smallest first, each written whole
+    while it fits its share.  An array that does not keeps a sample of its rows drawn with a fixed seed (sorted row numbers in
+    <name>_rows.npy), so that two runs of the same arguments write the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64) for k, v in result.items()}
+    arrays = {k: (v if v.ndim else v.reshape(1)) for k, v in arrays.items()}
+    first = [k for k in ("stno", "stVal") if k in arrays]
+    rest = sorted((k for k in arrays if k not in first), key=lambda k: (arrays[k].nbytes, k))
+    left = budget - NPY_HEADER_BYTES * 2 * len(arrays)  # (room for the headers of every file, row-number files included)
+    for i, name in enumerate(first + rest):
+        a = arrays[name]
+        share = (budget // 2 if name in first else left) // (len(first) if name in first else len(first) + len(rest) - i)
+        share = min(share, left)
+        if a.nbytes > share:
+            row_bytes = a.nbytes // a.shape[0]
+            keep = min(a.shape[0], share // (row_bytes + 8))  # (a row number costs 8 bytes as well)
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+            left -= 8 * keep
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        left -= a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -222,10 +255,15 @@ def main():
                          "sub-tree roots on half of the remaining ranks each")
     ap.add_argument("--extras", type=int, default=1, help="1: also the stand-alone SpMV streaming leg and the files-to-files CLI run "
                                                           "(N=1, default configuration sizes only); 0: skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final map of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all: a fixed, seeded "
+                         "row sample of the largest arrays, their row numbers in DIR/<name>_rows.npy), so that two builds can be compared")
     args = ap.parse_args()
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process starts the N ranks itself (torch.distributed.run as a CHILD,
         # before anything here has touched the GPU -- never an exec from a process that has), relays what they print (rank 0's
@@ -326,6 +364,12 @@ def main():
     for _ in range(max(0, args.warmup - 1)):
         tree.run()
     elapsed, acc, stats, worst = timed(args.steps)
+    if args.dump_outputs:
+        # what the last timed step left, before the other mode below runs the tree again (collective at N > 1, like the download below)
+        final = tree.download() if (world > 1 and args.top == "shard") or rank == 0 else None
+        if rank == 0:
+            dump_outputs(final, args.dump_outputs)
+        del final
     sw = sorted(step_wall)
     step_spread = {"min": sw[0], "median": sw[len(sw) // 2], "max": sw[-1]} if sw else None
     rdev = "cpu" if os.environ.get("LSFM_BENCH_ONE_GPU") else "cuda"
