@@ -193,6 +193,30 @@ int lsfm_solve_mono(lsfm_context* ctx, double* stVal, const double* eb, const do
  * variable that is not in the global state, a global variable no map holds, a Stereo map that holds the global reference pose). */
 int lsfm_gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, int type, lsfm_map* x, int iters, double* obj, double* gnorm, int* halvings);
 
+/* ---- marginal covariances of a map (NO reference counterpart: the reference keeps the information matrix and never inverts it) ----
+ * Sigma = I^-1 with I = [U W; W^T V] of `map` (any lsfm_map: a downloaded tree result, a checkpoint node, a local map).
+ * mono = 0: Stereo, I is used as it is (the map's Ref pose is not in its state).  mono = 1: the gauge of lsfm_solve_mono /
+ * lsfm_gn_polish -- the 6 scalars of the pose labelled map->Ref and scalar map->Fix (0..2) of the pose labelled map->ScaP are held
+ * fixed: Sigma is the inverse with those rows / columns removed, and it is reported as 0 there.
+ * Outputs (each optional, NULL = not wanted; all in the map's own order of poses / features, unscaled, unpermuted):
+ *   pose_cov[36 m]   Sigma_pp, row-major 6x6 per pose
+ *   feat_cov[9 n]    Sigma_ff, row-major 3x3 per feature
+ *   pair_cov[36 cap_blocks]  Sigma_pq for every block (p <= q) of the camera system's pattern, in the order lsfm_schur_pattern returns
+ *                    for the same map (row by row, diagonal block first); *nnzb receives the count (LSFM_ERR_ARG when cap_blocks is
+ *                    too small, *nnzb still set)
+ * Always fp64 and always the sparse factorisation (lsfm_set_precision / lsfm_set_small_solve do not apply); deterministic: the same
+ * input gives the same bits.  The camera system is factored as a tree level's is, then inverted on the factor's own pattern (selected
+ * inversion); the features follow from Sigma_ff = V^-1 + V^-1 (sum W^T Sigma W) V^-1.
+ * Returns LSFM_OK; LSFM_ERR_NOT_SPD when the factorisation met a non-positive pivot; > 0 (the number of floored pivots) when a pivot
+ * had to be floored (the result is then not the inverse of I and nothing is written); < 0 errors as elsewhere (LSFM_ERR_ARG: W not
+ * sorted by feature, a Mono map whose Ref / ScaP is not in its state).
+ * Lifetime: works in the context's arenas like lsfm_solve_* -- a tree's result must be downloaded first. */
+int lsfm_map_covariance(lsfm_context* ctx, const lsfm_map* map, int mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb);
+/* measurement entry: the same, and times[4] (may be NULL) = HIP-event ms of the Schur reduction + symbolic analysis, the numeric
+ * factorisation, the selected inversion (with the gather onto the pattern), the feature part */
+int lsfm_map_covariance_timed(lsfm_context* ctx, const lsfm_map* map, int mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb,
+                              double* times);
+
 /* replaces pba_inverseV (Imp.h:213, Imp.cpp:3022-3042): V^-1 of the n 3x3 feature blocks, IN PLACE like the reference's (which
  * inverts V in place and restores it afterwards, Imp.cpp:2210-2212, 2365): the upper triangle of the computed inverse, mirrored.
  * m is unused, as in the reference. */
@@ -355,6 +379,12 @@ int lsfm_mapset_info(const char* path, int* N, int* mono);
  * whenever it held enough maps of the right type). */
 int lsfm_mapset_stamp(const char* path, unsigned long long* stamp, const unsigned long long* set_to);
 int lsfm_read_mapset(const char* path, int mono, int first, int count, int threads, lsfm_map* out);
+/* -cov / -covf files of the command line: one line per pose (feature) in the order of the pose (feature) file -- ascending id --, the
+ * id followed by the 21 (6) upper-triangle entries of its covariance block, row by row, at %.17g.  pose_cov[36 m] / feat_cov[9 n] as
+ * lsfm_map_covariance writes them, stno[6m + 3n] the map's labels; a NULL path: that file is not written */
+int lsfm_save_covariances(const char* pose_path, const char* feat_path, const int* stno, int m, int n, const double* pose_cov, const double* feat_cov);
+/* reads such a file back (k = 6: poses, 3: features): ids[cap], the full symmetric blocks cov[cap k k]; *count = lines read */
+int lsfm_read_covariances(const char* path, int k, int* ids, double* cov, int cap, int* count);
 int lsfm_save_state(const char* path, const double* st, const int* stno, int n);
 /* the same state vector as raw doubles (parity tooling): int32 n, int32 0, stno[n] (+ 4 bytes of padding when n is odd),
  * st[n] float64 */

@@ -118,6 +118,10 @@ def lib():
         L.lsfm_inverse_v.argtypes = [vp, dp, C.c_int, C.c_int]
         L.lsfm_gn_polish.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), C.c_int, dp, dp, ip]
         L.lsfm_solve_features.argtypes = [vp, dp, dp, dp, dp, dp, dp, C.c_int, C.c_int, ip, ip]
+        L.lsfm_map_covariance.argtypes = [vp, P(LsfmMap), C.c_int, dp, dp, dp, C.c_int, ip]
+        L.lsfm_map_covariance_timed.argtypes = [vp, P(LsfmMap), C.c_int, dp, dp, dp, C.c_int, ip, dp]
+        L.lsfm_save_covariances.argtypes = [C.c_char_p, C.c_char_p, ip, C.c_int, C.c_int, dp, dp]
+        L.lsfm_read_covariances.argtypes = [C.c_char_p, C.c_int, ip, dp, C.c_int, ip]
         L.lsfm_spmv_bench.argtypes = [vp, C.c_int, ip, ip, dp, dp, dp, C.c_int, dp, dp]
         L.lsfm_wstream_bench.argtypes = [vp, C.c_longlong, C.c_int, C.c_int, dp]
         L.lsfm_selftest_prims.argtypes = [vp, C.c_int, C.c_uint]
@@ -131,7 +135,9 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_tree_download", "lsfm_tree_set_stop_level", "lsfm_tree_node_count", "lsfm_tree_download_node", "lsfm_tree_download_state", "lsfm_tree_set_plans", "lsfm_tree_export_size", "lsfm_tree_export_dev", "lsfm_packed_size",
            "lsfm_tree_upload_dev", "lsfm_tree_reload_dev", "lsfm_tree_set_comm", "lsfm_tree_set_comm_blocks", "lsfm_tree_export_slice_sizes", "lsfm_tree_export_slice_dev",
            "lsfm_tree_free", "lsfm_divide_conquer", "lsfm_read_localmap", "lsfm_read_localmaps", "lsfm_write_localmap", "lsfm_write_mapset", "lsfm_mapset_info", "lsfm_mapset_stamp", "lsfm_read_mapset", "lsfm_save_state_bin", "lsfm_save_state", "lsfm_save_poses", "lsfm_gn_polish",
-           "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features"]
+           "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
+           "lsfm_map_covariance", "lsfm_map_covariance_timed",
+           "lsfm_save_covariances", "lsfm_read_covariances"]
 
 
 def _c(a, dtype):
@@ -434,6 +440,42 @@ class Context:
                     "lsfm_schur_pattern")
         return rowptr, colidx[:nnzb.value].copy()
 
+    def covariance_raw(self, d, mono, pairs=False, cap_blocks=None, times=False):
+        """lsfm_map_covariance(_timed) as it is: (rc, pose [m,6,6], feature [n,3,3], pair blocks [nnzb,6,6] or None, nnzb, times[4] or None).
+        rc < 0 is returned, not raised (tests of the argument checks); cap_blocks: room for pair blocks (default: m (m + 1) / 2)."""
+        h = HostMap(d)
+        m, n = h.c.m, h.c.n
+        pose = np.zeros((m, 6, 6))
+        feat = np.zeros((n, 3, 3))
+        cap = m * (m + 1) // 2 if cap_blocks is None else int(cap_blocks)
+        pair = np.zeros((max(cap, 1), 6, 6)) if pairs else None
+        nnzb = C.c_int(0)
+        t = np.zeros(4) if times else None
+        rc = lib().lsfm_map_covariance_timed(self._h, C.byref(h.c), int(mono), _ptr(pose, C.c_double), _ptr(feat, C.c_double),
+                                             _ptr(pair, C.c_double) if pairs else None, cap if pairs else 0, C.byref(nnzb),
+                                             _ptr(t, C.c_double) if times else None)
+        return rc, pose, feat, (pair[:nnzb.value].copy() if pairs else None), nnzb.value, t
+
+    def covariance(self, d, mono, pairs=False):
+        """lsfm_map_covariance: marginal covariances of the map dict d's information matrix [U W; W^T V] (Mono: with the gauge of
+        lsfm_solve_mono held fixed -- rows / columns of the pose Ref and scalar Fix of pose ScaP, reported as 0).  No reference
+        counterpart.  Returns {"pose": (m,6,6), "feature": (n,3,3)} and, with pairs, "pairs": (rowptr, colidx, blocks) -- Sigma_pq on
+        the upper block pattern of the camera system (lsfm_schur_pattern's order).  Raises LsfmError on a non-zero status (> 0: a
+        pivot had to be floored, the result would not be the inverse)."""
+        rowptr = colidx = None
+        cap = 0
+        if pairs:
+            rowptr, colidx = self.schur_pattern(d)
+            cap = len(colidx)
+        rc, pose, feat, blocks, _, _ = self.covariance_raw(d, mono, pairs=pairs, cap_blocks=cap)
+        self._check(rc, "lsfm_map_covariance")
+        if rc != 0:
+            raise LsfmError(f"lsfm_map_covariance: {rc} pivot(s) floored -- the information matrix is too close to singular")
+        out = {"pose": pose, "feature": feat}
+        if pairs:
+            out["pairs"] = (rowptr, colidx, blocks)
+        return out
+
     def spmv_bench(self, rowptr, colidx, val, x, reps=20):
         rowptr = _c(rowptr, np.int32); colidx = _c(colidx, np.int32); val = _c(val, np.float64); x = _c(x, np.float64)
         m = len(rowptr) - 1
@@ -539,3 +581,28 @@ def read_localmaps(directory, count, mono, first=1, threads=0):
     if rc:
         raise LsfmError(f"lsfm_read_localmaps({directory}) failed at localmap_{bad.value}.txt (rc={rc})")
     return [map_to_dict(arr[k]) for k in range(count)]
+
+
+def save_covariances(pose_path, feat_path, d, pose_cov, feat_cov):
+    """lsfm_save_covariances: the -cov / -covf files of map dict d (either path may be None)."""
+    stno = _c(d["stno"], np.int32)
+    pc = _c(pose_cov, np.float64)
+    fc = _c(feat_cov if feat_cov is not None else np.zeros(0), np.float64)
+    rc = lib().lsfm_save_covariances(pose_path.encode() if pose_path else None, feat_path.encode() if feat_path else None, _ptr(stno, C.c_int),
+                                     int(d["m"]), int(d["n"]), _ptr(pc, C.c_double), _ptr(fc, C.c_double))
+    if rc != 0:
+        raise LsfmError(f"lsfm_save_covariances failed (rc={rc})")
+
+
+def read_covariances(path, k, cap=None):
+    """lsfm_read_covariances: a -cov (k = 6) / -covf (k = 3) file as (ids [count], blocks [count, k, k])."""
+    if cap is None:
+        with open(path) as f:
+            cap = sum(1 for line in f if line.strip())
+    ids = np.zeros(max(cap, 1), np.int32)
+    cov = np.zeros((max(cap, 1), k, k))
+    cnt = C.c_int(0)
+    rc = lib().lsfm_read_covariances(path.encode(), int(k), _ptr(ids, C.c_int), _ptr(cov, C.c_double), int(cap), C.byref(cnt))
+    if rc != 0:
+        raise LsfmError(f"lsfm_read_covariances({path}) failed (rc={rc})")
+    return ids[:cnt.value].copy(), cov[:cnt.value].copy()

@@ -876,6 +876,23 @@ int lsfm_gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, int type, lsf
 	return guarded(ctx, [&]() { return gn_polish(ctx, maps, N, type == 1, x, iters, obj, gnorm, halvings); });
 }
 
+int lsfm_map_covariance_timed(lsfm_context* ctx, const lsfm_map* map, int mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb,
+                              double* times)
+{
+	if (!map || (mono != 0 && mono != 1) || map->m <= 0 || map->n < 0 || map->nU < 0 || map->nW < 0 || (pair_cov && (cap_blocks < 0 || !nnzb))) return LSFM_ERR_ARG;
+	if ((map->nU && (!map->U || !map->Ui || !map->Uj)) || (map->nW && (!map->W || !map->photo || !map->feature)) || (map->n && !map->V) || (mono && !map->stno))
+		return LSFM_ERR_ARG;
+	int cnt = 0;
+	const int rc = guarded(ctx, [&]() { return map_covariance(ctx, map, mono == 1, pose_cov, feat_cov, pair_cov, cap_blocks, &cnt, times); });
+	if (nnzb) *nnzb = cnt;
+	return rc;
+}
+
+int lsfm_map_covariance(lsfm_context* ctx, const lsfm_map* map, int mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb)
+{
+	return lsfm_map_covariance_timed(ctx, map, mono, pose_cov, feat_cov, pair_cov, cap_blocks, nnzb, nullptr);
+}
+
 int lsfm_inverse_v(lsfm_context* ctx, double* V, int m, int n)
 {
 	(void)m;

@@ -1,0 +1,90 @@
+// The sparse block Cholesky factorisation of a camera system (K10's preconditioner, lsfm_pcg.hip): the device layout of the factor and
+// the host steps that make it -- shared by the refinement (lsfm_pcg.hip) and the marginal covariances (lsfm_cov.hip).
+#pragma once
+#include <vector>
+
+#include "lsfm_internal.hpp"
+#include "lsfm_solve.hpp"
+
+namespace lsfm {
+
+// ---------------------------------------------------------------------------------------------------------------
+// sparse block Cholesky: device side
+// ---------------------------------------------------------------------------------------------------------------
+struct CholDev {
+	int M = 0, nnzL = 0, nlevels = 0, tail_begin = 0; // columns [tail_begin, M) (in level order) run in one launch
+	int* colptr = nullptr;  // [M+1]
+	int* rowidx = nullptr;  // [nnzL] ascending inside a column, diagonal first
+	int* perm = nullptr;    // [M] new -> old
+	int* pinv = nullptr;    // [M] old -> new
+	int* order = nullptr;   // [M] columns sorted by elimination-tree level
+	std::vector<int> level_ptr; // host: order[level_ptr[l] .. level_ptr[l+1]) = columns of level l (before the tail)
+	// tasks: connected pieces of the elimination tree that one work-group walks serially (small sub-trees, chains)
+	int* task_cols = nullptr;          // [M] columns grouped by task, ascending inside a task
+	int* task_ptr = nullptr;           // [ntasks+1] tasks ordered by task level
+	std::vector<int> tlevel_ptr;       // host: tasks of task level l = [tlevel_ptr[l], tlevel_ptr[l+1])
+	std::vector<int> tlevel_maxsize;   // host: most columns in a task of the level (LDS of the solve launches)
+	int* col_task = nullptr;           // [M] task (position in task_ptr) of a column
+	int* col_lpos = nullptr;           // [M] position of a column inside its task
+	int* col_nin = nullptr;            // [M] leading rows of a column (below the diagonal) that belong to its own task
+	std::vector<int> tlevel_col0;      // host: task_cols[tlevel_col0[l] .. tlevel_col0[l+1]) = columns of the level's tasks
+	std::vector<int> tlevel_nsmall;    // host: the first tlevel_nsmall[l] tasks of level l fit LDS whole (small-task kernels)
+	std::vector<int> tlevel_small_lds; // host: dynamic LDS bytes of the level's small-task launches
+	std::vector<int> tlevel_outer;     // host: largest number of deferred update pairs of a column of the level
+	// supernode groups: the columns above the leaf tasks, cut into runs of <= CHOL_GS consecutive columns of one
+	// fundamental supernode (same rows below the run), ordered by group level (children before parents)
+	int ngroups = 0;
+	int *grp_c0 = nullptr, *grp_s = nullptr, *grp_nr = nullptr; // [ngroups] first column, columns, rows below the run
+	std::vector<int> glevel_ptr;    // host: groups of level l = [glevel_ptr[l], glevel_ptr[l+1])
+	std::vector<int> glevel_maxnr;  // host: most rows below a run of the level
+	std::vector<int> glevel_maxs;   // host: most block columns of a run of the level (LDS of k_sn_panel)
+	// distributed factorisation (lsfm_symbolic.hpp): owner of every column (-1: shared), null when off; the shared columns are the
+	// last ones, from first_shared on (their blocks: from block shared_blk0 of L on)
+	int* col_owner = nullptr;
+	int first_shared = 0, shared_blk0 = 0;
+	double work_total = 0, work_shared = 0;
+	std::vector<char> glevel_owned, glevel_shared;
+	int* blob = nullptr;    // all index arrays above are slices of this one allocation
+	size_t blob_ints = 0;
+	float *Lf = nullptr, *Dinvf = nullptr; // mixed precision: the factor rounded to fp32 for the triangular solves (null: fp64)
+	double* wv = nullptr;   // [M*6] forward-solve results of the group columns (lsfm_pcg.hip k_sn_fwd / k_sn_bwd)
+	double* Lg = nullptr;   // [nnzL*36] the factor of the supernode-group columns (same indexing as L; L keeps their unfactored blocks)
+	float* Lgf = nullptr;   // mixed precision: its fp32 copy
+	double* L = nullptr;    // [nnzL*36] block values, column major by blocks, each block row-major 6x6
+	double* Dinv = nullptr; // [M*36] inverse of the diagonal Cholesky factors (lower triangular)
+	double* diag0 = nullptr; // [M*6] diagonal of the scaled S as it was scattered (new numbering): what a pivot of the separators is held against
+	double* dscale = nullptr; // [M*6] the scaling D^-1/2 (powers of two; new numbering): right-hand sides enter and solutions leave through it
+	int* d_err = nullptr;
+};
+
+// Distributed factorisation (feature-sharded tree runs, lsfm_symbolic.hpp col_owner): which of a launch's work-groups take
+// part -- the ones whose first column belongs to `want` (a rank's block, or -1: the shared separator columns).  col_owner == null: all.
+struct OwnFilter {
+	const int* col_owner = nullptr;
+	int want = 0;
+	__device__ __forceinline__ bool skip(int col) const { return col_owner && col_owner[col] != want; }
+};
+__device__ __forceinline__ int find_row(const int* __restrict__ rowidx, int lo, int hi, int target)
+{
+	while (lo < hi) { int mid = (lo + hi) >> 1; if (rowidx[mid] < target) lo = mid + 1; else hi = mid; }
+	return lo;
+}
+
+
+struct CholHostIn {
+	std::vector<unsigned long long> keys; // sorted upper pattern of S
+	std::vector<int> origin;              // local map that brought each pose
+};
+
+// the two small device -> host copies of the analysis (a synchronisation)
+void chol_fetch(lsfm_context* ctx, const SchurSystem& sy, const int* d_origin, CholHostIn& in);
+// symbolic analysis on the host (lsfm_symbolic.cpp), index arrays to the device, value arrays allocated in ctx->scratch
+void chol_analyse(lsfm_context* ctx, const SchurSystem& sy, const CholHostIn& in, CholDev& ch);
+// the scaled, permuted S into the factor's storage (fixed scalars: identity rows / columns), the scaling to ch.dscale
+void chol_scatter(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* fixed, CholDev& ch);
+// numeric factorisation: the leaf columns' factor in ch.L, the supernode-group columns' in ch.Lg, every L_jj^-1 in ch.Dinv
+void chol_factor(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* fixed, CholDev& ch, double* fwd_v = nullptr);
+// the group columns' factor copied into ch.L (a no-op when chol_factor already did it): afterwards ch.L + ch.Dinv hold the whole factor
+void chol_merge_groups(lsfm_context* ctx, const CholDev& ch);
+
+} // namespace lsfm

@@ -8,7 +8,8 @@
 // -path <dir> -num <nodes> finishes the tree and gives the result of the uninterrupted run), -quiet 1 (no progress lines).
 // -cache <file> (binary cache of the set: read instead of the text files when it holds -num maps of -type, written after the text files
 // were parsed otherwise), -fullbin <file> (final state as raw doubles), -json <file> (the run's lsfm_stats and phase times as one JSON object),
-// -gn <steps> (Gauss-Newton polish of the map-joining objective from the tree's result: lsfm_gn_polish; no reference counterpart).
+// -gn <steps> (Gauss-Newton polish of the map-joining objective from the tree's result: lsfm_gn_polish; no reference counterpart),
+// -cov <file> / -covf <file> (marginal covariances of the final map's poses / features: lsfm_map_covariance; no reference counterpart).
 #include <chrono>
 #include <sys/stat.h>
 #include <cstdio>
@@ -37,7 +38,7 @@ static void print_help()
 
 int main(int argc, char** argv)
 {
-	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json;
+	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf;
 	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0;
 	bool has_path = false, has_num = false;
 	double tol = 0;
@@ -72,6 +73,8 @@ int main(int argc, char** argv)
 		else if (name == "fullbin") fullbin = next();
 		else if (name == "json") json = next();
 		else if (name == "gn") gn = atoi(next());
+		else if (name == "cov") cov = next();
+		else if (name == "covf") covf = next();
 	}
 	if (!has_path) { printf("LinerSFM Error: Please Input Right File Path:\n"); return 0; }
 	if (!has_num) { printf("LinerSFM Error: Please Set Local Map Number:\n"); return 0; }
@@ -235,6 +238,19 @@ int main(int argc, char** argv)
 	}
 	if (!info.empty() && lsfm_write_localmap(info.c_str(), type, &out)) fprintf(stderr, "LinearSFM: cannot write %s\n", info.c_str());
 	if (!fullbin.empty() && lsfm_save_state_bin(fullbin.c_str(), out.stVal, out.stno, r)) fprintf(stderr, "LinearSFM: cannot write %s\n", fullbin.c_str());
+	if (!cov.empty() || !covf.empty())
+	{
+		// marginal covariances of the map the files above hold (after -gn its information matrix is still the tree's)
+		std::vector<double> pc((size_t)out.m * 36), fc((size_t)out.n * 9);
+		const int crc = lsfm_map_covariance(ctx, &out, type, pc.data(), fc.data(), nullptr, 0, nullptr);
+		if (crc != LSFM_OK)
+		{
+			fprintf(stderr, "LinearSFM: covariance: %s\n", crc < 0 ? lsfm_last_error(ctx) : "pivots had to be floored (the information matrix is too close to singular)");
+			return 3;
+		}
+		if (lsfm_save_covariances(cov.empty() ? nullptr : cov.c_str(), covf.empty() ? nullptr : covf.c_str(), out.stno, out.m, out.n, pc.data(), fc.data()))
+			fprintf(stderr, "LinearSFM: cannot write the covariance files\n");
+	}
 	if (!json.empty())
 	{
 		FILE* f = fopen(json.c_str(), "w");

@@ -468,6 +468,10 @@ void small_solve_launch(lsfm_context* ctx, const SolveIO& io, int strips, int* s
 int solve_batch(lsfm_context* ctx, const SolveIO& io);
 // Gauss-Newton polish of the map-joining objective over all local maps at once (lsfm_gn.hip; C ABI: lsfm_gn_polish)
 int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_map* x, int iters, double* obj, double* gnorm, int* halvings);
+// marginal covariances of a map's information matrix (lsfm_cov.hip; C ABI: lsfm_map_covariance).  times (may be null): [4] ms of the
+// Schur reduction + analysis, the factorisation, the selected inversion + pose gather, the feature part
+int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb,
+                   double* times);
 // the two feature-side pieces of the solve on their own (C ABI: lsfm_inverse_v / lsfm_solve_features); device pointers
 void vinv_only(lsfm_context* ctx, int NF, const double* V, double* IV);
 void backsub_only(lsfm_context* ctx, int NF, const int* fptr, const int* photo, const double* W, const double* IV, const double* eb, const double* xp, double* xf);

@@ -486,4 +486,67 @@ int lsfm_save_poses(const char* pose_path, const char* feat_path, const int* stn
 	return LSFM_OK;
 }
 
+// -cov / -covf files (lsfm_map_covariance): one line per pose / feature in the order of the pose / feature files (ascending id, the
+// last state entry of an id), the id followed by the upper triangle of its covariance block, row by row, at %.17g
+int lsfm_save_covariances(const char* pose_path, const char* feat_path, const int* stno, int m, int n, const double* pose_cov, const double* feat_cov)
+{
+	if (m < 0 || n < 0 || !stno || (pose_path && !pose_cov) || (feat_path && n && !feat_cov)) return LSFM_ERR_ARG;
+	auto put = [](const char* path, std::vector<std::pair<int, int> >& L, const double* cov, int k) {
+		std::stable_sort(L.begin(), L.end());
+		FILE* fp = fopen(path, "w");
+		if (!fp) return LSFM_ERR_IO;
+		for (size_t i = 0; i < L.size(); i++)
+		{
+			if (i + 1 < L.size() && L[i + 1].first == L[i].first) continue;
+			const double* b = cov + (size_t)L[i].second * k * k;
+			fprintf(fp, "%d", L[i].first);
+			for (int r = 0; r < k; r++)
+				for (int c = r; c < k; c++) fprintf(fp, " %.17g", b[r * k + c]);
+			fprintf(fp, "\n");
+		}
+		return fclose(fp) == 0 ? LSFM_OK : LSFM_ERR_IO;
+	};
+	if (pose_path)
+	{
+		std::vector<std::pair<int, int> > P;
+		for (int p = 0; p < m; p++) P.push_back(std::make_pair(-stno[6 * p], p));
+		const int rc = put(pose_path, P, pose_cov, 6);
+		if (rc) return rc;
+	}
+	if (feat_path)
+	{
+		std::vector<std::pair<int, int> > F;
+		for (int f = 0; f < n; f++) F.push_back(std::make_pair(stno[6 * m + 3 * f], f));
+		const int rc = put(feat_path, F, feat_cov, 3);
+		if (rc) return rc;
+	}
+	return LSFM_OK;
+}
+
+// a -cov (k = 6) / -covf (k = 3) file back: ids[cap], full symmetric blocks cov[cap k k]; *count = lines read
+int lsfm_read_covariances(const char* path, int k, int* ids, double* cov, int cap, int* count)
+{
+	if (!path || (k != 3 && k != 6) || cap < 0 || !count || (cap && (!ids || !cov))) return LSFM_ERR_ARG;
+	FILE* fp = fopen(path, "r");
+	if (!fp) return LSFM_ERR_IO;
+	int cnt = 0, id = 0, rc = LSFM_OK;
+	while (rc == LSFM_OK && fscanf(fp, "%d", &id) == 1)
+	{
+		if (cnt >= cap) { rc = LSFM_ERR_ARG; break; }
+		double* b = cov + (size_t)cnt * k * k;
+		for (int r = 0; r < k && rc == LSFM_OK; r++)
+			for (int c = r; c < k; c++)
+			{
+				double v;
+				if (fscanf(fp, "%lf", &v) != 1) { rc = LSFM_ERR_IO; break; }
+				b[r * k + c] = b[c * k + r] = v;
+			}
+		if (rc == LSFM_OK) ids[cnt++] = id;
+	}
+	if (rc == LSFM_OK && !feof(fp)) rc = LSFM_ERR_IO;
+	fclose(fp);
+	*count = cnt;
+	return rc;
+}
+
 } // extern "C"

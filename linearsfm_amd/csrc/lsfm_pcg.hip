@@ -27,6 +27,7 @@
 #include "lsfm_internal.hpp"
 #include "lsfm_solve.hpp"
 #include "lsfm_symbolic.hpp"
+#include "lsfm_chol.hpp"
 
 namespace lsfm {
 
@@ -39,68 +40,6 @@ struct PcgSeg {
 };
 static_assert(sizeof(PcgSeg) % sizeof(double) == 0, "PcgSeg is strided in doubles by the fused dot products");
 #define SEG_STRIDE ((int)(sizeof(PcgSeg) / sizeof(double)))
-
-// ---------------------------------------------------------------------------------------------------------------
-// sparse block Cholesky: device side
-// ---------------------------------------------------------------------------------------------------------------
-struct CholDev {
-	int M = 0, nnzL = 0, nlevels = 0, tail_begin = 0; // columns [tail_begin, M) (in level order) run in one launch
-	int* colptr = nullptr;  // [M+1]
-	int* rowidx = nullptr;  // [nnzL] ascending inside a column, diagonal first
-	int* perm = nullptr;    // [M] new -> old
-	int* pinv = nullptr;    // [M] old -> new
-	int* order = nullptr;   // [M] columns sorted by elimination-tree level
-	std::vector<int> level_ptr; // host: order[level_ptr[l] .. level_ptr[l+1]) = columns of level l (before the tail)
-	// tasks: connected pieces of the elimination tree that one work-group walks serially (small sub-trees, chains)
-	int* task_cols = nullptr;          // [M] columns grouped by task, ascending inside a task
-	int* task_ptr = nullptr;           // [ntasks+1] tasks ordered by task level
-	std::vector<int> tlevel_ptr;       // host: tasks of task level l = [tlevel_ptr[l], tlevel_ptr[l+1])
-	std::vector<int> tlevel_maxsize;   // host: most columns in a task of the level (LDS of the solve launches)
-	int* col_task = nullptr;           // [M] task (position in task_ptr) of a column
-	int* col_lpos = nullptr;           // [M] position of a column inside its task
-	int* col_nin = nullptr;            // [M] leading rows of a column (below the diagonal) that belong to its own task
-	std::vector<int> tlevel_col0;      // host: task_cols[tlevel_col0[l] .. tlevel_col0[l+1]) = columns of the level's tasks
-	std::vector<int> tlevel_nsmall;    // host: the first tlevel_nsmall[l] tasks of level l fit LDS whole (small-task kernels)
-	std::vector<int> tlevel_small_lds; // host: dynamic LDS bytes of the level's small-task launches
-	std::vector<int> tlevel_outer;     // host: largest number of deferred update pairs of a column of the level
-	// supernode groups: the columns above the leaf tasks, cut into runs of <= CHOL_GS consecutive columns of one
-	// fundamental supernode (same rows below the run), ordered by group level (children before parents)
-	int ngroups = 0;
-	int *grp_c0 = nullptr, *grp_s = nullptr, *grp_nr = nullptr; // [ngroups] first column, columns, rows below the run
-	std::vector<int> glevel_ptr;    // host: groups of level l = [glevel_ptr[l], glevel_ptr[l+1])
-	std::vector<int> glevel_maxnr;  // host: most rows below a run of the level
-	std::vector<int> glevel_maxs;   // host: most block columns of a run of the level (LDS of k_sn_panel)
-	// distributed factorisation (lsfm_symbolic.hpp): owner of every column (-1: shared), null when off; the shared columns are the
-	// last ones, from first_shared on (their blocks: from block shared_blk0 of L on)
-	int* col_owner = nullptr;
-	int first_shared = 0, shared_blk0 = 0;
-	double work_total = 0, work_shared = 0;
-	std::vector<char> glevel_owned, glevel_shared;
-	int* blob = nullptr;    // all index arrays above are slices of this one allocation
-	size_t blob_ints = 0;
-	float *Lf = nullptr, *Dinvf = nullptr; // mixed precision: the factor rounded to fp32 for the triangular solves (null: fp64)
-	double* wv = nullptr;   // [M*6] forward-solve results of the group columns (lsfm_pcg.hip k_sn_fwd / k_sn_bwd)
-	double* Lg = nullptr;   // [nnzL*36] the factor of the supernode-group columns (same indexing as L; L keeps their unfactored blocks)
-	float* Lgf = nullptr;   // mixed precision: its fp32 copy
-	double* L = nullptr;    // [nnzL*36] block values, column major by blocks, each block row-major 6x6
-	double* Dinv = nullptr; // [M*36] inverse of the diagonal Cholesky factors (lower triangular)
-	double* diag0 = nullptr; // [M*6] diagonal of the scaled S as it was scattered (new numbering): what a pivot of the separators is held against
-	double* dscale = nullptr; // [M*6] the scaling D^-1/2 (powers of two; new numbering): right-hand sides enter and solutions leave through it
-	int* d_err = nullptr;
-};
-
-// Distributed factorisation (feature-sharded tree runs, lsfm_symbolic.hpp col_owner): which of a launch's work-groups take
-// part -- the ones whose first column belongs to `want` (a rank's block, or -1: the shared separator columns).  col_owner == null: all.
-struct OwnFilter {
-	const int* col_owner = nullptr;
-	int want = 0;
-	__device__ __forceinline__ bool skip(int col) const { return col_owner && col_owner[col] != want; }
-};
-__device__ __forceinline__ int find_row(const int* __restrict__ rowidx, int lo, int hi, int target)
-{
-	while (lo < hi) { int mid = (lo + hi) >> 1; if (rowidx[mid] < target) lo = mid + 1; else hi = mid; }
-	return lo;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Scaled matrix, fixed-point accumulators.  The factorisation works on  D^-1/2 (P S P^T) D^-1/2  with D the diagonal of S rounded
@@ -1642,13 +1581,9 @@ __global__ void k_rz_dot(int M, const double* __restrict__ z, const double* __re
 // ---------------------------------------------------------------------------------------------------------------
 // host: ordering + symbolic factorisation
 // ---------------------------------------------------------------------------------------------------------------
-struct CholHostIn {
-	std::vector<unsigned long long> keys; // sorted upper pattern of S
-	std::vector<int> origin;              // local map that brought each pose
-};
 // the two small device -> host copies of the analysis (a synchronisation), separate from the host work so that the
 // caller can enqueue the numeric Schur assembly in between and let it run under the symbolic factorisation
-static void chol_fetch(lsfm_context* ctx, const SchurSystem& sy, const int* d_origin, CholHostIn& in)
+void chol_fetch(lsfm_context* ctx, const SchurSystem& sy, const int* d_origin, CholHostIn& in)
 {
 	const int M = sy.M, nnzb = sy.nnzb;
 	in.keys.resize(nnzb);
@@ -1783,7 +1718,7 @@ static void chol_upload_symbolic(lsfm_context* ctx, const CholSymbolic& sym, Cho
 		fprintf(stderr, "\n");
 	}
 }
-static void chol_analyse(lsfm_context* ctx, const SchurSystem& sy, const CholHostIn& in, CholDev& ch)
+void chol_analyse(lsfm_context* ctx, const SchurSystem& sy, const CholHostIn& in, CholDev& ch)
 {
 	static thread_local CholSymbolic sym;
 	chol_symbolic(in.keys.data(), sy.nnzb, in.origin.data(), sy.M, sym, ctx->comm ? ctx->comm->block_maps : 0);
@@ -1959,7 +1894,7 @@ static void comm_sum(lsfm_context* ctx, void* p, size_t count, int dtype)
 
 // the scaled, permuted S into the factor's storage; also leaves the scaling (ch.dscale) that k_perm_in / k_perm_out_dot apply:
 // before anything is permuted in
-static void chol_scatter(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* fixed, CholDev& ch)
+void chol_scatter(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* fixed, CholDev& ch)
 {
 	static const bool groups = !getenv("LSFM_NO_GROUPS");
 	// (the columns above the leaf tasks -- what the supernode groups factor -- accumulate in fixed point; LSFM_NO_GROUPS: none does)
@@ -1973,7 +1908,7 @@ static void chol_scatter(lsfm_context* ctx, const SchurSystem& sy, const unsigne
 // groups level by level), whose updates into the shared separator columns it collects in its own copy of them; then the shared
 // columns' accumulators -- 64-bit integers: the sum is exact and the same bits on every rank -- and the shared rows of the forward
 // substitution's vector are summed over the ranks; phase 2 -- every rank factors the shared columns, alike.
-static void chol_factor(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* fixed, CholDev& ch, double* fwd_v = nullptr)
+void chol_factor(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* fixed, CholDev& ch, double* fwd_v)
 {
 	hipStream_t s = ctx->stream;
 	static const bool groups = !getenv("LSFM_NO_GROUPS");
@@ -2061,6 +1996,13 @@ static void chol_factor(lsfm_context* ctx, const SchurSystem& sy, const unsigned
 		if (ch.ngroups && !chol_group_solve(ch))
 			hipLaunchKernelGGL(k_sn_merge, dim3(ch.ngroups), dim3(256), 0, s, ch.grp_c0, ch.grp_s, ch.colptr, ch.Lg, ch.L);
 	}
+}
+
+void chol_merge_groups(lsfm_context* ctx, const CholDev& ch)
+{
+	static const bool groups = !getenv("LSFM_NO_GROUPS");
+	if (groups && ch.ngroups && chol_group_solve(ch))
+		hipLaunchKernelGGL(k_sn_merge, dim3(ch.ngroups), dim3(256), 0, ctx->stream, ch.grp_c0, ch.grp_s, ch.colptr, ch.Lg, ch.L);
 }
 
 // z = (L L^T)^-1 r in the original numbering, rz_dot[seg] += r . z

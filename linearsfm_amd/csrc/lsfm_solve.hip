@@ -21,8 +21,6 @@
 
 namespace lsfm {
 
-static const unsigned long long HEMPTY = ~0ull;
-
 // also what the panel kernel of K9 needs per feature: V^-1 = L L^T (l00 l10 l11 l20 l21 l22) and y = L^T eb, so that its
 // passes find them ready instead of running a Cholesky with square roots and divisions on a dependent load each;
 // l00 = NaN marks a V^-1 without a Cholesky factor (the tile then goes to k_schur_w)
@@ -147,46 +145,6 @@ __global__ void k_schur_finish(int nnzb, int M, const unsigned long long* __rest
 		const double v = ldexp((double)acc[ns + k], e) + ldexp((double)acc[ns + ne + k], e - 40);
 		E[k] = poison ? __builtin_nan("") : E[k] + v;
 	}
-}
-
-// ---- hash set of block coordinates ------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x)
-{
-	x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-	return x;
-}
-__device__ __forceinline__ void hash_insert(unsigned long long* tab, unsigned long long mask, unsigned long long key, int* overflow)
-{
-	unsigned long long h = mix64(key) & mask;
-	for (int probe = 0; probe < 4096; probe++)
-	{
-		unsigned long long cur = tab[h];
-		if (cur == key) return;
-		if (cur == HEMPTY)
-		{
-			unsigned long long old = atomicCAS(&tab[h], HEMPTY, key);
-			if (old == HEMPTY || old == key) return;
-		}
-		h = (h + 1) & mask;
-	}
-	*overflow = 1;
-}
-__device__ __forceinline__ int hash_find(const unsigned long long* __restrict__ tab, const int* __restrict__ val, unsigned long long mask,
-                                         unsigned long long key)
-{
-	unsigned long long h = mix64(key) & mask;
-	for (int probe = 0; probe < 4096; probe++)
-	{
-		unsigned long long cur = tab[h];
-		if (cur == key) return val[h];
-		if (cur == HEMPTY) return -1;
-		h = (h + 1) & mask;
-	}
-	return -1;
-}
-__device__ __forceinline__ unsigned long long pair_key(int p, int q)
-{
-	return p <= q ? (((unsigned long long)(unsigned)p << 32) | (unsigned)q) : (((unsigned long long)(unsigned)q << 32) | (unsigned)p);
 }
 
 __global__ void k_fill_u64(unsigned long long* p, size_t n, unsigned long long v)

@@ -109,4 +109,45 @@ void launch_schur_panel(lsfm_context* ctx, int NF, const int* fptr, const int* p
                         int max_poses_per_system, K9Cache kc, bool fresh_lists = false);
 void launch_backsub(lsfm_context* ctx, const SolveIO& io, const SchurSystem& sy, const double* x);
 
+// ---- hash set of block coordinates (pose pair -> block of S: SchurSystem::tab / hval) ----
+static const unsigned long long HEMPTY = ~0ull;
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x)
+{
+	x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
+	return x;
+}
+__device__ __forceinline__ void hash_insert(unsigned long long* tab, unsigned long long mask, unsigned long long key, int* overflow)
+{
+	unsigned long long h = mix64(key) & mask;
+	for (int probe = 0; probe < 4096; probe++)
+	{
+		unsigned long long cur = tab[h];
+		if (cur == key) return;
+		if (cur == HEMPTY)
+		{
+			unsigned long long old = atomicCAS(&tab[h], HEMPTY, key);
+			if (old == HEMPTY || old == key) return;
+		}
+		h = (h + 1) & mask;
+	}
+	*overflow = 1;
+}
+__device__ __forceinline__ int hash_find(const unsigned long long* __restrict__ tab, const int* __restrict__ val, unsigned long long mask,
+                                         unsigned long long key)
+{
+	unsigned long long h = mix64(key) & mask;
+	for (int probe = 0; probe < 4096; probe++)
+	{
+		unsigned long long cur = tab[h];
+		if (cur == key) return val[h];
+		if (cur == HEMPTY) return -1;
+		h = (h + 1) & mask;
+	}
+	return -1;
+}
+__device__ __forceinline__ unsigned long long pair_key(int p, int q)
+{
+	return p <= q ? (((unsigned long long)(unsigned)p << 32) | (unsigned)q) : (((unsigned long long)(unsigned)q << 32) | (unsigned)p);
+}
+
 } // namespace lsfm
