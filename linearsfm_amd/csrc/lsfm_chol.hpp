@@ -19,18 +19,18 @@ struct CholDev {
 	int* pinv = nullptr;    // [M] old -> new
 	int* order = nullptr;   // [M] columns sorted by elimination-tree level
 	std::vector<int> level_ptr; // host: order[level_ptr[l] .. level_ptr[l+1]) = columns of level l (before the tail)
-	// tasks: connected pieces of the elimination tree that one work-group walks serially (small sub-trees, chains)
+	// tasks: connected pieces of the elimination tree that one work-group walks serially (lsfm_symbolic.cpp).  Only the leaf tasks
+	// (task level 0, sub-trees of at most task_x blocks: tasks [0, ntask0), columns task_cols[0 .. ncol0)) are walked as tasks,
+	// each whole in LDS (chol_upload_index checks it); the columns above them go by supernode group
 	int* task_cols = nullptr;          // [M] columns grouped by task, ascending inside a task
 	int* task_ptr = nullptr;           // [ntasks+1] tasks ordered by task level
-	std::vector<int> tlevel_ptr;       // host: tasks of task level l = [tlevel_ptr[l], tlevel_ptr[l+1])
-	std::vector<int> tlevel_maxsize;   // host: most columns in a task of the level (LDS of the solve launches)
 	int* col_task = nullptr;           // [M] task (position in task_ptr) of a column
 	int* col_lpos = nullptr;           // [M] position of a column inside its task
 	int* col_nin = nullptr;            // [M] leading rows of a column (below the diagonal) that belong to its own task
-	std::vector<int> tlevel_col0;      // host: task_cols[tlevel_col0[l] .. tlevel_col0[l+1]) = columns of the level's tasks
-	std::vector<int> tlevel_nsmall;    // host: the first tlevel_nsmall[l] tasks of level l fit LDS whole (small-task kernels)
-	std::vector<int> tlevel_small_lds; // host: dynamic LDS bytes of the level's small-task launches
-	std::vector<int> tlevel_outer;     // host: largest number of deferred update pairs of a column of the level
+	int ntask0 = 0, ncol0 = 0;
+	int task0_maxsize = 0; // most columns in a leaf task (LDS of the solve launches)
+	int task0_lds = 0;     // dynamic LDS of the factorisation launch (k_chol_factor_level)
+	int task0_outer = 0;   // largest number of deferred update pairs of a leaf column (k_chol_update_outer)
 	// supernode groups: the columns above the leaf tasks, cut into runs of <= CHOL_GS consecutive columns of one
 	// fundamental supernode (same rows below the run), ordered by group level (children before parents)
 	int ngroups = 0;

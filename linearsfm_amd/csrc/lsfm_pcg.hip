@@ -116,8 +116,6 @@ __global__ void k_chol_scatter(int nnzb, const unsigned long long* __restrict__ 
 		}
 }
 
-// one work-group factors one block column: L_jj = chol(A_jj); L_ij = A_ij L_jj^-T; A_ik -= L_ij L_kj^T for the blocks
-// below (right-looking; targets in other columns are updated atomically because the columns of one level run together)
 // pivot block of column j (block c0 of Lb, memory or LDS): L_jj = chol(A_jj) in place, its inverse to Dinv and to sLi
 // (LDS, 36 doubles); ends with a barrier
 __device__ void chol_pivot(int j, int c0, double* L, double* __restrict__ Dinv, int* err, double* sLi)
@@ -184,50 +182,12 @@ __device__ void chol_scale_column(int c0, int n, double* L, const double* sLi)
 		for (int k = 0; k < 6; k++) blk[k] = o[k];
 	}
 }
-__device__ void chol_factor_column(int j, const int* __restrict__ colptr, const int* __restrict__ rowidx, double* __restrict__ L,
-                                   double* __restrict__ Dinv, int* err)
-{
-	__shared__ double sLi[36];
-	const int c0 = colptr[j], n = colptr[j + 1] - c0 - 1;
-	chol_pivot(j, c0, L, Dinv, err, sLi);
-	chol_scale_column(c0, n, L, sLi);
-	__syncthreads();
-}
-
-// one trailing update of column j: blocks a >= b below the diagonal give L_a L_b^T, subtracted from block (ra, rb)
-template <bool ATOMIC>
-__device__ __forceinline__ void chol_pair_update(int c0, int a, int b, const int* __restrict__ colptr, const int* __restrict__ rowidx, double* __restrict__ L)
-{
-	const int ra = rowidx[c0 + 1 + a], rb = rowidx[c0 + 1 + b];
-	double La[36], Lb[36], T[36];
-	ld<36>(La, L + (size_t)(c0 + 1 + a) * 36);
-	ld<36>(Lb, L + (size_t)(c0 + 1 + b) * 36);
-	mmt<6, 6, 6, false>(La, Lb, T);
-	// the rows of column j from rb on are a subset of column rb's rows; when the two lists coincide (columns of one
-	// separator: nested patterns) the target is at the same offset, else binary search
-	const int cb = colptr[rb], nb = colptr[rb + 1] - cb;
-	int pos = cb + (a - b);
-	if (!(a - b < nb && rowidx[pos] == ra)) pos = find_row(rowidx, cb, cb + nb, ra);
-	double* d = L + (size_t)pos * 36;
-	if (ATOMIC) { for (int q = 0; q < 36; q++) atomic_add_f64(d + q, -T[q]); }
-	else { for (int q = 0; q < 36; q++) d[q] -= T[q]; } // the caller owns the target column: one pair per target block
-}
-// the pairs whose target column rb is one of the first m rows (the rows inside the task): needed before the task's next column
-__device__ void chol_column_update_inner(int j, int m, const int* __restrict__ colptr, const int* __restrict__ rowidx, double* __restrict__ L, int first, int stride)
-{
-	const int c0 = colptr[j], n = colptr[j + 1] - c0 - 1;
-	for (int idx = first; idx < m * n; idx += stride)
-	{
-		const int b = idx / n, a = idx - b * n;
-		if (a >= b) chol_pair_update<false>(c0, a, b, colptr, rowidx, L); // in-task columns: only this work-group touches them now
-	}
-}
-// the pairs with b >= m: targets in columns outside the task, nobody inside the task waits for them.  Other columns
+// the deferred updates of leaf column j: the pairs of its blocks a >= b >= m (m: its rows inside its own task, which the LDS walk
+// updated) -- targets in columns outside the task, nobody inside the task waits for them.  Other columns
 // update the same blocks, so these are atomics -- made contiguous: every lane parks its 6x6 product in LDS and the
 // work-group adds block after block with consecutive lanes on consecutive doubles (one lane per block scatters 64
 // rows per wave instruction: ~0.1 TB/s)
 #define CHOL_OUT_THREADS 128
-template <bool FX>
 __device__ void chol_column_update_outer(int j, int m, const int* __restrict__ colptr, const int* __restrict__ rowidx, double* __restrict__ L, int first, int stride)
 {
 	__shared__ double sT[CHOL_OUT_THREADS * 37];
@@ -262,129 +222,28 @@ __device__ void chol_column_update_outer(int j, int m, const int* __restrict__ c
 		{
 			const int p = idx / 36, q = idx - p * 36;
 			const int ps = spos[p];
-			if (ps >= 0)
-			{
-				if (FX) fx_atomic_sub(L + (size_t)ps * 36 + q, sT[p * 37 + q]); // (targets are supernode-group columns: fixed point)
-				else atomic_add_f64(L + (size_t)ps * 36 + q, -sT[p * 37 + q]);
-			}
+			if (ps >= 0) fx_atomic_sub(L + (size_t)ps * 36 + q, sT[p * 37 + q]); // (targets are supernode-group columns: fixed point)
 		}
 		__syncthreads();
 	}
 }
 
-// forward substitution, right-looking: y_j = Li_j v_j ; v_i -= L_ij y_j
-__device__ void chol_fwd_column(int j, const int* __restrict__ colptr, const int* __restrict__ rowidx, const double* __restrict__ L,
-                                const double* __restrict__ Dinv, double* __restrict__ v)
-{
-	const int c0 = colptr[j], n = colptr[j + 1] - c0 - 1;
-	const int tid = threadIdx.x, nt = blockDim.x;
-	__shared__ double sy[6];
-	if (tid < 6)
-	{
-		const double* Li = Dinv + (size_t)j * 36;
-		double s = 0;
-		for (int k = 0; k <= tid; k++) s = fma(Li[tid * 6 + k], v[(size_t)j * 6 + k], s);
-		sy[tid] = s;
-	}
-	__syncthreads();
-	if (tid < 6) v[(size_t)j * 6 + tid] = sy[tid];
-	for (int w = tid; w < n * 6; w += nt)
-	{
-		const int e = c0 + 1 + w / 6, r = w % 6;
-		const double* blk = L + (size_t)e * 36 + r * 6;
-		double s = 0;
-		for (int k = 0; k < 6; k++) s = fma(blk[k], sy[k], s);
-		atomic_add_f64(v + (size_t)rowidx[e] * 6 + r, -s);
-	}
-}
-// backward substitution: x_j = Li_j^T (y_j - sum_i L_ij^T x_i)   (all i > j are final)
-__device__ void chol_bwd_column(int j, const int* __restrict__ colptr, const int* __restrict__ rowidx, const double* __restrict__ L,
-                                const double* __restrict__ Dinv, double* __restrict__ v)
-{
-	const int c0 = colptr[j], n = colptr[j + 1] - c0 - 1;
-	const int tid = threadIdx.x, nt = blockDim.x;
-	__shared__ double red[256];
-	__shared__ double ss[6];
-	const int c = tid % 6, g = tid / 6, ng = nt / 6;
-	double s = 0;
-	if (g < ng)
-		for (int e = g; e < n; e += ng)
-		{
-			const double* blk = L + (size_t)(c0 + 1 + e) * 36;
-			const double* xi = v + (size_t)rowidx[c0 + 1 + e] * 6;
-			for (int r = 0; r < 6; r++) s = fma(blk[r * 6 + c], xi[r], s);
-		}
-	red[tid] = (g < ng) ? s : 0.0;
-	__syncthreads();
-	if (tid < 6)
-	{
-		double t = v[(size_t)j * 6 + tid];
-		for (int k = 0; k < ng; k++) t -= red[k * 6 + tid];
-		ss[tid] = t;
-	}
-	__syncthreads();
-	if (tid < 6)
-	{
-		const double* Li = Dinv + (size_t)j * 36;
-		double t = 0;
-		for (int k = tid; k < 6; k++) t = fma(Li[k * 6 + tid], ss[k], t);
-		v[(size_t)j * 6 + tid] = t;
-	}
-}
-__global__ void __launch_bounds__(64) k_chol_fwd_level(const int* __restrict__ cols, const int* __restrict__ colptr, const int* __restrict__ rowidx,
-                                                        const double* __restrict__ L, const double* __restrict__ Dinv, double* __restrict__ v)
-{
-	chol_fwd_column(cols[blockIdx.x], colptr, rowidx, L, Dinv, v);
-}
-__global__ void __launch_bounds__(64) k_chol_bwd_level(const int* __restrict__ cols, const int* __restrict__ colptr, const int* __restrict__ rowidx,
-                                                        const double* __restrict__ L, const double* __restrict__ Dinv, double* __restrict__ v)
-{
-	chol_bwd_column(cols[blockIdx.x], colptr, rowidx, L, Dinv, v);
-}
-// tail: forward over the remaining columns in order, then straight back down over them
-__global__ void __launch_bounds__(256) k_chol_solve_tail(int ncols, const int* __restrict__ cols, const int* __restrict__ colptr,
-                                                          const int* __restrict__ rowidx, const double* __restrict__ L,
-                                                          const double* __restrict__ Dinv, double* __restrict__ v)
-{
-	for (int k = 0; k < ncols; k++) { chol_fwd_column(cols[k], colptr, rowidx, L, Dinv, v); __threadfence(); __syncthreads(); }
-	for (int k = ncols - 1; k >= 0; k--) { chol_bwd_column(cols[k], colptr, rowidx, L, Dinv, v); __threadfence(); __syncthreads(); }
-}
-
-// one work-group per task: its columns in ascending order (children before parents) / descending for the back solve
-__device__ void chol_factor_task_global(int task, const int* __restrict__ task_ptr, const int* __restrict__ task_cols,
-                                        const int* __restrict__ col_nin, const int* __restrict__ colptr,
-                                        const int* __restrict__ rowidx, double* __restrict__ L, double* __restrict__ Dinv, int* err)
-{
-	const int b = task_ptr[task], e = task_ptr[task + 1];
-	for (int k = b; k < e; k++)
-	{
-		const int j = task_cols[k];
-		chol_factor_column(j, colptr, rowidx, L, Dinv, err);
-		if (k + 1 < e)
-		{
-			chol_column_update_inner(j, col_nin[j], colptr, rowidx, L, threadIdx.x, blockDim.x);
-			__threadfence();
-			__syncthreads();
-		}
-	}
-}
-// the deferred updates of the level's tasks, into the columns above them: one column per blockIdx.x, pairs split over blockIdx.y
-template <bool FX>
+// the deferred updates of the leaf tasks, into the columns above them: one column per blockIdx.x, pairs split over blockIdx.y
 __global__ void __launch_bounds__(CHOL_OUT_THREADS) k_chol_update_outer(const int* __restrict__ cols, const int* __restrict__ col_nin,
                                                                          const int* __restrict__ colptr, const int* __restrict__ rowidx,
                                                                          double* __restrict__ L, OwnFilter of)
 {
 	const int j = cols[blockIdx.x];
 	if (of.skip(j)) return;
-	chol_column_update_outer<FX>(j, col_nin[j], colptr, rowidx, L, blockIdx.y * CHOL_OUT_THREADS, gridDim.y * CHOL_OUT_THREADS);
+	chol_column_update_outer(j, col_nin[j], colptr, rowidx, L, blockIdx.y * CHOL_OUT_THREADS, gridDim.y * CHOL_OUT_THREADS);
 }
 // Triangular solves by task.  The entries of v that belong to the task's own columns live in LDS while the work-group
 // walks the task: a column step inside a task then costs LDS latency instead of a global atomic + fence round trip
 // (measured 2.7 us per step, the critical path of the whole solve).  Rows outside the task (ancestors) are updated /
 // read in global memory; nobody inside the task reads them.
-// LDS per task column: its slice of v (6), the inverse pivot block (36) and three ints (column, first block, count):
-// everything a column step needs except the sub-diagonal blocks themselves is fetched side by side before the walk
-#define CHOL_TASK_LDS_PER_COL (6 * 8 + 36 * 8 + 3 * 4)
+// LDS per task column (CHOL_TASK_LDS_PER_COL, lsfm_symbolic.hpp): its slice of v (6), the inverse pivot block (36) and three
+// ints (column, first block, count): everything a column step needs except the sub-diagonal blocks themselves is fetched side
+// by side before the walk
 template <class FT>
 __device__ __forceinline__ void chol_task_stage(int b, int e, const int* __restrict__ task_cols, const int* __restrict__ colptr,
                                                 const FT* __restrict__ Dinv, const double* __restrict__ v, double* lv, double* sD, int* sj,
@@ -504,10 +363,10 @@ __global__ void __launch_bounds__(256) k_chol_bwd_tasks(const int* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Small tasks: everything the walk touches fits LDS.  The column steps of a task are a chain of dependent global
-// round trips (pivot block, scaled column, updated targets: ~6 per column, 10-14 us measured); when all blocks of the
-// task's columns (288 B each + row index) fit 60 KB they are fetched side by side once, the walk runs at LDS latency
-// and the result is written back once.  The host puts the small tasks first in every task level.
+// Leaf tasks: everything the walk touches fits LDS.  The column steps of a task are a chain of dependent global
+// round trips (pivot block, scaled column, updated targets: ~6 per column, 10-14 us measured); all blocks of the
+// task's columns (288 B each + row index) fit CHOL_FACTOR_LDS (lsfm_symbolic.hpp: LSFM_TASK_X is capped so that they
+// do), so they are fetched side by side once, the walk runs at LDS latency and the result is written back once.
 // ---------------------------------------------------------------------------------------------------------------
 struct SmallTask {
 	int nc, nb;          // columns, blocks (pivot blocks included)
@@ -612,15 +471,13 @@ __device__ void chol_factor_task_lds(int task, const int* __restrict__ task_ptr,
 	}
 }
 
-// one task level of the factorisation in one launch: the first nsmall tasks of the level fit LDS whole, the others walk
-// their columns in memory; both kinds run side by side
-__global__ void __launch_bounds__(256) k_chol_factor_level(int nsmall, const int* __restrict__ task_ptr, const int* __restrict__ task_cols,
+// the leaf tasks of the factorisation in one launch, one work-group per task
+__global__ void __launch_bounds__(256) k_chol_factor_level(const int* __restrict__ task_ptr, const int* __restrict__ task_cols,
                                                             const int* __restrict__ col_nin, const int* __restrict__ colptr,
                                                             const int* __restrict__ rowidx, double* __restrict__ L, double* __restrict__ Dinv, int* err, OwnFilter of)
 {
 	if (of.skip(task_cols[task_ptr[blockIdx.x]])) return;
-	if ((int)blockIdx.x < nsmall) chol_factor_task_lds(blockIdx.x, task_ptr, task_cols, col_nin, colptr, rowidx, L, Dinv, err);
-	else chol_factor_task_global(blockIdx.x, task_ptr, task_cols, col_nin, colptr, rowidx, L, Dinv, err);
+	chol_factor_task_lds(blockIdx.x, task_ptr, task_cols, col_nin, colptr, rowidx, L, Dinv, err);
 }
 
 
@@ -631,11 +488,12 @@ __global__ void __launch_bounds__(256) k_chol_factor_level(int nsmall, const int
 // NC3500-like set.  A group is a run of s <= CHOL_GS consecutive columns of one fundamental supernode: column c0+t
 // holds [its diagonal block, the s-1-t later columns of the run, the nr common rows below the run], so block
 // (row i of the common rows, column t) sits at colptr[c0+t] + (s-t) + i: the run is a dense trapezoid in the block
-// storage as it is.  Per group level (children before parents) two launches:
+// storage as it is.  Per group level (children before parents) two launches (one while the panels are short: k_sn_panel<true>
+// does both):
 //   k_sn_panel   every work-group factors the s x s diagonal blocks in LDS (redundantly: the other CUs would idle)
 //                and solves its 16 block rows of the panel against them:  X = A L_dd^-T
-//   k_sn_update  one lane per pair (a >= b) of common rows: block (r_a, r_b) -= sum_t X[a,t] X[b,t]^T, left through LDS
-//                as contiguous atomics (groups of one level share ancestors)
+//   k_sn_syrk    the rank update: block (r_a, r_b) -= sum_t X[a,t] X[b,t]^T for the pairs (a >= b) of common rows, on the
+//                matrix cores, left as contiguous atomics (groups of one level share ancestors)
 // ---------------------------------------------------------------------------------------------------------------
 /* CHOL_GS (most block columns of a group, 8): lsfm_symbolic.hpp */
 #define SN_RB 16                    /* block rows of the panel per work-group */
@@ -686,7 +544,7 @@ __device__ __forceinline__ int sn_idx(int s, int u, int t) { return t * s - t * 
 // level, known before the factorisation starts): fv_g^T is one more panel row, so the recurrence leaves y_g = L_dd^-1 fv_g
 // in it, and every work-group takes X y_g off fv at its common rows -- what k_sn_fwd does in a launch of its own per
 // group level (25 of them at the top join).  y_g goes to fw for the backward substitution.
-// FUSED = false: grid (groups, chunks of SN_RB block rows of the panel); k_sn_update follows with the rank update.
+// FUSED = false: grid (groups, chunks of SN_RB block rows of the panel); k_sn_syrk follows with the rank update.
 // FUSED = true:  grid (groups, pairs (ca >= cb) of chunks of SN_RB / 2 block rows): the work-group solves the panel rows of
 //                BOTH chunks and subtracts their product X_ca X_cb^T from the ancestors itself -- T = X X^T is a dense
 //                (48 x 6s) x (6s x 48) contraction on v_mfma_f64_16x16x4_f64, leaving as 36 contiguous atomics per block --
@@ -1144,68 +1002,8 @@ __global__ void __launch_bounds__(SN_PT) k_sn_panel(const int* __restrict__ grp_
 	}
 }
 
-#define SN_KS 4                      /* lanes per pair of rows in k_sn_update: each takes every 4th column of the run */
-#define SN_PAIRS (SN_THREADS / SN_KS)
-// the rank update of the levels whose panels are too tall for the fused kernel: X is read from the factor's array Lg, the
-// products are subtracted from the ancestors' (still unfactored) blocks in L
-__global__ void __launch_bounds__(SN_THREADS) k_sn_update(const int* __restrict__ grp_c0, const int* __restrict__ grp_s, const int* __restrict__ grp_nr,
-                                                           const int* __restrict__ colptr, const int* __restrict__ rowidx, double* __restrict__ L,
-                                                           const double* __restrict__ Lg, OwnFilter of)
-{
-	__shared__ double sT[SN_PAIRS * 37];
-	__shared__ int spos[SN_PAIRS];
-	const int g = blockIdx.x, c0 = grp_c0[g], s = grp_s[g], nr = grp_nr[g];
-	if (of.skip(c0)) return;
-	const int npairs = nr * (nr + 1) / 2;
-	const int tid = threadIdx.x;
-	const int rows0 = colptr[c0 + s - 1] + 1; // the common rows: what the last column of the run holds below its diagonal
-	const int pl = tid / SN_KS, sub = tid - pl * SN_KS; // pair of this lane inside the round, its share of the columns
-	for (int base = blockIdx.y * SN_PAIRS; base < npairs; base += gridDim.y * SN_PAIRS)
-	{
-		for (int q = tid; q < SN_PAIRS * 37; q += SN_THREADS) sT[q] = 0.0;
-		__syncthreads();
-		const int pr = base + pl;
-		if (pr < npairs)
-		{
-			int a = (int)((sqrt(8.0 * pr + 1.0) - 1.0) * 0.5);
-			while (a * (a + 1) / 2 > pr) a--;
-			while ((a + 1) * (a + 2) / 2 <= pr) a++;
-			const int b = pr - a * (a + 1) / 2;
-			double T[36];
-			zero<36>(T);
-			// a dependent chain of s block loads per pair cost ~2 us each: four lanes share the chain, their sums meet in LDS
-			for (int t = sub; t < s; t += SN_KS)
-			{
-				const size_t cb = (size_t)colptr[c0 + t] + (s - t);
-				double La[36], Lb[36];
-				ld<36>(La, Lg + (cb + a) * 36);
-				ld<36>(Lb, Lg + (cb + b) * 36);
-				mmt<6, 6, 6, true>(La, Lb, T);
-			}
-			if (sub < s)
-				for (int q = 0; q < 36; q++) lds_add_f64(&sT[pl * 37 + q], T[q]);
-			if (sub == 0)
-			{
-				const int ra = rowidx[rows0 + a], rb = rowidx[rows0 + b];
-				const int cbk = colptr[rb], nbk = colptr[rb + 1] - cbk;
-				int pos = cbk + (a - b);
-				if (!(a - b < nbk && rowidx[pos] == ra)) pos = find_row(rowidx, cbk, cbk + nbk, ra);
-				spos[pl] = pos;
-			}
-		}
-		else if (sub == 0) spos[pl] = -1;
-		__syncthreads();
-		for (int idx = tid; idx < SN_PAIRS * 36; idx += SN_THREADS)
-		{
-			const int p = idx / 36, q = idx - p * 36;
-			const int ps = spos[p];
-			if (ps >= 0) fx_atomic_sub(L + (size_t)ps * 36 + q, sT[p * 37 + q]);
-		}
-		__syncthreads();
-	}
-}
 // The same rank update on the matrix cores, for the panels too tall for the fused kernel (a synth-16k Mono tree: 100-300 common
-// rows per group at its upper levels -- k_sn_update, one scalar 6x6 product chain per PAIR of rows, was 11 % of that tree's
+// rows per group at its upper levels -- the round-2 update kernel, one scalar 6x6 product chain per PAIR of rows, was 11 % of that tree's
 // device time and loaded every block of X once per partner row).  One work-group per pair (ca >= cb) of 8-block-row chunks of a
 // group's solved panel X (read from Lg): both chunks go to LDS as dense scalar rows once, T = X_ca X_cb^T is a (48 x 6s) x (6s x
 // 48) contraction on v_mfma_f64_16x16x4_f64 (nine 16x16 tiles over the four waves), and the 64 products leave as 36 contiguous
@@ -1335,7 +1133,8 @@ static size_t sn_panel_lds(int smax)
 	const size_t LD = 6 * (size_t)smax, xs = ((LD + 3) & ~(size_t)3) + 1;
 	return std::max((LD + 6 * SN_RB + 1) * xs, (size_t)(6 * SN_RB / 2) * (6 * SN_RB / 2 + 1)) * sizeof(double);
 }
-// the factor of the group columns back into L (only for the fall-back solves that read one array: chol_apply)
+// the factor of the group columns back into L, for readers of the whole factor in one array (chol_merge_groups: the selected
+// inversion, lsfm_cov.hip)
 __global__ void k_sn_merge(const int* __restrict__ grp_c0, const int* __restrict__ grp_s, const int* __restrict__ colptr, const double* __restrict__ Lg,
                            double* __restrict__ L)
 {
@@ -1668,6 +1467,8 @@ static std::shared_ptr<void> solve_plan_store(lsfm_context* ctx, const SchurSyst
 	return sp;
 }
 
+// dynamic LDS of the leaf-task triangular solves (k_chol_fwd_tasks / k_chol_bwd_tasks): within CHOL_SOLVE_LDS (chol_upload_index)
+static size_t chol_task_lds(const CholDev& ch) { return (size_t)ch.task0_maxsize * CHOL_TASK_LDS_PER_COL + 8; }
 // symbolic analysis on the host (lsfm_symbolic.cpp), then every index array of it to the device in ONE copy
 // index arrays of a symbolic factorisation to the device (ctx->scratch / ctx->stream as the caller has set them), host vectors
 // copied: what a plan keeps
@@ -1676,8 +1477,16 @@ static void chol_upload_index(lsfm_context* ctx, const CholSymbolic& sym, CholDe
 	Arena& sc = ctx->scratch;
 	ch.M = sym.M; ch.nnzL = sym.nnzL; ch.nlevels = sym.nlevels; ch.tail_begin = sym.tail_begin;
 	ch.level_ptr = sym.level_ptr;
-	ch.tlevel_ptr = sym.tlevel_ptr; ch.tlevel_maxsize = sym.tlevel_maxsize; ch.tlevel_col0 = sym.tlevel_col0; ch.tlevel_nsmall = sym.tlevel_nsmall;
-	ch.tlevel_small_lds = sym.tlevel_small_lds; ch.tlevel_outer = sym.tlevel_outer;
+	if (!sym.tlevel_ptr.empty())
+	{
+		// the leaf tasks (task level 0) are the only ones walked as tasks, each whole in LDS -- by the factorisation and by the
+		// solves (LSFM_TASK_X <= CHOL_TASK_X_MAX makes sure of it)
+		ch.ntask0 = sym.tlevel_ptr[1]; ch.ncol0 = sym.tlevel_col0[1];
+		ch.task0_maxsize = sym.tlevel_maxsize[0]; ch.task0_lds = sym.tlevel_small_lds[0]; ch.task0_outer = sym.tlevel_outer[0];
+		if (sym.tlevel_nsmall[0] != ch.ntask0 || chol_task_lds(ch) > CHOL_SOLVE_LDS)
+			LSFM_FAIL(LSFM_ERR_INTERNAL, "a leaf task of the factorisation does not fit LDS (" + std::to_string(sym.tlevel_nsmall[0]) + " of " + std::to_string(ch.ntask0) +
+			                                 " fit, " + std::to_string(ch.task0_maxsize) + " columns at most)");
+	}
 	ch.ngroups = sym.ngroups; ch.glevel_ptr = sym.glevel_ptr; ch.glevel_maxnr = sym.glevel_maxnr; ch.glevel_maxs = sym.glevel_maxs;
 	ch.work_total = sym.work_total; ch.work_shared = sym.work_shared;
 	ch.first_shared = sym.first_shared; ch.shared_blk0 = sym.colptr[sym.first_shared]; ch.glevel_owned = sym.glevel_owned; ch.glevel_shared = sym.glevel_shared;
@@ -1863,21 +1672,10 @@ static std::shared_ptr<void> pre_plan_complete(lsfm_context* ctx)
 	return sp;
 }
 
-// the supernode-group path of the triangular solves applies (chol_apply): the forward substitution can ride on the factorisation
-static bool chol_group_solve(const CholDev& ch)
-{
-	static const bool on = !getenv("LSFM_LEVEL_SOLVE") && !getenv("LSFM_NO_GROUPS") && !getenv("LSFM_TASK_SOLVE") && !getenv("LSFM_NO_FUSED_FWD");
-	return on && !ch.tlevel_ptr.empty() && (size_t)ch.tlevel_maxsize[0] * CHOL_TASK_LDS_PER_COL <= 56 * 1024;
-}
-
-// fwd_v != null (chol_group_solve(ch) holds): a right-hand side in elimination order; on return it holds what the forward
-// substitution leaves (leaf columns in place, group columns in ch.wv) -- chol_apply(..., fwd_done) does the rest
-// the scaled, permuted S into the factor's storage; also leaves the scaling (ch.dscale) that k_perm_in / k_perm_out_dot apply:
-// before anything is permuted in
 // the factorisation of this system is distributed over the ranks of a feature-sharded run (CholDev::col_owner)
 static bool chol_distributed(const lsfm_context* ctx, const CholDev& ch)
 {
-	return ctx->comm && ctx->comm->world > 1 && ch.col_owner && ch.first_shared < ch.M && chol_group_solve(ch) && !getenv("LSFM_NO_GROUPS");
+	return ctx->comm && ctx->comm->world > 1 && ch.col_owner && ch.first_shared < ch.M;
 }
 // sums `count` 8-byte numbers at p over the ranks (through the caller's buffer: p lives in this context's arenas)
 static void comm_sum(lsfm_context* ctx, void* p, size_t count, int dtype)
@@ -1896,14 +1694,15 @@ static void comm_sum(lsfm_context* ctx, void* p, size_t count, int dtype)
 // before anything is permuted in
 void chol_scatter(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* fixed, CholDev& ch)
 {
-	static const bool groups = !getenv("LSFM_NO_GROUPS");
-	// (the columns above the leaf tasks -- what the supernode groups factor -- accumulate in fixed point; LSFM_NO_GROUPS: none does)
-	const int ntask0 = (groups && ch.tlevel_ptr.size() > 1) ? ch.tlevel_ptr[1] : INT_MAX;
+	// (the columns above the leaf tasks -- what the supernode groups factor -- accumulate in fixed point)
 	const bool dist = chol_distributed(ctx, ch);
 	if (sy.nnzb)
 		hipLaunchKernelGGL(k_chol_scatter, dim3((sy.nnzb + 127) / 128), dim3(128), 0, ctx->stream, sy.nnzb, sy.upper_keys, sy.S, sy.rowptr, ch.pinv, ch.colptr, ch.rowidx,
-		                   fixed, ch.col_task, ntask0, ch.L, ch.diag0, ch.dscale, dist ? ch.col_owner : (const int*)nullptr, dist ? ctx->comm->rank : 0);
+		                   fixed, ch.col_task, ch.ntask0, ch.L, ch.diag0, ch.dscale, dist ? ch.col_owner : (const int*)nullptr, dist ? ctx->comm->rank : 0);
 }
+// The leaf tasks in LDS, their deferred updates into the columns above them, then the supernode groups level by level.
+// fwd_v != null: a right-hand side in elimination order; on return it holds what the forward substitution leaves (leaf columns in
+// place, group columns in ch.wv) -- chol_apply(..., fwd_done) does the rest.
 // Distributed (chol_distributed): phase 1 -- every rank factors the columns of its own block (leaf sub-trees, then its supernode
 // groups level by level), whose updates into the shared separator columns it collects in its own copy of them; then the shared
 // columns' accumulators -- 64-bit integers: the sum is exact and the same bits on every rank -- and the shared rows of the forward
@@ -1911,97 +1710,69 @@ void chol_scatter(lsfm_context* ctx, const SchurSystem& sy, const unsigned char*
 void chol_factor(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* fixed, CholDev& ch, double* fwd_v)
 {
 	hipStream_t s = ctx->stream;
-	static const bool groups = !getenv("LSFM_NO_GROUPS");
 	const bool dist = chol_distributed(ctx, ch);
 	const OwnFilter mine{ dist ? ch.col_owner : nullptr, dist ? ctx->comm->rank : 0 }, shared{ dist ? ch.col_owner : nullptr, -1 };
-	for (size_t l = 0; l + 1 < ch.tlevel_ptr.size(); l++)
+	if (ch.ntask0)
 	{
-		if (groups && l > 0) break; // the chains above the leaf tasks go by supernode groups below
-		const int n = ch.tlevel_ptr[l + 1] - ch.tlevel_ptr[l];
-		if (!n) continue;
-		static const bool use_small = !getenv("LSFM_NO_SMALL_TASKS");
-		const int nsm = use_small ? ch.tlevel_nsmall[l] : 0;
-		hipLaunchKernelGGL(k_chol_factor_level, dim3(n), dim3(l ? 256 : 128), nsm ? (size_t)ch.tlevel_small_lds[l] : 0, s, nsm, ch.task_ptr + ch.tlevel_ptr[l],
-		                   ch.task_cols, ch.col_nin, ch.colptr, ch.rowidx, ch.L, ch.Dinv, ch.d_err, mine);
-		const int c0 = ch.tlevel_col0[l], nc = ch.tlevel_col0[l + 1] - c0, mp = ch.tlevel_outer[l];
-		if (mp > 0)
+		hipLaunchKernelGGL(k_chol_factor_level, dim3(ch.ntask0), dim3(128), (size_t)ch.task0_lds, s, ch.task_ptr, ch.task_cols, ch.col_nin, ch.colptr, ch.rowidx,
+		                   ch.L, ch.Dinv, ch.d_err, mine);
+		if (ch.task0_outer > 0)
 		{
-			const dim3 grid(nc, std::min((mp + CHOL_OUT_THREADS - 1) / CHOL_OUT_THREADS, 64));
-			if (groups) hipLaunchKernelGGL(k_chol_update_outer<true>, grid, dim3(CHOL_OUT_THREADS), 0, s, ch.task_cols + c0, ch.col_nin, ch.colptr, ch.rowidx, ch.L, mine);
-			else hipLaunchKernelGGL(k_chol_update_outer<false>, grid, dim3(CHOL_OUT_THREADS), 0, s, ch.task_cols + c0, ch.col_nin, ch.colptr, ch.rowidx, ch.L, mine);
+			const dim3 grid(ch.ncol0, std::min((ch.task0_outer + CHOL_OUT_THREADS - 1) / CHOL_OUT_THREADS, 64));
+			hipLaunchKernelGGL(k_chol_update_outer, grid, dim3(CHOL_OUT_THREADS), 0, s, ch.task_cols, ch.col_nin, ch.colptr, ch.rowidx, ch.L, mine);
 		}
-	}
-	if (fwd_v)
-	{
 		// the leaf sub-trees are factored: their part of the forward substitution, before the groups take theirs
-		const int n0 = ch.tlevel_ptr.size() > 1 ? ch.tlevel_ptr[1] - ch.tlevel_ptr[0] : 0;
-		const size_t lds0 = (size_t)ch.tlevel_maxsize[0] * CHOL_TASK_LDS_PER_COL + 8;
-		if (n0) hipLaunchKernelGGL(k_chol_fwd_tasks<double>, dim3(n0), dim3(128), lds0, s, ch.task_ptr + ch.tlevel_ptr[0], ch.task_cols, ch.col_task, ch.col_lpos, ch.tlevel_ptr[0], ch.colptr, ch.rowidx, (const double*)ch.L, (const double*)ch.Dinv, fwd_v, mine);
+		if (fwd_v)
+			hipLaunchKernelGGL(k_chol_fwd_tasks<double>, dim3(ch.ntask0), dim3(128), chol_task_lds(ch), s, ch.task_ptr, ch.task_cols, ch.col_task, ch.col_lpos, 0, ch.colptr,
+			                   ch.rowidx, (const double*)ch.L, (const double*)ch.Dinv, fwd_v, mine);
 	}
-	if (groups)
+	// one launch per group level while the panels are short enough for the fused kernel (pairs of 8-row chunks: a panel of
+	// 64 rows is 36 work-groups per group, each repeating the solve of its two chunks); taller ones take the panel kernel +
+	// the rank-update kernel (a synth-16k Mono tree, whose upper levels have panels of 100-300 rows: 684 ms against 826
+	// with everything fused)
+	static const int fuse_max = getenv("LSFM_SN_FUSE_MAX") ? atoi(getenv("LSFM_SN_FUSE_MAX")) : 96; // (groups of <= 8 columns: 64 -> 96 rows, 9.5 -> 9.2 ms per NC3500 tree; 128 costs synth-16k 143 -> 169 ms)
+	static const double piv_floor = getenv("LSFM_PIVOT_FLOOR") ? atof(getenv("LSFM_PIVOT_FLOOR")) : 1e-13; // (0: none)
+	static const bool lds_set = []() {
+		// (dynamic LDS beyond 64 KB has to be asked for once per kernel)
+		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sn_panel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sn_panel_lds(CHOL_GS));
+		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sn_panel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sn_panel_lds(CHOL_GS));
+		(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sn_syrk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sn_syrk_lds(CHOL_GS));
+		return true;
+	}();
+	(void)lds_set;
+	for (int phase = 0; phase < (dist ? 2 : 1); phase++)
 	{
-		// one launch per group level while the panels are short enough for the fused kernel (pairs of 8-row chunks: a panel of
-		// 64 rows is 36 work-groups per group, each repeating the solve of its two chunks); taller ones take the panel kernel +
-		// the rank-update kernel (a synth-16k Mono tree, whose upper levels have panels of 100-300 rows: 684 ms against 826
-		// with everything fused)
-		static const int fuse_max = getenv("LSFM_SN_FUSE_MAX") ? atoi(getenv("LSFM_SN_FUSE_MAX")) : 96; // (groups of <= 8 columns: 64 -> 96 rows, 9.5 -> 9.2 ms per NC3500 tree; 128 costs synth-16k 143 -> 169 ms)
-		static const double piv_floor = getenv("LSFM_PIVOT_FLOOR") ? atof(getenv("LSFM_PIVOT_FLOOR")) : 1e-13; // (0: none)
-		static const bool lds_set = []() {
-			// (dynamic LDS beyond 64 KB has to be asked for once per kernel)
-			(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sn_panel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sn_panel_lds(CHOL_GS));
-			(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sn_panel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sn_panel_lds(CHOL_GS));
-			(void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sn_syrk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sn_syrk_lds(CHOL_GS));
-			return true;
-		}();
-		(void)lds_set;
-		for (int phase = 0; phase < (dist ? 2 : 1); phase++)
+		const OwnFilter of = phase == 0 ? mine : shared;
+		if (phase == 1)
 		{
-			const OwnFilter of = phase == 0 ? mine : shared;
-			if (phase == 1)
-			{
-				comm_sum(ctx, ch.L + (size_t)ch.shared_blk0 * 36, ((size_t)ch.nnzL - ch.shared_blk0) * 36, LSFM_DTYPE_I64);
-				if (fwd_v) comm_sum(ctx, fwd_v + (size_t)ch.first_shared * 6, ((size_t)ch.M - ch.first_shared) * 6, LSFM_DTYPE_F64);
-			}
-			for (size_t l = 0; l + 1 < ch.glevel_ptr.size(); l++)
-			{
-				const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0, mnr = ch.glevel_maxnr[l];
-				if (!ng) continue;
-				if (dist && !(phase == 0 ? ch.glevel_owned[l] : ch.glevel_shared[l])) continue;
-				const int smax = l < ch.glevel_maxs.size() ? ch.glevel_maxs[l] : CHOL_GS;
-				if (mnr <= fuse_max)
-				{
-					const int nch = (mnr + SN_RB / 2 - 1) / (SN_RB / 2);
-					hipLaunchKernelGGL(k_sn_panel<true>, dim3(ng, std::max(1, nch * (nch + 1) / 2)), dim3(SN_PT), sn_panel_lds(smax), s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0,
-					                   ch.colptr, ch.L, ch.Lg, ch.Dinv, ch.d_err, ch.rowidx, fwd_v, ch.wv, smax, ch.diag0, piv_floor, ctx->d_run ? &ctx->d_run->floored : nullptr, of);
-					continue;
-				}
-				hipLaunchKernelGGL(k_sn_panel<false>, dim3(ng, std::max(1, (mnr + SN_RB - 1) / SN_RB)), dim3(SN_PT), sn_panel_lds(smax), s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0,
-				                   ch.colptr, ch.L, ch.Lg, ch.Dinv, ch.d_err, ch.rowidx, fwd_v, ch.wv, smax, ch.diag0, piv_floor, ctx->d_run ? &ctx->d_run->floored : nullptr, of);
-				static const bool scalar_update = getenv("LSFM_SN_SCALAR_UPDATE") != nullptr; // the round-2 kernel, kept for comparison
-				if (scalar_update)
-				{
-					const long np = (long)mnr * (mnr + 1) / 2;
-					hipLaunchKernelGGL(k_sn_update, dim3(ng, (unsigned)std::max<long>(1, std::min<long>((np + SN_PAIRS - 1) / SN_PAIRS, 4096))), dim3(SN_THREADS), 0, s,
-					                   ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, ch.colptr, ch.rowidx, ch.L, ch.Lg, of);
-				}
-				else
-				{
-					const long nch = (mnr + SN_RB / 2 - 1) / (SN_RB / 2), npair = nch * (nch + 1) / 2;
-					hipLaunchKernelGGL(k_sn_syrk, dim3(ng, (unsigned)std::max<long>(1, std::min<long>(npair, 8192))), dim3(SN_THREADS), sn_syrk_lds(smax), s,
-					                   ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, ch.colptr, ch.rowidx, ch.L, ch.Lg, smax, of);
-				}
-			}
+			comm_sum(ctx, ch.L + (size_t)ch.shared_blk0 * 36, ((size_t)ch.nnzL - ch.shared_blk0) * 36, LSFM_DTYPE_I64);
+			if (fwd_v) comm_sum(ctx, fwd_v + (size_t)ch.first_shared * 6, ((size_t)ch.M - ch.first_shared) * 6, LSFM_DTYPE_F64);
 		}
-		// the solves that walk columns by task or by level read ONE array: give them the group columns there
-		if (ch.ngroups && !chol_group_solve(ch))
-			hipLaunchKernelGGL(k_sn_merge, dim3(ch.ngroups), dim3(256), 0, s, ch.grp_c0, ch.grp_s, ch.colptr, ch.Lg, ch.L);
+		for (size_t l = 0; l + 1 < ch.glevel_ptr.size(); l++)
+		{
+			const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0, mnr = ch.glevel_maxnr[l];
+			if (!ng) continue;
+			if (dist && !(phase == 0 ? ch.glevel_owned[l] : ch.glevel_shared[l])) continue;
+			const int smax = l < ch.glevel_maxs.size() ? ch.glevel_maxs[l] : CHOL_GS;
+			if (mnr <= fuse_max)
+			{
+				const int nch = (mnr + SN_RB / 2 - 1) / (SN_RB / 2);
+				hipLaunchKernelGGL(k_sn_panel<true>, dim3(ng, std::max(1, nch * (nch + 1) / 2)), dim3(SN_PT), sn_panel_lds(smax), s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0,
+				                   ch.colptr, ch.L, ch.Lg, ch.Dinv, ch.d_err, ch.rowidx, fwd_v, ch.wv, smax, ch.diag0, piv_floor, ctx->d_run ? &ctx->d_run->floored : nullptr, of);
+				continue;
+			}
+			hipLaunchKernelGGL(k_sn_panel<false>, dim3(ng, std::max(1, (mnr + SN_RB - 1) / SN_RB)), dim3(SN_PT), sn_panel_lds(smax), s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0,
+			                   ch.colptr, ch.L, ch.Lg, ch.Dinv, ch.d_err, ch.rowidx, fwd_v, ch.wv, smax, ch.diag0, piv_floor, ctx->d_run ? &ctx->d_run->floored : nullptr, of);
+			const long nch = (mnr + SN_RB / 2 - 1) / (SN_RB / 2), npair = nch * (nch + 1) / 2;
+			hipLaunchKernelGGL(k_sn_syrk, dim3(ng, (unsigned)std::max<long>(1, std::min<long>(npair, 8192))), dim3(SN_THREADS), sn_syrk_lds(smax), s,
+			                   ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, ch.colptr, ch.rowidx, ch.L, ch.Lg, smax, of);
+		}
 	}
 }
 
 void chol_merge_groups(lsfm_context* ctx, const CholDev& ch)
 {
-	static const bool groups = !getenv("LSFM_NO_GROUPS");
-	if (groups && ch.ngroups && chol_group_solve(ch))
+	if (ch.ngroups)
 		hipLaunchKernelGGL(k_sn_merge, dim3(ch.ngroups), dim3(256), 0, ctx->stream, ch.grp_c0, ch.grp_s, ch.colptr, ch.Lg, ch.L);
 }
 
@@ -2022,87 +1793,47 @@ static void chol_apply(lsfm_context* ctx, const CholDev& ch, const double* r, do
 {
 	hipStream_t s = ctx->stream;
 	if (!fwd_done) chol_perm_in(ctx, ch, r, fixed, v);
-	static const bool task_solve = !getenv("LSFM_LEVEL_SOLVE");
-	int task_max = 0;
-	for (int m : ch.tlevel_maxsize) task_max = std::max(task_max, m);
-	static const bool group_solve = !getenv("LSFM_NO_GROUPS") && !getenv("LSFM_TASK_SOLVE");
-	const OwnFilter all{};
-	if (task_solve && group_solve && !ch.tlevel_ptr.empty() && (size_t)ch.tlevel_maxsize[0] * CHOL_TASK_LDS_PER_COL <= 56 * 1024)
-	{
-		// leaf sub-trees (task level 0) by task, everything above them by supernode group
-		const int n0 = ch.tlevel_ptr.size() > 1 ? ch.tlevel_ptr[1] - ch.tlevel_ptr[0] : 0;
-		const size_t lds0 = (size_t)ch.tlevel_maxsize[0] * CHOL_TASK_LDS_PER_COL + 8;
-		const int ngl = (int)ch.glevel_ptr.size() - 1;
-		const bool dist = chol_distributed(ctx, ch);
-		const OwnFilter mine{ dist ? ch.col_owner : nullptr, dist ? ctx->comm->rank : 0 }, shared{ dist ? ch.col_owner : nullptr, -1 };
-		// (Lx: the leaf columns' factor, in place in L; Gx: the group columns' factor, in its own array)
-		auto sweep = [&](auto tag, const auto* Lx, const auto* Gx, const auto* Dx) {
-			typedef decltype(tag) FT;
-			if (!fwd_done)
+	// leaf sub-trees (task level 0) by task, everything above them by supernode group
+	const int ngl = (int)ch.glevel_ptr.size() - 1;
+	const bool dist = chol_distributed(ctx, ch);
+	const OwnFilter mine{ dist ? ch.col_owner : nullptr, dist ? ctx->comm->rank : 0 }, shared{ dist ? ch.col_owner : nullptr, -1 };
+	// (Lx: the leaf columns' factor, in place in L; Gx: the group columns' factor, in its own array)
+	auto sweep = [&](auto tag, const auto* Lx, const auto* Gx, const auto* Dx) {
+		typedef decltype(tag) FT;
+		if (!fwd_done)
+		{
+			if (ch.ntask0) hipLaunchKernelGGL(k_chol_fwd_tasks<FT>, dim3(ch.ntask0), dim3(128), chol_task_lds(ch), s, ch.task_ptr, ch.task_cols, ch.col_task, ch.col_lpos, 0, ch.colptr, ch.rowidx, Lx, Dx, v, mine);
+			for (int phase = 0; phase < (dist ? 2 : 1); phase++)
 			{
-				if (n0) hipLaunchKernelGGL(k_chol_fwd_tasks<FT>, dim3(n0), dim3(128), lds0, s, ch.task_ptr + ch.tlevel_ptr[0], ch.task_cols, ch.col_task, ch.col_lpos, ch.tlevel_ptr[0], ch.colptr, ch.rowidx, Lx, Dx, v, mine);
-				for (int phase = 0; phase < (dist ? 2 : 1); phase++)
-				{
-					if (phase == 1) comm_sum(ctx, v + (size_t)ch.first_shared * 6, ((size_t)ch.M - ch.first_shared) * 6, LSFM_DTYPE_F64);
-					for (int l = 0; l < ngl; l++)
-					{
-						const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0;
-						if (!ng || (dist && !(phase == 0 ? ch.glevel_owned[l] : ch.glevel_shared[l]))) continue;
-						hipLaunchKernelGGL(k_sn_fwd<FT>, dim3(ng), dim3(SN_THREADS), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, ch.colptr, ch.rowidx, Gx, Dx, v, ch.wv, phase == 0 ? mine : shared);
-					}
-				}
-			}
-			for (int phase = (dist ? 1 : 0); phase >= 0; phase--) // backward: the shared columns first
-				for (int l = ngl - 1; l >= 0; l--)
+				if (phase == 1) comm_sum(ctx, v + (size_t)ch.first_shared * 6, ((size_t)ch.M - ch.first_shared) * 6, LSFM_DTYPE_F64);
+				for (int l = 0; l < ngl; l++)
 				{
 					const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0;
 					if (!ng || (dist && !(phase == 0 ? ch.glevel_owned[l] : ch.glevel_shared[l]))) continue;
-					hipLaunchKernelGGL(k_sn_bwd<FT>, dim3(ng), dim3(SN_THREADS), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, ch.colptr, ch.rowidx, Gx, Dx, v, ch.wv, (dist && phase == 1) ? shared : mine);
+					hipLaunchKernelGGL(k_sn_fwd<FT>, dim3(ng), dim3(SN_THREADS), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, ch.colptr, ch.rowidx, Gx, Dx, v, ch.wv, phase == 0 ? mine : shared);
 				}
-			if (n0) hipLaunchKernelGGL(k_chol_bwd_tasks<FT>, dim3(n0), dim3(128), lds0, s, ch.task_ptr + ch.tlevel_ptr[0], ch.task_cols, ch.col_task, ch.col_lpos, ch.tlevel_ptr[0], ch.colptr, ch.rowidx, Lx, Dx, v, mine);
-		};
-		if (ch.Lf) sweep(float(), (const float*)ch.Lf, (const float*)ch.Lgf, (const float*)ch.Dinvf); // mixed precision: the factor applied in fp32
-		else sweep(double(), (const double*)ch.L, (const double*)ch.Lg, (const double*)ch.Dinv);
-		if (dist)
-		{
-			hipLaunchKernelGGL(k_perm_out_dot, dim3((ch.M + 127) / 128), dim3(128), 0, s, ch.M, ch.pinv, v, r, fixed, ch.dscale, pose_seg, z, (double*)nullptr, dot_stride,
-			                   ch.col_owner, ctx->comm->rank);
-			ctx->comm->allreduce(s, z, (size_t)ch.M * 6, LSFM_DTYPE_F64);
-			hipLaunchKernelGGL(k_rz_dot, dim3((ch.M + 127) / 128), dim3(128), 0, s, ch.M, z, r, pose_seg, dot, dot_stride);
+			}
 		}
-		else
-			hipLaunchKernelGGL(k_perm_out_dot, dim3((ch.M + 127) / 128), dim3(128), 0, s, ch.M, ch.pinv, v, r, fixed, ch.dscale, pose_seg, z, dot, dot_stride, (const int*)nullptr, 0);
-		return;
-	}
-	if (task_solve && (size_t)task_max * CHOL_TASK_LDS_PER_COL <= 56 * 1024) // a task's per-column data must fit LDS; else one launch per tree level
+		for (int phase = (dist ? 1 : 0); phase >= 0; phase--) // backward: the shared columns first
+			for (int l = ngl - 1; l >= 0; l--)
+			{
+				const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0;
+				if (!ng || (dist && !(phase == 0 ? ch.glevel_owned[l] : ch.glevel_shared[l]))) continue;
+				hipLaunchKernelGGL(k_sn_bwd<FT>, dim3(ng), dim3(SN_THREADS), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, ch.colptr, ch.rowidx, Gx, Dx, v, ch.wv, (dist && phase == 1) ? shared : mine);
+			}
+		if (ch.ntask0) hipLaunchKernelGGL(k_chol_bwd_tasks<FT>, dim3(ch.ntask0), dim3(128), chol_task_lds(ch), s, ch.task_ptr, ch.task_cols, ch.col_task, ch.col_lpos, 0, ch.colptr, ch.rowidx, Lx, Dx, v, mine);
+	};
+	if (ch.Lf) sweep(float(), (const float*)ch.Lf, (const float*)ch.Lgf, (const float*)ch.Dinvf); // mixed precision: the factor applied in fp32
+	else sweep(double(), (const double*)ch.L, (const double*)ch.Lg, (const double*)ch.Dinv);
+	if (dist)
 	{
-		const int ntl = (int)ch.tlevel_ptr.size() - 1;
-		for (int l = 0; l < ntl; l++)
-		{
-			const int n = ch.tlevel_ptr[l + 1] - ch.tlevel_ptr[l];
-			if (n) hipLaunchKernelGGL(k_chol_fwd_tasks<double>, dim3(n), dim3(l ? 256 : 128), (size_t)ch.tlevel_maxsize[l] * CHOL_TASK_LDS_PER_COL + 8, s, ch.task_ptr + ch.tlevel_ptr[l], ch.task_cols, ch.col_task, ch.col_lpos, ch.tlevel_ptr[l], ch.colptr, ch.rowidx, ch.L, ch.Dinv, v, all);
-		}
-		for (int l = ntl - 1; l >= 0; l--)
-		{
-			const int n = ch.tlevel_ptr[l + 1] - ch.tlevel_ptr[l];
-			if (n) hipLaunchKernelGGL(k_chol_bwd_tasks<double>, dim3(n), dim3(l ? 256 : 128), (size_t)ch.tlevel_maxsize[l] * CHOL_TASK_LDS_PER_COL + 8, s, ch.task_ptr + ch.tlevel_ptr[l], ch.task_cols, ch.col_task, ch.col_lpos, ch.tlevel_ptr[l], ch.colptr, ch.rowidx, ch.L, ch.Dinv, v, all);
-		}
+		hipLaunchKernelGGL(k_perm_out_dot, dim3((ch.M + 127) / 128), dim3(128), 0, s, ch.M, ch.pinv, v, r, fixed, ch.dscale, pose_seg, z, (double*)nullptr, dot_stride,
+		                   ch.col_owner, ctx->comm->rank);
+		ctx->comm->allreduce(s, z, (size_t)ch.M * 6, LSFM_DTYPE_F64);
+		hipLaunchKernelGGL(k_rz_dot, dim3((ch.M + 127) / 128), dim3(128), 0, s, ch.M, z, r, pose_seg, dot, dot_stride);
+	}
+	else
 		hipLaunchKernelGGL(k_perm_out_dot, dim3((ch.M + 127) / 128), dim3(128), 0, s, ch.M, ch.pinv, v, r, fixed, ch.dscale, pose_seg, z, dot, dot_stride, (const int*)nullptr, 0);
-		return;
-	}
-	for (int l = 0; l < ch.nlevels; l++)
-	{
-		const int n = ch.level_ptr[l + 1] - ch.level_ptr[l];
-		if (n) hipLaunchKernelGGL(k_chol_fwd_level, dim3(n), dim3(64), 0, s, ch.order + ch.level_ptr[l], ch.colptr, ch.rowidx, ch.L, ch.Dinv, v);
-	}
-	if (ch.M - ch.tail_begin > 0)
-		hipLaunchKernelGGL(k_chol_solve_tail, dim3(1), dim3(256), 0, s, ch.M - ch.tail_begin, ch.order + ch.tail_begin, ch.colptr, ch.rowidx, ch.L, ch.Dinv, v);
-	for (int l = ch.nlevels - 1; l >= 0; l--)
-	{
-		const int n = ch.level_ptr[l + 1] - ch.level_ptr[l];
-		if (n) hipLaunchKernelGGL(k_chol_bwd_level, dim3(n), dim3(64), 0, s, ch.order + ch.level_ptr[l], ch.colptr, ch.rowidx, ch.L, ch.Dinv, v);
-	}
-	hipLaunchKernelGGL(k_perm_out_dot, dim3((ch.M + 127) / 128), dim3(128), 0, s, ch.M, ch.pinv, v, r, fixed, ch.dscale, pose_seg, z, dot, dot_stride, (const int*)nullptr, 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2551,7 +2282,10 @@ small_tail:
 	launch_spmv(ctx, sy, x, Ap, io.d_fixed, nullptr, nullptr, nullptr, 1);
 	hipLaunchKernelGGL(k_pcg_resid, dim3(nbr), dim3(128), 0, s, M, sy.E, Ap, io.d_pose_seg, io.d_fixed, r, seg, 1);
 	const bool mixed = ctx->pcg.mixed;
-	const bool fused_fwd = !mixed && chol_group_solve(ch); // (mixed: the factor is applied from its fp32 copy, made after the factorisation)
+	// (mixed: the factor is applied from its fp32 copy, made after the factorisation; LSFM_NO_FUSED_FWD: the first application too
+	// runs the forward substitution of its own, as every later one does)
+	static const bool no_fused_fwd = getenv("LSFM_NO_FUSED_FWD") != nullptr;
+	const bool fused_fwd = !mixed && !no_fused_fwd && ch.M > 0;
 	if (ctx->stats && chol_distributed(ctx, ch)) { ctx->stats->dist_solves++; ctx->stats->dist_work_total += ch.work_total; ctx->stats->dist_work_shared += ch.work_shared; }
 	chol_scatter(ctx, sy, io.d_fixed, ch);
 	if (fused_fwd) chol_perm_in(ctx, ch, r, io.d_fixed, v);
@@ -2722,8 +2456,8 @@ small_tail:
 	if (dbg)
 	{
 		LSFM_CHECK_HIP(hipStreamSynchronize(s));
-		fprintf(stderr, "[lsfm] solve M=%d nseg=%d nnzb=%d nnzL=%d etree levels=%d tail=%d task levels=%d group levels=%d %s| analyse %.2f ms, factor %.2f ms, cg(%d its) %.2f ms\n", M, nseg,
-		        sy.nnzb, ch.nnzL, ch.nlevels, ch.M - ch.tail_begin, (int)ch.tlevel_ptr.size() - 1, (int)ch.glevel_ptr.size() - 1, warm ? "(plan) " : "", tw1 - tw0, tw2 - tw1, its, wall() - tw2);
+		fprintf(stderr, "[lsfm] solve M=%d nseg=%d nnzb=%d nnzL=%d etree levels=%d tail=%d leaf tasks=%d group levels=%d %s| analyse %.2f ms, factor %.2f ms, cg(%d its) %.2f ms\n", M, nseg,
+		        sy.nnzb, ch.nnzL, ch.nlevels, ch.M - ch.tail_begin, ch.ntask0, (int)ch.glevel_ptr.size() - 1, warm ? "(plan) " : "", tw1 - tw0, tw2 - tw1, its, wall() - tw2);
 	}
 	if (ctx->comm)
 	{

@@ -640,7 +640,10 @@ void chol_symbolic(const unsigned long long* keys, int nnzb, const int* origin, 
 	// ---- tasks.  Sub-trees of at most task_x blocks are walked by one work-group each (task level 0); above them every
 	// chain of the tree (a separator of the dissection: each column the only large child of the next) is one task,
 	// levelled by the chains below it. ----
-	static const int task_x = getenv("LSFM_TASK_X") ? atoi(getenv("LSFM_TASK_X")) : 90;
+	// (LSFM_TASK_X is clamped to [1, CHOL_TASK_X_MAX]: every leaf task then fits LDS whole, lsfm_symbolic.hpp)
+	static const int task_x = std::min(std::max(getenv("LSFM_TASK_X") ? atoi(getenv("LSFM_TASK_X")) : 90, 1), CHOL_TASK_X_MAX);
+	static_assert(CHOL_TASK_X_MAX * CHOL_TASK_LDS_PER_COL + 8 <= CHOL_SOLVE_LDS && (CHOL_TASK_X_MAX + 1) * CHOL_TASK_LDS_PER_COL + 8 > CHOL_SOLVE_LDS &&
+	              CHOL_TASK_X_MAX * (288 + 4) + (5 * CHOL_TASK_X_MAX + 1) * 4 + 16 <= CHOL_FACTOR_LDS, "CHOL_TASK_X_MAX");
 	ch.task_x = task_x;
 	std::vector<int>&size = w.size, &ntc = w.ntc, &topchild = w.topchild, &task = w.task, &tlev = w.tlev;
 	// "size" of a sub-tree = its blocks (pivot blocks included): a leaf task must fit LDS whole (small-task kernels)
@@ -685,7 +688,7 @@ void chol_symbolic(const unsigned long long* keys, int nnzb, const int* origin, 
 	std::vector<long> tblocks(ntasks, 0), tcolsn(ntasks, 0);
 	for (int j = 0; j < M; j++) { tblocks[task[j]] += ccount[j]; tcolsn[task[j]]++; }
 	auto task_lds = [&](int t) { return tblocks[t] * (288 + 4) + (5 * tcolsn[t] + 1) * 4 + 16; };
-	const long small_cap = 60 * 1024;
+	const long small_cap = CHOL_FACTOR_LDS;
 	ch.tlevel_nsmall.assign(ntl, 0);
 	ch.tlevel_small_lds.assign(ntl, 0);
 	{

@@ -14,6 +14,18 @@ namespace lsfm {
  * LSFM_GS=<n <= CHOL_GS> narrows it further (measurements). */
 #define CHOL_GS 8
 
+/* LDS of the leaf tasks (task level 0: sub-trees of at most task_x blocks, each walked whole in LDS by one work-group, lsfm_pcg.hip).
+ * The triangular solves (k_chol_fwd_tasks / k_chol_bwd_tasks) keep per task column its slice of v (6 doubles), its inverse pivot
+ * block (36) and three ints, plus 8 bytes, within CHOL_SOLVE_LDS; the factorisation (k_chol_factor_level) keeps every block of the
+ * task (288 B + a row index) and five ints per column + 1, plus alignment, within CHOL_FACTOR_LDS. */
+#define CHOL_TASK_LDS_PER_COL (6 * 8 + 36 * 8 + 3 * 4)
+#define CHOL_SOLVE_LDS (56 * 1024)
+#define CHOL_FACTOR_LDS (60 * 1024)
+/* the largest LSFM_TASK_X for which every leaf task fits both (it has at most task_x blocks and no more columns than blocks):
+ *   solve:  348 task_x + 8 <= 57344                               ->  task_x <= 164
+ *   factor: 292 task_x + (5 task_x + 1) * 4 + 16 <= 61440         ->  task_x <= 196 */
+#define CHOL_TASK_X_MAX 164
+
 struct CholSymbolic {
 	int M = 0, nnzL = 0, nlevels = 0, tail_begin = 0;
 	// block CSC of L (row indices ascending inside a column, diagonal first), ordering
