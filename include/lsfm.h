@@ -193,6 +193,24 @@ int lsfm_solve_mono(lsfm_context* ctx, double* stVal, const double* eb, const do
  * variable that is not in the global state, a global variable no map holds, a Stereo map that holds the global reference pose). */
 int lsfm_gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, int type, lsfm_map* x, int iters, double* obj, double* gnorm, int* halvings);
 
+/* ---- per-map consistency of a joined map and the robust polish (NO reference counterpart: the reference has no objective to evaluate
+ * and no step -- PARITY UNPINNED; the tests hold both against the CPU checker's F with the local maps' information matrices scaled) ----
+ * chi2[N]: chi^2_k = r_k^T I_k r_k with r_k = x^_k - f_k(x) (angles wrapped) at the global state x, the terms of lsfm_gn_polish's F;
+ * dof[N] (optional, may be NULL): the length of map k's state vector, 6 m_k + 3 n_k.  Same arguments and errors as lsfm_gn_polish; x is
+ * read only.  One work-group per map sums its U, W and V terms in a fixed order (no atomics): the same input gives the same bits. */
+int lsfm_map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, double* chi2, int* dof);
+/* Gauss-Newton polish with whole local maps as the M-estimator's residuals (IRLS).  kind: 0 none (exactly lsfm_gn_polish), 1 Huber,
+ * 2 Cauchy; c > 0 (finite, checked for every kind) the threshold on s_k = chi2_k / dof_k.  Minimises G(x) = sum_k dof_k rho(chi2_k(x) / dof_k):
+ *   Huber  rho(s) = s (s <= c^2),  2 c sqrt(s) - c^2 otherwise;   w = rho'(s) = min(1, c / sqrt(s))
+ *   Cauchy rho(s) = c^2 ln(1 + s / c^2);                          w = rho'(s) = 1 / (1 + s / c^2)
+ * A step solves the Gauss-Newton system with I_k replaced by w_k I_k (w_k at the current state) and takes x += a d, a halved while G
+ * does not fall, exactly as lsfm_gn_polish does with F; the gauge (Mono) is lsfm_gn_polish's.  obj[iters + 1] = G per iterate (kind 0:
+ * F); gnorm[iters + 1] as lsfm_gn_polish, of the weighted gradient; halvings[iters] (may be NULL); chi2[N], weight[N] (each may be
+ * NULL): at the returned state (chi2 bit for bit what lsfm_map_chi2 gives there; kind 0: every weight 1).  Returns as lsfm_gn_polish;
+ * LSFM_ERR_ARG also for an unknown kind or c <= 0 / not finite. */
+int lsfm_gn_polish_robust(lsfm_context* ctx, const lsfm_map* maps, int N, int type, lsfm_map* x, int iters, int kind, double c,
+                          double* obj, double* gnorm, int* halvings, double* chi2, double* weight);
+
 /* ---- marginal covariances of a map (NO reference counterpart: the reference keeps the information matrix and never inverts it) ----
  * Sigma = I^-1 with I = [U W; W^T V] of `map` (any lsfm_map: a downloaded tree result, a checkpoint node, a local map).
  * mono = 0: Stereo, I is used as it is (the map's Ref pose is not in its state).  mono = 1: the gauge of lsfm_solve_mono /

@@ -117,6 +117,8 @@ def lib():
         L.lsfm_symbolic_analyse.argtypes = [C.c_int, ip, ip, ip, C.c_int, ip, ip, ip, C.c_int, ip, dp]
         L.lsfm_inverse_v.argtypes = [vp, dp, C.c_int, C.c_int]
         L.lsfm_gn_polish.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), C.c_int, dp, dp, ip]
+        L.lsfm_gn_polish_robust.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), C.c_int, C.c_int, C.c_double, dp, dp, ip, dp, dp]
+        L.lsfm_map_chi2.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, ip]
         L.lsfm_solve_features.argtypes = [vp, dp, dp, dp, dp, dp, dp, C.c_int, C.c_int, ip, ip]
         L.lsfm_map_covariance.argtypes = [vp, P(LsfmMap), C.c_int, dp, dp, dp, C.c_int, ip]
         L.lsfm_map_covariance_timed.argtypes = [vp, P(LsfmMap), C.c_int, dp, dp, dp, C.c_int, ip, dp]
@@ -135,6 +137,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_tree_download", "lsfm_tree_set_stop_level", "lsfm_tree_node_count", "lsfm_tree_download_node", "lsfm_tree_download_state", "lsfm_tree_set_plans", "lsfm_tree_export_size", "lsfm_tree_export_dev", "lsfm_packed_size",
            "lsfm_tree_upload_dev", "lsfm_tree_reload_dev", "lsfm_tree_set_comm", "lsfm_tree_set_comm_blocks", "lsfm_tree_export_slice_sizes", "lsfm_tree_export_slice_dev",
            "lsfm_tree_free", "lsfm_divide_conquer", "lsfm_read_localmap", "lsfm_read_localmaps", "lsfm_write_localmap", "lsfm_write_mapset", "lsfm_mapset_info", "lsfm_mapset_stamp", "lsfm_read_mapset", "lsfm_save_state_bin", "lsfm_save_state", "lsfm_save_poses", "lsfm_gn_polish",
+           "lsfm_gn_polish_robust", "lsfm_map_chi2",
            "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
            "lsfm_map_covariance", "lsfm_map_covariance_timed",
            "lsfm_save_covariances", "lsfm_read_covariances"]
@@ -192,6 +195,24 @@ def map_to_dict(g: LsfmMap, release=True):
     if release:
         lib().lsfm_map_release(C.byref(g))
     return d
+
+
+def _gn_args(maps, G):
+    """The arguments of the GN entry points: the local maps as lsfm_map views, the global state x (stVal a copy the call may update),
+    and what must stay alive while they are used."""
+    hms = [HostMap(d) for d in maps]
+    arr = (LsfmMap * len(hms))(*[h.c for h in hms])
+    x = LsfmMap()
+    stno = _c(G["stno"], np.int32)
+    st = np.array(np.asarray(G["stVal"], np.float64), copy=True)
+    x.m, x.n, x.Ref, x.FRef = int(G["m"]), int(G["n"]), int(G["Ref"]), int(G.get("FRef", G["Ref"]))
+    x.ScaP, x.Fix, x.Sign = int(G.get("ScaP", 0)), int(G.get("Fix", 0)), int(G.get("Sign", 1))
+    x.stno, x.stVal = _ptr(stno, C.c_int), _ptr(st, C.c_double)
+    org = None
+    if G.get("pose_origin") is not None:
+        org = _c(G["pose_origin"], np.int32)
+        x.pose_origin = _ptr(org, C.c_int)
+    return hms, arr, x, (stno, st, org)
 
 
 class Context:
@@ -390,23 +411,36 @@ class Context:
         """lsfm_gn_polish: `iters` Gauss-Newton steps of the map-joining objective over all local maps from the global state G (a map
         dict: stno, stVal, m, n, Ref; Mono: ScaP, Fix; e.g. what divide_conquer returned).  No reference counterpart (parity unpinned).
         Returns (stVal, obj[iters + 1], gnorm[iters + 1], halvings[iters], rc)."""
-        hms = [HostMap(d) for d in maps]
-        arr = (LsfmMap * len(hms))(*[h.c for h in hms])
-        x = LsfmMap()
-        stno = _c(G["stno"], np.int32)
-        st = np.array(np.asarray(G["stVal"], np.float64), copy=True)
-        x.m, x.n, x.Ref, x.FRef = int(G["m"]), int(G["n"]), int(G["Ref"]), int(G.get("FRef", G["Ref"]))
-        x.ScaP, x.Fix, x.Sign = int(G.get("ScaP", 0)), int(G.get("Fix", 0)), int(G.get("Sign", 1))
-        x.stno, x.stVal = _ptr(stno, C.c_int), _ptr(st, C.c_double)
-        org = None
-        if G.get("pose_origin") is not None:
-            org = _c(G["pose_origin"], np.int32)
-            x.pose_origin = _ptr(org, C.c_int)
+        hms, arr, x, keep = _gn_args(maps, G)
+        st = keep[1]
         obj, gn, hv = np.zeros(iters + 1), np.zeros(iters + 1), np.zeros(max(iters, 1), np.int32)
         rc = lib().lsfm_gn_polish(self._h, arr, len(hms), int(mono), C.byref(x), int(iters), _ptr(obj, C.c_double), _ptr(gn, C.c_double), _ptr(hv, C.c_int))
         if rc < 0:
             self._check(rc, "lsfm_gn_polish")
         return st, obj, gn, hv[:iters], rc
+
+    def map_chi2(self, maps, mono, G):
+        """lsfm_map_chi2: chi^2_k = r_k^T I_k r_k of every local map at the global state G (the terms of gn_polish's objective) and
+        dof_k = 6 m_k + 3 n_k.  Deterministic.  No reference counterpart.  Returns (chi2 [N], dof [N])."""
+        hms, arr, x, keep = _gn_args(maps, G)
+        chi2, dof = np.zeros(len(hms)), np.zeros(len(hms), np.int32)
+        self._check(lib().lsfm_map_chi2(self._h, arr, len(hms), int(mono), C.byref(x), _ptr(chi2, C.c_double), _ptr(dof, C.c_int)), "lsfm_map_chi2")
+        return chi2, dof
+
+    def gn_polish_robust(self, maps, mono, G, iters, kind, c):
+        """lsfm_gn_polish_robust: gn_polish with whole local maps down-weighted by an M-estimator on s_k = chi2_k / dof_k (IRLS);
+        kind 0 none (= gn_polish), 1 / "huber", 2 / "cauchy"; c > 0 the threshold.  No reference counterpart.
+        Returns (stVal, obj[iters + 1] (G per iterate), gnorm[iters + 1], halvings[iters], chi2 [N], weight [N], rc)."""
+        kind = {"none": 0, "huber": 1, "cauchy": 2}.get(kind, kind)
+        hms, arr, x, keep = _gn_args(maps, G)
+        st = keep[1]
+        obj, gn, hv = np.zeros(iters + 1), np.zeros(iters + 1), np.zeros(max(iters, 1), np.int32)
+        chi2, w = np.zeros(len(hms)), np.zeros(len(hms))
+        rc = lib().lsfm_gn_polish_robust(self._h, arr, len(hms), int(mono), C.byref(x), int(iters), int(kind), float(c), _ptr(obj, C.c_double),
+                                         _ptr(gn, C.c_double), _ptr(hv, C.c_int), _ptr(chi2, C.c_double), _ptr(w, C.c_double))
+        if rc < 0:
+            self._check(rc, "lsfm_gn_polish_robust")
+        return st, obj, gn, hv[:iters], chi2, w, rc
 
     def inverse_v(self, V):
         """lsfm_inverse_v (the reference's pba_inverseV, Imp.cpp:3022): V^-1 of the 3x3 feature blocks, [n, 9]."""

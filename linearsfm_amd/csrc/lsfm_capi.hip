@@ -873,7 +873,21 @@ int lsfm_solve_mono(lsfm_context* ctx, double* stVal, const double* eb, const do
 int lsfm_gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, int type, lsfm_map* x, int iters, double* obj, double* gnorm, int* halvings)
 {
 	if (!maps || N <= 0 || !x || iters < 0 || !obj || !gnorm || (type != 0 && type != 1)) return LSFM_ERR_ARG;
-	return guarded(ctx, [&]() { return gn_polish(ctx, maps, N, type == 1, x, iters, obj, gnorm, halvings); });
+	return guarded(ctx, [&]() { return gn_polish(ctx, maps, N, type == 1, x, iters, 0, 1.0, obj, gnorm, halvings, nullptr, nullptr); });
+}
+
+int lsfm_gn_polish_robust(lsfm_context* ctx, const lsfm_map* maps, int N, int type, lsfm_map* x, int iters, int kind, double c, double* obj,
+                          double* gnorm, int* halvings, double* chi2, double* weight)
+{
+	if (!maps || N <= 0 || !x || iters < 0 || !obj || !gnorm || (type != 0 && type != 1) || kind < 0 || kind > 2 || !(c > 0.0) || !std::isfinite(c))
+		return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() { return gn_polish(ctx, maps, N, type == 1, x, iters, kind, c, obj, gnorm, halvings, chi2, weight); });
+}
+
+int lsfm_map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, double* chi2, int* dof)
+{
+	if (!maps || N <= 0 || !x || !chi2 || (type != 0 && type != 1)) return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() { return map_chi2(ctx, maps, N, type == 1, x, chi2, dof); });
 }
 
 int lsfm_map_covariance_timed(lsfm_context* ctx, const lsfm_map* map, int mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb,

@@ -9,7 +9,10 @@
 // -cache <file> (binary cache of the set: read instead of the text files when it holds -num maps of -type, written after the text files
 // were parsed otherwise), -fullbin <file> (final state as raw doubles), -json <file> (the run's lsfm_stats and phase times as one JSON object),
 // -gn <steps> (Gauss-Newton polish of the map-joining objective from the tree's result: lsfm_gn_polish; no reference counterpart),
-// -cov <file> / -covf <file> (marginal covariances of the final map's poses / features: lsfm_map_covariance; no reference counterpart).
+// -cov <file> / -covf <file> (marginal covariances of the final map's poses / features: lsfm_map_covariance; no reference counterpart),
+// -robust huber|cauchy <c> (-gn uses lsfm_gn_polish_robust: whole local maps down-weighted by an M-estimator on chi2_k / dof_k),
+// -chi2 <file> (per local map, in input order, "index dof chi2 weight" at the final state: lsfm_map_chi2; no reference counterpart).
+#include <cmath>
 #include <chrono>
 #include <sys/stat.h>
 #include <cstdio>
@@ -33,13 +36,16 @@ static void print_help()
 	printf("Data Type Listed As Following:\n");
 	printf("			I  : Monocular\n");
 	printf("			II : Stereo\n");
+	printf("-robust huber|cauchy <c>	With -gn: Down-Weight Inconsistent Local Maps (Threshold c On chi2 / dof)\n");
+	printf("-chi2 <file>		Save chi2 Of Every Local Map: index dof chi2 weight\n");
 	printf("\n");
 }
 
 int main(int argc, char** argv)
 {
-	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf;
-	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0;
+	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err;
+	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0;
+	double robust_c = 0.0;
 	bool has_path = false, has_num = false;
 	double tol = 0;
 	for (int i = 1; i < argc; i++)
@@ -75,12 +81,24 @@ int main(int argc, char** argv)
 		else if (name == "gn") gn = atoi(next());
 		else if (name == "cov") cov = next();
 		else if (name == "covf") covf = next();
+		else if (name == "chi2") chi2f = next();
+		else if (name == "robust")
+		{
+			const std::string k = next(), v = next();
+			char* end = nullptr;
+			robust_c = strtod(v.c_str(), &end);
+			robust = k == "huber" ? 1 : (k == "cauchy" ? 2 : 0);
+			if (!robust) robust_err = "-robust: the kind must be huber or cauchy (got '" + k + "')";
+			else if (v.empty() || *end || !std::isfinite(robust_c) || robust_c <= 0) robust_err = "-robust " + k + " <c>: c must be a positive number (got '" + v + "')";
+		}
 	}
 	if (!has_path) { printf("LinerSFM Error: Please Input Right File Path:\n"); return 0; }
 	if (!has_num) { printf("LinerSFM Error: Please Set Local Map Number:\n"); return 0; }
 	if (type < 0) { printf("LinerSFM Error: Please Set Data Type:\n"); return 0; }
 	if (num <= 0) { fprintf(stderr, "LinearSFM: -num must be positive (got %d)\n", num); return 1; }
 	if ((levels > 0) != !nodes.empty() || levels < 0) { fprintf(stderr, "LinearSFM: -levels <L > 0> and -nodes <dir> go together\n"); return 1; }
+	if (!robust_err.empty()) { fprintf(stderr, "LinearSFM: %s\n", robust_err.c_str()); return 1; }
+	if (robust && gn <= 0) { fprintf(stderr, "LinearSFM: -robust applies to -gn <steps>: give -gn too\n"); return 1; }
 
 	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double w0 = now();
@@ -209,6 +227,7 @@ int main(int argc, char** argv)
 		fprintf(stderr, "LinearSFM: WARNING: %d camera system(s) not solved to the residual of a direct solve (max relative residual %.3e)\n",
 		        stats.not_converged, stats.max_rel_residual);
 	printf("Total Used Time:  %lf  sec\n\n", stats.t_total_ms * 1e-3); // Imp.cpp:2072
+	std::vector<double> chi2v, weightv; // -robust: per-map chi2 and weights at the polished state
 	if (gn > 0)
 	{
 		// -gn <steps>: Gauss-Newton polish of the map-joining objective over all local maps, from the tree's result (lsfm_gn_polish; the
@@ -216,7 +235,9 @@ int main(int argc, char** argv)
 		std::vector<double> obj(gn + 1), gnorm(gn + 1);
 		std::vector<int> halv(gn);
 		const double g0 = now();
-		const int grc = lsfm_gn_polish(ctx, maps.data(), num, type, &out, gn, obj.data(), gnorm.data(), halv.data());
+		if (robust) { chi2v.resize(num); weightv.resize(num); }
+		const int grc = robust ? lsfm_gn_polish_robust(ctx, maps.data(), num, type, &out, gn, robust, robust_c, obj.data(), gnorm.data(), halv.data(), chi2v.data(), weightv.data())
+		                       : lsfm_gn_polish(ctx, maps.data(), num, type, &out, gn, obj.data(), gnorm.data(), halv.data());
 		if (grc < 0) { fprintf(stderr, "LinearSFM: %s\n", lsfm_last_error(ctx)); return 3; }
 		if (!quiet)
 		{
@@ -266,6 +287,26 @@ int main(int argc, char** argv)
 			fclose(f);
 		}
 		else fprintf(stderr, "LinearSFM: cannot write %s\n", json.c_str());
+	}
+	if (!chi2f.empty())
+	{
+		// per-map chi2 of the state the files above hold (-robust: the polish's own, with its weights; otherwise weight 1)
+		std::vector<int> dof(num);
+		if (chi2v.empty())
+		{
+			chi2v.resize(num);
+			weightv.assign(num, 1.0);
+			if (lsfm_map_chi2(ctx, maps.data(), num, type, &out, chi2v.data(), dof.data()) < 0) { fprintf(stderr, "LinearSFM: chi2: %s\n", lsfm_last_error(ctx)); return 3; }
+		}
+		else
+			for (int k = 0; k < num; k++) dof[k] = 6 * maps[k].m + 3 * maps[k].n;
+		FILE* f = fopen(chi2f.c_str(), "w");
+		if (f)
+		{
+			for (int k = 0; k < num; k++) fprintf(f, "%d %d %.17g %.17g\n", k + 1, dof[k], chi2v[k], weightv[k]);
+			fclose(f);
+		}
+		else fprintf(stderr, "LinearSFM: cannot write %s\n", chi2f.c_str());
 	}
 	if (want_stats)
 		fprintf(stderr, "lsfm_e2e: read %.3f s, context %.3f s, upload %.3f s, join tree %.3f s, download %.3f s, write %.3f s\n", w1 - w0, w2 - w1, w3 - w2,

@@ -41,6 +41,7 @@ struct GnMap {
 	int fix;       // Mono: Fix_k
 	int p0, m, f0, n, u0, nu; // its poses / features / U blocks in the uploaded batch
 	int ubase;     // its first block in the joint U: nh * m blocks (a, h_s), nh (nh + 1) / 2 blocks (h_s, h_t), nu own blocks
+	double w;      // weight of the map's information matrix in the step (1 unless the robust polish re-weights it: k_gn_robust_weights)
 	// the frame at the current state (k_gn_hubs)
 	double R[9], dRA[9], dRB[9], dRG[9], t[3];
 	double Scale, Scale2, dSdt[3], dSdtt[3], dSdA, dSdB, dSdG; // (row Fix_k of the reference's dSdt / dSdtt, component Fix_k of dSdA..)
@@ -205,6 +206,8 @@ k_gn_ublocks(int NU, int P, const int* __restrict__ Ui, const int* __restrict__ 
 	const GnMap& t = gm[pose_map[a]];
 	double Ub[36], X[36], Y[36];
 	ld<36>(Ub, U + (size_t)i * 36);
+#pragma unroll
+	for (int q = 0; q < 36; q++) Ub[q] *= t.w;
 	for (int s = 0; s < 2; s++)
 	{
 		ld<36>(X, Cp + (size_t)s * P * 36 + (size_t)b * 36);
@@ -269,6 +272,8 @@ k_gn_features(int NF, int P, const int* __restrict__ feat_map, const GnMap* __re
 		}
 	}
 	ld<9>(Vb, V + (size_t)fc * 9);
+#pragma unroll
+	for (int q = 0; q < 9; q++) Vb[q] *= t.w;
 	double gfv[3], Gf[NH][18];
 	mm<3, 3, 1, false>(Vb, rf, gfv);
 #pragma unroll
@@ -285,6 +290,8 @@ k_gn_features(int NF, int P, const int* __restrict__ feat_map, const GnMap* __re
 		const int a = photo[j];
 		double Wb[18], pc[GN_GW];
 		ld<18>(Wb, W + (size_t)j * 18);
+#pragma unroll
+		for (int q = 0; q < 18; q++) Wb[q] *= t.w;
 		{
 			double ra[6], T[18], Da[36];
 			ld<6>(ra, rp + (size_t)a * 6);
@@ -454,6 +461,113 @@ __global__ void k_gn_gather_pose(int M, const int* __restrict__ sptr, const int*
 	st<6>(ea + (size_t)g * 6, e);
 }
 
+// ---- per-map chi^2 and the robust weights (lsfm_map_chi2, lsfm_gn_polish_robust) ----
+// chi2_k = r_k^T I_k r_k = sum_U (2 - delta_ab) r_a^T U_ab r_b + 2 sum_W r_a^T W_af r_f + sum_f r_f^T V_f r_f over map k's own blocks, at
+// the frames of k_gn_hubs and the pose residuals of k_gn_poses.  One work-group per map: its lanes stride over the map's U blocks and its
+// features (each with its run of W), every lane sums in a fixed order, then the wave sums and a fixed-order sum over the waves in LDS --
+// no atomics, so the same state gives the same bits.  256 lanes: a map of the NC3500-like set holds 520-763 W blocks (one per feature),
+// one of the RS468-like set 1200-1882 over 600-941 features -- two to four features per lane.  The feature residual is recomputed here
+// (f = R (x_f - t) / Scale, as gn_trans forms it): k_gn_features, which forms it too, runs after the weights that need chi2 are set.
+#define GN_CHI2_LANES 256
+__global__ void __launch_bounds__(GN_CHI2_LANES)
+k_gn_map_chi2(const GnMap* __restrict__ gm, const double* __restrict__ U, const int* __restrict__ Ui, const int* __restrict__ Uj,
+              const double* __restrict__ rp, const int* __restrict__ gf, const double* __restrict__ xf, const double* __restrict__ fhat,
+              const int* __restrict__ fptr, const int* __restrict__ photo, const double* __restrict__ W, const double* __restrict__ V,
+              double* __restrict__ chi2)
+{
+	__shared__ double part[GN_CHI2_LANES / LSFM_WAVE];
+	const int k = blockIdx.x;
+	const GnMap& t = gm[k];
+	double acc = 0.0;
+	for (int i = t.u0 + (int)threadIdx.x; i < t.u0 + t.nu; i += GN_CHI2_LANES)
+	{
+		const int a = Ui[i], b = Uj[i];
+		double Ub[36], ra[6], rb[6], y[6];
+		ld<36>(Ub, U + (size_t)i * 36);
+		ld<6>(ra, rp + (size_t)a * 6);
+		ld<6>(rb, rp + (size_t)b * 6);
+		mm<6, 6, 1, false>(Ub, rb, y);
+		double d = 0.0;
+#pragma unroll
+		for (int q = 0; q < 6; q++) d += ra[q] * y[q];
+		acc += a == b ? d : 2.0 * d;
+	}
+	for (int f = t.f0 + (int)threadIdx.x; f < t.f0 + t.n; f += GN_CHI2_LANES)
+	{
+		const double* xn = xf + (size_t)gf[f] * 3;
+		double t222[3] = { xn[0] - t.t[0], xn[1] - t.t[1], xn[2] - t.t[2] }, t22[3], rf[3], Vb[9], y[3];
+		mv3(t.R, t222, t22);
+#pragma unroll
+		for (int r = 0; r < 3; r++) rf[r] = fhat[(size_t)f * 3 + r] - t22[r] / t.Scale;
+		ld<9>(Vb, V + (size_t)f * 9);
+		mm<3, 3, 1, false>(Vb, rf, y);
+		double d = rf[0] * y[0] + rf[1] * y[1] + rf[2] * y[2];
+		for (int j = fptr[f]; j < fptr[f + 1]; j++)
+		{
+			double Wb[18], ra[6], z[6];
+			ld<18>(Wb, W + (size_t)j * 18);
+			ld<6>(ra, rp + (size_t)photo[j] * 6);
+			mm<6, 3, 1, false>(Wb, rf, z);
+			double e = 0.0;
+#pragma unroll
+			for (int q = 0; q < 6; q++) e += ra[q] * z[q];
+			d += 2.0 * e;
+		}
+		acc += d;
+	}
+	acc = wave_sum(acc);
+	if ((threadIdx.x & (LSFM_WAVE - 1)) == 0) part[threadIdx.x / LSFM_WAVE] = acc;
+	__syncthreads();
+	if (threadIdx.x == 0)
+	{
+		double sum = 0.0;
+#pragma unroll
+		for (int w = 0; w < GN_CHI2_LANES / LSFM_WAVE; w++) sum += part[w];
+		chi2[k] = sum;
+	}
+}
+
+// one work-group: s_k = chi2_k / dof_k, w_k = rho'(s_k) into the maps' frames (the next assembly's weights) and weight[k], and
+// G = sum_k dof_k rho(s_k) summed in a fixed order (lane-strided, wave sums, waves in order).  kind 1 Huber, 2 Cauchy.
+#define GN_WEIGHT_LANES 256
+__global__ void __launch_bounds__(GN_WEIGHT_LANES)
+k_gn_robust_weights(int N, int kind, double c, const int* __restrict__ dof, const double* __restrict__ chi2, GnMap* __restrict__ gm,
+                    double* __restrict__ weight, double* __restrict__ Gsum)
+{
+	__shared__ double part[GN_WEIGHT_LANES / LSFM_WAVE];
+	const double c2 = c * c;
+	double acc = 0.0;
+	for (int k = threadIdx.x; k < N; k += GN_WEIGHT_LANES)
+	{
+		const double n = (double)dof[k], s = chi2[k] / n;
+		double w, rho;
+		if (kind == 1)
+		{
+			const bool in = s <= c2;
+			w = in ? 1.0 : c / sqrt(s);
+			rho = in ? s : 2.0 * c * sqrt(s) - c2;
+		}
+		else
+		{
+			w = 1.0 / (1.0 + s / c2);
+			rho = c2 * log1p(s / c2);
+		}
+		gm[k].w = w;
+		weight[k] = w;
+		acc += n * rho;
+	}
+	acc = wave_sum(acc);
+	if ((threadIdx.x & (LSFM_WAVE - 1)) == 0) part[threadIdx.x / LSFM_WAVE] = acc;
+	__syncthreads();
+	if (threadIdx.x == 0)
+	{
+		double sum = 0.0;
+#pragma unroll
+		for (int w = 0; w < GN_WEIGHT_LANES / LSFM_WAVE; w++) sum += part[w];
+		*Gsum = sum;
+	}
+}
+
 // largest |v| over the scalars that are not fixed, as the bits of a non-negative double (they order like the numbers)
 __global__ void k_gn_maxabs(size_t n, const double* __restrict__ v, const unsigned char* __restrict__ fixed, unsigned long long* out)
 {
@@ -479,21 +593,30 @@ int lab_find(const std::vector<Lab>& t, int id)
 	return (it != t.end() && it->id == id) ? it->idx : -1;
 }
 inline dim3 grid_for(size_t n, int b) { return dim3((unsigned)std::max<size_t>(1, (n + b - 1) / b)); }
-} // namespace
 
-// x: the global state (stno / stVal / m / n, Ref; Mono: ScaP, Fix; optional pose_origin); stVal is updated in place.
-// obj / gnorm: [iters + 1]; halvings: [iters] or null.  Returns LSFM_OK or LSFM_NOT_CONVERGED (a step's camera system was left above its
-// residual bound); throws Error for invalid input.
-int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_map* x, int iters, double* obj, double* gnorm, int* halvings)
+// what gn_setup leaves on the device for the calls' steps: the uploaded local maps, the joint system's structure, the work arrays
+struct GnCall {
+	int N = 0, M = 0, NFG = 0, P = 0, FI = 0, NUJ = 0, NWJ = 0;
+	size_t RS = 0; // scalars of the global state
+	bool mono = false;
+	DevBatch X;
+	std::vector<int> dof; // 6 m_k + 3 n_k
+	GnMap* d_gm = nullptr;
+	int *d_gp = nullptr, *d_gf = nullptr, *d_wdst = nullptr, *d_fptrJ = nullptr, *d_photoJ = nullptr, *d_fsp = nullptr, *d_fsi = nullptr, *d_psp = nullptr,
+	    *d_psi = nullptr, *d_UiJ = nullptr, *d_UjJ = nullptr, *d_org = nullptr, *d_seg = nullptr, *d_dof = nullptr;
+	unsigned char* d_fixed = nullptr;
+	double *d_x = nullptr, *d_x0 = nullptr, *d_dl = nullptr, *Dp = nullptr, *Cp = nullptr, *rp = nullptr, *Gacc = nullptr, *Hacc = nullptr, *Fsum = nullptr;
+	double *ePinst = nullptr, *Vinst = nullptr, *eFinst = nullptr, *UJ = nullptr, *WJ = nullptr, *VJ = nullptr, *ea = nullptr, *eb = nullptr;
+	double *d_chi2 = nullptr, *d_w = nullptr, *d_G = nullptr;
+	unsigned long long* d_max = nullptr;
+};
+
+// the structure of a call, on the host from the labels, and the upload: which global variable every local one is, where every local
+// block lands in the joint system, the gauge (Mono); the state x goes to d_x.  Throws Error (LSFM_ERR_ARG) for what it cannot place.
+void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, GnCall& c)
 {
-	hipStream_t s = ctx->stream;
-	const int M = x->m, NFG = x->n;
-	// LSFM_GN_TIMING=1: wall clock of the call's parts on stderr (every part ends with a synchronisation of its own)
-	static const bool timing = getenv("LSFM_GN_TIMING") != nullptr;
-	auto wall = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-	const double tw0 = wall();
-	double t_asm = 0.0, t_solve = 0.0;
-	int n_asm = 0, n_solve = 0;
+	const int M = c.M = x->m, NFG = c.NFG = x->n;
+	c.N = N; c.mono = mono;
 	if (M <= 0 || NFG < 0 || !x->stno || !x->stVal) LSFM_FAIL(LSFM_ERR_ARG, "gn polish: the global state is empty");
 	// ---- structure, once per call (host): which global variable every local one is, where every local block lands ----
 	std::vector<Lab> pt(M), ft(NFG);
@@ -505,15 +628,16 @@ int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_ma
 	{
 		size_t P = 0, FI = 0, nW = 0, nU = 0;
 		for (int k = 0; k < N; k++) { P += maps[k].m; FI += maps[k].n; nW += maps[k].nW; nU += maps[k].nU; }
-		need += ((nW + 2 * FI) * 400 + (nU + 3 * P + 3 * (size_t)N) * 800 + (FI + NFG) * 500 + (P + M) * 6000) * 2;
+		need += ((nW + 2 * FI) * 400 + (nU + 3 * P + 3 * (size_t)N) * 800 + (FI + NFG) * 500 + (P + M) * 6000) * 2 + (size_t)N * 64;
 	}
 	ctx->ensure_arenas(need);
 	ctx->arena[0].reset(); ctx->arena[1].reset(); ctx->scratch.reset();
 	Arena& ar = ctx->arena[0];
-	DevBatch X;
+	DevBatch& X = c.X;
 	batch_upload(ctx, ar, maps, N, mono, X);
-	const int P = X.M, FI = X.NF;
+	const int P = c.P = X.M, FI = c.FI = X.NF;
 	std::vector<GnMap> gm(N);
+	c.dof.resize(N);
 	std::vector<int> gp(P), gfi(FI), wdst(FI), origin(M, INT32_MAX);
 	std::vector<int> fcnt(NFG + 1, 0), pcnt(M + 1, 0);
 	int NUJ = 0;
@@ -524,6 +648,8 @@ int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_ma
 		memset(&t, 0, sizeof t);
 		t.p0 = X.pose_off[k]; t.m = L.m; t.f0 = X.feat_off[k]; t.n = L.n; t.u0 = X.u_off[k]; t.nu = L.nU;
 		t.hub[0] = t.hub[1] = -1;
+		t.w = 1.0;
+		if ((c.dof[k] = 6 * L.m + 3 * L.n) <= 0) LSFM_FAIL(LSFM_ERR_ARG, "gn polish: local map " + std::to_string(k + 1) + " is empty");
 		if (!mono && L.Ref == x->Ref) t.nh = 0;
 		else
 		{
@@ -574,7 +700,7 @@ int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_ma
 		if (!pcnt[g + 1]) LSFM_FAIL(LSFM_ERR_ARG, "gn polish: a pose of the global state is in no local map");
 		pcnt[g + 1] += pcnt[g];
 	}
-	const int NWJ = fptrJ[NFG];
+	const int NWJ = c.NWJ = fptrJ[NFG];
 	std::vector<int> photoJ(NWJ), fsrc(FI), psrc(pcnt[M]);
 	{
 		std::vector<int> wcur(fptrJ.begin(), fptrJ.end() - 1), fcur(fcnt.begin(), fcnt.end() - 1), pcur(pcnt.begin(), pcnt.end() - 1);
@@ -620,19 +746,22 @@ int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_ma
 		fixed[(size_t)ps * 6 + x->Fix] = 1;
 	}
 	// ---- device arrays ----
-	const size_t RS = (size_t)M * 6 + (size_t)NFG * 3;
-	GnMap* d_gm = ar.alloc<GnMap>(N);
-	int *d_gp = ar.alloc<int>(P), *d_gf = ar.alloc<int>(FI), *d_wdst = ar.alloc<int>(FI), *d_fptrJ = ar.alloc<int>(NFG + 1), *d_photoJ = ar.alloc<int>(NWJ);
-	int *d_fsp = ar.alloc<int>(NFG + 1), *d_fsi = ar.alloc<int>(FI), *d_psp = ar.alloc<int>(M + 1), *d_psi = ar.alloc<int>(psrc.size());
-	int *d_UiJ = ar.alloc<int>(NUJ), *d_UjJ = ar.alloc<int>(NUJ), *d_org = ar.alloc<int>(M), *d_seg = ar.alloc<int>(M + NFG + 1);
-	unsigned char* d_fixed = mono ? ar.alloc<unsigned char>(RS) : nullptr;
-	double *d_x = ar.alloc<double>(RS), *d_x0 = ar.alloc<double>(RS), *d_dl = ar.alloc<double>(RS);
-	double *Dp = ar.alloc<double>((size_t)P * 36), *Cp = ar.alloc<double>((size_t)P * 72), *rp = ar.alloc<double>((size_t)P * 6);
-	double *Gacc = ar.alloc<double>((size_t)P * GN_GW + (size_t)N * GN_HW + 2), *Hacc = Gacc + (size_t)P * GN_GW, *Fsum = Hacc + (size_t)N * GN_HW;
-	double *ePinst = ar.alloc<double>((size_t)P * 6), *Vinst = ar.alloc<double>((size_t)FI * 9), *eFinst = ar.alloc<double>((size_t)FI * 3);
-	double *UJ = ar.alloc<double>((size_t)NUJ * 36), *WJ = ar.alloc<double>((size_t)NWJ * 18), *VJ = ar.alloc<double>((size_t)NFG * 9);
-	double *ea = ar.alloc<double>((size_t)M * 6), *eb = ar.alloc<double>((size_t)NFG * 3);
-	unsigned long long* d_max = ar.alloc<unsigned long long>(2);
+	const size_t RS = c.RS = (size_t)M * 6 + (size_t)NFG * 3;
+	c.NUJ = NUJ;
+	GnMap* d_gm = c.d_gm = ar.alloc<GnMap>(N);
+	int *d_gp = c.d_gp = ar.alloc<int>(P), *d_gf = c.d_gf = ar.alloc<int>(FI), *d_wdst = c.d_wdst = ar.alloc<int>(FI);
+	int *d_fptrJ = c.d_fptrJ = ar.alloc<int>(NFG + 1), *d_photoJ = c.d_photoJ = ar.alloc<int>(NWJ);
+	int *d_fsp = c.d_fsp = ar.alloc<int>(NFG + 1), *d_fsi = c.d_fsi = ar.alloc<int>(FI), *d_psp = c.d_psp = ar.alloc<int>(M + 1), *d_psi = c.d_psi = ar.alloc<int>(psrc.size());
+	int *d_UiJ = c.d_UiJ = ar.alloc<int>(NUJ), *d_UjJ = c.d_UjJ = ar.alloc<int>(NUJ), *d_org = c.d_org = ar.alloc<int>(M), *d_seg = c.d_seg = ar.alloc<int>(M + NFG + 1);
+	unsigned char* d_fixed = c.d_fixed = mono ? ar.alloc<unsigned char>(RS) : nullptr;
+	c.d_x = ar.alloc<double>(RS); c.d_x0 = ar.alloc<double>(RS); c.d_dl = ar.alloc<double>(RS);
+	c.Dp = ar.alloc<double>((size_t)P * 36); c.Cp = ar.alloc<double>((size_t)P * 72); c.rp = ar.alloc<double>((size_t)P * 6);
+	c.Gacc = ar.alloc<double>((size_t)P * GN_GW + (size_t)N * GN_HW + 2); c.Hacc = c.Gacc + (size_t)P * GN_GW; c.Fsum = c.Hacc + (size_t)N * GN_HW;
+	c.ePinst = ar.alloc<double>((size_t)P * 6); c.Vinst = ar.alloc<double>((size_t)FI * 9); c.eFinst = ar.alloc<double>((size_t)FI * 3);
+	c.UJ = ar.alloc<double>((size_t)NUJ * 36); c.WJ = ar.alloc<double>((size_t)NWJ * 18); c.VJ = ar.alloc<double>((size_t)NFG * 9);
+	c.ea = ar.alloc<double>((size_t)M * 6); c.eb = ar.alloc<double>((size_t)NFG * 3);
+	c.d_max = ar.alloc<unsigned long long>(2);
+	c.d_dof = ar.alloc<int>(N); c.d_chi2 = ar.alloc<double>(N); c.d_w = ar.alloc<double>(N); c.d_G = ar.alloc<double>(1);
 	h2d(ctx, d_gm, gm.data(), gm.size() * sizeof(GnMap));
 	h2d(ctx, d_gp, gp.data(), gp.size() * sizeof(int)); h2d(ctx, d_gf, gfi.data(), gfi.size() * sizeof(int)); h2d(ctx, d_wdst, wdst.data(), wdst.size() * sizeof(int));
 	h2d(ctx, d_fptrJ, fptrJ.data(), fptrJ.size() * sizeof(int)); h2d(ctx, d_photoJ, photoJ.data(), photoJ.size() * sizeof(int));
@@ -641,44 +770,97 @@ int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_ma
 	h2d(ctx, d_UiJ, UiJ.data(), UiJ.size() * sizeof(int)); h2d(ctx, d_UjJ, UjJ.data(), UjJ.size() * sizeof(int));
 	h2d(ctx, d_org, origin.data(), origin.size() * sizeof(int));
 	if (mono) h2d(ctx, d_fixed, fixed.data(), fixed.size());
-	h2d(ctx, d_x, x->stVal, RS * sizeof(double));
+	h2d(ctx, c.d_dof, c.dof.data(), c.dof.size() * sizeof(int));
+	h2d(ctx, c.d_x, x->stVal, RS * sizeof(double));
 	dev_zero(ctx, d_seg, (size_t)(M + NFG + 1) * sizeof(int));
 
-	// F and the step's system at the state in d_x
+}
+
+// the frames of the maps at the state in d_x, the pose residuals r_a with their D_a and C_s,a
+void gn_frames(lsfm_context* ctx, const GnCall& c)
+{
+	hipStream_t s = ctx->stream;
+	hipLaunchKernelGGL(k_gn_hubs, grid_for(c.N, 128), dim3(128), 0, s, c.N, c.d_gm, c.d_x);
+	hipLaunchKernelGGL(k_gn_poses, grid_for(c.P, 128), dim3(128), 0, s, c.P, c.X.pose_map, c.d_gm, c.d_gp, c.d_x, c.X.pose, c.Dp, c.Cp, c.rp);
+}
+
+// chi2_k of every map into d_chi2 (after gn_frames)
+void gn_chi2(lsfm_context* ctx, const GnCall& c)
+{
+	hipLaunchKernelGGL(k_gn_map_chi2, dim3(c.N), dim3(GN_CHI2_LANES), 0, ctx->stream, c.d_gm, c.X.U, c.X.Ui, c.X.Uj, c.rp, c.d_gf,
+	                   c.d_x + (size_t)c.M * 6, c.X.feat, c.X.fptr, c.X.photo, c.X.W, c.X.V, c.d_chi2);
+}
+} // namespace
+
+// x: the global state (stno / stVal / m / n, Ref; Mono: ScaP, Fix; optional pose_origin); stVal is updated in place.
+// kind: 0 the plain polish (F, every weight 1: no chi^2 is formed during the steps), 1 Huber, 2 Cauchy on s_k = chi2_k / dof_k with
+// threshold c (IRLS: every assembly forms chi2, the weights w_k = rho'(s_k) and G first, then the system with w_k I_k).
+// obj / gnorm: [iters + 1]; halvings: [iters] or null; chi2 / weight: [N] or null, at the returned state.  Returns LSFM_OK or
+// LSFM_NOT_CONVERGED (a step's camera system was left above its residual bound); throws Error for invalid input.
+int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_map* x, int iters, int kind, double cth, double* obj, double* gnorm,
+              int* halvings, double* chi2, double* weight)
+{
+	hipStream_t s = ctx->stream;
+	// LSFM_GN_TIMING=1: wall clock of the call's parts on stderr (every part ends with a synchronisation of its own)
+	static const bool timing = getenv("LSFM_GN_TIMING") != nullptr;
+	auto wall = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+	const double tw0 = wall();
+	double t_asm = 0.0, t_solve = 0.0, t_chi2 = 0.0;
+	int n_asm = 0, n_solve = 0;
+	GnCall c;
+	gn_setup(ctx, maps, N, mono, x, c);
+	const int M = c.M, NFG = c.NFG, P = c.P, FI = c.FI;
+	const size_t RS = c.RS;
+	const DevBatch& X = c.X;
+	const bool robust = kind != 0;
+
+	// F (robust: G) and the step's system at the state in d_x
 	auto assemble = [&]() -> double {
 		const double ta = wall();
-		dev_zero(ctx, Gacc, ((size_t)P * GN_GW + (size_t)N * GN_HW + 2) * sizeof(double));
-		hipLaunchKernelGGL(k_gn_hubs, grid_for(N, 128), dim3(128), 0, s, N, d_gm, d_x);
-		hipLaunchKernelGGL(k_gn_poses, grid_for(P, 128), dim3(128), 0, s, P, X.pose_map, d_gm, d_gp, d_x, X.pose, Dp, Cp, rp);
-		if (X.NU) hipLaunchKernelGGL(k_gn_ublocks, grid_for(X.NU, 128), dim3(128), 0, s, X.NU, P, X.Ui, X.Uj, X.U, X.pose_map, d_gm, d_gp, Dp, Cp, rp, Gacc, UJ);
+		dev_zero(ctx, c.Gacc, ((size_t)P * GN_GW + (size_t)N * GN_HW + 2) * sizeof(double));
+		gn_frames(ctx, c);
+		if (robust)
+		{
+			if (timing) LSFM_CHECK_HIP(hipEventRecord(ctx->ev0, s));
+			gn_chi2(ctx, c);
+			hipLaunchKernelGGL(k_gn_robust_weights, dim3(1), dim3(GN_WEIGHT_LANES), 0, s, N, kind, cth, c.d_dof, c.d_chi2, c.d_gm, c.d_w, c.d_G);
+			if (timing) LSFM_CHECK_HIP(hipEventRecord(ctx->ev1, s));
+		}
+		if (X.NU) hipLaunchKernelGGL(k_gn_ublocks, grid_for(X.NU, 128), dim3(128), 0, s, X.NU, P, X.Ui, X.Uj, X.U, X.pose_map, c.d_gm, c.d_gp, c.Dp, c.Cp, c.rp, c.Gacc, c.UJ);
 		if (FI)
 		{
-			if (mono) hipLaunchKernelGGL((k_gn_features<2>), grid_for(FI, 256), dim3(256), 0, s, FI, P, X.feat_map, d_gm, d_gf, d_x + (size_t)M * 6, X.feat, X.fptr, X.photo, X.W, X.V, Dp, Cp, rp, d_wdst, WJ, Vinst, eFinst, Gacc, Hacc);
-			else hipLaunchKernelGGL((k_gn_features<1>), grid_for(FI, 256), dim3(256), 0, s, FI, P, X.feat_map, d_gm, d_gf, d_x + (size_t)M * 6, X.feat, X.fptr, X.photo, X.W, X.V, Dp, Cp, rp, d_wdst, WJ, Vinst, eFinst, Gacc, Hacc);
+			if (mono) hipLaunchKernelGGL((k_gn_features<2>), grid_for(FI, 256), dim3(256), 0, s, FI, P, X.feat_map, c.d_gm, c.d_gf, c.d_x + (size_t)M * 6, X.feat, X.fptr, X.photo, X.W, X.V, c.Dp, c.Cp, c.rp, c.d_wdst, c.WJ, c.Vinst, c.eFinst, c.Gacc, c.Hacc);
+			else hipLaunchKernelGGL((k_gn_features<1>), grid_for(FI, 256), dim3(256), 0, s, FI, P, X.feat_map, c.d_gm, c.d_gf, c.d_x + (size_t)M * 6, X.feat, X.fptr, X.photo, X.W, X.V, c.Dp, c.Cp, c.rp, c.d_wdst, c.WJ, c.Vinst, c.eFinst, c.Gacc, c.Hacc);
 		}
-		hipLaunchKernelGGL(k_gn_pose_post, grid_for(P, 128), dim3(128), 0, s, P, X.pose_map, d_gm, d_gp, Dp, Cp, rp, Gacc, UJ, ePinst, Hacc);
-		hipLaunchKernelGGL(k_gn_hubhub, grid_for(N, 128), dim3(128), 0, s, N, d_gm, Hacc, UJ, Fsum);
-		if (NFG) hipLaunchKernelGGL(k_gn_gather_feat, grid_for(NFG, 256), dim3(256), 0, s, NFG, d_fsp, d_fsi, Vinst, eFinst, VJ, eb);
-		hipLaunchKernelGGL(k_gn_gather_pose, grid_for(M, 128), dim3(128), 0, s, M, d_psp, d_psi, ePinst, Hacc, ea);
+		hipLaunchKernelGGL(k_gn_pose_post, grid_for(P, 128), dim3(128), 0, s, P, X.pose_map, c.d_gm, c.d_gp, c.Dp, c.Cp, c.rp, c.Gacc, c.UJ, c.ePinst, c.Hacc);
+		hipLaunchKernelGGL(k_gn_hubhub, grid_for(N, 128), dim3(128), 0, s, N, c.d_gm, c.Hacc, c.UJ, c.Fsum);
+		if (NFG) hipLaunchKernelGGL(k_gn_gather_feat, grid_for(NFG, 256), dim3(256), 0, s, NFG, c.d_fsp, c.d_fsi, c.Vinst, c.eFinst, c.VJ, c.eb);
+		hipLaunchKernelGGL(k_gn_gather_pose, grid_for(M, 128), dim3(128), 0, s, M, c.d_psp, c.d_psi, c.ePinst, c.Hacc, c.ea);
 		double F = 0.0;
-		d2h(ctx, &F, Fsum, sizeof(double));
+		d2h(ctx, &F, robust ? c.d_G : c.Fsum, sizeof(double));
+		if (robust && timing)
+		{
+			float ms = 0.0f;
+			LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+			t_chi2 += ms;
+		}
 		t_asm += wall() - ta; n_asm++;
 		return F;
 	};
 	auto grad_norm = [&]() -> double {
-		dev_zero(ctx, d_max, 2 * sizeof(unsigned long long));
-		hipLaunchKernelGGL(k_gn_maxabs, dim3(256), dim3(256), 0, s, (size_t)M * 6, ea, d_fixed, d_max);
-		if (NFG) hipLaunchKernelGGL(k_gn_maxabs, dim3(256), dim3(256), 0, s, (size_t)NFG * 3, eb, (const unsigned char*)nullptr, d_max);
+		dev_zero(ctx, c.d_max, 2 * sizeof(unsigned long long));
+		hipLaunchKernelGGL(k_gn_maxabs, dim3(256), dim3(256), 0, s, (size_t)M * 6, c.ea, c.d_fixed, c.d_max);
+		if (NFG) hipLaunchKernelGGL(k_gn_maxabs, dim3(256), dim3(256), 0, s, (size_t)NFG * 3, c.eb, (const unsigned char*)nullptr, c.d_max);
 		double v = 0.0;
-		d2h(ctx, &v, d_max, sizeof(double));
+		d2h(ctx, &v, c.d_max, sizeof(double));
 		return v;
 	};
 	SolveIO io;
-	io.M = M; io.NF = NFG; io.NU = NUJ; io.NW = NWJ; io.nseg = 1;
-	io.d_pose_seg = d_seg; io.d_feat_seg = d_seg + M;
-	io.U = UJ; io.Ui = d_UiJ; io.Uj = d_UjJ; io.W = WJ; io.photo = d_photoJ; io.fptr = d_fptrJ; io.V = VJ;
-	io.ea = ea; io.eb = eb; io.x_pose = d_dl; io.x_feat = d_dl + (size_t)M * 6;
-	io.d_fixed = d_fixed; io.d_pose_origin = d_org;
+	io.M = M; io.NF = NFG; io.NU = c.NUJ; io.NW = c.NWJ; io.nseg = 1;
+	io.d_pose_seg = c.d_seg; io.d_feat_seg = c.d_seg + M;
+	io.U = c.UJ; io.Ui = c.d_UiJ; io.Uj = c.d_UjJ; io.W = c.WJ; io.photo = c.d_photoJ; io.fptr = c.d_fptrJ; io.V = c.VJ;
+	io.ea = c.ea; io.eb = c.eb; io.x_pose = c.d_dl; io.x_feat = c.d_dl + (size_t)M * 6;
+	io.d_fixed = c.d_fixed; io.d_pose_origin = c.d_org;
 	io.seg_rows.assign(1, M);
 
 	int ret = LSFM_OK;
@@ -700,31 +882,54 @@ int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_ma
 		t_solve += wall() - ts; n_solve++;
 		ctx->scratch.release(smark);
 		if (rc) ret = LSFM_NOT_CONVERGED;
-		LSFM_CHECK_HIP(hipMemcpyAsync(d_x0, d_x, RS * sizeof(double), hipMemcpyDeviceToDevice, s));
+		LSFM_CHECK_HIP(hipMemcpyAsync(c.d_x0, c.d_x, RS * sizeof(double), hipMemcpyDeviceToDevice, s));
 		double alpha = 1.0, F1 = 0.0;
 		int h = 0;
 		for (; h <= 8; h++, alpha *= 0.5)
 		{
-			hipLaunchKernelGGL(k_gn_step, grid_for(RS, 256), dim3(256), 0, s, RS, d_x0, d_dl, alpha, d_fixed, d_x);
+			hipLaunchKernelGGL(k_gn_step, grid_for(RS, 256), dim3(256), 0, s, RS, c.d_x0, c.d_dl, alpha, c.d_fixed, c.d_x);
 			F1 = assemble(); // (the system at the new state: the next step's, when this one is taken)
 			if (F1 <= F + 1e-12 * fabs(F)) break; // (at the minimiser two evaluations differ by their rounding)
 		}
 		if (h > 8)
 		{
 			// no decrease along the step: the state stays where it was, the run ends
-			LSFM_CHECK_HIP(hipMemcpyAsync(d_x, d_x0, RS * sizeof(double), hipMemcpyDeviceToDevice, s));
+			LSFM_CHECK_HIP(hipMemcpyAsync(c.d_x, c.d_x0, RS * sizeof(double), hipMemcpyDeviceToDevice, s));
 			F = assemble();
 			stopped = true;
 		}
 		else F = F1;
 		if (halvings) halvings[it] = h > 8 ? 9 : h;
 	}
-	d2h(ctx, x->stVal, d_x, RS * sizeof(double));
+	d2h(ctx, x->stVal, c.d_x, RS * sizeof(double));
+	// chi2 / weights at the returned state: the last assembly's (robust), or formed once now from its frames and residuals (plain)
+	if (chi2)
+	{
+		if (!robust) gn_chi2(ctx, c);
+		d2h(ctx, chi2, c.d_chi2, (size_t)N * sizeof(double));
+	}
+	if (weight)
+	{
+		if (robust) d2h(ctx, weight, c.d_w, (size_t)N * sizeof(double));
+		else std::fill(weight, weight + N, 1.0);
+	}
 	if (timing)
-		fprintf(stderr, "lsfm_gn: %d maps, %d poses, %d features, joint system %d U / %d W blocks; structure + upload %.2f ms, %d assemblies %.2f ms each, "
-		                "%d solves %.2f ms each, call %.2f ms\n", N, M, NFG, NUJ, NWJ, tw1 - tw0, n_asm, n_asm ? t_asm / n_asm : 0.0, n_solve,
-		        n_solve ? t_solve / n_solve : 0.0, wall() - tw0);
+		fprintf(stderr, "lsfm_gn: %d maps, %d poses, %d features, joint system %d U / %d W blocks; structure + upload %.2f ms, %d assemblies %.2f ms each "
+		                "(chi2 + weights %.3f ms each), %d solves %.2f ms each, call %.2f ms\n", N, M, NFG, c.NUJ, c.NWJ, tw1 - tw0, n_asm,
+		        n_asm ? t_asm / n_asm : 0.0, n_asm ? t_chi2 / n_asm : 0.0, n_solve, n_solve ? t_solve / n_solve : 0.0, wall() - tw0);
 	return ret;
+}
+
+// chi2_k of every local map at the global state x (x is read only); dof (may be null) = 6 m_k + 3 n_k
+int map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, double* chi2, int* dof)
+{
+	GnCall c;
+	gn_setup(ctx, maps, N, mono, x, c);
+	gn_frames(ctx, c);
+	gn_chi2(ctx, c);
+	d2h(ctx, chi2, c.d_chi2, (size_t)N * sizeof(double));
+	if (dof) std::copy(c.dof.begin(), c.dof.end(), dof);
+	return LSFM_OK;
 }
 
 } // namespace lsfm

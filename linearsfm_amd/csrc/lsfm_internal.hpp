@@ -467,7 +467,10 @@ int small_solve_strips(int most_poses, int cap); // 16-row strips of the dense p
 void small_solve_launch(lsfm_context* ctx, const SolveIO& io, int strips, int* status, double* max_rel);
 int solve_batch(lsfm_context* ctx, const SolveIO& io);
 // Gauss-Newton polish of the map-joining objective over all local maps at once (lsfm_gn.hip; C ABI: lsfm_gn_polish)
-int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_map* x, int iters, double* obj, double* gnorm, int* halvings);
+int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_map* x, int iters, int kind, double c, double* obj, double* gnorm,
+              int* halvings, double* chi2, double* weight);
+// per-map chi^2 of the map-joining objective at a global state (lsfm_gn.hip; C ABI: lsfm_map_chi2)
+int map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, double* chi2, int* dof);
 // marginal covariances of a map's information matrix (lsfm_cov.hip; C ABI: lsfm_map_covariance).  times (may be null): [4] ms of the
 // Schur reduction + analysis, the factorisation, the selected inversion + pose gather, the feature part
 int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb,

@@ -1,8 +1,11 @@
 """lsfm_gn_polish on a named stand-in set, from the device's own tree result: the objective / gradient trace and the wall clock of the
-call's parts (LSFM_GN_TIMING=1: structure + upload, per assembly, per solve).  usage: python tools/gn_bench.py <config> [steps] [maps]
--> one JSON object per call on stdout (profiles/r06_gn_polish_<config>.json)."""
+call's parts (LSFM_GN_TIMING=1: structure + upload, per assembly (with the chi2 + weights kernels' HIP-event time when robust), per
+solve).  usage: python tools/gn_bench.py <config> [steps] [maps] [--robust huber|cauchy --c <c>]
+-> one JSON object per call on stdout (profiles/r06_gn_polish_<config>.json).  --robust: lsfm_gn_polish_robust instead, and the same
+steps of the plain polish beside it (wall clock per step of each, the chi2 kernel's share of an assembly)."""
 import json
 import os
+import re
 import subprocess
 import sys
 import time
@@ -19,15 +22,35 @@ if len(sys.argv) > 1 and sys.argv[1] != "--child":
         sys.exit(p.stdout + p.stderr)
     d = json.loads(line[0])
     d["library_timing"] = tim
+    if "robust" in d and len(tim) >= 4:
+        # per step = one solve + the assemblies of the line search; from the warm call of each kind
+        def parse(t):
+            g = lambda pat: float(re.search(pat, t).group(1))
+            return {"assembly_ms": g(r"assemblies ([0-9.]+) ms each"), "chi2_weights_ms": g(r"chi2 \+ weights ([0-9.]+) ms each"),
+                    "solve_ms": g(r"solves ([0-9.]+) ms each"), "n_asm": int(re.search(r"(\d+) assemblies", t).group(1)),
+                    "n_solve": int(re.search(r"(\d+) solves", t).group(1)), "call_ms": g(r"call ([0-9.]+) ms")}
+        p_, r_ = parse(tim[1]), parse(tim[3])
+        for k, v in (("plain_warm", p_), ("robust_warm", r_)):
+            v["step_ms"] = (v["n_asm"] * v["assembly_ms"] + v["n_solve"] * v["solve_ms"]) / max(v["n_solve"], 1)
+            d[k] = v
+        d["chi2_share_of_robust_assembly"] = r_["chi2_weights_ms"] / r_["assembly_ms"]
+        d["robust_over_plain_step"] = r_["step_ms"] / p_["step_ms"]
     print(json.dumps(d, indent=1))
     sys.exit(0)
+
+import argparse  # noqa: E402
 
 import numpy as np  # noqa: E402
 from linearsfm_amd import api, synth  # noqa: E402
 
-cfg = sys.argv[2]
-steps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
-nmaps = int(sys.argv[4]) if len(sys.argv) > 4 else 0
+ap = argparse.ArgumentParser()
+ap.add_argument("config")
+ap.add_argument("steps", nargs="?", type=int, default=3)
+ap.add_argument("maps", nargs="?", type=int, default=0)
+ap.add_argument("--robust", choices=["huber", "cauchy"])
+ap.add_argument("--c", type=float, default=1.0)
+a = ap.parse_args(sys.argv[2:])
+cfg, steps, nmaps = a.config, a.steps, a.maps
 typ, maps = synth.make_config(cfg, nmaps or None)
 mono = typ == "Monocular"
 d = [m.__dict__ for m in maps]
@@ -38,6 +61,20 @@ for rep in range(2):
     t0 = time.perf_counter()
     st, obj, gn, hv, rc2 = ctx.gn_polish(d, mono, G, steps)
     calls.append(1e3 * (time.perf_counter() - t0))
+if a.robust:
+    rcalls = []
+    for rep in range(2):
+        t0 = time.perf_counter()
+        rst, robj, rgn, rhv, chi2, w, rrc = ctx.gn_polish_robust(d, mono, G, steps, a.robust, a.c)
+        rcalls.append(1e3 * (time.perf_counter() - t0))
+    sys.stdout.flush()
+    print(json.dumps({"config": cfg, "type": typ, "maps": len(maps), "poses": int(G["m"]), "features": int(G["n"]), "steps": steps,
+                      "robust": a.robust, "c": a.c, "plain": {"objective": obj.tolist(), "halvings": hv.tolist(), "call_wall_ms": calls},
+                      "robust_run": {"objective": robj.tolist(), "halvings": rhv.tolist(), "call_wall_ms": rcalls, "rc": rrc,
+                                     "weight_min": float(np.min(w)), "weight_median": float(np.median(w))},
+                      "note": "plain = lsfm_gn_polish, robust_run = lsfm_gn_polish_robust, same steps from the device's tree result; library_timing: "
+                              "the library's own clocks, in call order plain, plain, robust, robust (the second of each warm)"}))
+    sys.exit(0)
 print(json.dumps({"config": cfg, "type": typ, "maps": len(maps), "poses": int(G["m"]), "features": int(G["n"]), "steps": steps, "tree_ms": stats["t_total_ms"], "tree_rc": rc,
                   "gn_rc": rc2, "objective": obj.tolist(), "gradient_max": gn.tolist(), "halvings": hv.tolist(), "call_wall_ms": calls,
                   "max_state_change": float(np.max(np.abs(st - G["stVal"]))),
