@@ -12,9 +12,11 @@ independent joins of the lower levels), then the sub-tree roots are cut by featu
 all-reduces of the sums that cross features (`--top merge`: pairwise merge rounds instead).  `value` is the wall time of
 the whole tree.  Inputs are uploaded once and stay in HBM; no level writes its input, so every step reads
 them in place.  Every timed step does the symbolic work of every join itself (pattern of S, ordering, symbolic
-factorisation), as the reference's timed region does; the repeat runs that reuse it are reported as `resolve_ms`.
-At N = 1 the line also carries the CPU baseline (the oracle on the host cores, three ways), the stand-alone streaming
-rate of the CG's SpMV kernel and one files-to-files run of the command line.  Prints ONE JSON line on rank 0.
+factorisation), as the reference's timed region does.  Prints ONE JSON line on rank 0.
+
+A plain run does only what `value` needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  With --full the line
+also carries the repeat runs that reuse the symbolic work (`resolve_ms`) and, at N = 1, the CPU baseline (the oracle on the
+host cores, three ways), the stand-alone streaming rate of the CG's SpMV kernel and one files-to-files run of the command line.
 """
 import argparse
 import glob
@@ -242,18 +244,20 @@ def main():
     ap.add_argument("--maps", type=int, default=0, help="local maps (0 = the configuration's own count)")
     ap.add_argument("--new-per-frame", type=int, default=0)
     ap.add_argument("--vis", type=int, default=0)
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="1: time the oracle on the SAME set on the host cores (N=1 only); 0: skip")
+    ap.add_argument("--full", action="store_true", help="also measure what `value` does not need: the other mode of --plans "
+                                                        "(resolve_ms / analysing_run_ms) and, at N=1, the --cpu-baseline and --extras legs")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="with --full, 1: time the oracle on the SAME set on the host cores (N=1 only); 0: skip")
     ap.add_argument("--cpu-max-maps", type=int, default=4096, help="sets larger than this time the oracle on their first maps only")
     ap.add_argument("--tol", type=float, default=1e-12, help="relative residual at which the refinement of a system stops (library default)")
     ap.add_argument("--mixed", action="store_true", help="Cholesky preconditioner kept and applied in fp32, fp64 residual correction (BASELINE configs[4])")
     ap.add_argument("--plans", action="store_true", help="time the repeat runs of the resident tree (structure analysed once) instead of "
-                                                         "runs that analyse every join like the reference does; the default reports both")
+                                                         "runs that analyse every join like the reference does; --full reports both")
     ap.add_argument("--no-plans", action="store_true", help="(the default since round 3; kept for old command lines)")
     ap.add_argument("--top", default="shard", choices=("shard", "merge"),
                     help="N > 1: how the levels above the ranks' blocks run -- shard: feature-sharded on ALL ranks, RCCL all-reduces of the "
                          "transform's pose rows, the camera system and the pose solution per level; merge: pairwise merge rounds of packed "
                          "sub-tree roots on half of the remaining ranks each")
-    ap.add_argument("--extras", type=int, default=1, help="1: also the stand-alone SpMV streaming leg and the files-to-files CLI run "
+    ap.add_argument("--extras", type=int, default=1, help="with --full, 1: also the stand-alone SpMV streaming leg and the files-to-files CLI run "
                                                           "(N=1, default configuration sizes only); 0: skip")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the final map of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all: a fixed, seeded "
@@ -378,15 +382,17 @@ def main():
         dist.all_reduce(tm, op=dist.ReduceOp.MAX)
     elapsed, first_ms = float(tm[0].item()), 1e3 * float(tm[1].item())
     ms_per_step = 1e3 * elapsed / args.steps
-    # ---- the other mode, same steps: plans on (one analysing run leaves them, then the repeats) / off ----
-    tree.set_plans(analysing)
-    tree.run()
-    tree.run()
-    other_s, acc2, _, _ = timed(args.steps)
-    tm = torch.tensor([other_s], dtype=torch.float64, device=rdev)
-    if world > 1:
-        dist.all_reduce(tm, op=dist.ReduceOp.MAX)
-    other_ms = 1e3 * float(tm[0].item()) / args.steps
+    other_ms = None
+    if args.full:
+        # ---- the other mode, same steps: plans on (one analysing run leaves them, then the repeats) / off ----
+        tree.set_plans(analysing)
+        tree.run()
+        tree.run()
+        other_s, _, _, _ = timed(args.steps)
+        tm = torch.tensor([other_s], dtype=torch.float64, device=rdev)
+        if world > 1:
+            dist.all_reduce(tm, op=dist.ReduceOp.MAX)
+        other_ms = 1e3 * float(tm[0].item()) / args.steps
     analyse_ms, resolve_ms = (ms_per_step, other_ms) if analysing else (other_ms, ms_per_step)
     # per-rank busy time of the timed steps (where a multi-GPU run loses its efficiency): device time of the trees the rank ran
     busy = torch.zeros(world, dtype=torch.float64, device=rdev)
@@ -459,7 +465,8 @@ def main():
             "resolve_note": "resolve_ms: the same tree joined again with NEW work only (lsfm_tree_set_plans(tree, 1): container sizes, pattern of S, "
                             "ordering and symbolic factorisation of every level kept from an earlier run, a level enqueued without host round trips); "
                             "analysing_run_ms: every run does that analysis itself, as every run of the reference does (cholmod_analyze_p in every "
-                            "join).  `value` is " + ("analysing_run_ms" if analysing else "resolve_ms") + ".",
+                            "join).  `value` is " + ("analysing_run_ms" if analysing else "resolve_ms") + "; the other is timed with --full "
+                            "only (null without it).",
             "first_run_ms": first_ms,
             "upload_ms": upload_ms,
             "upload_c_abi_ms": (stats or {}).get("upload_ms"),
@@ -522,7 +529,7 @@ def main():
                             **({"algorithmic_TFLOPs": v["tflops"], "frac_of_f64_mfma_peak": v["tflops"] / F64_MFMA_PEAK_TFLOPS} if k == "schur" else {})}
                         for k, v in kern.items()},
         }
-        extras = args.extras and world == 1
+        extras = args.full and args.extras and world == 1
         if extras:
             # the CG's SpMV kernel where it streams: a Schur-like matrix far beyond the caches (same kernel, same entry point as
             # `--config spmv-stream`, a little shorter: 196 608 poses, 1.0 GB of upper blocks)
@@ -537,7 +544,7 @@ def main():
                                       "note": "k_spmv (K10a) stand-alone through lsfm_spmv_bench, HIP events around the timed launches; "
                                               "algorithmic bytes nnzb*(288+4) + 4(m+1) + 96 m (SURVEY 8d)"}
             del rp32, colidx, val
-        if args.cpu_baseline and world == 1:  # the CPU leg runs at N=1 only, on the same set
+        if args.full and args.cpu_baseline and world == 1:  # the CPU leg runs at N=1 only, on the same set
             from oracle import pyoracle as po
             S = min(n_maps, args.cpu_max_maps)
             dicts = [po.localmap_to_dict(m) for m in block[:S]]

@@ -1,6 +1,6 @@
 # A/B of build variants on ONE box:  gpurun -- bash tools/ab_build.sh "<label>|<make flags>" ...   (first entry usually "default|")
 #   [CONFIG=<name> STEPS=<n> REPS=<n>]
-# every variant: rebuild the library in place, 2 x `bench.py --steps 20 --warmup 3` (analysing / repeat ms, K9 ms per level, stage times)
+# every variant: rebuild the library in place, 2 x `bench.py --full --steps 20 --warmup 3` (analysing / repeat ms, K9 ms per level, stage times)
 ulimit -c 0
 D=gpurun_out/ab; mkdir -p $D
 for spec in "$@"; do
@@ -8,7 +8,7 @@ for spec in "$@"; do
   touch linearsfm_amd/csrc/lsfm_solve.hpp linearsfm_amd/csrc/lsfm_symbolic.hpp linearsfm_amd/csrc/lsfm_small.hip
   ( cd linearsfm_amd/csrc && make -s -j16 $flags > /dev/null 2>&1 ) || { echo "$label: build failed"; continue; }
   for rep in $(seq 1 ${REPS:-2}); do
-    timeout 600 python bench.py --config ${CONFIG:-nc3500} ${MAPS:+--maps $MAPS} --cpu-baseline 0 --extras 0 --steps ${STEPS:-20} --warmup 3 2>/dev/null | python -c "
+    timeout 600 python bench.py --full --config ${CONFIG:-nc3500} ${MAPS:+--maps $MAPS} --cpu-baseline 0 --extras 0 --steps ${STEPS:-20} --warmup 3 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@ CONFIG=${CONFIG:-nc3500}; STEPS=${STEPS:-20}
 for rep in $(seq 1 ${REPS:-2}); do
 for spec in "$@"; do
   label="${spec%%|*}"; envs="${spec#*|}"
-  env $envs timeout 600 python bench.py --config $CONFIG --cpu-baseline 0 --extras 0 --steps $STEPS --warmup 3 2>/dev/null | python -c "
+  env $envs timeout 600 python bench.py --full --config $CONFIG --cpu-baseline 0 --extras 0 --steps $STEPS --warmup 3 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

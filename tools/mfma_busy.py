@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The matrix cores' busy share of the SIMD cycles per kernel from a counter pass
-    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES --output-format csv -d <dir> -o run -- python3 bench.py --config <c> --steps 2 --warmup 1 --cpu-baseline 0 --extras 0
+    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES --output-format csv -d <dir> -o run -- python3 bench.py --full --config <c> --steps 2 --warmup 1 --cpu-baseline 0 --extras 0
 (counters alone: never combined with a trace domain) -> profiles/<round>_pmc_mfma_busy_<config>.json
 usage: python tools/mfma_busy.py <dir>/run_counter_collection.csv <round> <config>"""
 import collections
@@ -20,7 +20,7 @@ for r in csv.DictReader(open(path)):
     acc[m.group(1)][r["Counter_Name"]] += float(r["Counter_Value"])
     if r["Counter_Name"] == "SQ_BUSY_CU_CYCLES":
         n[m.group(1)] += 1
-out = {"command": f"rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES -- python3 bench.py --config {cfg} --steps 2 --warmup 1 --cpu-baseline 0 --extras 0 (counters alone, no trace domain)",
+out = {"command": f"rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES -- python3 bench.py --full --config {cfg} --steps 2 --warmup 1 --cpu-baseline 0 --extras 0 (counters alone, no trace domain)",
        "note": "SQ_VALU_MFMA_BUSY_CYCLES sums the four SIMDs of a CU, SQ_BUSY_CU_CYCLES counts the CU: their ratio / 4 = the share of SIMD cycles the matrix cores were busy while the kernel held the CU",
        "kernels": {}}
 for k, v in sorted(acc.items(), key=lambda kv: -kv[1].get("SQ_VALU_MFMA_BUSY_CYCLES", 0)):

@@ -75,7 +75,7 @@ if "k_schur_w" in detail and "k_schur_panel" in detail:
 for n in names[:14]:
     print(f"{n[:44]:44s} n={detail[n]['launches']:5d} -> {per_launch[n] / 1e6:8.1f} MB/launch")
 res = dict(config=config, trees_in_profiled_run=trees, bytes_per_tree=total / trees, per_launch=per_launch, kernels=detail,
-           source=f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of bench.py --config {config}; FETCH_SIZE doubled (gfx950), KB -> bytes")
+           source=f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of bench.py --full --config {config}; FETCH_SIZE doubled (gfx950), KB -> bytes")
 json.dump(res, open(f"{OUT}/{tag}_pmc_traffic_summary_{config}.json", "w"), indent=1)
 print("HBM bytes per tree: %.2f GB" % (total / trees / 1e9))
 st = glob.glob(f"{src}/stats/**/*kernel_stats.csv", recursive=True)
