@@ -165,7 +165,6 @@ void run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level)
 		Range r("lsfm join + solve");
 		js.smark = smark; // everything of this level goes at once
 		join_stereo_finish(ctx, Xt, Y, js, nullptr, nullptr);
-		if (ctx->pre_pending) ctx->drop_prepared(); // (a plan the level's solve did not take up)
 		ctx->pre_plan = LevelPlan(); // (consumed, if it was this level's)
 		ctx->pre_plan_level = -1;
 		if (analysing && Y.B > 1 && !ctx->comm)
@@ -302,8 +301,6 @@ int lsfm_tree_run(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* stats)
 				memset(st, 0, sizeof *st);
 				st->attempts = attempt + 1;
 				ctx->timed.clear(); ctx->ev_next = 0;
-				static const bool no_hints = getenv("LSFM_NO_STEP_HINTS") != nullptr; // debug: every run asks after every refinement step
-				if (no_hints) t->step_hint.clear();
 				ctx->timeline_on = getenv("LSFM_TIMELINE") != nullptr;
 				ctx->timeline.clear();
 				ctx->mark("run");
@@ -827,7 +824,7 @@ static int solve_raw(lsfm_context* ctx, double* stVal, const double* eb, const d
 		io.U = dU; io.Ui = dUi; io.Uj = dUj; io.W = dW; io.photo = dph; io.fptr = dfp; io.V = dV;
 		io.ea = dea; io.eb = deb; io.x0 = dx0; io.x_pose = dxp; io.x_feat = dxf;
 		io.seg_rows.assign(1, m);
-		if (ctx->small_max > 0 && small_solve_strips(m, ctx->small_max))
+		if (small_level_strips(ctx, m))
 		{
 			const int offs[6] = { 0, m, 0, n, 0, nU };
 			int* d_offs = ar.alloc<int>(6);

@@ -24,6 +24,10 @@ namespace lsfm {
 
 struct Error { int code; std::string msg; };
 struct DevBatch;
+struct IndexHold;    // device memory a plan owns (lsfm_prims.hip)
+struct SolvePlan;    // the solve part of a level's plan (lsfm_pcg.hip)
+struct PreLevel;     // a level prepared one level ahead (lsfm_pcg.hip)
+struct EarlyPattern; // an early pattern build in flight (lsfm_solve.hip)
 
 #define LSFM_CHECK_HIP(expr)                                                                                   \
 	do {                                                                                                        \
@@ -82,9 +86,9 @@ struct DevBatch {
 	// such a map is W_alias[j + d_alias[map]] in the transform's INPUT (d_alias[map] == INT_MIN: materialised in W)
 	const double* W_alias = nullptr;
 	const int* d_alias = nullptr;
-	// Stereo tree levels that analyse: the sorted upper block pattern of the camera system this batch was solved with (null: not
+	// Mono tree levels that analyse: the sorted upper block pattern of the camera system this batch was solved with (null: not
 	// kept).  The next level's pattern contains it -- a joint feature is seen by everything its sources were seen by -- so it
-	// only adds the hub links and the pose pairs across the two maps of a pair (schur_pattern_early_issue)
+	// only adds what the join itself brings (PatternSeed, lsfm_join_mono.hip)
 	const unsigned long long* s_keys = nullptr;
 	int s_nnzb = 0;
 };
@@ -107,7 +111,7 @@ struct LevelIndex {
 	int NU = -1, NW = -1, NF = -1;             // sizes of the level's INPUT batch they belong to
 	const int *KU = nullptr, *KW = nullptr;    // [NU + 2] / [NW + 2] (transform_batch)
 	const int *match = nullptr, *R = nullptr;  // [NF + 1] / [NF + 2] (join_stereo_prepare)
-	std::shared_ptr<void> own;                 // plan-owned device memory; null: the arrays live in the preparer's arena
+	std::shared_ptr<IndexHold> own;            // plan-owned device memory; null: the arrays live in the preparer's arena
 };
 const int* level_index_keep(lsfm_context* ctx, LevelIndex& li, const int* src, size_t n); // a copy of src[0..n) in memory li owns
 
@@ -120,7 +124,7 @@ struct LevelPlan {
 	std::vector<int> tr_sign;
 	std::vector<int> join_rb;    // join: ranks of the unmatched features at the map boundaries
 	std::vector<int> join_uo, join_wo; // Mono join: kept-U prefix at the map boundaries, W offsets of the joint maps
-	std::shared_ptr<void> solve; // pattern of S + symbolic factorisation + iteration count (lsfm_pcg.hip)
+	std::shared_ptr<SolvePlan> solve; // pattern of S + symbolic factorisation + iteration count (lsfm_pcg.hip)
 };
 
 // per-run accumulators on the device, read back once at the end of a run (a warm level does not stop for them)
@@ -287,7 +291,7 @@ struct lsfm_context {
 	// waits for them (lsfm_solve.hip: schur_pattern_early_*).  tr_in / tr_hub: set by transform_batch around its hook.
 	const lsfm::DevBatch* tr_in = nullptr;
 	const int* tr_hub = nullptr;        // [B] global pose index of the hub column of every transformed map, -1: passed through
-	std::shared_ptr<void> early;        // the build in flight (null: none)
+	std::shared_ptr<lsfm::EarlyPattern> early; // the build in flight (null: none)
 	hipEvent_t ev_k9[2] = { nullptr, nullptr }; // K9: the 32-slot panel variant of a level runs on the side stream, beside the others (lsfm_schur_panel.hip)
 	hipStream_t stream3 = nullptr;      // its own stream: the side stream carries the transform's U stage, which waits for the block kernel
 	// One level ahead (Stereo tree runs that analyse): while the device factors and refines level L, the pattern of level
@@ -295,22 +299,17 @@ struct lsfm_context {
 	// solve ends) and the host analyses it -- level L + 1 then finds its pattern and its symbolic factorisation waiting
 	// (lsfm_pcg.hip: prefetch_next_level).  Their arrays live in two small arenas used in turn.
 	lsfm::Arena sarena[2];
-	std::shared_ptr<void> pre;          // what was prepared for the level about to run (null: nothing)
+	// what was prepared for the level about to run (null: nothing).  Its symbolic factorisation (host work) may still be under way on
+	// the helper thread when the level starts; releasing the object waits for it -- nothing the thread reads goes before (~PreLevel)
+	std::shared_ptr<lsfm::PreLevel> pre;
 	// ... and, when an earlier run of the tree has left the refinement step count of that level, everything else the level
 	// would stop for (kept-block counts of its transform, unmatched-feature ranks of its join): a plan of the level made
-	// one level ahead -- the level then runs like a planned one, without a single host <-> device round trip
+	// one level ahead -- the level then runs like a planned one, without a single host <-> device round trip: its transform, join
+	// and Schur assembly are enqueued while the helper thread works, solve_batch completes the plan (lsfm_pcg.hip)
 	lsfm::LevelPlan pre_plan;
 	int pre_plan_level = -1;
-	// ... whose solve part (symbolic factorisation: host work) may still be under way on the helper thread when the level starts:
-	// its transform, join and Schur assembly are enqueued meanwhile, solve_batch completes the plan (lsfm_pcg.hip)
-	std::shared_ptr<void> pre_pending;
 	std::unique_ptr<lsfm::HostWorker> worker;
-	// nothing the helper thread still reads may be dropped: wait for it, then forget what was prepared
-	void drop_prepared()
-	{
-		if (worker) { try { worker->wait(); } catch (...) {} }
-		pre.reset(); pre_pending.reset(); pre_plan = lsfm::LevelPlan(); pre_plan_level = -1;
-	}
+	void drop_prepared() { pre.reset(); pre_plan = lsfm::LevelPlan(); pre_plan_level = -1; }
 	hipEvent_t ev_solve_end = nullptr; // (LSFM_LEVEL_GAPS=1: the event behind the last solve, against the next level's first)
 	double dbg_gap_ms = 0.0;
 	hipEvent_t evY = nullptr, evP = nullptr; // joint index arrays of the level final (main stream) / prefetch complete (stream3)
@@ -353,6 +352,16 @@ struct lsfm_context {
 };
 
 namespace lsfm {
+
+// "This stretch runs on another stream (and allocates from another arena)": until the end of the scope -- however it is left --
+// ctx->stream names `other` (and ctx->scratch names `arena`), so everything called inside enqueues and allocates there.
+struct OnStream {
+	lsfm_context* c; hipStream_t& s; Arena* a;
+	OnStream(lsfm_context* ctx, hipStream_t& other, Arena* arena = nullptr) : c(ctx), s(other), a(arena) { std::swap(c->stream, s); if (a) std::swap(c->scratch, *a); }
+	~OnStream() { if (a) std::swap(c->scratch, *a); std::swap(c->stream, s); }
+	OnStream(const OnStream&) = delete;
+	OnStream& operator=(const OnStream&) = delete;
+};
 
 // ---- primitives (lsfm_prims.hip; rocPRIM scan / radix sort on the context stream) ------------------------
 void dev_exclusive_scan(lsfm_context* ctx, const int* in, int* out, size_t n); // out[n] = total (n+1 entries written)
@@ -463,7 +472,10 @@ struct SolveIO {
 	// from every pose pair of every feature again (lsfm_solve.hpp PatternSeed; null: from scratch)
 	const struct PatternSeed* seed = nullptr;
 };
-int small_solve_strips(int most_poses, int cap); // 16-row strips of the dense path's panel; 0: the systems are too large for it (cap: lsfm_context::small_max)
+// Does a level whose largest system has most_rows poses take the one-launch dense path?  16-row strips of its panel; 0: no (the
+// systems are too large -- lsfm_context::small_max --, or the run is feature-sharded or in mixed precision).  The ONE place that
+// decides it: the join (offsets, fused right-hand sides, early pattern), the preparation one level ahead and the solve must agree
+int small_level_strips(const lsfm_context* ctx, int most_rows);
 void small_solve_launch(lsfm_context* ctx, const SolveIO& io, int strips, int* status, double* max_rel);
 int solve_batch(lsfm_context* ctx, const SolveIO& io);
 // Gauss-Newton polish of the map-joining objective over all local maps at once (lsfm_gn.hip; C ABI: lsfm_gn_polish)
@@ -484,8 +496,6 @@ struct EarlyPatternIn {
 	int M = 0, NFY = 0, NU = 0;
 	const int *Ui = nullptr, *Uj = nullptr, *pose_map = nullptr, *hub = nullptr;
 	const int *fptr = nullptr, *photo = nullptr, *feat_map = nullptr, *srcE = nullptr, *srcC = nullptr;
-	const unsigned long long* prev_keys = nullptr; // pattern of the level below (DevBatch::s_keys), null: none
-	int prev_nnzb = 0;
 };
 void schur_pattern_early_issue(lsfm_context* ctx, const EarlyPatternIn& in); // enqueues on the side stream; the caller has recorded evC
 void schur_pattern_early_drop(lsfm_context* ctx);

@@ -280,12 +280,11 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 	st.ar = &ar;
 
 	// ---- common features (K5) ---- (from the level's plan when it holds them: LevelIndex, lsfm_internal.hpp)
-	static const bool reuse_index = !getenv("LSFM_NO_INDEX_REUSE");
 	LevelPlan* plan = ctx->plan;
 	const int *match = nullptr, *R = nullptr;
 	const int nb = (in.NF + 255) / 256;
 	std::vector<int> rb(B + 1);
-	if (reuse_index && ctx->warm() && plan->idx.match && plan->idx.R && plan->idx.NF == in.NF)
+	if (ctx->warm() && plan->idx.match && plan->idx.R && plan->idx.NF == in.NF)
 	{
 		match = plan->idx.match; R = plan->idx.R;
 		rb = plan->join_rb;
@@ -309,7 +308,7 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 			d2h_ints(ctx, d_rb, rb.data(), B + 1);
 			ctx->mark("jn_rb");
 			if (plan) plan->join_rb = rb;
-			if (reuse_index && plan && plan != &ctx->pre_plan && ctx->in_tree_run)
+			if (plan && plan != &ctx->pre_plan && ctx->in_tree_run)
 			{
 				// a resident tree records the level: its later runs skip the matching and its scan
 				plan->idx.match = level_index_keep(ctx, plan->idx, mt, (size_t)in.NF + 1);
@@ -383,16 +382,14 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 	double* eP = st.eP = ctx->scratch.alloc<double>((size_t)in.M * 6);
 	dev_zero(ctx, eP, (size_t)in.M * 6 * sizeof(double));
 	// a level that analyses, reached through the transform's hook: the sources of every joint feature, for the early pattern of S
-	static const bool early_on = !getenv("LSFM_NO_EARLY_PATTERN");
-	// (a level of small systems takes the dense path: no pattern at all)
+	// (a level of small systems takes the dense path: no pattern at all; a level prepared one level ahead brings its pattern -- or,
+	// prepared with a plan, is warm)
 	int most_rows = 0;
 	for (int r : seg_rows) most_rows = std::max(most_rows, r);
-	static const bool no_small = getenv("LSFM_NO_SMALL") != nullptr;
-	const bool small_level = ctx->small_max > 0 && !ctx->comm && !ctx->pcg.mixed && !no_small && small_solve_strips(most_rows, ctx->small_max) > 0;
-	const bool early = early_on && !small_level && !ctx->comm && !ctx->pre && ctx->tr_in && ctx->tr_hub && !ctx->warm() && ctx->tr_in->NF == in.NF && ctx->tr_in->M == in.M;
+	const bool small_level = small_level_strips(ctx, most_rows) > 0;
+	const bool early = !small_level && !ctx->comm && !(ctx->pre && !ctx->pre_plan.valid) && ctx->tr_in && ctx->tr_hub && !ctx->warm() && ctx->tr_in->NF == in.NF && ctx->tr_in->M == in.M;
 	// the W part of the right-hand sides left to the Schur assembly (lsfm_solve.hpp RhsFused): a level on the sparse pipeline, one GPU
-	static const bool fuse_on = !getenv("LSFM_NO_FUSED_RHS");
-	st.fuse_rhs = fuse_on && !small_level && !ctx->comm && !ctx->pcg.mixed;
+	st.fuse_rhs = !small_level && !ctx->comm && !ctx->pcg.mixed;
 	int *srcE = nullptr, *srcC = nullptr;
 	if (early || st.fuse_rhs)
 	{
@@ -410,7 +407,6 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 		ei.M = in.M; ei.NFY = NFY; ei.NU = X.NU;
 		ei.Ui = X.Ui; ei.Uj = X.Uj; ei.pose_map = X.pose_map; ei.hub = ctx->tr_hub;
 		ei.fptr = X.fptr; ei.photo = X.photo; ei.feat_map = X.feat_map; ei.srcE = srcE; ei.srcC = srcC;
-		ei.prev_keys = X.s_keys; ei.prev_nnzb = X.s_nnzb;
 		LSFM_CHECK_HIP(hipEventRecord(ctx->evC, s));
 		schur_pattern_early_issue(ctx, ei);
 	}
@@ -481,7 +477,7 @@ void join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch& out, Jo
 		// a level of small systems goes to the one-launch dense path, which walks the joins by their ranges (lsfm_small.hip)
 		int most = 0;
 		for (int r : seg_rows) most = std::max(most, r);
-		if (ctx->small_max > 0 && small_solve_strips(most, ctx->small_max))
+		if (small_level_strips(ctx, most))
 		{
 			int* d_uo = ctx->scratch.alloc<int>(G + 1);
 			h2d(ctx, d_uo, out.u_off.data(), sizeof(int) * (size_t)(G + 1));
@@ -491,13 +487,6 @@ void join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch& out, Jo
 	const bool warm = ctx->warm();
 	ctx->solved_keys = nullptr; ctx->solved_nnzb = 0;
 	int rc = solve_batch(ctx, io);
-	if (!warm && st.ar && ctx->in_tree_run && ctx->solved_keys && getenv("LSFM_NO_PREFETCH") && !getenv("LSFM_NO_EARLY_PATTERN"))
-	{
-		// the pattern of this level's system stays with its output for the level above (schur_pattern_early_issue)
-		unsigned long long* k = st.ar->alloc<unsigned long long>((size_t)ctx->solved_nnzb + 1);
-		LSFM_CHECK_HIP(hipMemcpyAsync(k, ctx->solved_keys, (size_t)ctx->solved_nnzb * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
-		out.s_keys = k; out.s_nnzb = ctx->solved_nnzb;
-	}
 	// a level of a tree run is only enqueued (its scratch is reused in stream order, errors are read at the end of the run); a
 	// stage-level call stops here so that a failure surfaces at its stage
 	if (!warm && !ctx->in_tree_run) LSFM_CHECK_HIP(hipStreamSynchronize(s));

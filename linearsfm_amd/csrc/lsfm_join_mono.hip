@@ -192,72 +192,9 @@ __global__ void k_mono_w_count(int NFY, const int* __restrict__ srcE, const int*
 	lens[nf] = cnt;
 }
 
-// writes the joint run of every feature and the W part of the right-hand sides (Imp.cpp:7602-7821)
-__global__ void k_mono_w_fill(int NFY, const int* __restrict__ srcE, const int* __restrict__ srcC, const int* __restrict__ fptr,
-                              const int* __restrict__ photo, const double* __restrict__ W, const int* __restrict__ feat_map_y,
-                              const MGroup* __restrict__ grp, const int* __restrict__ pnew, const double* __restrict__ prior,
-                              const double* __restrict__ feat, const int* __restrict__ fptr_y, double* __restrict__ Wy, int* __restrict__ photo_y,
-                              int* __restrict__ feature_y, double* __restrict__ eP, double* __restrict__ eF,
-                              const int* __restrict__ feat_map_src, const double* __restrict__ W_alias, const int* __restrict__ alias)
-{
-	// eP: summed per work-group in an LDS table keyed by pose and flushed once (every feature adds to its hub poses:
-	// global atomics on those few rows serialised -- 30 of the 55 ms of an RS468-like tree)
-	constexpr int ECAP = 128;
-	__shared__ int ekeys[ECAP];
-	__shared__ double evals[ECAP * 6];
-	for (int i = threadIdx.x; i < ECAP; i += blockDim.x) ekeys[i] = -1;
-	for (int i = threadIdx.x; i < ECAP * 6; i += blockDim.x) evals[i] = 0.0;
-	__syncthreads();
-	const int nf = blockIdx.x * blockDim.x + threadIdx.x;
-	const bool inb = nf < NFY;
-	const MGroup& g = grp[feat_map_y[inb ? nf : 0]];
-	int pos = inb ? fptr_y[nf] : 0, flpos = -1;
-	double ef[3] = { 0, 0, 0 };
-	for (int side = 0; side < 2 && inb; side++)
-	{
-		const int f = side ? srcC[nf] : srcE[nf];
-		if (f < 0) continue;
-		const double* xf = feat + (size_t)f * 3;
-		// blocks of a map the transform passed through are still in the transform's input
-		const int delta = alias ? alias[feat_map_src[f]] : INT_MIN;
-		const double* Wsrc = delta != INT_MIN ? W_alias + (ptrdiff_t)delta * 18 : W;
-		for (int j = fptr[f]; j < fptr[f + 1]; j++)
-		{
-			const int k = photo[j];
-			if (g.pair && (k == g.P1 || k == g.C1)) continue;
-			double w[18];
-			ld<18>(w, Wsrc + (size_t)j * 18);
-			const int kn = pnew[k];
-			if (side == 1 && g.pair && k == g.C2 && flpos >= 0)
-			{
-				for (int q = 0; q < 18; q++) Wy[(size_t)flpos * 18 + q] += w[q]; // only this lane touches the feature's run
-			}
-			else
-			{
-				if (side == 0 && g.pair && k == g.P2) flpos = pos;
-				st<18>(Wy + (size_t)pos * 18, w);
-				photo_y[pos] = kn; feature_y[pos] = nf;
-				pos++;
-			}
-			const double* xp = prior + (size_t)k * 6;
-			const int es = lds_slot(ekeys, ECAP, kn);
-			for (int r = 0; r < 6; r++)
-			{
-				const double y = w[3 * r] * xf[0] + w[3 * r + 1] * xf[1] + w[3 * r + 2] * xf[2];
-				if (es >= 0) lds_add_f64(&evals[es * 6 + r], y); else atomic_add_f64(eP + (size_t)kn * 6 + r, y);
-			}
-			for (int c = 0; c < 3; c++)
-				for (int r = 0; r < 6; r++) ef[c] = fma(w[3 * r + c], xp[r], ef[c]);
-		}
-	}
-	if (inb) { eF[(size_t)nf * 3] += ef[0]; eF[(size_t)nf * 3 + 1] += ef[1]; eF[(size_t)nf * 3 + 2] += ef[2]; }
-	__syncthreads();
-	tile_flush<6>(ekeys, evals, ECAP, eP);
-}
-
-// ---- the same in two steps (the default): where every source block goes is index work, one lane per joint feature as above
-// but ints only; the blocks themselves -- 144 bytes each -- are then moved one lane per SOURCE block, consecutive lanes
-// on consecutive blocks, with the right-hand-side parts summed per source feature through LDS (tile_runs).  One lane per
+// ---- the joint run of every feature and the W part of the right-hand sides (Imp.cpp:7602-7821), in two steps: where every source
+// block goes is index work, one lane per joint feature, ints only; the blocks themselves -- 144 bytes each -- are then moved one
+// lane per SOURCE block, consecutive lanes on consecutive blocks, with the right-hand-side parts summed per source feature through LDS (tile_runs).  One lane per
 // feature walking its 9-40 blocks, 144-byte loads a run length apart, was 7 % of an RS468-like tree. ----
 #define MW_DROP (-1)            /* P1 / C1 block: gone, no contribution */
 #define MW_SUMMED (-2)          /* Cur's block to C2: added into End's block to P2, contributes to the right-hand sides */
@@ -548,11 +485,7 @@ void join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch&
 	}
 	out.NW = out.w_off[G];
 	out.W = ar.alloc<double>((size_t)out.NW * 18); out.photo = ar.alloc<int>(out.NW); out.feature = ar.alloc<int>(out.NW);
-	static const bool one_lane_per_feature = getenv("LSFM_MONO_FILL_BY_FEATURE") != nullptr; // the round-1 kernel, kept for comparison
-	if (NFY && one_lane_per_feature)
-		hipLaunchKernelGGL(k_mono_w_fill, dim3((NFY + 127) / 128), dim3(128), 0, s, NFY, srcE, srcC, in.fptr, in.photo, in.W, out.feat_map, d_mg,
-		                   pnew, prior, in.feat, out.fptr, out.W, out.photo, out.feature, eP, eF, in.feat_map, in.W_alias, in.d_alias);
-	else if (NFY)
+	if (NFY)
 	{
 		int* dst = sc.alloc<int>((size_t)in.NW + 1);
 		int* jf = sc.alloc<int>((size_t)in.NF + 1);
@@ -593,7 +526,7 @@ void join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch&
 	{
 		int most = 0;
 		for (int r : seg_rows) most = std::max(most, r);
-		if (ctx->small_max > 0 && small_solve_strips(most, ctx->small_max))
+		if (small_level_strips(ctx, most))
 		{
 			int* d_uo = sc.alloc<int>(G + 1);
 			h2d(ctx, d_uo, out.u_off.data(), sizeof(int) * (size_t)(G + 1));
@@ -602,8 +535,7 @@ void join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch&
 	}
 	// the pattern of this level's system from the one below (a level that analyses; the level below left its pattern with its maps)
 	PatternSeed seed;
-	static const bool seed_on = !getenv("LSFM_NO_MONO_SEED");
-	if (seed_on && !warm && in.s_keys && in.s_nnzb > 0 && !ctx->comm)
+	if (!warm && in.s_keys && in.s_nnzb > 0 && !ctx->comm)
 	{
 		seed.prev_keys = in.s_keys; seed.prev_nnzb = in.s_nnzb; seed.pnew = pnew; seed.dropped = dropped;
 		seed.NFY = NFY; seed.srcE = srcE; seed.srcC = srcC; seed.fptr_in = in.fptr; seed.photo_in = in.photo;

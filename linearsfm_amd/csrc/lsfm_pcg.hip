@@ -1418,7 +1418,7 @@ struct SolvePlan {
 	char* mem = nullptr;
 	~SolvePlan() { if (mem) (void)hipFree(mem); }
 };
-static std::shared_ptr<void> solve_plan_store(lsfm_context* ctx, const SchurSystem& sy, const CholDev& ch, int its)
+static std::shared_ptr<SolvePlan> solve_plan_store(lsfm_context* ctx, const SchurSystem& sy, const CholDev& ch, int its)
 {
 	auto sp = std::make_shared<SolvePlan>();
 	const size_t M = sy.M, nnzb = sy.nnzb, cap = (size_t)sy.mask + 1;
@@ -1546,30 +1546,31 @@ struct PreLevel {
 	CholSymbolic sym;
 	CholHostIn hin;          // what the symbolic analysis reads (kept here: it may run on the helper thread)
 	int M = 0;
-	bool on_worker = false;  // sym is being made by ctx->worker: wait() before it is read
-	// the level's whole plan (counts in ctx->pre_plan already): what completes its solve part
+	HostWorker* worker = nullptr; // non-null: sym is being made there -- wait() before it is read
+	// the level's whole plan (counts in ctx->pre_plan): its solve part is completed by the level's solve (pre_plan_complete)
 	bool whole = false;
 	int level = -1, its = 0;
+	void wait()
+	{
+		HostWorker* w = worker;
+		worker = nullptr;
+		if (w) w->wait();
+	}
+	// nothing the helper thread reads goes before the thread is done with it -- whichever path drops the object, exceptions included
+	~PreLevel() { try { wait(); } catch (...) {} }
 };
-static void pre_wait(lsfm_context* ctx, PreLevel* pl)
-{
-	if (pl && pl->on_worker) { ctx->worker->wait(); pl->on_worker = false; }
-}
 void prefetch_next_level(lsfm_context* ctx, const DevBatch& Y, const std::vector<int>& target_ref, int next_level, int step_hint)
 {
 	ctx->drop_prepared();
-	static const bool on = !getenv("LSFM_NO_PREFETCH") && !getenv("LSFM_NO_EARLY_PATTERN");
-	if (!on || !Y.M || Y.B < 2) return;
+	if (!Y.M || Y.B < 2) return;
 	// the next level's systems (pairs of Y's maps): small enough for the one-launch dense path?  Then it needs no pattern and no
 	// symbolic factorisation, only -- to be enqueued without a host round trip -- its counts
 	int most_next = 0;
 	for (int b = 0; b < Y.B; b += 2) most_next = std::max(most_next, Y.pose_off[std::min(b + 2, Y.B)] - Y.pose_off[b]);
-	static const bool no_small = getenv("LSFM_NO_SMALL") != nullptr;
-	const bool next_small = ctx->small_max > 0 && !ctx->comm && !ctx->pcg.mixed && !no_small && small_solve_strips(most_next, ctx->small_max) > 0;
+	const bool next_small = small_level_strips(ctx, most_next) > 0;
 	// with the step count an earlier run left for that level, the level can run like a planned one (no round trip at all): then
 	// its counts are prepared too.  (LSFM_CHECK_EARLY_PATTERN keeps to the path that compares the pattern.)
-	static const bool plan_on = !getenv("LSFM_NO_PREPLAN");
-	const bool whole = plan_on && step_hint > 0 && !getenv("LSFM_CHECK_EARLY_PATTERN");
+	const bool whole = step_hint > 0 && !getenv("LSFM_CHECK_EARLY_PATTERN");
 	if (next_small && !whole) return; // (nothing to prepare: the level reads its counts back itself)
 	ctx->mark("pre_start");
 	auto pl = std::make_shared<PreLevel>();
@@ -1577,69 +1578,45 @@ void prefetch_next_level(lsfm_context* ctx, const DevBatch& Y, const std::vector
 	Arena& sa = ctx->sarena[next_level & 1];
 	sa.reset();
 	// The joint maps' index arrays are final at evY: the pattern kernels start there, beside the level's right-hand-side kernels and
-	// K9.  Measured alternative (LSFM_PREFETCH_LATE=1): start them once K9 has left the main stream (evK), beside the
-	// factorisation's chain of small launches -- K9 then runs undisturbed (0.66 -> 0.58 ms per level) but the host gets its
-	// pattern 0.6 ms later at every level and the next level is enqueued late: 54.5 instead of 50.4 ms per tree.
-	static const bool late_start = getenv("LSFM_PREFETCH_LATE") != nullptr;
-	LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream3, late_start ? ctx->evK : ctx->evY, 0));
+	// K9.  Measured alternative: start them once K9 has left the main stream (evK), beside the factorisation's chain of small
+	// launches -- K9 then runs undisturbed (0.66 -> 0.58 ms per level) but the host gets its pattern 0.6 ms later at every level and
+	// the next level is enqueued late: 54.5 instead of 50.4 ms per tree.
+	LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream3, ctx->evY, 0));
 	if (ctx->timeline_on) { (void)hipEventSynchronize(ctx->evY); ctx->mark("pre_evY"); }
-	CholHostIn& hin = pl->hin;
 	std::vector<int> counts;
 	LevelIndex kept;
 	bool ok = false;
-	struct Swap { // this stretch runs on stream3 and allocates from the small arena of the level's parity
-		lsfm_context* c; Arena& a;
-		Swap(lsfm_context* x, Arena& y) : c(x), a(y) { std::swap(c->stream, c->stream3); std::swap(c->scratch, a); }
-		~Swap() { std::swap(c->scratch, a); std::swap(c->stream, c->stream3); }
-	};
 	{
-		Swap sw(ctx, sa);
+		OnStream on(ctx, ctx->stream3, &sa); // (the small arena of the level's parity)
 		int* d_tref = ctx->scratch.alloc<int>(Y.B);
 		h2d(ctx, d_tref, target_ref.data(), sizeof(int) * (size_t)Y.B);
 		ok = schur_pattern_prefetch(ctx, Y, d_tref, ctx->solved_keys, ctx->solved_nnzb, pl->sy, whole ? &counts : nullptr, !next_small, whole ? &kept : nullptr);
 		if (ok)
 		{
-			if (!next_small) chol_fetch(ctx, pl->sy, Y.pose_origin, hin); // (synchronises stream3: the counts have arrived too)
+			if (!next_small) chol_fetch(ctx, pl->sy, Y.pose_origin, pl->hin); // (synchronises stream3: the counts have arrived too)
 			LSFM_CHECK_HIP(hipEventRecord(ctx->evP, ctx->stream));
 		}
 	}
 	ctx->mark("pre_pat");
 	if (!ok) return;
-	if (next_small)
+	if (!next_small)
 	{
-		// the plan of a small level is its counts: its solve is one launch that asks the host nothing
-		const int B = Y.B;
-		ctx->pre_plan.tr_cnt.assign(counts.begin(), counts.begin() + 2 * (B + 1));
-		ctx->pre_plan.join_rb.assign(counts.begin() + 2 * (B + 1), counts.end());
-		ctx->pre_plan.solve.reset();
-		ctx->pre_plan.idx = kept;
-		ctx->pre_plan.valid = true;
-		ctx->pre_plan_level = next_level;
-		ctx->mark("pre_plan");
-		return;
-	}
-	// The symbolic factorisation is host work that only the level's FACTORISATION needs: it goes to the helper thread, and the
-	// caller enqueues the next level's transform, join and Schur assembly meanwhile -- they need the counts only, which arrived
-	// with the pattern.  (Done here, on this thread, the device sat idle 1-3 ms at every level boundary waiting for the next
-	// level to be enqueued: 9 of an analysing run's 50 ms.)  LSFM_NO_WORKER=1: on this thread, as before.
-	static const bool use_worker = !getenv("LSFM_NO_WORKER");
-	if (use_worker)
-	{
+		// The symbolic factorisation is host work that only the level's FACTORISATION needs: it goes to the helper thread, and the
+		// caller enqueues the next level's transform, join and Schur assembly meanwhile -- they need the counts only, which arrived
+		// with the pattern.  (Done here, on this thread, the device sat idle 1-3 ms at every level boundary waiting for the next
+		// level to be enqueued: 9 of an analysing run's 50 ms.)
 		if (!ctx->worker) ctx->worker.reset(new HostWorker());
-		PreLevel* raw = pl.get(); // (kept alive by ctx->pre / ctx->pre_pending until pre_wait has returned)
-		pl->on_worker = true;
+		PreLevel* raw = pl.get(); // (alive until its wait() has returned: ~PreLevel)
 		ctx->worker->run([raw]() { chol_symbolic(raw->hin.keys.data(), raw->sy.nnzb, raw->hin.origin.data(), raw->sy.M, raw->sym); });
-	}
-	else chol_symbolic(hin.keys.data(), pl->sy.nnzb, hin.origin.data(), pl->sy.M, pl->sym);
-	ctx->mark("pre_sym");
-	if (!whole)
-	{
+		pl->worker = ctx->worker.get();
+		ctx->mark("pre_sym");
+		pl->whole = whole; pl->level = next_level; pl->its = step_hint;
 		ctx->pre = pl;
-		return;
 	}
-	// the whole plan of the level: the counts as the host read them now; its solve part (index arrays of the factorisation to the
-	// device) is completed by the level's solve_batch -> pre_plan_complete
-	pl->whole = true; pl->level = next_level; pl->its = step_hint;
+	if (!whole) return;
+	// the whole plan of the level: the counts as the host read them now.  A small level's plan is its counts -- its solve is one launch
+	// that asks the host nothing; a sparse level's solve part (index arrays of the factorisation to the device) is completed by the
+	// level's solve_batch -> pre_plan_complete
 	const int B = Y.B;
 	ctx->pre_plan.tr_cnt.assign(counts.begin(), counts.begin() + 2 * (B + 1));
 	ctx->pre_plan.join_rb.assign(counts.begin() + 2 * (B + 1), counts.end());
@@ -1647,26 +1624,20 @@ void prefetch_next_level(lsfm_context* ctx, const DevBatch& Y, const std::vector
 	ctx->pre_plan.idx = kept;
 	ctx->pre_plan.valid = true;
 	ctx->pre_plan_level = next_level;
-	ctx->pre_pending = pl;
 	ctx->mark("pre_plan");
 }
 // the solve part of a plan made one level ahead: waits for the symbolic factorisation, sends its index arrays to the device (stream3,
 // the small arena of the level's parity) and makes the main stream wait for them
-static std::shared_ptr<void> pre_plan_complete(lsfm_context* ctx)
+static std::shared_ptr<SolvePlan> pre_plan_complete(lsfm_context* ctx, PreLevel& pl)
 {
-	std::shared_ptr<void> keep = ctx->pre_pending;
-	ctx->pre_pending.reset();
-	PreLevel* pl = static_cast<PreLevel*>(keep.get());
-	pre_wait(ctx, pl);
+	pl.wait();
 	auto sp = std::make_shared<SolvePlan>();
-	sp->sy = pl->sy;
-	sp->its = pl->its; sp->mixed = ctx->pcg.mixed; sp->rel_tol = ctx->pcg.rel_tol;
-	Arena& sa = ctx->sarena[pl->level & 1];
+	sp->sy = pl.sy;
+	sp->its = pl.its; sp->mixed = ctx->pcg.mixed; sp->rel_tol = ctx->pcg.rel_tol;
 	{
-		std::swap(ctx->stream, ctx->stream3); std::swap(ctx->scratch, sa);
-		try { chol_upload_index(ctx, pl->sym, sp->ch); LSFM_CHECK_HIP(hipEventRecord(ctx->evP, ctx->stream)); }
-		catch (...) { std::swap(ctx->scratch, sa); std::swap(ctx->stream, ctx->stream3); throw; }
-		std::swap(ctx->scratch, sa); std::swap(ctx->stream, ctx->stream3);
+		OnStream on(ctx, ctx->stream3, &ctx->sarena[pl.level & 1]);
+		chol_upload_index(ctx, pl.sym, sp->ch);
+		LSFM_CHECK_HIP(hipEventRecord(ctx->evP, ctx->stream));
 	}
 	LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->evP, 0));
 	return sp;
@@ -2046,219 +2017,261 @@ __global__ void k_chol_err_to_run(const int* err, RunStatsDev* run)
 	if (*err && !run->chol_err) run->chol_err = *err;
 }
 
+// LSFM_CHECK_EARLY_PATTERN=1 (debug / tests): a pattern put together ahead of the joint map must be the one built from the finished
+// joint map.  s: the stream the joint map's index arrays were written on
+static void check_pattern_made_ahead(lsfm_context* ctx, const SolveIO& io, const SchurSystem& sy, hipStream_t s, const char* what)
+{
+	if (!getenv("LSFM_CHECK_EARLY_PATTERN")) return;
+	LSFM_CHECK_HIP(hipStreamSynchronize(s));
+	SchurSystem ref;
+	build_schur_pattern(ctx, io, ref);
+	std::vector<unsigned long long> a(sy.nnzb), b(ref.nnzb);
+	d2h(ctx, a.data(), sy.upper_keys, a.size() * sizeof(unsigned long long));
+	d2h(ctx, b.data(), ref.upper_keys, b.size() * sizeof(unsigned long long));
+	if (a != b) LSFM_FAIL(LSFM_ERR_INTERNAL, std::string(what) + " pattern of S (" + std::to_string(a.size()) + " blocks) differs from the joint map's (" + std::to_string(b.size()) + ")");
+}
+
+// The structure of a level on the sparse pipeline, from wherever the level gets it: the camera system with its values assembled, the
+// factorisation ready to be scattered into (ch.d_err zeroed), evK recorded behind the Schur assembly.
+struct LevelStructure {
+	SchurSystem sy;
+	CholDev ch;
+	SolvePlan* sp = nullptr; // the level's plan (recorded by an earlier run of the tree, or made one level ahead); null: the level analysed
+	double tw0 = 0, tw1 = 0; // host clock around the analysis (LSFM_DEBUG)
+};
+static double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// sp: the plan an earlier run recorded (null: none); pre: what was prepared one level ahead (null: nothing), pending: it is this
+// level's whole plan, whose symbolic factorisation may still be under way on the helper thread
+static LevelStructure level_structure(lsfm_context* ctx, const SolveIO& io, SolvePlan* sp, PreLevel* pre, bool pending, hipEvent_t eb)
+{
+	hipStream_t s = ctx->stream;
+	Arena& sc = ctx->scratch;
+	LevelStructure ls;
+	SchurSystem& sy = ls.sy;
+	CholDev& ch = ls.ch;
+	// the caller's mark (evA) of the point where the joint map's index arrays were complete: consumed by whichever case runs
+	const bool pattern_dep = ctx->pattern_dep;
+	ctx->pattern_dep = false;
+	// K9 behind the pattern; the chain of the factorisation starts at evK
+	auto assemble = [&]() {
+		build_schur_values(ctx, io, sy);
+		LSFM_REC_T(eb, s); if (roctx().mark) roctx().mark("lsfm factor + refine: begin");
+		LSFM_CHECK_HIP(hipEventRecord(ctx->evK, s));
+	};
+	if (sp || pending)
+	{
+		// 1. a recorded plan / 2. a plan made one level ahead: the Schur assembly needs the pattern only, so it is enqueued before
+		// the host waits for the helper thread
+		sy = pending ? pre->sy : sp->sy;
+		schur_vinv(ctx, io, sy);
+		assemble();
+		if (pending)
+		{
+			ctx->mark("k9_enq");
+			ctx->plan->solve = pre_plan_complete(ctx, *pre);
+			sp = ctx->plan->solve.get();
+			ctx->mark("sym_wait");
+		}
+		ls.sp = sp;
+		ch = sp->ch;
+		chol_alloc_values(ctx, ch);
+		ch.d_err = sc.alloc<int>(1);
+		dev_zero(ctx, ch.d_err, sizeof(int));
+		return ls;
+	}
+	// the level analyses: pattern -> (copy it to the host) -> numeric assembly K9 enqueued -> symbolic factorisation on the host
+	// while K9 runs -> numeric factorisation
+	schur_vinv(ctx, io, sy);
+	CholHostIn hin;
+	bool have = false;
+	if (pre && !(pre->M == io.M && !ctx->comm)) pre = nullptr; // (not this level's: dropped by the caller)
+	if (pre)
+	{
+		// 3. prepared while the level below was being solved: pattern (device) and symbolic factorisation (host)
+		schur_pattern_early_drop(ctx);
+		SchurSystem prepared = pre->sy; // the index members; V^-1 and its factor are this level's (schur_vinv above)
+		prepared.IV = sy.IV; prepared.LY = sy.LY; prepared.ymax = sy.ymax; prepared.uu = sy.uu;
+		sy = prepared;
+		have = true;
+		LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->evP, 0));
+		check_pattern_made_ahead(ctx, io, sy, s, "prefetched");
+	}
+	else if (ctx->early && !ctx->comm)
+	{
+		// 4. the pattern was put together on stream3 from the level's inputs while the transform ran (a Stereo level that
+		// analyses): its second half, and the copy of it for the host's analysis, stay there
+		LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream3, ctx->evC, 0)); // (recorded again once the joint run pointers were enqueued)
+		{
+			OnStream on(ctx, ctx->stream3);
+			ctx->mark("sv_start");
+			have = schur_pattern_early_finish(ctx, io, sy);
+			ctx->mark("pat_fin");
+			if (have)
+			{
+				check_pattern_made_ahead(ctx, io, sy, s, "early");
+				chol_fetch(ctx, sy, io.d_pose_origin, hin);
+				ctx->mark("fetch");
+				schur_pattern_early_extras(ctx, io, sy);
+				LSFM_CHECK_HIP(hipEventRecord(ctx->evB, ctx->stream));
+			}
+		}
+		if (have) LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->evB, 0));
+	}
+	else if (pattern_dep && !ctx->comm)
+	{
+		// 5. the pattern depends on index arrays only: the caller marked the point of the main stream where those were complete
+		// (evA) and went on to enqueue its right-hand-side kernels -- the pattern is built on the side stream next to them
+		LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream2, ctx->evA, 0));
+		{
+			OnStream on(ctx, ctx->stream2);
+			build_schur_pattern(ctx, io, sy);
+			chol_fetch(ctx, sy, io.d_pose_origin, hin);
+			LSFM_CHECK_HIP(hipEventRecord(ctx->evB, ctx->stream));
+		}
+		LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->evB, 0));
+		have = true;
+	}
+	if (!have)
+	{
+		// 6. in line, on the main stream (a feature-sharded run; an early build whose table overflowed)
+		build_schur_pattern(ctx, io, sy);
+		chol_fetch(ctx, sy, io.d_pose_origin, hin);
+	}
+	assemble();
+	ls.tw0 = wall_ms();
+	ctx->mark("k9_enq");
+	if (pre) { pre->wait(); chol_upload_symbolic(ctx, pre->sym, ch); }
+	else chol_analyse(ctx, sy, hin, ch);
+	ctx->mark("analyse");
+	ls.tw1 = wall_ms();
+	return ls;
+}
+
+// A level of small systems (at most 16 poses each): assembled, factored and solved by one launch (lsfm_small.hip) -- no pattern of S,
+// no symbolic factorisation; the level above builds its pattern from its own joint maps when this one leaves none
+// (schur_pattern_prefetch / k_pat_insert_w_early).  warm: the level has a recorded plan (SolvePlan::small)
+static int solve_level_dense(lsfm_context* ctx, const SolveIO& io, int strips, bool warm, hipEvent_t eb, hipEvent_t ec, hipEvent_t ed)
+{
+	hipStream_t s = ctx->stream;
+	LevelPlan* lp = ctx->plan;
+	ctx->pattern_dep = false;
+	if (!warm) schur_pattern_early_drop(ctx);
+	int* d_small = nullptr; // [2] status of the small path + (as a double behind them) the level's largest relative residual
+	auto enqueue = [&]() {
+		d_small = ctx->scratch.alloc<int>(4);
+		dev_zero(ctx, d_small, 4 * sizeof(int));
+		hipEvent_t esm0 = nullptr, esm1 = nullptr;
+		if (ctx->stats) { esm0 = ctx->pool_event(); esm1 = ctx->pool_event(); LSFM_REC_T(esm0, s); }
+		small_solve_launch(ctx, io, strips, d_small, reinterpret_cast<double*>(d_small + 2));
+		if (ctx->stats) { LSFM_REC_T(esm1, s); ctx->defer_time(esm0, esm1, &ctx->stats->t_small_ms); ctx->stats->small_levels++; }
+	};
+	// (a planned level brackets its launch like a level on the sparse pipeline brackets its factorisation)
+	if (!warm) enqueue();
+	LSFM_REC_T(eb, s); if (warm && roctx().mark) roctx().mark("lsfm factor + refine: begin");
+	LSFM_CHECK_HIP(hipEventRecord(ctx->evK, s));
+	if (warm) enqueue();
+	LSFM_REC_T(ec, s);
+	LSFM_REC_T(ed, s); if (roctx().mark) roctx().mark("lsfm solve: end");
+	ctx->ev_solve_end = ed;
+	ctx->solved_keys = nullptr; ctx->solved_nnzb = 0; // (no pattern left for the level above)
+	if (ctx->stats) ctx->stats->pcg_iterations += 1;
+	ctx->steps_used = 1;
+	// (a plan made one level ahead is the run's own: nothing to record, nothing to stop for)
+	const bool deferred = ctx->in_tree_run && ctx->d_run && (warm || !lp || lp == &ctx->pre_plan);
+	if (deferred) return 0; // the kernel left its verdict in the run's device record (read at the end of the run)
+	int hs[4];
+	d2h_ints(ctx, d_small, hs, 4); // synchronises
+	if (hs[1]) LSFM_FAIL(LSFM_ERR_NOT_SPD, "Schur system is not positive definite (system " + std::to_string(hs[1] - 1) + " of the level)");
+	double mr;
+	memcpy(&mr, hs + 2, sizeof mr);
+	if (ctx->stats) ctx->stats->max_rel_residual = std::max(ctx->stats->max_rel_residual, mr);
+	if (lp && !lp->solve && hs[0] == 0)
+	{
+		// the plan of a small level: nothing but the fact that it is one (the structure of its solve is the batch's offsets)
+		auto small_plan = std::make_shared<SolvePlan>();
+		small_plan->its = 1; small_plan->mixed = false; small_plan->rel_tol = ctx->pcg.rel_tol; small_plan->small = true;
+		lp->solve = small_plan;
+	}
+	return hs[0];
+}
+
+// LSFM_FACTOR_DIGEST=1 (tests): digests of S and of the factor into the run's device record, and -- one GPU -- the same system
+// assembled and factored a second time: the bits must not depend on the order in which the work-groups land their sums
+static void factor_digest_check(lsfm_context* ctx, const SolveIO& io, const SchurSystem& sy, CholDev& ch)
+{
+	static const bool digest = getenv("LSFM_FACTOR_DIGEST") != nullptr;
+	if (!digest || !ctx->d_run) return;
+	hipStream_t s = ctx->stream;
+	Arena& sc = ctx->scratch;
+	const int M = io.M;
+	auto dg = [&](const double* a, size_t n, unsigned long long* out) {
+		if (a && n) hipLaunchKernelGGL(k_digest, dim3(256), dim3(256), 0, s, n, reinterpret_cast<const unsigned long long*>(a), out);
+	};
+	dg(sy.S, (size_t)sy.nnzb * 36, &ctx->d_run->s_digest);
+	if (!ctx->comm)
+	{
+		// the SAME camera systems assembled a second time (U scatter, K9 with all its variants, the fallback kernel): their
+		// work-groups land their sums in another order -- the bits of S and E must not depend on it (fixed-point sums,
+		// lsfm_schur_panel.hip).  (The stage timings and flop counts of the run count this second assembly too: a debug mode.)
+		SchurSystem sy2 = sy;
+		build_schur_values(ctx, io, sy2);
+		unsigned long long* d = sc.alloc<unsigned long long>(2);
+		dev_zero(ctx, d, 2 * sizeof(unsigned long long));
+		dg(sy.S, (size_t)sy.nnzb * 36, d); dg(sy.E, (size_t)M * 6, d);
+		dg(sy2.S, (size_t)sy.nnzb * 36, d + 1); dg(sy2.E, (size_t)M * 6, d + 1);
+		hipLaunchKernelGGL(k_digest_compare, dim3(1), dim3(1), 0, s, d, &ctx->d_run->s_rebuild_mismatch);
+	}
+	// leaf columns: factored in place in L; group columns: in Lg (their slots of L hold the spent accumulators: integers, summed alike)
+	auto factor_digest = [&](unsigned long long* out) {
+		dg(ch.Dinv, (size_t)ch.M * 36, out);
+		dg(ch.L, (size_t)ch.nnzL * 36, out);
+		if (ch.Lg) dg(ch.Lg, (size_t)ch.nnzL * 36, out);
+	};
+	factor_digest(&ctx->d_run->factor_digest);
+	if (!ctx->comm)
+	{
+		// ... and the SAME system factored a second time (its work-groups will be scheduled differently, the atomics land in another
+		// order): the two factors must be the same bits.  d[0], d[1]: the digests of this system's two factors alone
+		unsigned long long* d = sc.alloc<unsigned long long>(2);
+		dev_zero(ctx, d, 2 * sizeof(unsigned long long));
+		factor_digest(d);
+		dev_zero(ctx, ch.L, (size_t)ch.nnzL * 36 * sizeof(double));
+		if (ch.Lg) dev_zero(ctx, ch.Lg, (size_t)ch.nnzL * 36 * sizeof(double));
+		chol_scatter(ctx, sy, io.d_fixed, ch);
+		chol_factor(ctx, sy, io.d_fixed, ch, nullptr);
+		factor_digest(d + 1);
+		hipLaunchKernelGGL(k_digest_compare, dim3(1), dim3(1), 0, s, d, &ctx->d_run->refactor_mismatch);
+	}
+}
+
 int solve_batch(lsfm_context* ctx, const SolveIO& io)
 {
 	hipStream_t s = ctx->stream;
 	Arena& sc = ctx->scratch;
 	const int M = io.M, nseg = io.nseg;
 	LevelPlan* lp = ctx->plan;
-	// a plan made one level ahead whose symbolic factorisation may still be under way on the helper thread: the Schur assembly
-	// needs the pattern only, so it is enqueued first
-	PreLevel* pending = (lp && lp == &ctx->pre_plan && !lp->solve && ctx->pre_pending) ? static_cast<PreLevel*>(ctx->pre_pending.get()) : nullptr;
-	if (!pending && ctx->pre_pending) { pre_wait(ctx, static_cast<PreLevel*>(ctx->pre_pending.get())); ctx->pre_pending.reset(); } // (not this level's: dropped)
-	// a level of small systems (at most 16 poses each): assembled, factored and solved by one launch (lsfm_small.hip).  The pattern of
-	// S and its symbolic analysis are still made -- the levels above build theirs on them, and a plan of the level keeps them
 	int most_rows = 0;
 	for (int rws : io.seg_rows) most_rows = std::max(most_rows, rws);
-	const int strips = (ctx->small_max > 0 && !ctx->comm && !ctx->pcg.mixed && io.d_pose_off && io.d_feat_off && io.d_u_off && !getenv("LSFM_NO_SMALL"))
-	                       ? small_solve_strips(most_rows, ctx->small_max) : 0;
-	SolvePlan* sp = lp ? static_cast<SolvePlan*>(lp->solve.get()) : nullptr;
+	const int strips = (io.d_pose_off && io.d_feat_off && io.d_u_off) ? small_level_strips(ctx, most_rows) : 0;
+	SolvePlan* sp = lp ? lp->solve.get() : nullptr;
 	// (a plan recorded on the other path -- lsfm_set_small_solve was changed between two runs of a resident tree -- is void)
 	if (sp && sp->small != (strips > 0)) { lp->solve.reset(); sp = nullptr; }
-	const bool warm = sp != nullptr || pending != nullptr; // pattern + symbolic factorisation known from an earlier run of the same tree level (or made one level ahead)
+	// what was prepared one level ahead leaves the context here; wherever it is dropped, its release waits for the helper thread.
+	// pending: it is this level's whole plan, whose symbolic factorisation may still be under way there
+	std::shared_ptr<PreLevel> pre = std::move(ctx->pre);
+	const bool pending = !strips && !sp && pre && pre->whole && lp == &ctx->pre_plan;
+	if (pre && !pending && (strips || sp || pre->whole || pre->M != M || ctx->comm)) pre.reset(); // (not this level's, or of no use to it)
+	const bool warm = sp != nullptr || pending; // pattern + symbolic factorisation known from an earlier run of the same tree level (or made one level ahead)
 	hipEvent_t ea = ctx->pool_event(), eb = ctx->pool_event(), ec = ctx->pool_event(), ed = ctx->pool_event();
 	LSFM_REC_T(ea, s); if (roctx().mark) roctx().mark("lsfm schur: begin");
-	SchurSystem sy;
-	CholDev ch;
-	CholHostIn hin;
+	if (strips) return solve_level_dense(ctx, io, strips, warm, eb, ec, ed);
+	LevelStructure ls = level_structure(ctx, io, sp, pre.get(), pending, eb);
+	pre.reset();
+	const SchurSystem& sy = ls.sy;
+	CholDev& ch = ls.ch;
+	sp = ls.sp;
+	int* const d_err = ch.d_err;
 	const bool dbg = getenv("LSFM_DEBUG") != nullptr;
-	auto wall = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-	double tw0 = 0, tw1 = 0;
-	int* d_err = nullptr;
-	int* d_small = nullptr; // [2] status of the small path + (as a double behind them) the level's largest relative residual
-	hipEvent_t esm0 = nullptr, esm1 = nullptr;
-	auto small_enqueue = [&]() {
-		d_small = sc.alloc<int>(4);
-		dev_zero(ctx, d_small, 4 * sizeof(int));
-		if (ctx->stats) { esm0 = ctx->pool_event(); esm1 = ctx->pool_event(); LSFM_REC_T(esm0, s); }
-		small_solve_launch(ctx, io, strips, d_small, reinterpret_cast<double*>(d_small + 2));
-		if (ctx->stats) { LSFM_REC_T(esm1, s); ctx->defer_time(esm0, esm1, &ctx->stats->t_small_ms); ctx->stats->small_levels++; }
-	};
-	if (warm)
-	{
-		ctx->pattern_dep = false;
-		sy = pending ? pending->sy : sp->sy;
-		if (!strips)
-		{
-			schur_vinv(ctx, io, sy);
-			build_schur_values(ctx, io, sy);
-		}
-		LSFM_REC_T(eb, s); if (roctx().mark) roctx().mark("lsfm factor + refine: begin");
-		LSFM_CHECK_HIP(hipEventRecord(ctx->evK, s));
-		if (pending)
-		{
-			ctx->mark("k9_enq");
-			lp->solve = pre_plan_complete(ctx);
-			sp = static_cast<SolvePlan*>(lp->solve.get());
-			ctx->mark("sym_wait");
-		}
-		ch = sp->ch;
-		if (!strips)
-		{
-			chol_alloc_values(ctx, ch);
-			d_err = ch.d_err = sc.alloc<int>(1);
-			dev_zero(ctx, d_err, sizeof(int));
-		}
-	}
-	else
-	{
-		// pattern -> (copy it to the host) -> numeric assembly K9 enqueued -> symbolic factorisation on the host while K9
-		// runs -> numeric factorisation
-		// The pattern depends on index arrays only.  When the caller marked the point of the main stream where those were
-		// complete (evA) and went on to enqueue its right-hand-side kernels, the pattern is built on the side stream next
-		// to them; the values wait for both.
-		static const bool side = !getenv("LSFM_NO_SIDE_STREAM");
-		if (strips)
-		{
-			// no pattern of S, no symbolic factorisation: the dense path needs neither, and the level above builds its pattern from
-			// its own joint maps when this one leaves none (schur_pattern_prefetch / k_pat_insert_w_early)
-			ctx->pattern_dep = false;
-			schur_pattern_early_drop(ctx);
-			if (ctx->pre) { std::shared_ptr<void> keep = ctx->pre; ctx->pre.reset(); pre_wait(ctx, static_cast<PreLevel*>(keep.get())); }
-			small_enqueue();
-			LSFM_REC_T(eb, s);
-			LSFM_CHECK_HIP(hipEventRecord(ctx->evK, s));
-			goto small_tail;
-		}
-		schur_vinv(ctx, io, sy);
-		bool have = false;
-		std::shared_ptr<void> pre_keep = ctx->pre;
-		ctx->pre.reset();
-		PreLevel* pre = static_cast<PreLevel*>(pre_keep.get());
-		// (drop_prepared() no longer sees the object: whatever throws below, it must not go while the helper thread still works on it)
-		struct PreGuard { lsfm_context* c; PreLevel* p; ~PreGuard() { try { pre_wait(c, p); } catch (...) {} } } pre_guard{ ctx, pre };
-		if (pre && !(pre->M == M && !ctx->comm)) pre_wait(ctx, pre); // (not used: nothing of it may go while the helper thread reads it)
-		if (pre && pre->M == M && !ctx->comm)
-		{
-			// prepared while the level below was being solved: pattern (device) and symbolic factorisation (host)
-			ctx->pattern_dep = false;
-			schur_pattern_early_drop(ctx);
-			{
-				SchurSystem prepared = pre->sy; // the index members; V^-1 and its factor are this level's (schur_vinv above)
-				prepared.IV = sy.IV; prepared.LY = sy.LY; prepared.ymax = sy.ymax; prepared.uu = sy.uu;
-				sy = prepared;
-			}
-			have = true;
-			LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->evP, 0));
-			if (getenv("LSFM_CHECK_EARLY_PATTERN"))
-			{
-				LSFM_CHECK_HIP(hipStreamSynchronize(s));
-				SchurSystem ref;
-				build_schur_pattern(ctx, io, ref);
-				std::vector<unsigned long long> a(sy.nnzb), b(ref.nnzb);
-				d2h(ctx, a.data(), sy.upper_keys, a.size() * sizeof(unsigned long long));
-				d2h(ctx, b.data(), ref.upper_keys, b.size() * sizeof(unsigned long long));
-				if (a != b) LSFM_FAIL(LSFM_ERR_INTERNAL, "prefetched pattern of S (" + std::to_string(a.size()) + " blocks) differs from the joint map's (" + std::to_string(b.size()) + ")");
-			}
-		}
-		else pre = nullptr;
-		if (have) {}
-		else if (ctx->early && !ctx->comm)
-		{
-			// the pattern was put together on the side stream from the level's inputs while the transform ran (a Stereo level
-			// that analyses): its second half, and the copy of it for the host's analysis, stay there
-			ctx->pattern_dep = false;
-			LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream3, ctx->evC, 0)); // (recorded again once the joint run pointers were enqueued)
-			std::swap(ctx->stream, ctx->stream3);
-			ctx->mark("sv_start");
-			try
-			{
-				have = schur_pattern_early_finish(ctx, io, sy);
-				ctx->mark("pat_fin");
-				if (have)
-				{
-					if (getenv("LSFM_CHECK_EARLY_PATTERN"))
-					{
-						// debug / test: the pattern built from the finished joint map must be the same one
-						LSFM_CHECK_HIP(hipStreamSynchronize(ctx->stream3)); // (the main stream, swapped out: the joint map's index arrays)
-						SchurSystem ref;
-						build_schur_pattern(ctx, io, ref);
-						std::vector<unsigned long long> a(sy.nnzb), b(ref.nnzb);
-						d2h(ctx, a.data(), sy.upper_keys, a.size() * sizeof(unsigned long long));
-						d2h(ctx, b.data(), ref.upper_keys, b.size() * sizeof(unsigned long long));
-						if (a != b) LSFM_FAIL(LSFM_ERR_INTERNAL, "early pattern of S (" + std::to_string(a.size()) + " blocks) differs from the joint map's (" + std::to_string(b.size()) + ")");
-					}
-					chol_fetch(ctx, sy, io.d_pose_origin, hin);
-					ctx->mark("fetch");
-					schur_pattern_early_extras(ctx, io, sy);
-					LSFM_CHECK_HIP(hipEventRecord(ctx->evB, ctx->stream));
-				}
-			}
-			catch (...) { std::swap(ctx->stream, ctx->stream3); throw; }
-			std::swap(ctx->stream, ctx->stream3);
-			if (have) LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->evB, 0));
-		}
-		if (have) {}
-		else if (side && ctx->pattern_dep && !ctx->comm)
-		{
-			ctx->pattern_dep = false;
-			LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream2, ctx->evA, 0));
-			std::swap(ctx->stream, ctx->stream2);
-			try
-			{
-				build_schur_pattern(ctx, io, sy);
-				chol_fetch(ctx, sy, io.d_pose_origin, hin);
-				LSFM_CHECK_HIP(hipEventRecord(ctx->evB, ctx->stream));
-			}
-			catch (...) { std::swap(ctx->stream, ctx->stream2); throw; }
-			std::swap(ctx->stream, ctx->stream2);
-			LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->evB, 0));
-		}
-		else
-		{
-			ctx->pattern_dep = false;
-			build_schur_pattern(ctx, io, sy);
-			chol_fetch(ctx, sy, io.d_pose_origin, hin);
-		}
-		build_schur_values(ctx, io, sy);
-		LSFM_REC_T(eb, s); if (roctx().mark) roctx().mark("lsfm factor + refine: begin");
-		LSFM_CHECK_HIP(hipEventRecord(ctx->evK, s));
-		tw0 = wall();
-		ctx->mark("k9_enq");
-		if (pre) { pre_wait(ctx, pre); chol_upload_symbolic(ctx, pre->sym, ch); }
-		else chol_analyse(ctx, sy, hin, ch);
-		ctx->mark("analyse");
-		tw1 = wall();
-		d_err = ch.d_err;
-	}
-small_tail:
-	if (strips)
-	{
-		if (warm) small_enqueue();
-		LSFM_REC_T(ec, s);
-		LSFM_REC_T(ed, s); if (roctx().mark) roctx().mark("lsfm solve: end");
-		ctx->ev_solve_end = ed;
-		ctx->solved_keys = nullptr; ctx->solved_nnzb = 0; // (no pattern left for the level above)
-		if (ctx->stats) ctx->stats->pcg_iterations += 1;
-		ctx->steps_used = 1;
-		// (a plan made one level ahead is the run's own: nothing to record, nothing to stop for)
-		const bool deferred = ctx->in_tree_run && ctx->d_run && (warm || !lp || lp == &ctx->pre_plan);
-		if (deferred) return 0; // the kernel left its verdict in the run's device record (read at the end of the run)
-		int hs[4];
-		d2h_ints(ctx, d_small, hs, 4); // synchronises
-		if (hs[1]) LSFM_FAIL(LSFM_ERR_NOT_SPD, "Schur system is not positive definite (system " + std::to_string(hs[1] - 1) + " of the level)");
-		double mr;
-		memcpy(&mr, hs + 2, sizeof mr);
-		if (ctx->stats) ctx->stats->max_rel_residual = std::max(ctx->stats->max_rel_residual, mr);
-		if (lp && !lp->solve && hs[0] == 0)
-		{
-			// the plan of a small level: nothing but the fact that it is one (the structure of its solve is the batch's offsets)
-			auto small_plan = std::make_shared<SolvePlan>();
-			small_plan->its = 1; small_plan->mixed = false; small_plan->rel_tol = ctx->pcg.rel_tol; small_plan->small = true;
-			lp->solve = small_plan;
-		}
-		return hs[0];
-	}
 	// ---- CG set-up first: the residual of the starting point is the right-hand side of the first preconditioner
 	// application, whose forward substitution rides on the factorisation (k_sn_panel) ----
 	int* d_misc = sc.alloc<int>(4); // [1] ndone (zeroed by k_x_init)
@@ -2304,50 +2317,9 @@ small_tail:
 		}
 		hipLaunchKernelGGL(k_to_float, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, s, nd, ch.Dinv, ch.Dinvf);
 	}
-	static const bool digest = getenv("LSFM_FACTOR_DIGEST") != nullptr;
-	if (digest && ctx->d_run)
-	{
-		auto dg = [&](const double* a, size_t n, unsigned long long* out) {
-			if (a && n) hipLaunchKernelGGL(k_digest, dim3(256), dim3(256), 0, s, n, reinterpret_cast<const unsigned long long*>(a), out);
-		};
-		dg(sy.S, (size_t)sy.nnzb * 36, &ctx->d_run->s_digest);
-		if (!ctx->comm)
-		{
-			// the SAME camera systems assembled a second time (U scatter, K9 with all its variants, the fallback kernel): their
-			// work-groups land their sums in another order -- the bits of S and E must not depend on it (fixed-point sums,
-			// lsfm_schur_panel.hip).  (The stage timings and flop counts of the run count this second assembly too: a debug mode.)
-			SchurSystem sy2 = sy;
-			build_schur_values(ctx, io, sy2);
-			unsigned long long* d = sc.alloc<unsigned long long>(2);
-			dev_zero(ctx, d, 2 * sizeof(unsigned long long));
-			dg(sy.S, (size_t)sy.nnzb * 36, d); dg(sy.E, (size_t)M * 6, d);
-			dg(sy2.S, (size_t)sy.nnzb * 36, d + 1); dg(sy2.E, (size_t)M * 6, d + 1);
-			hipLaunchKernelGGL(k_digest_compare, dim3(1), dim3(1), 0, s, d, &ctx->d_run->s_rebuild_mismatch);
-		}
-		// leaf columns: factored in place in L; group columns: in Lg (their slots of L hold the spent accumulators: integers, summed alike)
-		auto factor_digest = [&](unsigned long long* out) {
-			dg(ch.Dinv, (size_t)ch.M * 36, out);
-			dg(ch.L, (size_t)ch.nnzL * 36, out);
-			if (ch.Lg) dg(ch.Lg, (size_t)ch.nnzL * 36, out);
-		};
-		factor_digest(&ctx->d_run->factor_digest);
-		if (!ctx->comm)
-		{
-			// ... and the SAME system factored a second time (its work-groups will be scheduled differently, the atomics land in another
-			// order): the two factors must be the same bits.  d[0], d[1]: the digests of this system's two factors alone
-			unsigned long long* d = sc.alloc<unsigned long long>(2);
-			dev_zero(ctx, d, 2 * sizeof(unsigned long long));
-			factor_digest(d);
-			dev_zero(ctx, ch.L, (size_t)ch.nnzL * 36 * sizeof(double));
-			if (ch.Lg) dev_zero(ctx, ch.Lg, (size_t)ch.nnzL * 36 * sizeof(double));
-			chol_scatter(ctx, sy, io.d_fixed, ch);
-			chol_factor(ctx, sy, io.d_fixed, ch, nullptr);
-			factor_digest(d + 1);
-			hipLaunchKernelGGL(k_digest_compare, dim3(1), dim3(1), 0, s, d, &ctx->d_run->refactor_mismatch);
-		}
-	}
+	factor_digest_check(ctx, io, sy, ch);
 	if (dbg) { LSFM_CHECK_HIP(hipStreamSynchronize(s)); }
-	double tw2 = wall();
+	const double tw2 = wall_ms();
 	chol_apply(ctx, ch, r, v, z, io.d_fixed, io.d_pose_seg, &seg[0].rz[0], SEG_STRIDE, fused_fwd);
 	hipLaunchKernelGGL(k_copy, dim3(nbe), dim3(256), 0, s, nscal, z, p);
 	// (Ap is zero again: k_pcg_resid leaves it so)
@@ -2457,7 +2429,7 @@ small_tail:
 	{
 		LSFM_CHECK_HIP(hipStreamSynchronize(s));
 		fprintf(stderr, "[lsfm] solve M=%d nseg=%d nnzb=%d nnzL=%d etree levels=%d tail=%d leaf tasks=%d group levels=%d %s| analyse %.2f ms, factor %.2f ms, cg(%d its) %.2f ms\n", M, nseg,
-		        sy.nnzb, ch.nnzL, ch.nlevels, ch.M - ch.tail_begin, ch.ntask0, (int)ch.glevel_ptr.size() - 1, warm ? "(plan) " : "", tw1 - tw0, tw2 - tw1, its, wall() - tw2);
+		        sy.nnzb, ch.nnzL, ch.nlevels, ch.M - ch.tail_begin, ch.ntask0, (int)ch.glevel_ptr.size() - 1, warm ? "(plan) " : "", ls.tw1 - ls.tw0, tw2 - ls.tw1, its, wall_ms() - tw2);
 	}
 	if (ctx->comm)
 	{
@@ -2476,8 +2448,7 @@ small_tail:
 	// gone -- except in a feature-sharded run, whose x has just been replaced by rank 0's.  One of the loop's products is timed with
 	// HIP events (es0, es1).  Nothing here waits for the device before the back-substitution is enqueued ----
 	const int nsample = 1;
-	static const bool final_again = getenv("LSFM_FINAL_RESIDUAL") != nullptr; // (as until round 6: for comparison)
-	if (ctx->comm || !es_done || final_again)
+	if (ctx->comm || !es_done)
 	{
 		PcgSeg* seg2 = seg + nseg;
 		if (!es_done) LSFM_REC_T(es0, s);

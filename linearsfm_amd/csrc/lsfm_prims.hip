@@ -87,19 +87,16 @@ void* Arena::alloc_bytes(size_t bytes)
 	return base + a;
 }
 
-namespace {
 struct IndexHold {
 	std::vector<void*> p;
 	~IndexHold() { for (void* q : p) (void)hipFree(q); }
 };
-} // namespace
 const int* level_index_keep(lsfm_context* ctx, LevelIndex& li, const int* src, size_t n)
 {
 	if (!li.own) li.own = std::make_shared<IndexHold>();
-	IndexHold* h = static_cast<IndexHold*>(li.own.get());
 	void* d = nullptr;
 	LSFM_CHECK_HIP(hipMalloc(&d, std::max<size_t>(n, 1) * sizeof(int)));
-	h->p.push_back(d);
+	li.own->p.push_back(d);
 	if (n) LSFM_CHECK_HIP(hipMemcpyAsync(d, src, n * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
 	return static_cast<const int*>(d);
 }
@@ -376,11 +373,10 @@ namespace lsfm {
 // release -- cache write-back and invalidation for the HOST's sake -- and the kernel behind it starts 5-15 us late (rocprofv3
 // kernel trace of round 5: every gap of that size on the main queue sat at a hipEventRecord).  Nothing here needs that: the events that
 // bracket phases are read by hipEventElapsedTime after the run's stream synchronisation, the others order streams of ONE device
-// (device-scope release); what the host reads it reads behind a stream synchronisation of its own.  LSFM_EVENTS_DEFAULT=1: as before.
-static bool events_default() { static const bool v = getenv("LSFM_EVENTS_DEFAULT") != nullptr; return v; }
+// (device-scope release); what the host reads it reads behind a stream synchronisation of its own.
 bool no_timing_events() { static const bool v = getenv("LSFM_NO_TIMING_EVENTS") != nullptr; return v; }
-unsigned timing_event_flags() { return events_default() ? hipEventDefault : hipEventDisableSystemFence; }
-unsigned order_event_flags() { return events_default() ? hipEventDisableTiming : (hipEventDisableTiming | hipEventReleaseToDevice); }
+unsigned timing_event_flags() { return hipEventDisableSystemFence; }
+unsigned order_event_flags() { return hipEventDisableTiming | hipEventReleaseToDevice; }
 }
 hipEvent_t lsfm_context::pool_event()
 {
@@ -407,7 +403,7 @@ void lsfm_context::flush_times()
 static void alloc_arenas(lsfm_context* c, size_t bytes_each)
 {
 	// The helper thread may still be analysing the level an error interrupted (prefetch_next_level hands it a raw pointer into what
-	// ctx->pre / ctx->pre_pending keep alive, and its index arrays live in sarena[]): wait for it and forget what was prepared BEFORE
+	// ctx->pre keeps alive, and its index arrays live in sarena[]): wait for it and forget what was prepared BEFORE
 	// anything is freed -- grow_arenas() is called from the handler of an LSFM_ERR_OOM thrown mid-level
 	c->drop_prepared();
 	c->early.reset(); c->solved_keys = nullptr; c->solved_nnzb = 0; // (pointers into the arenas about to go)

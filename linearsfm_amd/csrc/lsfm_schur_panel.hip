@@ -853,16 +853,11 @@ void launch_schur_panel(lsfm_context* ctx, int NF, const int* fptr, const int* p
 	// Measured and dropped: streams of their own for the variants (five streams on the context slowed EVERY launch of the run down,
 	// 40 -> 55 ms per tree); the next-level stream (it has the pattern of the next level queued at this point); a head start for
 	// part of the 32-slot list (7.9 -> 8.4); everything in one stream (8.5-9.1); half / twice as many work-groups on the lists.
-	// LSFM_K9_SERIAL=1: one stream.
-	static const bool serial = getenv("LSFM_K9_SERIAL") != nullptr;
 	static const int ncu = []() { int d = 0, n = 0; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
-	hipStream_t s1 = serial ? s : ctx->stream2;
+	hipStream_t s1 = ctx->stream2;
 	if (!fresh_lists) fill_async(s, kc.wcnt + 4, 0, 4 * sizeof(int)); // the variants' cursors into their lists (k_schur_lists zeroes them when it has just run)
-	if (!serial)
-	{
-		LSFM_CHECK_HIP(hipEventRecord(ctx->ev_k9[0], s));
-		LSFM_CHECK_HIP(hipStreamWaitEvent(s1, ctx->ev_k9[0], 0));
-	}
+	LSFM_CHECK_HIP(hipEventRecord(ctx->ev_k9[0], s));
+	LSFM_CHECK_HIP(hipStreamWaitEvent(s1, ctx->ev_k9[0], 0));
 	const dim3 wgrid(std::min(ntiles, ncu));
 	// (widest first: a work-group of the 64-slot variant needs a CU's whole LDS to start -- behind the others it would wait for the
 	// 16-slot variant to drain even when its list is empty)
@@ -870,11 +865,8 @@ void launch_schur_panel(lsfm_context* ctx, int NF, const int* fptr, const int* p
 	hipLaunchKernelGGL((k_schur_panel<PM_SMAX_BIG, PM_WIDE, true>), wgrid, dim3(PM_WIDE), 0, s, NF, fptr, photo, W, LY, tab, val, mask, out, fallback, 0, kc.wlist + ntiles, kc.wcnt + 1, kc.wcnt + 5, 0, kc);
 	hipLaunchKernelGGL((k_schur_panel<PM_SMAX, LSFM_K9_T32, true>), wgrid, dim3(LSFM_K9_T32), 0, s, NF, fptr, photo, W, LY, tab, val, mask, out, fallback, 0, kc.wlist, kc.wcnt, kc.wcnt + 4, 0, kc);
 	hipLaunchKernelGGL((k_schur_panel<16, LSFM_K9_T16, false>), grid, dim3(LSFM_K9_T16), 0, s1, NF, fptr, photo, W, LY, tab, val, mask, out, fallback, 0, none, none, (int*)nullptr, 0, kc);
-	if (!serial)
-	{
-		LSFM_CHECK_HIP(hipEventRecord(ctx->ev_k9[1], s1));
-		LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->ev_k9[1], 0));
-	}
+	LSFM_CHECK_HIP(hipEventRecord(ctx->ev_k9[1], s1));
+	LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->ev_k9[1], 0));
 }
 
 } // namespace lsfm

@@ -465,7 +465,7 @@ k_small_solve(SmallArgs a)
 }
 
 // strips of 16 rows that hold 6 * most scalars; 0: too large for this path
-int small_solve_strips(int most_poses, int cap)
+static int small_solve_strips(int most_poses, int cap)
 {
 	if (most_poses > cap) return 0;
 	if (most_poses <= 2) return 1;
@@ -473,6 +473,10 @@ int small_solve_strips(int most_poses, int cap)
 	if (most_poses <= 8) return 3;
 	if (most_poses <= 16) return 6;
 	return 0;
+}
+int small_level_strips(const lsfm_context* ctx, int most_rows)
+{
+	return (ctx->small_max > 0 && !ctx->comm && !ctx->pcg.mixed) ? small_solve_strips(most_rows, ctx->small_max) : 0;
 }
 
 template <int NTR>

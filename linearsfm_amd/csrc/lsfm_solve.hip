@@ -1046,29 +1046,6 @@ k_pat_insert_w_early(int NFY, const int* __restrict__ srcE, const int* __restric
 	}
 }
 
-// the pairs across the two sources of a matched joint feature (everything else of the level's pattern is in the pattern of the
-// level below or a hub link): (poses of End's run + End's hub) x (poses of Cur's run + Cur's hub)
-__global__ void __launch_bounds__(256)
-k_pat_insert_w_cross(int NFY, const int* __restrict__ srcE, const int* __restrict__ srcC, const int* __restrict__ fptr, const int* __restrict__ photo,
-                     const int* __restrict__ feat_map, const int* __restrict__ hub, unsigned long long* tab, unsigned long long mask, int* overflow)
-{
-	const int nf = blockIdx.x * blockDim.x + threadIdx.x;
-	if (nf >= NFY) return;
-	const int fe = srcE[nf], fc = srcC[nf];
-	if (fe < 0 || fc < 0) return;
-	const int jE = fptr[fe], lenE = fptr[fe + 1] - jE, hE = hub[feat_map[fe]];
-	const int jC = fptr[fc], lenC = fptr[fc + 1] - jC, hC = hub[feat_map[fc]];
-	for (int a = 0; a <= lenE; a++)
-	{
-		const int pa = a < lenE ? photo[jE + a] : hE;
-		if (pa < 0) continue;
-		for (int b = 0; b <= lenC; b++)
-		{
-			const int pb = b < lenC ? photo[jC + b] : hC;
-			if (pb >= 0) hash_insert(tab, mask, pair_key(pa, pb), overflow);
-		}
-	}
-}
 __global__ void k_pat_insert_keys(int n, const unsigned long long* __restrict__ keys, unsigned long long* tab, unsigned long long mask, int* overflow)
 {
 	int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1137,22 +1114,13 @@ bool schur_pattern_prefetch(lsfm_context* ctx, const DevBatch& Y, const int* d_t
 	if (!Y.M) return false;
 	hipStream_t s = ctx->stream;
 	Arena& sc = ctx->scratch;
-	static const bool dbg = getenv("LSFM_DEBUG_SYNC") != nullptr;
-	auto chk = [&](const char* what) {
-		if (!dbg) return;
-		hipError_t e = hipDeviceSynchronize();
-		fprintf(stderr, "[prefetch] %s: %s\n", what, hipGetErrorString(e));
-	};
-	chk("before");
 	int* hub = sc.alloc<int>(Y.B);
 	fill_async(s, hub, 0xff, sizeof(int) * (size_t)Y.B);
 	hipLaunchKernelGGL(k_pre_hubs, dim3((Y.M + 255) / 256), dim3(256), 0, s, Y.M, Y.pose_id, Y.pose_map, d_tref, hub);
-	chk("hubs");
 	int* match = sc.alloc<int>(Y.NF + 1);
 	int* unm = sc.alloc<int>(Y.NF + 2);
 	if (Y.NF) join_match_features(ctx, Y, match, unm);
 	else dev_zero(ctx, unm, 2 * sizeof(int));
-	chk("match");
 	if (counts)
 	{
 		const int B = Y.B;
@@ -1195,16 +1163,11 @@ bool schur_pattern_prefetch(lsfm_context* ctx, const DevBatch& Y, const int* d_t
 		pattern_begin(ctx, cap, pb);
 		const unsigned long long mask = (unsigned long long)(cap - 1);
 		const int nu = std::max(Y.NU, Y.M);
-		chk("begin");
 		hipLaunchKernelGGL(k_pat_insert_u_early, dim3((nu + 255) / 256), dim3(256), 0, s, Y.NU, Y.M, Y.Ui, Y.Uj, Y.pose_map, hub, pb.tab, mask, pb.d_flags);
-		chk("insert_u");
 		if (prev_keys && prev_nnzb) hipLaunchKernelGGL(k_pat_insert_keys, dim3((prev_nnzb + 255) / 256), dim3(256), 0, s, prev_nnzb, prev_keys, pb.tab, mask, pb.d_flags);
 		if (!prev_keys && Y.NF) hipLaunchKernelGGL(k_pat_insert_w, dim3((Y.NF + 255) / 256), dim3(256), 0, s, Y.NF, Y.fptr, Y.photo, pb.tab, mask, pb.d_flags);
-		chk("insert_keys");
 		if (Y.NF) hipLaunchKernelGGL(k_pat_insert_w_cross_match, dim3((Y.NF + 255) / 256), dim3(256), 0, s, Y.NF, Y.feat_map, match, Y.fptr, Y.photo, hub, pb.tab, mask, pb.d_flags);
-		chk("insert_cross");
 		pattern_compact(ctx, pb);
-		chk("compact");
 		int cnt = 0;
 		if (pattern_count(ctx, pb, &cnt))
 		{
@@ -1227,27 +1190,18 @@ void schur_pattern_early_issue(lsfm_context* ctx, const EarlyPatternIn& in)
 	ep->M = in.M;
 	// on the side stream, behind the point of the main stream where the matches and the hub poses are known (evC)
 	LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream3, ctx->evC, 0));
-	std::swap(ctx->stream, ctx->stream3);
-	try
 	{
+		OnStream on(ctx, ctx->stream3);
 		hipStream_t s = ctx->stream;
-		const size_t cap = pattern_capacity(std::max((size_t)in.NU + in.M, (size_t)in.prev_nnzb + in.M), in.M);
+		const size_t cap = pattern_capacity((size_t)in.NU + in.M, in.M);
 		pattern_begin(ctx, cap, ep->pb);
 		const int nu = std::max(in.NU, in.M);
 		const unsigned long long mask = (unsigned long long)(cap - 1);
 		if (nu) hipLaunchKernelGGL(k_pat_insert_u_early, dim3((nu + 255) / 256), dim3(256), 0, s, in.NU, in.M, in.Ui, in.Uj, in.pose_map, in.hub, ep->pb.tab, mask, ep->pb.d_flags);
-		if (in.prev_keys)
-		{
-			// the level below left its pattern: every pair inside one source map is in it; what is new are the pairs across
-			if (in.prev_nnzb) hipLaunchKernelGGL(k_pat_insert_keys, dim3((in.prev_nnzb + 255) / 256), dim3(256), 0, s, in.prev_nnzb, in.prev_keys, ep->pb.tab, mask, ep->pb.d_flags);
-			if (in.NFY) hipLaunchKernelGGL(k_pat_insert_w_cross, dim3((in.NFY + 255) / 256), dim3(256), 0, s, in.NFY, in.srcE, in.srcC, in.fptr, in.photo, in.feat_map, in.hub, ep->pb.tab, mask, ep->pb.d_flags);
-		}
-		else if (in.NFY) hipLaunchKernelGGL(k_pat_insert_w_early, dim3((in.NFY + 255) / 256), dim3(256), 0, s, in.NFY, in.srcE, in.srcC, in.fptr, in.photo, in.feat_map, in.hub, ep->pb.tab, mask, ep->pb.d_flags);
+		if (in.NFY) hipLaunchKernelGGL(k_pat_insert_w_early, dim3((in.NFY + 255) / 256), dim3(256), 0, s, in.NFY, in.srcE, in.srcC, in.fptr, in.photo, in.feat_map, in.hub, ep->pb.tab, mask, ep->pb.d_flags);
 		pattern_compact(ctx, ep->pb);
 		LSFM_CHECK_HIP(hipGetLastError());
 	}
-	catch (...) { std::swap(ctx->stream, ctx->stream3); throw; }
-	std::swap(ctx->stream, ctx->stream3);
 	ctx->early = ep;
 }
 void schur_pattern_early_drop(lsfm_context* ctx) { ctx->early.reset(); }
@@ -1256,9 +1210,7 @@ void schur_pattern_early_drop(lsfm_context* ctx) { ctx->early.reset(); }
 // false: no early build in flight, or its table overflowed -- the caller builds the pattern from the joint map instead.
 bool schur_pattern_early_finish(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy)
 {
-	std::shared_ptr<void> keep = ctx->early;
-	ctx->early.reset();
-	EarlyPattern* ep = static_cast<EarlyPattern*>(keep.get());
+	std::shared_ptr<EarlyPattern> ep = std::move(ctx->early);
 	if (!ep || ep->M != io.M) return false;
 	int cnt = 0;
 	if (!pattern_count(ctx, ep->pb, &cnt)) return false;

@@ -28,6 +28,12 @@
 #include <utility>
 
 namespace lsfm {
+// threads of a large analysis: half the cores, at most LSFM_SYM_THREADS (default 8)
+static int sym_threads()
+{
+	static const int cap = getenv("LSFM_SYM_THREADS") ? std::max(1, atoi(getenv("LSFM_SYM_THREADS"))) : 8;
+	return std::min<int>(cap, std::max(1u, std::thread::hardware_concurrency() / 2));
+}
 // most block columns of a supernode group: CHOL_GS, or less (LSFM_GS, for measurements)
 static const int gs_cap = []() { const char* e = getenv("LSFM_GS"); const int v = e ? atoi(e) : CHOL_GS; return v >= 1 && v <= CHOL_GS ? v : CHOL_GS; }();
 
@@ -336,8 +342,7 @@ void chol_symbolic(const unsigned long long* keys, int nnzb, const int* origin, 
 	// tree spent 330 ms of an analysing run's 570 in this function, on one thread, while the device waited.
 	std::vector<int> cut_row(1, 0), cut_key(1, 0); // chunk c: rows [cut_row[c], cut_row[c+1]), keys [cut_key[c], cut_key[c+1])
 	{
-		static const int max_threads = getenv("LSFM_SYM_THREADS") ? std::max(1, atoi(getenv("LSFM_SYM_THREADS"))) : 8;
-		const int want = (nnzb < 60000 || block_maps > 0) ? 1 : std::min<int>(max_threads, std::max(1u, std::thread::hardware_concurrency() / 2));
+		const int want = (nnzb < 60000 || block_maps > 0) ? 1 : sym_threads();
 		if (want > 1)
 		{
 			const long target = (nnzb + want - 1) / want;
@@ -366,8 +371,7 @@ void chol_symbolic(const unsigned long long* keys, int nnzb, const int* origin, 
 		static thread_local std::vector<CoverJob> jobs_tl;
 		std::vector<CoverJob>& jobs = jobs_tl; // (a reference: the lambdas below run on other threads, whose own jobs_tl is not this one)
 		if ((int)jobs.size() < nchunk) jobs.resize(nchunk);
-		static const int max_threads = getenv("LSFM_SYM_THREADS") ? std::max(1, atoi(getenv("LSFM_SYM_THREADS"))) : 8;
-		const int threads = block_maps > 0 ? 1 : std::min<int>(max_threads, std::max(1u, std::thread::hardware_concurrency() / 2));
+		const int threads = block_maps > 0 ? 1 : sym_threads();
 		// twice as many pieces as threads between all the chunks: the groups of a job differ in work
 		const int want_groups = threads > 1 ? std::max(1, 2 * threads / nchunk) : 1;
 		par_chunks([&](int c) {
@@ -424,8 +428,7 @@ void chol_symbolic(const unsigned long long* keys, int nnzb, const int* origin, 
 	}
 	// ---- strict lower adjacency by row, new numbering ------------------------------------------------------------------
 	std::vector<int>&rcnt = w.rcnt, &radj = w.radj, &fill = w.fill;
-	static const int max_threads_a = getenv("LSFM_SYM_THREADS") ? std::max(1, atoi(getenv("LSFM_SYM_THREADS"))) : 8;
-	const int athreads = (nnzb < 60000 || block_maps > 0) ? 1 : std::min<int>(max_threads_a, std::max(1u, std::thread::hardware_concurrency() / 2));
+	const int athreads = (nnzb < 60000 || block_maps > 0) ? 1 : sym_threads();
 	if (athreads > 1 && nnzb >= 400000)
 	{
 		// a stable counting sort by row over ranges of the keys, one range per thread: every range counts its entries per row, the running
@@ -520,8 +523,7 @@ void chol_symbolic(const unsigned long long* keys, int nnzb, const int* origin, 
 	// exactly as the one-thread walk over all rows leaves them.  (One system of 16 386 poses, 2.07 M blocks of L: 9 of its
 	// analysis's 30 ms were these two walks on one thread.)
 	std::vector<int>&colptr = ch.colptr, &rowidx = ch.rowidx;
-	static const int max_threads_w = getenv("LSFM_SYM_THREADS") ? std::max(1, atoi(getenv("LSFM_SYM_THREADS"))) : 8;
-	const int wthreads = (nnzb < 60000 || block_maps > 0) ? 1 : std::min<int>(max_threads_w, std::max(1u, std::thread::hardware_concurrency() / 2));
+	const int wthreads = (nnzb < 60000 || block_maps > 0) ? 1 : sym_threads();
 	// (a level of many independent systems is cut into chunks of whole systems instead, one thread each, below: no counters per range,
 	// no sums over them -- 16 384 columns x 32 ranges of those cost a level of small systems more than its walks)
 	if (wthreads > 1 && nchunk < 4)

@@ -1002,8 +1002,6 @@ static void launch_stage(lsfm_context* ctx, const DevBatch& in, DevBatch& out, c
 	hipStream_t s = ctx->stream;
 	const int M = in.M;
 	bool ev_entries = false, u_early = false;
-	static const bool side = !getenv("LSFM_NO_SIDE_STREAM");
-	static const bool early_u = !getenv("LSFM_U_STAGE_LATE");
 	if (!in.NF && hook) (void)(*hook)(out); // nothing to redirect, but the consumer still lays out its container
 	if (in.NF)
 	{
@@ -1022,8 +1020,8 @@ static void launch_stage(lsfm_context* ctx, const DevBatch& in, DevBatch& out, c
 		// rows of G like they do: it goes to the side stream HERE, beside the block kernel of the features, not behind it -- one lane per
 		// 6x6 block with a few hundred dependent multiply-adds each, it takes 160-190 us whatever the level's size, and behind the
 		// block kernel the main stream waited 60 us per level for it (k_tr_diag needs the U stage).  Only the poses' kernel, which
-		// reads the finished rows, still waits for the block kernel.  LSFM_U_STAGE_LATE=1: as until round 6.
-		if (side && early_u && !ctx->comm && in.NU)
+		// reads the finished rows, still waits for the block kernel.
+		if (!ctx->comm && in.NU)
 		{
 			LSFM_CHECK_HIP(hipEventRecord(ctx->evU, s));
 			LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream2, ctx->evU, 0));
@@ -1058,7 +1056,7 @@ static void launch_stage(lsfm_context* ctx, const DevBatch& in, DevBatch& out, c
 	// feature-sharded run: what the features of this rank's slice added to the pose rows of G (k_tr_entries) and to the hub-hub
 	// blocks (k_tr_feat_post) becomes the sum over all slices before the pose kernels read and extend it
 	if (ctx->comm) ctx->comm->allreduce(s, Gpose, (size_t)M * 36 * NH + (size_t)in.B * 3 * 36, LSFM_DTYPE_F64);
-	hipStream_t su = (side && ev_entries && !ctx->comm) ? ctx->stream2 : s;
+	hipStream_t su = (ev_entries && !ctx->comm) ? ctx->stream2 : s;
 	if (su != s) LSFM_CHECK_HIP(hipStreamWaitEvent(su, ctx->evA, 0));
 	if (in.NU && !u_early)
 		hipLaunchKernelGGL(k_tr_ublocks<NH>, dim3((in.NU + 127) / 128), dim3(128), 0, su, in.NU, M, d_tm, in.pose_map, in.U, in.Ui, in.Uj, KU,
@@ -1198,9 +1196,8 @@ void transform_batch(lsfm_context* ctx, Arena& ar, const DevBatch& in, const std
 	// them (LevelIndex: left by the preparation one level ahead, or kept by a resident tree), worked out here otherwise
 	LevelPlan* plan = ctx->plan;
 	const bool warm = ctx->warm();
-	static const bool reuse_index = !getenv("LSFM_NO_INDEX_REUSE");
 	const int *KU = nullptr, *KW = nullptr;
-	if (reuse_index && warm && plan->idx.KW && plan->idx.KU && plan->idx.NU == in.NU && plan->idx.NW == in.NW) { KU = plan->idx.KU; KW = plan->idx.KW; }
+	if (warm && plan->idx.KW && plan->idx.KU && plan->idx.NU == in.NU && plan->idx.NW == in.NW) { KU = plan->idx.KU; KW = plan->idx.KW; }
 	else
 	{
 		int* keepU = ctx->scratch.alloc<int>(in.NU + 1);
@@ -1212,7 +1209,7 @@ void transform_batch(lsfm_context* ctx, Arena& ar, const DevBatch& in, const std
 		dev_exclusive_scan(ctx, keepU, kU, in.NU);
 		dev_exclusive_scan(ctx, keepW, kW, in.NW);
 		KU = kU; KW = kW;
-		if (reuse_index && plan && !warm && plan != &ctx->pre_plan && ctx->in_tree_run)
+		if (plan && !warm && plan != &ctx->pre_plan && ctx->in_tree_run)
 		{
 			// a resident tree records the level: its later runs skip the three launches above
 			plan->idx.KU = level_index_keep(ctx, plan->idx, kU, (size_t)in.NU + 2);
