@@ -169,7 +169,7 @@ void run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level)
 		ctx->pre_plan_level = -1;
 		if (analysing && Y.B > 1 && !ctx->comm)
 		{
-			// while the device solves this level: the next level's pattern and symbolic factorisation (lsfm_pcg.hip)
+			// while the device solves this level: the next level's pattern and symbolic factorisation (lsfm_level.hip)
 			const int nb = Y.B;
 			std::vector<int> nref(nb, -1);
 			for (int i = 0; i < nb / 2; i++)
@@ -336,7 +336,7 @@ int lsfm_tree_run(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* stats)
 					try { tree_pass(ctx, t, st); }
 					catch (const Error& e)
 					{
-						// a level that was recording its plan found a pivot far below zero itself (lsfm_pcg.hip check_factor): treated like the
+						// a level that was recording its plan found a pivot far below zero itself (lsfm_pcg.hip pcg_run): treated like the
 						// same finding at the end of a run, below -- the tree is joined again while attempts are left
 						if (e.code == LSFM_ERR_NOT_SPD && attempt < 3)
 						{

@@ -1,5 +1,6 @@
-// The sparse block Cholesky factorisation of a camera system (K10's preconditioner, lsfm_pcg.hip): the device layout of the factor and
-// the host steps that make it -- shared by the refinement (lsfm_pcg.hip) and the marginal covariances (lsfm_cov.hip).
+// The sparse block Cholesky factorisation of a camera system (K10's preconditioner, lsfm_chol.hip): the device layout of the factor and
+// the host steps that make and apply it -- shared by the level solve (lsfm_level.hip), the refinement (lsfm_pcg.hip) and the marginal
+// covariances (lsfm_cov.hip).
 #pragma once
 #include <vector>
 
@@ -47,7 +48,7 @@ struct CholDev {
 	int* blob = nullptr;    // all index arrays above are slices of this one allocation
 	size_t blob_ints = 0;
 	float *Lf = nullptr, *Dinvf = nullptr; // mixed precision: the factor rounded to fp32 for the triangular solves (null: fp64)
-	double* wv = nullptr;   // [M*6] forward-solve results of the group columns (lsfm_pcg.hip k_sn_fwd / k_sn_bwd)
+	double* wv = nullptr;   // [M*6] forward-solve results of the group columns (lsfm_chol.hip k_sn_fwd / k_sn_bwd)
 	double* Lg = nullptr;   // [nnzL*36] the factor of the supernode-group columns (same indexing as L; L keeps their unfactored blocks)
 	float* Lgf = nullptr;   // mixed precision: its fp32 copy
 	double* L = nullptr;    // [nnzL*36] block values, column major by blocks, each block row-major 6x6
@@ -71,6 +72,7 @@ __device__ __forceinline__ int find_row(const int* __restrict__ rowidx, int lo, 
 }
 
 
+struct CholSymbolic; // lsfm_symbolic.hpp
 struct CholHostIn {
 	std::vector<unsigned long long> keys; // sorted upper pattern of S
 	std::vector<int> origin;              // local map that brought each pose
@@ -80,11 +82,27 @@ struct CholHostIn {
 void chol_fetch(lsfm_context* ctx, const SchurSystem& sy, const int* d_origin, CholHostIn& in);
 // symbolic analysis on the host (lsfm_symbolic.cpp), index arrays to the device, value arrays allocated in ctx->scratch
 void chol_analyse(lsfm_context* ctx, const SchurSystem& sy, const CholHostIn& in, CholDev& ch);
+// the two halves of chol_analyse's device part, for callers that hold a symbolic factorisation already (a level prepared ahead):
+// its index arrays to the device (what a plan keeps); the same + chol_alloc_values
+void chol_upload_index(lsfm_context* ctx, const CholSymbolic& sym, CholDev& ch);
+void chol_upload_symbolic(lsfm_context* ctx, const CholSymbolic& sym, CholDev& ch);
+// the value arrays of a run (ctx->scratch) for index arrays that are in place, ch.L and the error flag ch.d_err zeroed
+void chol_alloc_values(lsfm_context* ctx, CholDev& ch);
 // the scaled, permuted S into the factor's storage (fixed scalars: identity rows / columns), the scaling to ch.dscale
 void chol_scatter(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* fixed, CholDev& ch);
 // numeric factorisation: the leaf columns' factor in ch.L, the supernode-group columns' in ch.Lg, every L_jj^-1 in ch.Dinv
 void chol_factor(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* fixed, CholDev& ch, double* fwd_v = nullptr);
 // the group columns' factor copied into ch.L (a no-op when chol_factor already did it): afterwards ch.L + ch.Dinv hold the whole factor
 void chol_merge_groups(lsfm_context* ctx, const CholDev& ch);
+// mixed precision: the factor rounded to fp32 (ch.Lf, ch.Lgf, ch.Dinvf, in ctx->scratch), which chol_apply then applies
+void chol_round_to_float(lsfm_context* ctx, CholDev& ch);
+// v = D^-1/2 P r: a right-hand side into elimination order (what chol_factor's fwd_v and chol_apply's fwd_done expect)
+void chol_perm_in(lsfm_context* ctx, const CholDev& ch, const double* r, const unsigned char* fixed, double* v);
+// z = (L L^T)^-1 r in the original numbering (v: work vector in elimination order), dot[seg * dot_stride] += r . z per system
+void chol_apply(lsfm_context* ctx, const CholDev& ch, const double* r, double* v, double* z, const unsigned char* fixed, const int* pose_seg, double* dot, int dot_stride, bool fwd_done = false);
+// the factorisation of this system is distributed over the ranks of a feature-sharded run (CholDev::col_owner)
+bool chol_distributed(const lsfm_context* ctx, const CholDev& ch);
+// feature-sharded run: one or two host numbers summed over the ranks, in place (a synchronisation)
+void comm_sum_host(lsfm_context* ctx, long long* h, int n);
 
 } // namespace lsfm

@@ -25,8 +25,8 @@ namespace lsfm {
 struct Error { int code; std::string msg; };
 struct DevBatch;
 struct IndexHold;    // device memory a plan owns (lsfm_prims.hip)
-struct SolvePlan;    // the solve part of a level's plan (lsfm_pcg.hip)
-struct PreLevel;     // a level prepared one level ahead (lsfm_pcg.hip)
+struct SolvePlan;    // the solve part of a level's plan (lsfm_level.hip)
+struct PreLevel;     // a level prepared one level ahead (lsfm_level.hip)
 struct EarlyPattern; // an early pattern build in flight (lsfm_solve.hip)
 
 #define LSFM_CHECK_HIP(expr)                                                                                   \
@@ -124,7 +124,7 @@ struct LevelPlan {
 	std::vector<int> tr_sign;
 	std::vector<int> join_rb;    // join: ranks of the unmatched features at the map boundaries
 	std::vector<int> join_uo, join_wo; // Mono join: kept-U prefix at the map boundaries, W offsets of the joint maps
-	std::shared_ptr<SolvePlan> solve; // pattern of S + symbolic factorisation + iteration count (lsfm_pcg.hip)
+	std::shared_ptr<SolvePlan> solve; // pattern of S + symbolic factorisation + iteration count (lsfm_level.hip)
 };
 
 // per-run accumulators on the device, read back once at the end of a run (a warm level does not stop for them)
@@ -134,7 +134,7 @@ struct RunStatsDev {
 	int tr_err;            // 1 + map whose transform target was not found
 	int plan_stale;        // a planned level met VALUES the plan does not fit (Mono: the sign of a new scale): the run is repeated without plans
 	int undone;            // systems whose refinement was enqueued with a step count from an earlier run and had not met its stopping rule when the steps ran out
-	int floored;           // pivots of the separators replaced by their lower bound (static pivoting, lsfm_pcg.hip k_sn_panel)
+	int floored;           // pivots of the separators replaced by their lower bound (static pivoting, lsfm_chol.hip k_sn_panel)
 	double max_rel_residual;
 	unsigned long long s_digest, factor_digest; // LSFM_FACTOR_DIGEST=1 (lsfm_stats)
 	int refactor_mismatch;                      // ... systems whose second factorisation gave other bits than the first
@@ -187,7 +187,7 @@ struct Comm {
 };
 
 // One helper thread per context for host work that the enqueuing thread need not wait for at once (the symbolic factorisation
-// of the next level: lsfm_pcg.hip prefetch_next_level).  One job at a time; wait() returns when it is done and rethrows what
+// of the next level: lsfm_level.hip prefetch_next_level).  One job at a time; wait() returns when it is done and rethrows what
 // it threw.  The thread lives as long as the context, so that what it keeps per thread (the symbolic analysis' workspace)
 // is kept between jobs.
 struct HostWorker {
@@ -297,7 +297,7 @@ struct lsfm_context {
 	// One level ahead (Stereo tree runs that analyse): while the device factors and refines level L, the pattern of level
 	// L + 1's system is put together on stream3 from level L's joint maps (their index arrays are final long before the
 	// solve ends) and the host analyses it -- level L + 1 then finds its pattern and its symbolic factorisation waiting
-	// (lsfm_pcg.hip: prefetch_next_level).  Their arrays live in two small arenas used in turn.
+	// (lsfm_level.hip: prefetch_next_level).  Their arrays live in two small arenas used in turn.
 	lsfm::Arena sarena[2];
 	// what was prepared for the level about to run (null: nothing).  Its symbolic factorisation (host work) may still be under way on
 	// the helper thread when the level starts; releasing the object waits for it -- nothing the thread reads goes before (~PreLevel)
@@ -305,7 +305,7 @@ struct lsfm_context {
 	// ... and, when an earlier run of the tree has left the refinement step count of that level, everything else the level
 	// would stop for (kept-block counts of its transform, unmatched-feature ranks of its join): a plan of the level made
 	// one level ahead -- the level then runs like a planned one, without a single host <-> device round trip: its transform, join
-	// and Schur assembly are enqueued while the helper thread works, solve_batch completes the plan (lsfm_pcg.hip)
+	// and Schur assembly are enqueued while the helper thread works, solve_batch completes the plan (lsfm_level.hip)
 	lsfm::LevelPlan pre_plan;
 	int pre_plan_level = -1;
 	std::unique_ptr<lsfm::HostWorker> worker;
@@ -476,6 +476,10 @@ struct SolveIO {
 // systems are too large -- lsfm_context::small_max --, or the run is feature-sharded or in mixed precision).  The ONE place that
 // decides it: the join (offsets, fused right-hand sides, early pattern), the preparation one level ahead and the solve must agree
 int small_level_strips(const lsfm_context* ctx, int most_rows);
+inline int most_rows(const std::vector<int>& seg_rows) { int most = 0; for (int r : seg_rows) most = r > most ? r : most; return most; }
+inline int small_level_strips(const lsfm_context* ctx, const std::vector<int>& seg_rows) { return small_level_strips(ctx, most_rows(seg_rows)); }
+// the join of such a level (io.seg_rows set): the ranges of its joins in the joint maps `out`, by which the dense path walks them, to io
+void small_level_offsets(lsfm_context* ctx, const DevBatch& out, SolveIO& io);
 void small_solve_launch(lsfm_context* ctx, const SolveIO& io, int strips, int* status, double* max_rel);
 int solve_batch(lsfm_context* ctx, const SolveIO& io);
 // Gauss-Newton polish of the map-joining objective over all local maps at once (lsfm_gn.hip; C ABI: lsfm_gn_polish)

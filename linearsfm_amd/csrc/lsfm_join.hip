@@ -384,9 +384,7 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 	// a level that analyses, reached through the transform's hook: the sources of every joint feature, for the early pattern of S
 	// (a level of small systems takes the dense path: no pattern at all; a level prepared one level ahead brings its pattern -- or,
 	// prepared with a plan, is warm)
-	int most_rows = 0;
-	for (int r : seg_rows) most_rows = std::max(most_rows, r);
-	const bool small_level = small_level_strips(ctx, most_rows) > 0;
+	const bool small_level = small_level_strips(ctx, seg_rows) > 0;
 	const bool early = !small_level && !ctx->comm && !(ctx->pre && !ctx->pre_plan.valid) && ctx->tr_in && ctx->tr_hub && !ctx->warm() && ctx->tr_in->NF == in.NF && ctx->tr_in->M == in.M;
 	// the W part of the right-hand sides left to the Schur assembly (lsfm_solve.hpp RhsFused): a level on the sparse pipeline, one GPU
 	st.fuse_rhs = !small_level && !ctx->comm && !ctx->pcg.mixed;
@@ -473,17 +471,7 @@ void join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch& out, Jo
 		rhs.srcE = st.srcE; rhs.srcC = st.srcC; rhs.feat_src = in.feat; rhs.pose_src = in.pose; rhs.pose_map_src = in.pose_map;
 		io.rhs = &rhs;
 	}
-	{
-		// a level of small systems goes to the one-launch dense path, which walks the joins by their ranges (lsfm_small.hip)
-		int most = 0;
-		for (int r : seg_rows) most = std::max(most, r);
-		if (small_level_strips(ctx, most))
-		{
-			int* d_uo = ctx->scratch.alloc<int>(G + 1);
-			h2d(ctx, d_uo, out.u_off.data(), sizeof(int) * (size_t)(G + 1));
-			io.d_pose_off = out.d_pose_off; io.d_feat_off = out.d_feat_off; io.d_u_off = d_uo;
-		}
-	}
+	small_level_offsets(ctx, out, io); // a level of small systems goes to the one-launch dense path, which walks the joins by their ranges (lsfm_small.hip)
 	const bool warm = ctx->warm();
 	ctx->solved_keys = nullptr; ctx->solved_nnzb = 0;
 	int rc = solve_batch(ctx, io);

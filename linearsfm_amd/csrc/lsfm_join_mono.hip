@@ -523,16 +523,7 @@ void join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch&
 	io.ea = eP; io.eb = eF; io.x0 = x0; io.d_fixed = fixed; io.d_pose_origin = out.pose_origin;
 	io.x_pose = out.pose; io.x_feat = out.feat;
 	io.seg_rows = seg_rows;
-	{
-		int most = 0;
-		for (int r : seg_rows) most = std::max(most, r);
-		if (small_level_strips(ctx, most))
-		{
-			int* d_uo = sc.alloc<int>(G + 1);
-			h2d(ctx, d_uo, out.u_off.data(), sizeof(int) * (size_t)(G + 1));
-			io.d_pose_off = out.d_pose_off; io.d_feat_off = out.d_feat_off; io.d_u_off = d_uo;
-		}
-	}
+	small_level_offsets(ctx, out, io);
 	// the pattern of this level's system from the one below (a level that analyses; the level below left its pattern with its maps)
 	PatternSeed seed;
 	if (!warm && in.s_keys && in.s_nnzb > 0 && !ctx->comm)

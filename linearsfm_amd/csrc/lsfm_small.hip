@@ -2,7 +2,7 @@
 // thousands of independent joins a level) solved by ONE launch, one work-group per join, the whole camera system in LDS.
 //
 // What it replaces for such a level (lmj_solveLinearSFM{Stereo,Mono}, Imp.cpp:2119-2378 / 6756-7041, as the level pipeline runs it,
-// lsfm_pcg.hip solve_batch): k_vinv, k_schur_u, k_schur_scale, k_schur_slots / lists, k_schur_panel, k_schur_w, k_schur_finish, the
+// lsfm_level.hip solve_batch): k_vinv, k_schur_u, k_schur_scale, k_schur_slots / lists, k_schur_panel, k_schur_w, k_schur_finish, the
 // scatter into the factor's storage, the leaf factorisation, two triangular sweeps, four products with S, the CG bookkeeping
 // kernels, k_backsub and ~20 fills / copies -- some 55 launches of which 40 are 5 us of dispatch latency each, on systems of 12-96
 // scalars: 0.8 of the 2.1 ms such a level took (profiles/r04 kernel trace).  Here a work-group
@@ -477,6 +477,14 @@ static int small_solve_strips(int most_poses, int cap)
 int small_level_strips(const lsfm_context* ctx, int most_rows)
 {
 	return (ctx->small_max > 0 && !ctx->comm && !ctx->pcg.mixed) ? small_solve_strips(most_rows, ctx->small_max) : 0;
+}
+void small_level_offsets(lsfm_context* ctx, const DevBatch& out, SolveIO& io)
+{
+	if (!small_level_strips(ctx, io.seg_rows)) return;
+	const int G = io.nseg;
+	int* d_uo = ctx->scratch.alloc<int>(G + 1);
+	h2d(ctx, d_uo, out.u_off.data(), sizeof(int) * (size_t)(G + 1));
+	io.d_pose_off = out.d_pose_off; io.d_feat_off = out.d_feat_off; io.d_u_off = d_uo;
 }
 
 template <int NTR>

@@ -6,7 +6,7 @@
 //                         (replaces smask, Imp.cpp:2131-2205), sorted into block-CSR
 //   K9  k_schur_*         S(p,q) -= W_pf V_f^-1 W_qf^T, E_p -= W_pf V_f^-1 eb_f (Imp.cpp:2244-2332): k_schur_panel
 //                         (lsfm_schur_panel.hip, fp64 MFMA on 128-feature tiles); k_schur_w here takes the tiles it flags
-//   K10 k_spmv / k_pcg_*  Cholesky-preconditioned CG (lsfm_pcg.hip) on the symmetric 6x6-block system, all independent
+//   K10 k_spmv / k_pcg_*  Cholesky-preconditioned CG (lsfm_pcg.hip; the factor: lsfm_chol.hip) on the symmetric 6x6-block system, all independent
 //                         systems of the level together with per-system scalars (replaces Imp.cpp:2334-2361)
 //   K11 k_backsub         features: x_f = V_f^-1 (eb_f - sum W_pf^T x_p)     (pba_solveFeatures, Imp.cpp:2980-3020)
 // S is kept as its upper block triangle (diagonal blocks full); the SpMV reads every stored block once and adds its
@@ -1052,7 +1052,7 @@ __global__ void k_pat_insert_keys(int n, const unsigned long long* __restrict__ 
 	if (i < n) hash_insert(tab, mask, keys[i], overflow);
 }
 
-// ---- the pattern of the NEXT level's system, from this level's joint maps (prefetch_next_level, lsfm_pcg.hip) -------------
+// ---- the pattern of the NEXT level's system, from this level's joint maps (prefetch_next_level, lsfm_level.hip) -------------
 // hub pose of every map of the batch in the next level's transform: the pose whose id is the map's target reference
 __global__ void k_pre_hubs(int M, const int* __restrict__ pose_id, const int* __restrict__ pose_map, const int* __restrict__ tref, int* __restrict__ hub)
 {
@@ -1284,8 +1284,6 @@ void build_schur_values(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy)
 		hipEvent_t e2 = nullptr, e3 = nullptr;
 		if (ctx->stats) { e2 = ctx->pool_event(); e3 = ctx->pool_event(); LSFM_REC_T(e2, s); }
 		static_assert(LSFM_PM_TILE % SCHUR_TILE == 0, "a tile of the panel kernel must be whole tiles of the fallback kernel");
-		int most = 0;
-		for (int r : io.seg_rows) most = std::max(most, r);
 		// the per-tile slots of the panel variants: from the plan of the level, or worked out now (and left for the plan, if this
 		// run makes one)
 		bool fresh_lists = false;
@@ -1300,7 +1298,7 @@ void build_schur_values(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy)
 			sy.k9_tiles = ntiles; sy.k9_NW = io.NW;
 			launch_schur_slots(ctx, NF, io.fptr, io.photo, fb, sy.k9);
 		}
-		launch_schur_panel(ctx, NF, io.fptr, io.photo, io.W, sy.LY, tab, hval, mask, ko, fb, most, sy.k9, fresh_lists);
+		launch_schur_panel(ctx, NF, io.fptr, io.photo, io.W, sy.LY, tab, hval, mask, ko, fb, most_rows(io.seg_rows), sy.k9, fresh_lists);
 		hipLaunchKernelGGL(k_schur_w, dim3(ntiles), dim3(SCHUR_TILE), 0, s, NF, io.fptr, io.photo, io.W, sy.IV, io.eb, tab, hval, mask, ko, fb, sy.LY);
 		if (ctx->stats)
 		{

@@ -1,4 +1,5 @@
-// Shared between lsfm_solve.hip (Schur assembly, SpMV, back-substitution) and lsfm_pcg.hip (preconditioned CG).
+// Shared between lsfm_solve.hip (Schur assembly, SpMV, back-substitution), lsfm_level.hip (the level driver), lsfm_chol.hip (the
+// factorisation) and lsfm_pcg.hip (the refinement).
 #pragma once
 #include "lsfm_internal.hpp"
 

@@ -6,7 +6,7 @@
 //     are eliminated by ascending separator level.
 //   * elimination tree, column counts and column patterns by row sub-tree walks.
 //   * tasks (leaf sub-trees that fit LDS, chains above them) and supernode groups (runs of <= CHOL_GS columns of one
-//     fundamental supernode) for the device kernels of lsfm_pcg.hip.
+//     fundamental supernode) for the device kernels of lsfm_chol.hip.
 //
 // This runs once per tree level inside the timed region of a run that analyses (the reference's cholmod_analyze_p runs
 // once per join), so it is written for speed: one workspace kept between calls, counting sorts instead of comparison

@@ -7,14 +7,14 @@
 
 namespace lsfm {
 
-/* most block columns of a supernode group (lsfm_pcg.hip: k_sn_panel keeps 6 * CHOL_GS dense scalar rows in LDS).  8 since round 4 (16
+/* most block columns of a supernode group (lsfm_chol.hip: k_sn_panel keeps 6 * CHOL_GS dense scalar rows in LDS).  8 since round 4 (16
  * before): the panel kernel is left-looking inside a group -- the dot products of a column grow with the columns before it in the group
  * -- while the update between groups runs on the matrix pipes of the whole chip; measured on the NC3500-like set (factorisation +
  * refinement per tree): 16 columns 10.8 ms, 12 10.2, 8 9.4, 6 9.5, 4 9.9; RS468-like 5.76 -> 5.05, synth-16k 141 -> 131.
  * LSFM_GS=<n <= CHOL_GS> narrows it further (measurements). */
 #define CHOL_GS 8
 
-/* LDS of the leaf tasks (task level 0: sub-trees of at most task_x blocks, each walked whole in LDS by one work-group, lsfm_pcg.hip).
+/* LDS of the leaf tasks (task level 0: sub-trees of at most task_x blocks, each walked whole in LDS by one work-group, lsfm_chol.hip).
  * The triangular solves (k_chol_fwd_tasks / k_chol_bwd_tasks) keep per task column its slice of v (6 doubles), its inverse pivot
  * block (36) and three ints, plus 8 bytes, within CHOL_SOLVE_LDS; the factorisation (k_chol_factor_level) keeps every block of the
  * task (288 B + a row index) and five ints per column + 1, plus alignment, within CHOL_FACTOR_LDS. */

@@ -410,7 +410,7 @@ def test_factorisation_is_bit_reproducible(config, n_maps):
     """LSFM_FACTOR_DIGEST=1 (read when the library loads: a process of its own): every camera system of every level is factored
     TWICE -- scatter, leaf sub-trees, supernode groups with their rank updates into the ancestors -- and the two factors (leaf columns,
     group columns, inverse diagonal blocks, the spent accumulators) are compared through an order-independent digest on the device.
-    The updates that several work-groups of a launch add to one block are 64-bit fixed-point integers (lsfm_pcg.hip): whatever order
+    The updates that several work-groups of a launch add to one block are 64-bit fixed-point integers (lsfm_chol.hip): whatever order
     the atomics land in, the sum is the same.  Round 3 added doubles there and two runs never gave the same factor.  Since round 5 the
     assembly of S and E (K9) is held to the same: `s_rebuild_mismatch`."""
     import subprocess
@@ -463,7 +463,7 @@ def test_mono_pattern_from_the_level_below_equals_the_joint_maps(ctx, oracle, mo
 
 def test_hinted_mono_refinement_asks_once_when_the_hint_is_short(ctx, oracle):
     """A run that analyses enqueues, per level, the refinement steps the run before needed.  A Mono level waits for the device at its end
-    anyway, so when that count turns out short it asks ONCE and goes on step by step (lsfm_pcg.hip, `ask_after`) -- until round 6 the whole
+    anyway, so when that count turns out short it asks ONCE and goes on step by step (lsfm_pcg.hip `pcg_run`, `ask_after`) -- until round 6 the whole
     run was joined again.  Forced here: the first runs leave the step counts of the fp64 preconditioner (one step per level), then the
     preconditioner is switched to fp32, which needs two -- the next run's hints are short at every level above the dense path's, it
     must still converge in ONE attempt, and its map must be the oracle's."""

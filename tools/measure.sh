@@ -49,7 +49,7 @@ for c in nc3500 synth16k rs468; do
     rm -rf $D/$c/pmc_mfma
   fi
 done
-touch linearsfm_amd/csrc/lsfm_pcg.hip linearsfm_amd/csrc/lsfm_schur_panel.hip linearsfm_amd/csrc/lsfm_transform.hip
+touch linearsfm_amd/csrc/lsfm_chol.hip linearsfm_amd/csrc/lsfm_schur_panel.hip linearsfm_amd/csrc/lsfm_transform.hip
 make -s -C linearsfm_amd/csrc K9_TIMING=1 -j16 > $D/build_timing.log 2>&1
 timeout 600 python tools/tr_phase_times.py > $D/tr_phase.txt 2>&1
 timeout 600 python tools/k9_phase_times.py > $D/k9_phase.txt 2>&1

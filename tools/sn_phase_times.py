@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where k_sn_panel (the supernode panel kernel of the factorisation chain) spends its clocks, phase by phase, over one tree.
-Needs the library built with the profiling aid:  make -C linearsfm_amd/csrc K9_TIMING=1 (touch lsfm_pcg.hip first).
+Needs the library built with the profiling aid:  make -C linearsfm_amd/csrc K9_TIMING=1 (touch lsfm_chol.hip first).
 usage: python tools/sn_phase_times.py [config]"""
 import ctypes as C
 import os
