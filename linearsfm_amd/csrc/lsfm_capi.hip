@@ -7,6 +7,7 @@
 
 #include "lsfm_internal.hpp"
 #include "lsfm_join.hpp"
+#include "lsfm_solve.hpp"
 
 using namespace lsfm;
 
@@ -106,19 +107,9 @@ void run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level)
 	ctx->step_hint = t->step_hint[level];
 	ctx->steps_used = 0;
 	DevBatch& X = t->level;
-	const int B = X.B, npairs = B / 2;
-	std::vector<int> tref(B, -1), tscap(B, 0), tfix(B, 0);
-	int ntr = 0;
-	for (int i = 0; i < npairs; i++)
-	{
-		const int e = 2 * i, c = 2 * i + 1;
-		// odd outputs of the previous level go back to their first frame (Imp.cpp:1997-2025 / 6576-6602) ...
-		const bool re = X.Ref[c] > X.FRef[c];
-		int cref = X.Ref[c], cscap = X.ScaP[c], cfix = X.Fix[c];
-		if (re) { cref = X.FRef[c]; cscap = X.FScaP[c]; cfix = X.FFix[c]; tref[c] = cref; tscap[c] = cscap; tfix[c] = cfix; ntr++; }
-		// ... and End is expressed in Cur's frame (Imp.cpp:1964 / 6549)
-		tref[e] = cref; tscap[e] = cscap; tfix[e] = cfix; ntr++;
-	}
+	const int npairs = X.B / 2;
+	std::vector<int> tref, tscap, tfix;
+	const int ntr = level_targets(X, t->mono, tref, tscap, tfix);
 	// stage times from events on the stream (a warm level is only enqueued: host clocks say nothing about it)
 	hipEvent_t e_t0 = ctx->pool_event(), e_t1 = ctx->pool_event(), e_t2 = ctx->pool_event();
 	LSFM_REC_T(e_t0, ctx->stream);
@@ -170,17 +161,8 @@ void run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level)
 		if (analysing && Y.B > 1 && !ctx->comm)
 		{
 			// while the device solves this level: the next level's pattern and symbolic factorisation (lsfm_level.hip)
-			const int nb = Y.B;
-			std::vector<int> nref(nb, -1);
-			for (int i = 0; i < nb / 2; i++)
-			{
-				const int e2 = 2 * i, c2 = 2 * i + 1;
-				const bool re = Y.Ref[c2] > Y.FRef[c2];
-				const int cref = re ? Y.FRef[c2] : Y.Ref[c2];
-				if (re) nref[c2] = cref;
-				nref[e2] = cref;
-			}
-			for (int b = 0; b < nb; b++) if (nref[b] >= 0 && Y.Ref[b] == nref[b]) nref[b] = -1; // (same frame: passed through, Imp.cpp:352)
+			std::vector<int> nref, nscap, nfix;
+			level_targets(Y, false, nref, nscap, nfix);
 			prefetch_next_level(ctx, Y, nref, level + 1, level + 1 < (int)t->step_hint.size() ? t->step_hint[level + 1] : 0);
 		}
 		else ctx->drop_prepared();

@@ -8,6 +8,14 @@
 
 namespace lsfm {
 
+// What a level's transform does to the index structure of a map, stated once: for the transform itself (lsfm_transform.hip) and for
+// the preparation one level ahead, whose prediction of it is used in its place (lsfm_pattern.hip).
+// Stereo: the hub of a transformed map -- the dense column it gets -- is the pose whose id is the target reference (< 0: passed through)
+__device__ __forceinline__ bool tr_stereo_hub(int pose_id, int tref) { return tref >= 0 && pose_id == tref; }
+// a U block (a, b) / the W block of pose k survives as it is unless it touches a hub pose of its map (h0, h1; < 0: no such hub)
+__device__ __forceinline__ bool tr_keeps_u(int a, int b, int h0, int h1) { return a != h0 && b != h0 && a != h1 && b != h1; }
+__device__ __forceinline__ bool tr_keeps_w(int k, int h0, int h1) { return k != h0 && k != h1; }
+
 // ---------------------------------------------------------------------------------------------------------
 // block algebra (all row-major, sizes are compile-time so everything stays in registers)
 // ---------------------------------------------------------------------------------------------------------

@@ -27,7 +27,7 @@ struct DevBatch;
 struct IndexHold;    // device memory a plan owns (lsfm_prims.hip)
 struct SolvePlan;    // the solve part of a level's plan (lsfm_level.hip)
 struct PreLevel;     // a level prepared one level ahead (lsfm_level.hip)
-struct EarlyPattern; // an early pattern build in flight (lsfm_solve.hip)
+struct EarlyPattern; // an early pattern build in flight (lsfm_pattern.hip)
 
 #define LSFM_CHECK_HIP(expr)                                                                                   \
 	do {                                                                                                        \
@@ -288,7 +288,7 @@ struct lsfm_context {
 	// Early pattern of S (Stereo tree levels that analyse): the pose pairs of the JOINT map follow from the level's input index
 	// arrays, the feature matches and the hub pose of every transformed map, all known before the transform's heavy kernels
 	// run -- the pattern is put together on the side stream while those run, and the host's symbolic analysis no longer
-	// waits for them (lsfm_solve.hip: schur_pattern_early_*).  tr_in / tr_hub: set by transform_batch around its hook.
+	// waits for them (lsfm_pattern.hip: schur_pattern_early_*).  tr_in / tr_hub: set by transform_batch around its hook.
 	const lsfm::DevBatch* tr_in = nullptr;
 	const int* tr_hub = nullptr;        // [B] global pose index of the hub column of every transformed map, -1: passed through
 	std::shared_ptr<lsfm::EarlyPattern> early; // the build in flight (null: none)
@@ -422,6 +422,12 @@ unsigned long long batch_structure_digest(lsfm_context* ctx, const DevBatch& b);
 // ---- transform (lsfm_transform.hip): K1-K4 ------------------------------------------------------------------
 // target_ref[b] < 0 ... map b is passed through unchanged; otherwise the pose id the map is re-expressed in
 // (Mono: target_scap / target_fix as well).  out is allocated from `ar`.
+// level_targets: those of a tree level's transform, whose maps (2i, 2i + 1) = (End, Cur) are joined next: an odd output of the
+// level below goes back to its first frame and End is expressed in Cur's frame; a map already in its target frame is passed
+// through (map_in_frame).  Returns the transforms the reference counts (those included).  The level's own transform and the
+// preparation one level ahead (prefetch_next_level, on the joint maps) both take it from here.
+inline bool map_in_frame(const DevBatch& X, int b, int tref, int tscap, bool mono) { return X.Ref[b] == tref && (!mono || X.ScaP[b] == tscap); } // Imp.cpp:352 / 3176
+int level_targets(const DevBatch& X, bool mono, std::vector<int>& tref, std::vector<int>& tscap, std::vector<int>& tfix);
 // Where the transform's W stage writes when its consumer has already laid out the next container (a join): the run of
 // input feature f starts at wbase[f] of W / photo / feature, blocks are labelled newf[f], srcf[] records the input feature.
 struct TrRedirect {
@@ -437,7 +443,7 @@ void transform_batch(lsfm_context* ctx, Arena& ar, const DevBatch& in, const std
                      const std::vector<int>& target_scap, const std::vector<int>& target_fix, bool mono, DevBatch& out,
                      bool alias_passthrough = false, const std::function<TrRedirect(DevBatch&)>* hook = nullptr);
 
-// ---- join + solve (lsfm_join.hip, lsfm_solve.hip): K5-K11 ---------------------------------------------------
+// ---- join + solve (lsfm_join.hip, lsfm_pattern.hip, lsfm_solve.hip): K5-K11 ---------------------------------------------------
 struct JoinWork; // device work arrays shared between assembly and solve
 // groups: consecutive maps (2g, 2g+1) of `in` are joined, a trailing unpaired map is carried over unchanged.
 // Produces `out` (ceil(B/2) maps) with the solved state.  eP_out / eF_out (host, optional) receive the right-hand
@@ -494,23 +500,11 @@ int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* po
 // the two feature-side pieces of the solve on their own (C ABI: lsfm_inverse_v / lsfm_solve_features); device pointers
 void vinv_only(lsfm_context* ctx, int NF, const double* V, double* IV);
 void backsub_only(lsfm_context* ctx, int NF, const int* fptr, const int* photo, const double* W, const double* IV, const double* eb, const double* xp, double* xf);
-// what the early pattern is made from: X = the level's input batch (index arrays only), per joint feature its source
-// features in X (srcE / srcC, -1: none), per map of X its hub pose
-struct EarlyPatternIn {
-	int M = 0, NFY = 0, NU = 0;
-	const int *Ui = nullptr, *Uj = nullptr, *pose_map = nullptr, *hub = nullptr;
-	const int *fptr = nullptr, *photo = nullptr, *feat_map = nullptr, *srcE = nullptr, *srcC = nullptr;
-};
-void schur_pattern_early_issue(lsfm_context* ctx, const EarlyPatternIn& in); // enqueues on the side stream; the caller has recorded evC
-void schur_pattern_early_drop(lsfm_context* ctx);
-// target_ref[b] of the NEXT level's transform for every map of `Y` (-1: passed through), as run_level will compute it
 bool no_timing_events(); // (LSFM_NO_TIMING_EVENTS=1: the phase brackets are not recorded -- the stage times of lsfm_stats stay zero)
 #define LSFM_REC_T(e, s) do { if (!lsfm::no_timing_events()) LSFM_CHECK_HIP(hipEventRecord(e, s)); } while (0)
 unsigned timing_event_flags(); // (lsfm_prims.hip: events without the system-scope fence)
 unsigned order_event_flags();
 void prefetch_next_level(lsfm_context* ctx, const DevBatch& Y, const std::vector<int>& target_ref, int next_level, int step_hint);
-// the block pattern of S alone (K8), from the index members of io: upper block CSR left in the scratch arena
-void schur_pattern_only(lsfm_context* ctx, const SolveIO& io, int* nnzb, const int** rowptr, const int** colidx);
 int spmv_external(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const double* x, double* y, int reps,
                   double* avg_ms, double* bytes);
 

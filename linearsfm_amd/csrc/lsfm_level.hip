@@ -58,7 +58,6 @@ static std::shared_ptr<SolvePlan> solve_plan_store(lsfm_context* ctx, const Schu
 		{ sy.k9.eslot, sy.k9.eslot ? (size_t)sy.k9_NW : 0, (void**)&P.sy.k9.eslot },
 		{ sy.k9.wlist, sy.k9.wlist ? (size_t)sy.k9_tiles * 3 * 4 : 0, (void**)&P.sy.k9.wlist }, { sy.k9.wcnt, sy.k9.wcnt ? (size_t)32 : (size_t)0, (void**)&P.sy.k9.wcnt },
 	};
-	P.sy.k9.record = 0;
 	size_t total = 0;
 	for (const Item& it : items) total += (it.bytes + 255) & ~(size_t)255;
 	LSFM_CHECK_HIP(hipMalloc((void**)&P.mem, total + 256));
@@ -235,20 +234,6 @@ __global__ void k_chol_err_to_run(const int* err, RunStatsDev* run)
 	if (*err && !run->chol_err) run->chol_err = *err;
 }
 
-// LSFM_CHECK_EARLY_PATTERN=1 (debug / tests): a pattern put together ahead of the joint map must be the one built from the finished
-// joint map.  s: the stream the joint map's index arrays were written on
-static void check_pattern_made_ahead(lsfm_context* ctx, const SolveIO& io, const SchurSystem& sy, hipStream_t s, const char* what)
-{
-	if (!getenv("LSFM_CHECK_EARLY_PATTERN")) return;
-	LSFM_CHECK_HIP(hipStreamSynchronize(s));
-	SchurSystem ref;
-	build_schur_pattern(ctx, io, ref);
-	std::vector<unsigned long long> a(sy.nnzb), b(ref.nnzb);
-	d2h(ctx, a.data(), sy.upper_keys, a.size() * sizeof(unsigned long long));
-	d2h(ctx, b.data(), ref.upper_keys, b.size() * sizeof(unsigned long long));
-	if (a != b) LSFM_FAIL(LSFM_ERR_INTERNAL, std::string(what) + " pattern of S (" + std::to_string(a.size()) + " blocks) differs from the joint map's (" + std::to_string(b.size()) + ")");
-}
-
 // The structure of a level on the sparse pipeline, from wherever the level gets it: the camera system with its values assembled, the
 // factorisation ready to be scattered into (ch.d_err zeroed), evK recorded behind the Schur assembly.
 struct LevelStructure {
@@ -309,7 +294,7 @@ static LevelStructure level_structure(lsfm_context* ctx, const SolveIO& io, Solv
 		sy = prepared;
 		have = true;
 		LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->evP, 0));
-		check_pattern_made_ahead(ctx, io, sy, s, "prefetched");
+		if (getenv("LSFM_CHECK_EARLY_PATTERN")) schur_pattern_check(ctx, io, sy, "prefetched");
 	}
 	else if (ctx->early && !ctx->comm)
 	{
@@ -323,10 +308,10 @@ static LevelStructure level_structure(lsfm_context* ctx, const SolveIO& io, Solv
 			ctx->mark("pat_fin");
 			if (have)
 			{
-				check_pattern_made_ahead(ctx, io, sy, s, "early");
+				if (getenv("LSFM_CHECK_EARLY_PATTERN")) schur_pattern_check(ctx, io, sy, "early");
 				chol_fetch(ctx, sy, io.d_pose_origin, hin);
 				ctx->mark("fetch");
-				schur_pattern_early_extras(ctx, io, sy);
+				schur_pattern_early_extras(ctx, sy);
 				LSFM_CHECK_HIP(hipEventRecord(ctx->evB, ctx->stream));
 			}
 		}

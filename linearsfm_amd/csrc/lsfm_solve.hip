@@ -2,8 +2,7 @@
 // Replaces lmj_solveLinearSFM{Stereo,Mono} (Imp.cpp:2119-2378 / 6756-7041): the reference builds S = U - W V^-1 W^T
 // through a dense m x m byte mask and hands it to CHOLMOD; here
 //   K7  k_vinv            V^-1 per feature                                   (pba_inverseV, Imp.cpp:3022-3042)
-//   K8  k_pat_*           block pattern of S by hashing the pose pairs that share a feature + U's pattern
-//                         (replaces smask, Imp.cpp:2131-2205), sorted into block-CSR
+//   K8  (lsfm_pattern.hip) block pattern of S by hashing the pose pairs that share a feature + U's pattern, sorted into block CSR
 //   K9  k_schur_*         S(p,q) -= W_pf V_f^-1 W_qf^T, E_p -= W_pf V_f^-1 eb_f (Imp.cpp:2244-2332): k_schur_panel
 //                         (lsfm_schur_panel.hip, fp64 MFMA on 128-feature tiles); k_schur_w here takes the tiles it flags
 //   K10 k_spmv / k_pcg_*  Cholesky-preconditioned CG (lsfm_pcg.hip; the factor: lsfm_chol.hip) on the symmetric 6x6-block system, all independent
@@ -16,7 +15,6 @@
 
 #include "lsfm_device.hpp"
 #include "lsfm_internal.hpp"
-#include "lsfm_join.hpp"
 #include "lsfm_solve.hpp"
 
 namespace lsfm {
@@ -147,52 +145,6 @@ __global__ void k_schur_finish(int nnzb, int M, const unsigned long long* __rest
 	}
 }
 
-__global__ void k_fill_u64(unsigned long long* p, size_t n, unsigned long long v)
-{
-	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) p[i] = v;
-}
-
-__global__ void k_pat_insert_u(int NU, int M, const int* __restrict__ Ui, const int* __restrict__ Uj, unsigned long long* tab,
-                               unsigned long long mask, int* overflow)
-{
-	int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < NU) hash_insert(tab, mask, pair_key(Ui[i], Uj[i]), overflow);
-	if (i < M) hash_insert(tab, mask, pair_key(i, i), overflow); // every block row owns its diagonal block
-}
-
-// one lane per feature; all pose pairs of its W run (Imp.cpp:2155-2173).  When the whole wave asks for the same
-// pair (hub poses shared by neighbouring features) one lane inserts.
-__global__ void __launch_bounds__(256)
-k_pat_insert_w(int NF, const int* __restrict__ fptr, const int* __restrict__ photo, unsigned long long* tab, unsigned long long mask,
-               int* overflow)
-{
-	int f = blockIdx.x * blockDim.x + threadIdx.x;
-	const bool inb = f < NF;
-	int j0 = 0, len = 0;
-	if (inb) { j0 = fptr[f]; len = fptr[f + 1] - j0; }
-	int maxlen = len;
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) maxlen = max(maxlen, __shfl_xor(maxlen, off, LSFM_WAVE));
-	const int lane = threadIdx.x & (LSFM_WAVE - 1);
-	for (int a = 0; a < maxlen; a++)
-	{
-		const int pa = (inb && a < len) ? photo[j0 + a] : -1;
-		for (int b = a + 1; b < maxlen; b++)
-		{
-			const bool v = inb && b < len;
-			unsigned long long key = v ? pair_key(pa, photo[j0 + b]) : 0ull;
-			unsigned long long m = __ballot(v);
-			if (m == 0ull) continue;
-			int leader = __ffsll((long long)m) - 1;
-			unsigned long long first = (unsigned long long)__shfl((long long)key, leader, LSFM_WAVE);
-			bool uniform = __ballot(v && key != first) == 0ull;
-			if (uniform) { if (lane == leader) hash_insert(tab, mask, key, overflow); }
-			else if (v) hash_insert(tab, mask, key, overflow);
-		}
-	}
-}
-
 // sum over the features of (run length)^2: the pose pairs of K9 (for its algorithmic flop count)
 __global__ void __launch_bounds__(256) k_sum_run_squares(int NF, const int* __restrict__ fptr, unsigned long long* out)
 {
@@ -209,37 +161,6 @@ __global__ void __launch_bounds__(256) k_sum_run_squares(int NF, const int* __re
 	if ((threadIdx.x & (LSFM_WAVE - 1)) == 0) part[threadIdx.x >> 6] = v;
 	__syncthreads();
 	if (threadIdx.x == 0) { v = part[0] + part[1] + part[2] + part[3]; if (v) atomicAdd(out, v); }
-}
-
-__global__ void k_pat_compact(size_t cap, const unsigned long long* __restrict__ tab, unsigned long long* __restrict__ list, int* __restrict__ count)
-{
-	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= cap) return;
-	unsigned long long k = tab[i];
-	if (k != HEMPTY) list[atomicAdd(count, 1)] = k;
-}
-
-__global__ void k_pat_assign(int nnzb, const unsigned long long* __restrict__ sorted, const unsigned long long* __restrict__ tab,
-                             int* __restrict__ val, unsigned long long mask, int* __restrict__ colidx)
-{
-	int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= nnzb) return;
-	unsigned long long key = sorted[i];
-	unsigned long long h = mix64(key) & mask;
-	while (tab[h] != key) h = (h + 1) & mask;
-	val[h] = i;
-	colidx[i] = (int)(key & 0xffffffffull);
-}
-
-// rowptr[r] = first index whose key >= (r << 32)
-__global__ void k_rowptr_from_keys(int rows, int n, const unsigned long long* __restrict__ sorted, int shift, int* __restrict__ rowptr)
-{
-	int r = blockIdx.x * blockDim.x + threadIdx.x;
-	if (r > rows) return;
-	unsigned long long target = (unsigned long long)(unsigned)r << shift;
-	int lo = 0, hi = n;
-	while (lo < hi) { int mid = (lo + hi) >> 1; if (sorted[mid] < target) lo = mid + 1; else hi = mid; }
-	rowptr[r] = lo;
 }
 
 // ---- numeric Schur complement ------------------------------------------------------------------------------
@@ -731,16 +652,16 @@ __global__ void k_low_words(int n, const unsigned long long* __restrict__ keys, 
 	if (i < n) out[i] = (int)(keys[i] & 0xffffffffull);
 }
 
-void build_spmv_index(lsfm_context* ctx, SchurSystem& sy, const unsigned long long* sorted_upper, int* d_flags, int)
+// the SpMV's index of a system whose sorted upper pattern exists (and, from lsfm_pattern.hip, its block CSR)
+void build_spmv_index(lsfm_context* ctx, SchurSystem& sy, const unsigned long long* sorted_upper)
 {
 	hipStream_t s = ctx->stream;
 	Arena& sc = ctx->scratch;
 	const int M = sy.M, cnt = sy.nnzb;
-	(void)d_flags;
 	if (!sy.rowptr)
 	{
 		sy.rowptr = sc.alloc<int>(M + 1);
-		hipLaunchKernelGGL(k_rowptr_from_keys, dim3((M + 1 + 255) / 256), dim3(256), 0, s, M, cnt, sorted_upper, 32, sy.rowptr);
+		rowptr_from_keys(ctx, M, cnt, sorted_upper, sy.rowptr);
 	}
 	if (!sy.colidx)
 	{
@@ -779,456 +700,6 @@ void schur_vinv(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy)
 	sy.uu = nullptr;
 	if (io.rhs) sy.uu = ctx->scratch.alloc<double>((size_t)io.NF * 6);
 	if (io.NF) hipLaunchKernelGGL(k_vinv, dim3((io.NF + 255) / 256), dim3(256), 0, ctx->stream, io.NF, io.V, io.eb, sy.IV, sy.LY, sy.ymax, io.rhs ? *io.rhs : RhsFused(), sy.uu);
-}
-
-// ---- Pattern of S (hash of pose pairs, sorted key list, block CSR, SpMV index): depends on the index structure only ----
-// In three steps so that the pair insertion can come from the joint map (build_schur_pattern) or, earlier, from what the
-// joint map is made of (schur_pattern_early_issue): table set-up, [inserts], compaction (all enqueued); then -- after the
-// one read-back of the count -- sort, block CSR, SpMV index.
-struct PatternBuild {
-	unsigned long long *tab = nullptr, *list = nullptr, *d_k2 = nullptr;
-	int *hval = nullptr, *d_flags = nullptr; // [0] overflow, [1] count
-	size_t cap = 0;
-};
-static size_t pattern_capacity(size_t NU, size_t M)
-{
-	// S has little more than U's pattern (the W-induced pairs are mostly hub links that U already holds): 4x head room over
-	// NU + 8 M entries; a table that overflows is rebuilt larger
-	size_t cap = 1024;
-	while (cap < 4 * (NU + 8 * M + 64)) cap <<= 1;
-	return cap;
-}
-static void pattern_begin(lsfm_context* ctx, size_t cap, PatternBuild& pb)
-{
-	Arena& sc = ctx->scratch;
-	pb.cap = cap;
-	pb.tab = sc.alloc<unsigned long long>(cap);
-	pb.hval = sc.alloc<int>(cap);
-	pb.list = sc.alloc<unsigned long long>(cap);
-	pb.d_flags = sc.alloc<int>(4);
-	dev_zero(ctx, pb.d_flags, 4 * sizeof(int));
-	hipLaunchKernelGGL(k_fill_u64, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, pb.tab, cap, HEMPTY);
-}
-static void pattern_compact(lsfm_context* ctx, PatternBuild& pb)
-{
-	hipLaunchKernelGGL(k_pat_compact, dim3((unsigned)((pb.cap + 255) / 256)), dim3(256), 0, ctx->stream, pb.cap, pb.tab, pb.list, pb.d_flags + 1);
-}
-// reads the count back (synchronises ctx->stream); false: the table overflowed or is more than half full
-static bool pattern_count(lsfm_context* ctx, const PatternBuild& pb, int* cnt)
-{
-	int fl[2];
-	d2h_ints(ctx, pb.d_flags, fl, 2);
-	*cnt = fl[1];
-	return !fl[0] && (size_t)fl[1] * 2 <= pb.cap;
-}
-// sorted key list + block CSR: all that the host's symbolic analysis and K9 wait for (enqueued, nothing read back)
-static void pattern_finish(lsfm_context* ctx, const SolveIO& io, const PatternBuild& pb, int cnt, SchurSystem& sy)
-{
-	hipStream_t s = ctx->stream;
-	Arena& sc = ctx->scratch;
-	const int M = io.M;
-	sy.M = M;
-	sy.nnzb = cnt;
-	const unsigned long long mask = (unsigned long long)(pb.cap - 1);
-	// keys are (row << 32 | column) with both below M: two stable sorts over the bits in use (columns, then rows) instead of
-	// one over all 64 -- a third of the passes
-	int rb = 1;
-	while ((1 << rb) <= M) rb++;
-	dev_sort_keys_u64(ctx, pb.list, cnt, 0, rb);
-	dev_sort_keys_u64(ctx, pb.list, cnt, 32, 32 + rb);
-	sy.rowptr = sc.alloc<int>(M + 1);
-	sy.colidx = sc.alloc<int>(cnt + 1);
-	if (cnt) hipLaunchKernelGGL(k_pat_assign, dim3((cnt + 255) / 256), dim3(256), 0, s, cnt, pb.list, pb.tab, pb.hval, mask, sy.colidx);
-	hipLaunchKernelGGL(k_rowptr_from_keys, dim3((M + 1 + 255) / 256), dim3(256), 0, s, M, cnt, pb.list, 32, sy.rowptr);
-	sy.tab = pb.tab; sy.hval = pb.hval; sy.mask = mask;
-	sy.upper_keys = pb.list;
-	LSFM_CHECK_HIP(hipGetLastError());
-}
-
-__global__ void k_pat_insert_keys(int n, const unsigned long long* __restrict__ keys, unsigned long long* tab, unsigned long long mask, int* overflow);
-// the pattern of the level below through the join's pose renumbering (PatternSeed)
-__global__ void k_pat_insert_keys_remap(int n, const unsigned long long* __restrict__ keys, const int* __restrict__ pnew, const unsigned char* __restrict__ dropped,
-                                        unsigned long long* tab, unsigned long long mask, int* overflow)
-{
-	int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const int a = (int)(keys[i] >> 32), b = (int)(keys[i] & 0xffffffffull);
-	if (dropped[a] || dropped[b]) return;
-	hash_insert(tab, mask, pair_key(pnew[a], pnew[b]), overflow);
-}
-// ... and the pairs across the two sources of a matched joint feature
-__global__ void __launch_bounds__(256)
-k_pat_insert_cross_remap(PatternSeed sd, unsigned long long* tab, unsigned long long mask, int* overflow)
-{
-	// (the wave in step, like k_pat_insert_w: neighbouring features are seen by the same poses -- when every lane asks for the same
-	// pair, one lane inserts it)
-	const int nf = blockIdx.x * blockDim.x + threadIdx.x;
-	int jE = 0, lenE = 0, jC = 0, lenC = 0;
-	if (nf < sd.NFY)
-	{
-		const int fe = sd.srcE[nf], fc = sd.srcC[nf];
-		if (fe >= 0 && fc >= 0) { jE = sd.fptr_in[fe]; lenE = sd.fptr_in[fe + 1] - jE; jC = sd.fptr_in[fc]; lenC = sd.fptr_in[fc + 1] - jC; }
-	}
-	int maxE = lenE, maxC = lenC;
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) { maxE = max(maxE, __shfl_xor(maxE, off, LSFM_WAVE)); maxC = max(maxC, __shfl_xor(maxC, off, LSFM_WAVE)); }
-	const int lane = threadIdx.x & (LSFM_WAVE - 1);
-	for (int a = 0; a < maxE; a++)
-	{
-		int na = -1;
-		if (a < lenE) { const int pa = sd.photo_in[jE + a]; if (!sd.dropped[pa]) na = sd.pnew[pa]; }
-		for (int b = 0; b < maxC; b++)
-		{
-			int nb = -1;
-			if (na >= 0 && b < lenC) { const int pb = sd.photo_in[jC + b]; if (!sd.dropped[pb]) nb = sd.pnew[pb]; }
-			const bool v = nb >= 0;
-			const unsigned long long key = v ? pair_key(na, nb) : 0ull;
-			const unsigned long long m = __ballot(v);
-			if (m == 0ull) continue;
-			const int leader = __ffsll((long long)m) - 1;
-			const unsigned long long first = (unsigned long long)__shfl((long long)key, leader, LSFM_WAVE);
-			const bool uniform = __ballot(v && key != first) == 0ull;
-			if (uniform) { if (lane == leader) hash_insert(tab, mask, key, overflow); }
-			else if (v) hash_insert(tab, mask, key, overflow);
-		}
-	}
-}
-void build_schur_pattern(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy)
-{
-	hipStream_t s = ctx->stream;
-	Arena& sc = ctx->scratch;
-	const int M = io.M, NF = io.NF;
-	size_t cap = pattern_capacity(io.NU, M);
-	for (int attempt = 0;; attempt++)
-	{
-		const size_t mk = sc.mark();
-		PatternBuild pb;
-		pattern_begin(ctx, cap, pb);
-		const int nu = std::max(io.NU, M);
-		if (nu) hipLaunchKernelGGL(k_pat_insert_u, dim3((nu + 255) / 256), dim3(256), 0, s, io.NU, M, io.Ui, io.Uj, pb.tab, (unsigned long long)(cap - 1), pb.d_flags);
-		const PatternSeed* sd = (io.seed && io.seed->prev_keys && !ctx->comm) ? io.seed : nullptr;
-		if (sd)
-		{
-			// (until round 5 every Mono level that analyses hashed every pose pair of every feature again: 66 GB and 28 ms of a
-			// synth-16k tree, profiles/r04_pmc_traffic_summary_synth16k.json)
-			if (sd->prev_nnzb) hipLaunchKernelGGL(k_pat_insert_keys_remap, dim3((sd->prev_nnzb + 255) / 256), dim3(256), 0, s, sd->prev_nnzb, sd->prev_keys, sd->pnew, sd->dropped, pb.tab, (unsigned long long)(cap - 1), pb.d_flags);
-			if (sd->NFY) hipLaunchKernelGGL(k_pat_insert_cross_remap, dim3((sd->NFY + 255) / 256), dim3(256), 0, s, *sd, pb.tab, (unsigned long long)(cap - 1), pb.d_flags);
-		}
-		else if (NF) hipLaunchKernelGGL(k_pat_insert_w, dim3((NF + 255) / 256), dim3(256), 0, s, NF, io.fptr, io.photo, pb.tab, (unsigned long long)(cap - 1), pb.d_flags);
-		pattern_compact(ctx, pb);
-		int cnt = 0;
-		bool ok = pattern_count(ctx, pb, &cnt);
-		if (ctx->comm)
-		{
-			// feature-sharded run: the pattern of S is the UNION of what the ranks' slices induce.  Every rank learns every rank's
-			// count (a vector with one slot per rank, summed), then every rank's keys (each writes its list at its offset of a
-			// zeroed array, summed as integers), inserts them all and compacts again.  A rank whose table overflowed says so in
-			// the count exchange and all of them start over with a larger table together.
-			Comm& cm = *ctx->comm;
-			cm.restart();
-			long long* d_counts = cm.alloc<long long>(cm.world + 1);
-			std::vector<long long> hc(cm.world + 1, 0);
-			hc[cm.rank] = ok ? cnt : 0;
-			hc[cm.world] = ok ? 0 : 1;
-			h2d(ctx, d_counts, hc.data(), sizeof(long long) * hc.size());
-			cm.allreduce(s, d_counts, hc.size(), LSFM_DTYPE_I64);
-			d2h(ctx, hc.data(), d_counts, sizeof(long long) * hc.size());
-			ok = hc[cm.world] == 0;
-			if (ok)
-			{
-				long long total = 0, mine = 0;
-				for (int r = 0; r < cm.world; r++) { if (r == cm.rank) mine = total; total += hc[r]; }
-				if ((size_t)total * 2 > cap) ok = false; // (the same answer on every rank)
-				else
-				{
-					unsigned long long* all = cm.alloc<unsigned long long>((size_t)total + 1);
-					fill_async(s, all, 0, sizeof(unsigned long long) * (size_t)total);
-					if (cnt) LSFM_CHECK_HIP(hipMemcpyAsync(all + mine, pb.list, sizeof(unsigned long long) * (size_t)cnt, hipMemcpyDeviceToDevice, s));
-					cm.allreduce(s, all, (size_t)total, LSFM_DTYPE_I64);
-					if (total) hipLaunchKernelGGL(k_pat_insert_keys, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (int)total, all, pb.tab, (unsigned long long)(cap - 1), pb.d_flags);
-					dev_zero(ctx, pb.d_flags + 1, sizeof(int));
-					pattern_compact(ctx, pb);
-					ok = pattern_count(ctx, pb, &cnt); // replicated from here on: the same table contents on every rank
-				}
-			}
-		}
-		if (ok)
-		{
-			pattern_finish(ctx, io, pb, cnt, sy);
-			if (sd && getenv("LSFM_CHECK_MONO_SEED"))
-			{
-				// debug / test: the pattern built from the finished joint map must be contained in the seeded one (a pair the seeded
-				// pattern lacked would lose its share of S without a word) -- and, the seed being exact, equal to it
-				LSFM_CHECK_HIP(hipDeviceSynchronize());
-				SolveIO plain = io;
-				plain.seed = nullptr;
-				SchurSystem ref;
-				build_schur_pattern(ctx, plain, ref);
-				std::vector<unsigned long long> a(sy.nnzb), b(ref.nnzb);
-				d2h(ctx, a.data(), sy.upper_keys, a.size() * sizeof(unsigned long long));
-				d2h(ctx, b.data(), ref.upper_keys, b.size() * sizeof(unsigned long long));
-				size_t missing = 0, ia = 0;
-				for (unsigned long long k : b)
-				{
-					while (ia < a.size() && a[ia] < k) ia++;
-					if (ia == a.size() || a[ia] != k) missing++;
-				}
-				if (missing || a.size() != b.size())
-					LSFM_FAIL(LSFM_ERR_INTERNAL, "seeded pattern of S (" + std::to_string(a.size()) + " blocks) against the joint map's (" + std::to_string(b.size()) + "): " +
-					                                 std::to_string(missing) + " pair(s) missing");
-			}
-			build_spmv_index(ctx, sy, pb.list, pb.d_flags);
-			return;
-		}
-		sc.release(mk);
-		cap <<= 2;
-		if (attempt > 10) LSFM_FAIL(LSFM_ERR_INTERNAL, "Schur pattern hash table kept overflowing");
-	}
-}
-
-// ---- the same pattern, earlier ------------------------------------------------------------------------------------------
-// The joint map of a Stereo join is the two input maps side by side: a joint feature is seen by the poses of its End source,
-// the poses of its Cur source, and the hub pose of either map that is transformed on the way (the transform gives every feature
-// of the map a block to the hub pose, Imp.cpp:1303-1309, and folds old blocks to it into that one); U' holds U's pairs and
-// (k, hub) for every pose k of a transformed map (Imp.cpp:711-723).  All of that is known from the level's INPUT index arrays
-// once the features are matched -- before the transform's block kernels have run.
-__global__ void k_pat_insert_u_early(int NU, int M, const int* __restrict__ Ui, const int* __restrict__ Uj, const int* __restrict__ pose_map,
-                                     const int* __restrict__ hub, unsigned long long* tab, unsigned long long mask, int* overflow)
-{
-	int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < NU) hash_insert(tab, mask, pair_key(Ui[i], Uj[i]), overflow);
-	if (i < M)
-	{
-		hash_insert(tab, mask, pair_key(i, i), overflow);
-		const int h = hub[pose_map[i]];
-		if (h >= 0) hash_insert(tab, mask, pair_key(i, h), overflow);
-	}
-}
-__global__ void __launch_bounds__(256)
-k_pat_insert_w_early(int NFY, const int* __restrict__ srcE, const int* __restrict__ srcC, const int* __restrict__ fptr, const int* __restrict__ photo,
-                     const int* __restrict__ feat_map, const int* __restrict__ hub, unsigned long long* tab, unsigned long long mask, int* overflow)
-{
-	const int nf = blockIdx.x * blockDim.x + threadIdx.x;
-	const bool inb = nf < NFY;
-	int jE = 0, lenE = 0, hE = -1, jC = 0, lenC = 0, hC = -1;
-	if (inb)
-	{
-		const int fe = srcE[nf], fc = srcC[nf];
-		if (fe >= 0) { jE = fptr[fe]; lenE = fptr[fe + 1] - jE; hE = hub[feat_map[fe]]; }
-		if (fc >= 0) { jC = fptr[fc]; lenC = fptr[fc + 1] - jC; hC = hub[feat_map[fc]]; }
-	}
-	const int nE = lenE + (hE >= 0 ? 1 : 0), len = nE + lenC + (hC >= 0 ? 1 : 0);
-	auto pose_at = [&](int i) -> int {
-		if (i < lenE) return photo[jE + i];
-		if (i < nE) return hE;
-		i -= nE;
-		return i < lenC ? photo[jC + i] : hC;
-	};
-	int maxlen = len;
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) maxlen = max(maxlen, __shfl_xor(maxlen, off, LSFM_WAVE));
-	const int lane = threadIdx.x & (LSFM_WAVE - 1);
-	for (int a = 0; a < maxlen; a++)
-	{
-		const int pa = (inb && a < len) ? pose_at(a) : -1;
-		for (int b = a + 1; b < maxlen; b++)
-		{
-			const bool v = inb && b < len;
-			unsigned long long key = v ? pair_key(pa, pose_at(b)) : 0ull;
-			unsigned long long m = __ballot(v);
-			if (m == 0ull) continue;
-			int leader = __ffsll((long long)m) - 1;
-			unsigned long long first = (unsigned long long)__shfl((long long)key, leader, LSFM_WAVE);
-			bool uniform = __ballot(v && key != first) == 0ull;
-			if (uniform) { if (lane == leader) hash_insert(tab, mask, key, overflow); }
-			else if (v) hash_insert(tab, mask, key, overflow);
-		}
-	}
-}
-
-__global__ void k_pat_insert_keys(int n, const unsigned long long* __restrict__ keys, unsigned long long* tab, unsigned long long mask, int* overflow)
-{
-	int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) hash_insert(tab, mask, keys[i], overflow);
-}
-
-// ---- the pattern of the NEXT level's system, from this level's joint maps (prefetch_next_level, lsfm_level.hip) -------------
-// hub pose of every map of the batch in the next level's transform: the pose whose id is the map's target reference
-__global__ void k_pre_hubs(int M, const int* __restrict__ pose_id, const int* __restrict__ pose_map, const int* __restrict__ tref, int* __restrict__ hub)
-{
-	int k = blockIdx.x * blockDim.x + threadIdx.x;
-	if (k >= M) return;
-	const int b = pose_map[k];
-	if (tref[b] >= 0 && pose_id[k] == tref[b]) hub[b] = k;
-}
-// pairs across the two maps of a pair, one lane per feature of the second map that has a match in the first
-__global__ void __launch_bounds__(256)
-k_pat_insert_w_cross_match(int NF, const int* __restrict__ feat_map, const int* __restrict__ match, const int* __restrict__ fptr,
-                           const int* __restrict__ photo, const int* __restrict__ hub, unsigned long long* tab, unsigned long long mask, int* overflow)
-{
-	const int fc = blockIdx.x * blockDim.x + threadIdx.x;
-	if (fc >= NF || !(feat_map[fc] & 1)) return;
-	const int fe = match[fc];
-	if (fe < 0) return;
-	const int jE = fptr[fe], lenE = fptr[fe + 1] - jE, hE = hub[feat_map[fe]];
-	const int jC = fptr[fc], lenC = fptr[fc + 1] - jC, hC = hub[feat_map[fc]];
-	for (int a = 0; a <= lenE; a++)
-	{
-		const int pa = a < lenE ? photo[jE + a] : hE;
-		if (pa < 0) continue;
-		for (int b = 0; b <= lenC; b++)
-		{
-			const int pb = b < lenC ? photo[jC + b] : hC;
-			if (pb >= 0) hash_insert(tab, mask, pair_key(pa, pb), overflow);
-		}
-	}
-}
-// which blocks of the batch survive the next level's transform as they are (k_tr_flags of lsfm_transform.hip, from the hubs alone)
-__global__ void k_pre_flags(const int* __restrict__ Ui, const int* __restrict__ Uj, int NU, const int* __restrict__ photo, int NW,
-                            const int* __restrict__ pose_map, const int* __restrict__ hub, int* __restrict__ keepU, int* __restrict__ keepW)
-{
-	int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < NU) { const int a = Ui[i], b = Uj[i], h = hub[pose_map[a]]; keepU[i] = (h < 0 || (a != h && b != h)) ? 1 : 0; }
-	if (i < NW) { const int k = photo[i], h = hub[pose_map[k]]; keepW[i] = (h < 0 || k != h) ? 1 : 0; }
-	if (i == 0) { keepU[NU] = 0; keepW[NW] = 0; }
-}
-__global__ void k_pre_gather(const int* __restrict__ KU, const int* __restrict__ KW, const int* __restrict__ R, const int* __restrict__ uoff,
-                             const int* __restrict__ woff, const int* __restrict__ foff, int B, int* __restrict__ out)
-{
-	int b = blockIdx.x * blockDim.x + threadIdx.x;
-	if (b > B) return;
-	out[b] = KU[uoff[b]];
-	out[B + 1 + b] = KW[woff[b]];
-	out[2 * (B + 1) + b] = R[foff[b]];
-}
-// ctx->stream / ctx->scratch name the stream and the arena the caller wants this on.  prev_keys: the pattern of the level that
-// produced Y (every pair inside one of Y's maps).  false: nothing to build from.  counts (optional): what the next level's
-// transform and join read back from the device -- kept-block prefixes at the map boundaries (U, then W: transform_batch's
-// `cnt`) and the ranks of the unmatched features there (join_stereo_prepare's `rb`), 3 (B + 1) ints, valid after the
-// caller's next synchronisation of the stream.
-bool schur_pattern_prefetch(lsfm_context* ctx, const DevBatch& Y, const int* d_tref, const unsigned long long* prev_keys, int prev_nnzb, SchurSystem& sy,
-                            std::vector<int>* counts, bool want_pattern, LevelIndex* keep)
-{
-	// prev_keys == null: the level that produced Y left no pattern (its systems were small enough for the dense path, which needs
-	// none): the pairs inside every map of Y are then taken from Y's own W runs (k_pat_insert_w), as a level without a predecessor does
-	if (!Y.M) return false;
-	hipStream_t s = ctx->stream;
-	Arena& sc = ctx->scratch;
-	int* hub = sc.alloc<int>(Y.B);
-	fill_async(s, hub, 0xff, sizeof(int) * (size_t)Y.B);
-	hipLaunchKernelGGL(k_pre_hubs, dim3((Y.M + 255) / 256), dim3(256), 0, s, Y.M, Y.pose_id, Y.pose_map, d_tref, hub);
-	int* match = sc.alloc<int>(Y.NF + 1);
-	int* unm = sc.alloc<int>(Y.NF + 2);
-	if (Y.NF) join_match_features(ctx, Y, match, unm);
-	else dev_zero(ctx, unm, 2 * sizeof(int));
-	if (counts)
-	{
-		const int B = Y.B;
-		int* keepU = sc.alloc<int>(Y.NU + 1); int* keepW = sc.alloc<int>(Y.NW + 1);
-		int* KU = sc.alloc<int>(Y.NU + 2); int* KW = sc.alloc<int>(Y.NW + 2); int* R = sc.alloc<int>(Y.NF + 2);
-		const int nmax = std::max(std::max(Y.NU, Y.NW), 1);
-		hipLaunchKernelGGL(k_pre_flags, dim3((nmax + 255) / 256), dim3(256), 0, s, Y.Ui, Y.Uj, Y.NU, Y.photo, Y.NW, Y.pose_map, hub, keepU, keepW);
-		dev_exclusive_scan(ctx, keepU, KU, Y.NU);
-		dev_exclusive_scan(ctx, keepW, KW, Y.NW);
-		dev_exclusive_scan(ctx, unm, R, Y.NF);
-		int* d_off = sc.alloc<int>(2 * (B + 1));
-		h2d(ctx, d_off, Y.u_off.data(), (B + 1) * sizeof(int));
-		h2d(ctx, d_off + B + 1, Y.w_off.data(), (B + 1) * sizeof(int));
-		int* d_cnt = sc.alloc<int>(3 * (B + 1));
-		hipLaunchKernelGGL(k_pre_gather, dim3((B + 1 + 127) / 128), dim3(128), 0, s, KU, KW, R, d_off, d_off + B + 1, Y.d_feat_off, B, d_cnt);
-		counts->resize(3 * (size_t)(B + 1));
-		LSFM_CHECK_HIP(hipMemcpyAsync(counts->data(), d_cnt, counts->size() * sizeof(int), hipMemcpyDeviceToHost, s));
-		if (keep)
-		{
-			// what the next level's transform and join would work out again from the same index arrays (they live in this arena until
-			// the level after next prepares ITS successor)
-			*keep = LevelIndex();
-			keep->NU = Y.NU; keep->NW = Y.NW; keep->NF = Y.NF;
-			keep->KU = KU; keep->KW = KW; keep->match = match; keep->R = R;
-		}
-	}
-	if (!want_pattern)
-	{
-		// (the next level's systems are small: it needs the counts alone; they arrive with the caller's next synchronisation)
-		LSFM_CHECK_HIP(hipStreamSynchronize(s));
-		return true;
-	}
-	size_t cap = pattern_capacity(std::max((size_t)Y.NU + Y.M, (size_t)prev_nnzb + Y.M), Y.M);
-	SolveIO io;
-	io.M = Y.M;
-	for (int attempt = 0;; attempt++)
-	{
-		const size_t mk = sc.mark();
-		PatternBuild pb;
-		pattern_begin(ctx, cap, pb);
-		const unsigned long long mask = (unsigned long long)(cap - 1);
-		const int nu = std::max(Y.NU, Y.M);
-		hipLaunchKernelGGL(k_pat_insert_u_early, dim3((nu + 255) / 256), dim3(256), 0, s, Y.NU, Y.M, Y.Ui, Y.Uj, Y.pose_map, hub, pb.tab, mask, pb.d_flags);
-		if (prev_keys && prev_nnzb) hipLaunchKernelGGL(k_pat_insert_keys, dim3((prev_nnzb + 255) / 256), dim3(256), 0, s, prev_nnzb, prev_keys, pb.tab, mask, pb.d_flags);
-		if (!prev_keys && Y.NF) hipLaunchKernelGGL(k_pat_insert_w, dim3((Y.NF + 255) / 256), dim3(256), 0, s, Y.NF, Y.fptr, Y.photo, pb.tab, mask, pb.d_flags);
-		if (Y.NF) hipLaunchKernelGGL(k_pat_insert_w_cross_match, dim3((Y.NF + 255) / 256), dim3(256), 0, s, Y.NF, Y.feat_map, match, Y.fptr, Y.photo, hub, pb.tab, mask, pb.d_flags);
-		pattern_compact(ctx, pb);
-		int cnt = 0;
-		if (pattern_count(ctx, pb, &cnt))
-		{
-			pattern_finish(ctx, io, pb, cnt, sy);
-			build_spmv_index(ctx, sy, pb.list, pb.d_flags);
-			return true;
-		}
-		sc.release(mk);
-		cap <<= 2;
-		if (attempt > 10) return false;
-	}
-}
-
-struct EarlyPattern { PatternBuild pb; int M = 0; };
-
-void schur_pattern_early_issue(lsfm_context* ctx, const EarlyPatternIn& in)
-{
-	ctx->early.reset();
-	auto ep = std::make_shared<EarlyPattern>();
-	ep->M = in.M;
-	// on the side stream, behind the point of the main stream where the matches and the hub poses are known (evC)
-	LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream3, ctx->evC, 0));
-	{
-		OnStream on(ctx, ctx->stream3);
-		hipStream_t s = ctx->stream;
-		const size_t cap = pattern_capacity((size_t)in.NU + in.M, in.M);
-		pattern_begin(ctx, cap, ep->pb);
-		const int nu = std::max(in.NU, in.M);
-		const unsigned long long mask = (unsigned long long)(cap - 1);
-		if (nu) hipLaunchKernelGGL(k_pat_insert_u_early, dim3((nu + 255) / 256), dim3(256), 0, s, in.NU, in.M, in.Ui, in.Uj, in.pose_map, in.hub, ep->pb.tab, mask, ep->pb.d_flags);
-		if (in.NFY) hipLaunchKernelGGL(k_pat_insert_w_early, dim3((in.NFY + 255) / 256), dim3(256), 0, s, in.NFY, in.srcE, in.srcC, in.fptr, in.photo, in.feat_map, in.hub, ep->pb.tab, mask, ep->pb.d_flags);
-		pattern_compact(ctx, ep->pb);
-		LSFM_CHECK_HIP(hipGetLastError());
-	}
-	ctx->early = ep;
-}
-void schur_pattern_early_drop(lsfm_context* ctx) { ctx->early.reset(); }
-
-// Second half, on the stream ctx->stream currently names (the caller has swapped the side stream in): count, sort, block CSR.
-// false: no early build in flight, or its table overflowed -- the caller builds the pattern from the joint map instead.
-bool schur_pattern_early_finish(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy)
-{
-	std::shared_ptr<EarlyPattern> ep = std::move(ctx->early);
-	if (!ep || ep->M != io.M) return false;
-	int cnt = 0;
-	if (!pattern_count(ctx, ep->pb, &cnt)) return false;
-	pattern_finish(ctx, io, ep->pb, cnt, sy);
-	return true;
-}
-// after the keys have gone to the host: -- enqueued only -- the SpMV index, which nothing needs before the first product of the CG
-void schur_pattern_early_extras(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy)
-{
-	(void)io;
-	build_spmv_index(ctx, sy, sy.upper_keys, nullptr);
-}
-
-void schur_pattern_only(lsfm_context* ctx, const SolveIO& io, int* nnzb, const int** rowptr, const int** colidx)
-{
-	SchurSystem sy;
-	build_schur_pattern(ctx, io, sy);
-	*nnzb = sy.nnzb; *rowptr = sy.rowptr; *colidx = sy.colidx;
 }
 
 // Values of S and E: enqueued without a host synchronisation (the caller overlaps host work with K9); the K9 launch is
@@ -1393,14 +864,10 @@ int spmv_external(lsfm_context* ctx, int m, const int* rowptr, const int* colidx
 	sy.S = sc.alloc<double>((size_t)nnzb * 36);
 	double* dx = sc.alloc<double>((size_t)m * 6);
 	double* dy = sc.alloc<double>((size_t)m * 6);
-	int* d_flags = sc.alloc<int>(4);
 	h2d(ctx, dk, keys.data(), (size_t)nnzb * sizeof(unsigned long long));
 	h2d(ctx, sy.S, val, (size_t)nnzb * 36 * sizeof(double));
 	h2d(ctx, dx, x, (size_t)m * 6 * sizeof(double));
-	int nmir = 0;
-	for (int p = 0; p < m; p++)
-		for (int k = rowptr[p]; k < rowptr[p + 1]; k++) nmir += colidx[k] != p;
-	build_spmv_index(ctx, sy, dk, d_flags, nmir);
+	build_spmv_index(ctx, sy, dk);
 	float total = 0;
 	for (int k = 0; k < reps + 2; k++)
 	{

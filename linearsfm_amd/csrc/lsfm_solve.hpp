@@ -1,6 +1,7 @@
-// Shared between lsfm_solve.hip (Schur assembly, SpMV, back-substitution), lsfm_level.hip (the level driver), lsfm_chol.hip (the
-// factorisation) and lsfm_pcg.hip (the refinement).
+// Shared between lsfm_pattern.hip (the pattern of S), lsfm_solve.hip (Schur assembly, SpMV, back-substitution), lsfm_level.hip (the
+// level driver), lsfm_chol.hip (the factorisation) and lsfm_pcg.hip (the refinement).
 #pragma once
+#include "lsfm_device.hpp"
 #include "lsfm_internal.hpp"
 
 // features per tile of K9's panel kernel (lsfm_schur_panel.hip); the per-feature fallback k_schur_w keeps tiles of 128 and looks its
@@ -20,7 +21,6 @@ struct K9Cache {
 	unsigned char* eslot = nullptr; // [NW]
 	int* wlist = nullptr;         // [3 * tiles] tiles of the 32- / 48- / 64-slot variants, wcnt[v] of them each
 	int* wcnt = nullptr;          // [8]: [0..2] tiles in the lists (structure, kept by a plan), [4..6] the cursors of a launch
-	int record = 0; // (unused since the slots have a kernel of their own)
 };
 
 struct SchurSystem {
@@ -52,6 +52,7 @@ struct SchurSystem {
 	double k9_flops = 0; // algorithmic flops of the numeric Schur complement of this system (structure only)
 };
 
+// ---- the pattern of S (lsfm_pattern.hip) ----
 // The pattern of a Mono level's camera system from the one below (the Stereo levels have had this since round 3, through the early
 // pattern): every pose pair inside one source map is in the level below's pattern -- a joint feature is seen by everything its
 // sources were seen by --, the transform's hub links are blocks of the joint U, and what is new are the pairs ACROSS the two sources of
@@ -66,14 +67,30 @@ struct PatternSeed {
 	const int *srcE = nullptr, *srcC = nullptr; // [NFY] source features in the input batch (-1: none)
 	const int *fptr_in = nullptr, *photo_in = nullptr; // W runs of the input batch
 };
+// what the early pattern is made from: X = the level's input batch (index arrays only), per joint feature its source
+// features in X (srcE / srcC, -1: none), per map of X its hub pose
+struct EarlyPatternIn {
+	int M = 0, NFY = 0, NU = 0;
+	const int *Ui = nullptr, *Uj = nullptr, *pose_map = nullptr, *hub = nullptr;
+	const int *fptr = nullptr, *photo = nullptr, *feat_map = nullptr, *srcE = nullptr, *srcC = nullptr;
+};
 void build_schur_pattern(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy);
+// the block pattern of S alone (K8), from the index members of io: upper block CSR left in the scratch arena
+void schur_pattern_only(lsfm_context* ctx, const SolveIO& io, int* nnzb, const int** rowptr, const int** colidx);
+void schur_pattern_early_issue(lsfm_context* ctx, const EarlyPatternIn& in); // enqueues on the side stream; the caller has recorded evC
+void schur_pattern_early_drop(lsfm_context* ctx);
 bool schur_pattern_early_finish(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy);
-void schur_pattern_early_extras(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy);
+void schur_pattern_early_extras(lsfm_context* ctx, SchurSystem& sy);
 bool schur_pattern_prefetch(lsfm_context* ctx, const DevBatch& Y, const int* d_tref, const unsigned long long* prev_keys, int prev_nnzb, SchurSystem& sy,
                             std::vector<int>* counts = nullptr, bool want_pattern = true, LevelIndex* keep = nullptr);
+// debug / tests (LSFM_CHECK_EARLY_PATTERN, LSFM_CHECK_MONO_SEED): a pattern made ahead of the joint map (`what`: early, prefetched,
+// seeded) must be the one built from the finished joint map `io` -- synchronises the device, fails unless the key lists are equal
+void schur_pattern_check(lsfm_context* ctx, const SolveIO& io, const SchurSystem& sy, const char* what);
+void rowptr_from_keys(lsfm_context* ctx, int M, int cnt, const unsigned long long* sorted_upper, int* rowptr);
+
 void build_schur_values(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy);
 void schur_vinv(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy);
-void build_spmv_index(lsfm_context* ctx, SchurSystem& sy, const unsigned long long* sorted_upper, int* d_flags, int nmir = -1);
+void build_spmv_index(lsfm_context* ctx, SchurSystem& sy, const unsigned long long* sorted_upper);
 void launch_spmv(lsfm_context* ctx, const SchurSystem& sy, const double* x, double* y, const unsigned char* fixed, const double* dotw,
                  const int* pose_seg, double* dot, int dot_stride);
 double spmv_bytes(const SchurSystem& sy);
@@ -132,6 +149,17 @@ __device__ __forceinline__ void hash_insert(unsigned long long* tab, unsigned lo
 		h = (h + 1) & mask;
 	}
 	*overflow = 1;
+}
+// the wave in step (every lane of it calls): when all the lanes that have a key ask for the same one -- hub poses shared by
+// neighbouring features --, one lane inserts it
+__device__ __forceinline__ void hash_insert_wave(unsigned long long* tab, unsigned long long mask, bool valid, unsigned long long key, int* overflow)
+{
+	const unsigned long long m = __ballot(valid);
+	if (m == 0ull) return;
+	const int leader = __ffsll((long long)m) - 1;
+	const unsigned long long first = (unsigned long long)__shfl((long long)key, leader, LSFM_WAVE);
+	const bool uniform = __ballot(valid && key != first) == 0ull;
+	if (uniform ? (int)(threadIdx.x & (LSFM_WAVE - 1)) == leader : valid) hash_insert(tab, mask, key, overflow);
 }
 __device__ __forceinline__ int hash_find(const unsigned long long* __restrict__ tab, const int* __restrict__ val, unsigned long long mask,
                                          unsigned long long key)

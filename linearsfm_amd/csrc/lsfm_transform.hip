@@ -53,7 +53,7 @@ __global__ void k_tr_find(const int* __restrict__ pose_id, const int* __restrict
 		if (id == t.oldref) t.hub[0] = k;
 		if (id == t.oldscap) t.hub[1] = k;
 	}
-	else if (id == t.tref) t.hub[0] = k; // Stereo: the slot of the new reference pose holds the old one afterwards
+	else if (tr_stereo_hub(id, t.tref)) t.hub[0] = k; // (the slot of the new reference pose holds the old one afterwards)
 }
 
 // Imp.cpp:389-400 / 3216-3244
@@ -122,7 +122,7 @@ __global__ void k_tr_new_poses(const double* __restrict__ pose, const int* __res
 }
 
 // Imp.cpp:459-471 / 3311-3365
-// hub_out (optional): hub pose of every map for the early pattern of S (lsfm_solve.hip): the dense column a transformed map gets,
+// hub_out (optional): hub pose of every map for the early pattern of S (lsfm_pattern.hip): the dense column a transformed map gets,
 // -1: passed through
 __global__ void k_tr_params2(const double* __restrict__ npose, TMap* tm, int B, int* __restrict__ hub_out)
 {
@@ -301,20 +301,16 @@ __global__ void k_tr_flags(const int* __restrict__ Ui, const int* __restrict__ U
                            const int* __restrict__ pose_map, const TMap* __restrict__ tm, int* __restrict__ keepU, int* __restrict__ keepW)
 {
 	int i = blockIdx.x * blockDim.x + threadIdx.x;
+	// (hub[1] of a Stereo map stays -1; a map that is passed through has no hub)
 	if (i < NU)
 	{
 		const TMap& t = tm[pose_map[Ui[i]]];
-		int a = Ui[i], b = Uj[i], keep = 1;
-		if (t.active > 0) keep = (a != t.hub[0] && b != t.hub[0] && (t.nh == 1 || (a != t.hub[1] && b != t.hub[1])));
-		keepU[i] = keep;
+		keepU[i] = t.active > 0 ? tr_keeps_u(Ui[i], Uj[i], t.hub[0], t.hub[1]) : 1;
 	}
 	if (i < NW)
 	{
-		int k = photo[i];
-		const TMap& t = tm[pose_map[k]];
-		int keep = 1;
-		if (t.active > 0) keep = (k != t.hub[0] && (t.nh == 1 || k != t.hub[1]));
-		keepW[i] = keep;
+		const TMap& t = tm[pose_map[photo[i]]];
+		keepW[i] = t.active > 0 ? tr_keeps_w(photo[i], t.hub[0], t.hub[1]) : 1;
 	}
 	if (i == 0) { keepU[NU] = 0; keepW[NW] = 0; }
 }
@@ -1096,6 +1092,25 @@ __global__ void k_tr_sign_check(const TMap* __restrict__ tm, const int* __restri
 	if (b < B && tm[b].active > 0 && tm[b].sign1 != planned[b]) atomicExch(&run->plan_stale, 1);
 }
 
+int level_targets(const DevBatch& X, bool mono, std::vector<int>& tref, std::vector<int>& tscap, std::vector<int>& tfix)
+{
+	const int B = X.B;
+	tref.assign(B, -1); tscap.assign(B, 0); tfix.assign(B, 0);
+	int ntr = 0;
+	for (int c = 1; c < B; c += 2)
+	{
+		const int e = c - 1;
+		// odd outputs of the previous level go back to their first frame (Imp.cpp:1997-2025 / 6576-6602) ...
+		const bool re = X.Ref[c] > X.FRef[c];
+		int cref = X.Ref[c], cscap = X.ScaP[c], cfix = X.Fix[c];
+		if (re) { cref = X.FRef[c]; cscap = X.FScaP[c]; cfix = X.FFix[c]; tref[c] = cref; tscap[c] = cscap; tfix[c] = cfix; ntr++; }
+		// ... and End is expressed in Cur's frame (Imp.cpp:1964 / 6549)
+		tref[e] = cref; tscap[e] = cscap; tfix[e] = cfix; ntr++;
+	}
+	for (int b = 0; b < B; b++) if (tref[b] >= 0 && map_in_frame(X, b, tref[b], tscap[b], mono)) tref[b] = -1;
+	return ntr;
+}
+
 void transform_batch(lsfm_context* ctx, Arena& ar, const DevBatch& in, const std::vector<int>& target_ref,
                      const std::vector<int>& target_scap, const std::vector<int>& target_fix, bool mono, DevBatch& out,
                      bool alias_passthrough, const std::function<TrRedirect(DevBatch&)>* hook)
@@ -1104,7 +1119,6 @@ void transform_batch(lsfm_context* ctx, Arena& ar, const DevBatch& in, const std
 	const int B = in.B, nh = mono ? 2 : 1;
 	size_t smark = ctx->scratch.mark();
 	std::vector<TMap> tm(B);
-	bool any = false;
 	for (int b = 0; b < B; b++)
 	{
 		TMap& t = tm[b];
@@ -1114,9 +1128,7 @@ void transform_batch(lsfm_context* ctx, Arena& ar, const DevBatch& in, const std
 		t.F0 = in.feat_off[b]; t.n = in.feat_off[b + 1] - t.F0;
 		t.U0 = in.u_off[b]; t.W0 = in.w_off[b];
 		t.hub[0] = t.hub[1] = t.nref = t.nscap = -1;
-		bool act = target_ref[b] >= 0 && !(in.Ref[b] == target_ref[b] && (!mono || in.ScaP[b] == target_scap[b])); // Imp.cpp:352 / 3176
-		t.active = act ? 1 : 0;
-		any |= act;
+		t.active = target_ref[b] >= 0 && !map_in_frame(in, b, target_ref[b], mono ? target_scap[b] : 0, mono);
 		t.tref = target_ref[b]; t.tscap = mono ? target_scap[b] : 0; t.newFix = mono ? target_fix[b] : 0;
 		t.oldref = in.Ref[b]; t.oldscap = mono ? in.ScaP[b] : 0; t.oldFix = mono ? in.Fix[b] : 0;
 		t.newLabel = in.Ref[b];
@@ -1301,7 +1313,6 @@ void transform_batch(lsfm_context* ctx, Arena& ar, const DevBatch& in, const std
 	else launch_stage<1>(ctx, in, out, d_tm, KU, KW, Dp, Cp, Gpose, PP, nw_act_in, nw_act_out, nf_act, hook);
 	ctx->mark("tr_done");
 	LSFM_CHECK_HIP(hipGetLastError());
-	(void)any;
 	ctx->tr_in = nullptr; ctx->tr_hub = nullptr;
 	// Scratch is released for the caller's next stage: everything that touches it is ordered on the main stream (the side
 	// stream's part rejoins it through evB above).  A first run also stops here so that a failure surfaces at its stage --

@@ -441,7 +441,7 @@ def test_factorisation_is_bit_reproducible(config, n_maps):
 @pytest.mark.parametrize("n_maps", [24, 150])
 def test_mono_pattern_from_the_level_below_equals_the_joint_maps(ctx, oracle, monkeypatch, n_maps):
     """Mono levels that analyse build the pattern of S from the pattern of the level below (through the join's pose renumbering) +
-    the joint U + the pairs across the two sources of matched features (PatternSeed, lsfm_solve.hip).  LSFM_CHECK_MONO_SEED=1 makes
+    the joint U + the pairs across the two sources of matched features (PatternSeed, lsfm_pattern.hip).  LSFM_CHECK_MONO_SEED=1 makes
     every such level ALSO hash every pose pair of every feature of its joint maps, as before, and fail unless the two patterns are
     the same set -- a pair the seed lacked would lose its share of S silently.  The dense path is switched off so that every level
     has a pattern; the result is held to the oracle's."""
