@@ -136,6 +136,10 @@ int lsfm_set_small_solve(lsfm_context* ctx, int max_poses);
  * blocks, a larger one streams its upper blocks from HBM once.  1: always the streaming kernel.  2: always the list.
  * A measurement / test knob; it applies to the systems analysed after the call (a recorded plan keeps its choice). */
 int lsfm_set_spmv_variant(lsfm_context* ctx, int variant);
+/* Which kernel of lsfm_map_covariance_columns multiplies a supernode group's dense panel with the solved columns.  0 (default): the
+ * faster one where measured.  1: lane per column, inside the group's own launch.  2: 16x16 tiles on
+ * v_mfma_f64_16x16x4_f64 in a launch of their own.  A measurement / test knob: the results agree to rounding. */
+int lsfm_set_covcols_panel(lsfm_context* ctx, int variant);
 const char* lsfm_last_error(lsfm_context* ctx);
 void* lsfm_stream(lsfm_context* ctx); /* hipStream_t the library launches on */
 
@@ -234,6 +238,40 @@ int lsfm_map_covariance(lsfm_context* ctx, const lsfm_map* map, int mono, double
  * factorisation, the selected inversion (with the gather onto the pattern), the feature part */
 int lsfm_map_covariance_timed(lsfm_context* ctx, const lsfm_map* map, int mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb,
                               double* times);
+
+/* ---- whole columns of Sigma for chosen poses (NO reference counterpart) ----
+ * Sigma_{.,Q} for the k distinct poses Q = poses[0..k) (indices into the map's own pose order, 0 <= poses[a] < m, k >= 1): every block
+ * Sigma_{p,q} and Sigma_{f,q}, on AND off the camera system's pattern -- what gating a loop closure between two poses that share no
+ * feature, the uncertainty of a relative pose or the joint marginal of a few key frames need.  map, mono, the gauge, the argument
+ * checks and the lifetime in the context's arenas are lsfm_map_covariance's.  The camera system is factored as there; the 6 k unit
+ * right-hand sides are solved side by side against the factor (in chunks of 32 poses) and refined in fp64 against S itself:
+ * always one step, then while some column's correction |delta|_inf / |x|_inf is above the context's rel_tol (lsfm_set_pcg; default
+ * 1e-12) and fell by at least half in the last step, at most max_steps steps.  On the 200-map Mono chain, where the unrefined
+ * lsfm_map_covariance is 1e-6 of the variances off, three steps leave 2e-10.
+ * Outputs (each optional, at least one non-NULL; unscaled, unpermuted):
+ *   pose_cols[36 k m]  block Sigma_{p, poses[a]} at pose_cols + 36 (a m + p), row-major 6x6: rows = scalars of p, columns = scalars of poses[a]
+ *   feat_cols[18 k n]  block Sigma_{f, poses[a]} at feat_cols + 18 (a n + f), row-major 3x6
+ *   joint[6k * 6k]     Sigma_QQ, row-major, EXACTLY symmetric: block (a, b), a < b, is taken from column b and mirrored, a diagonal
+ *                      block is (X + X^T) / 2
+ *   steps              refinement steps taken (the most over the chunks)
+ *   last_corr[k]       per requested pose the largest |delta_c|_inf / |x_c|_inf of the last correction over its six columns
+ * Fixed scalars (Mono gauge) have zero rows and columns: asking for the Ref pose gives zeros.
+ * Always fp64 and always the sparse factorisation (lsfm_set_precision / lsfm_set_small_solve do not apply).  NOT bit-reproducible
+ * from call to call (the sweeps add into the rows of a column's ancestors by atomics); the refinement leaves the difference at
+ * rounding level of the result.  lsfm_set_spmv_variant does not apply either: the residual is always taken from the row-sorted
+ * list of S's blocks, built for this call.
+ * Returns LSFM_OK; LSFM_NOT_CONVERGED when max_steps steps were taken and the last correction was still above rel_tol (the results are
+ * written; a refinement that stops because its corrections no longer halve has reached what fp64 gives and is LSFM_OK -- last_corr
+ * says where it ended); LSFM_ERR_NOT_SPD, and > 0 = the number of floored pivots (nothing written, *steps = 0), exactly as
+ * lsfm_map_covariance -- LSFM_NOT_CONVERGED is 1 too, so pass `steps` to tell one floored pivot from a refinement that ran out of
+ * steps; LSFM_ERR_OOM when the columns of a chunk do not fit the device (24 + 18 n / m doubles per pose scalar and
+ * column); LSFM_ERR_ARG for all outputs NULL, k < 1, an index out of range or given twice, and whatever lsfm_map_covariance refuses. */
+int lsfm_map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, int mono, const int* poses, int k, double* pose_cols, double* feat_cols,
+                                double* joint, int* steps, double* last_corr);
+/* measurement entry: the same, and times[4] (may be NULL) = HIP-event ms of the Schur reduction + symbolic analysis, the numeric
+ * factorisation, all sweeps and products of the solve and its refinement, the feature part */
+int lsfm_map_covariance_columns_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* poses, int k, double* pose_cols, double* feat_cols,
+                                      double* joint, int* steps, double* last_corr, double* times);
 
 /* replaces pba_inverseV (Imp.h:213, Imp.cpp:3022-3042): V^-1 of the n 3x3 feature blocks, IN PLACE like the reference's (which
  * inverts V in place and restores it afterwards, Imp.cpp:2210-2212, 2365): the upper triangle of the computed inverse, mirrored.
@@ -403,6 +441,14 @@ int lsfm_read_mapset(const char* path, int mono, int first, int count, int threa
 int lsfm_save_covariances(const char* pose_path, const char* feat_path, const int* stno, int m, int n, const double* pose_cov, const double* feat_cov);
 /* reads such a file back (k = 6: poses, 3: features): ids[cap], the full symmetric blocks cov[cap k k]; *count = lines read */
 int lsfm_read_covariances(const char* path, int k, int* ids, double* cov, int cap, int* count);
+/* The -covcols file (lsfm_map_covariance_columns): one line per (requested pose, pose) -- "id_q id_p" and the 36 entries of
+ * Sigma_{p,q} row by row at %.17g.  Requested poses in the order given (poses[k]: indices into the map's pose order), within one the
+ * poses in the pose file's order (ascending id, the last state entry of an id).  pose_cols[36 k m] as lsfm_map_covariance_columns
+ * writes it, stno the map's labels.  Written through a temporary file that is renamed into place. */
+int lsfm_save_cov_columns(const char* path, const int* stno, int m, const int* poses, int k, const double* pose_cols);
+/* ... and back: ids_q[cap], ids_p[cap], blocks[36 cap]; *count = lines read.  LSFM_ERR_IO for a line cut short, LSFM_ERR_ARG when
+ * cap is too small */
+int lsfm_read_cov_columns(const char* path, int* ids_q, int* ids_p, double* blocks, int cap, int* count);
 int lsfm_save_state(const char* path, const double* st, const int* stno, int n);
 /* the same state vector as raw doubles (parity tooling): int32 n, int32 0, stno[n] (+ 4 bytes of padding when n is odd),
  * st[n] float64 */

@@ -68,6 +68,7 @@ def lib():
         L.lsfm_set_precision.argtypes = [vp, C.c_int]
         L.lsfm_set_small_solve.argtypes = [vp, C.c_int]
         L.lsfm_set_spmv_variant.argtypes = [vp, C.c_int]
+        L.lsfm_set_covcols_panel.argtypes = [vp, C.c_int]
         L.lsfm_last_error.argtypes = [vp]
         L.lsfm_last_error.restype = C.c_char_p
         L.lsfm_stream.argtypes = [vp]
@@ -124,6 +125,10 @@ def lib():
         L.lsfm_map_covariance_timed.argtypes = [vp, P(LsfmMap), C.c_int, dp, dp, dp, C.c_int, ip, dp]
         L.lsfm_save_covariances.argtypes = [C.c_char_p, C.c_char_p, ip, C.c_int, C.c_int, dp, dp]
         L.lsfm_read_covariances.argtypes = [C.c_char_p, C.c_int, ip, dp, C.c_int, ip]
+        L.lsfm_map_covariance_columns.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, dp, ip, dp]
+        L.lsfm_map_covariance_columns_timed.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, dp, ip, dp, dp]
+        L.lsfm_save_cov_columns.argtypes = [C.c_char_p, ip, C.c_int, ip, C.c_int, dp]
+        L.lsfm_read_cov_columns.argtypes = [C.c_char_p, ip, ip, dp, C.c_int, ip]
         L.lsfm_spmv_bench.argtypes = [vp, C.c_int, ip, ip, dp, dp, dp, C.c_int, dp, dp]
         L.lsfm_wstream_bench.argtypes = [vp, C.c_longlong, C.c_int, C.c_int, dp]
         L.lsfm_selftest_prims.argtypes = [vp, C.c_int, C.c_uint]
@@ -131,7 +136,7 @@ def lib():
     return _LIB
 
 
-EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_set_precision", "lsfm_set_small_solve", "lsfm_set_spmv_variant", "lsfm_last_error", "lsfm_stream",
+EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_set_precision", "lsfm_set_small_solve", "lsfm_set_spmv_variant", "lsfm_set_covcols_panel", "lsfm_last_error", "lsfm_stream",
            "lsfm_map_release", "lsfm_transform_stereo", "lsfm_transform_mono", "lsfm_join_stereo", "lsfm_join_mono",
            "lsfm_solve_stereo", "lsfm_solve_mono", "lsfm_tree_upload", "lsfm_tree_run", "lsfm_tree_set_final_reanchor",
            "lsfm_tree_download", "lsfm_tree_set_stop_level", "lsfm_tree_node_count", "lsfm_tree_download_node", "lsfm_tree_download_state", "lsfm_tree_set_plans", "lsfm_tree_export_size", "lsfm_tree_export_dev", "lsfm_packed_size",
@@ -140,7 +145,8 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_gn_polish_robust", "lsfm_map_chi2",
            "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
            "lsfm_map_covariance", "lsfm_map_covariance_timed",
-           "lsfm_save_covariances", "lsfm_read_covariances"]
+           "lsfm_save_covariances", "lsfm_read_covariances",
+           "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns"]
 
 
 def _c(a, dtype):
@@ -257,6 +263,10 @@ class Context:
     def set_spmv_variant(self, variant):
         """0: by size (default); 1: always the kernel that streams the upper blocks once; 2: always the row-sorted list."""
         self._check(lib().lsfm_set_spmv_variant(self._h, int(variant)), "lsfm_set_spmv_variant")
+
+    def set_covcols_panel(self, variant):
+        """covariance_columns, a supernode group's panel product: 0 the default; 1 lane per column; 2 on the MFMA unit."""
+        self._check(lib().lsfm_set_covcols_panel(self._h, int(variant)), "lsfm_set_covcols_panel")
 
     def stream(self):
         return lib().lsfm_stream(self._h)
@@ -510,6 +520,37 @@ class Context:
             out["pairs"] = (rowptr, colidx, blocks)
         return out
 
+    def covariance_columns_raw(self, d, mono, poses, features=False, joint=False, times=False):
+        """lsfm_map_covariance_columns(_timed) as it is: (rc, pose [k,m,6,6], feature [k,n,3,6] or None, joint [6k,6k] or None, steps,
+        last_corr [k], times[4] or None).  rc is returned, not raised (tests of the argument checks and statuses)."""
+        h = HostMap(d)
+        m, n = h.c.m, h.c.n
+        q = _c(poses, np.int32)
+        k = len(q)
+        pose = np.zeros((k, m, 6, 6))
+        feat = np.zeros((k, n, 3, 6)) if features else None
+        jt = np.zeros((6 * k, 6 * k)) if joint else None
+        steps = C.c_int(0)
+        corr = np.zeros(max(k, 1))
+        t = np.zeros(4) if times else None
+        rc = lib().lsfm_map_covariance_columns_timed(self._h, C.byref(h.c), int(mono), _ptr(q, C.c_int) if k else None, k, _ptr(pose, C.c_double),
+                                                     _ptr(feat, C.c_double) if features else None, _ptr(jt, C.c_double) if joint else None,
+                                                     C.byref(steps), _ptr(corr, C.c_double), _ptr(t, C.c_double) if times else None)
+        return rc, pose, feat, jt, steps.value, corr[:k], t
+
+    def covariance_columns(self, d, mono, poses, features=False, joint=False):
+        """lsfm_map_covariance_columns: the whole columns of Sigma = I^-1 of map dict d for the poses `poses` (indices into d's pose
+        order, distinct) -- every block Sigma_{p,q}, on and off the camera system's pattern, solved side by side against one factor
+        and refined in fp64 (Mono: the gauge of covariance()).  No reference counterpart.  Returns {"pose": (k,m,6,6) with [a, p] =
+        Sigma_{p, poses[a]}, "feature": (k,n,3,6) or None, "joint": (6k,6k) exactly symmetric or None, "steps", "last_corr": (k,),
+        "converged"}.  Raises LsfmError on an error or floored pivots; a refinement that ran out of steps is reported by "converged" (an extra key).
+        The status 1 means both "not converged" and "one pivot floored": the two are told apart by steps (0: floored, nothing written)."""
+        rc, pose, feat, jt, steps, corr, _ = self.covariance_columns_raw(d, mono, poses, features=features, joint=joint)
+        self._check(rc, "lsfm_map_covariance_columns")
+        if rc > 0 and steps == 0:
+            raise LsfmError(f"lsfm_map_covariance_columns: {rc} pivot(s) floored -- the information matrix is too close to singular")
+        return {"pose": pose, "feature": feat, "joint": jt, "steps": steps, "last_corr": corr, "converged": rc == 0}
+
     def spmv_bench(self, rowptr, colidx, val, x, reps=20):
         rowptr = _c(rowptr, np.int32); colidx = _c(colidx, np.int32); val = _c(val, np.float64); x = _c(x, np.float64)
         m = len(rowptr) - 1
@@ -640,3 +681,28 @@ def read_covariances(path, k, cap=None):
     if rc != 0:
         raise LsfmError(f"lsfm_read_covariances({path}) failed (rc={rc})")
     return ids[:cnt.value].copy(), cov[:cnt.value].copy()
+
+
+def save_cov_columns(path, d, poses, pose_cols):
+    """lsfm_save_cov_columns: the -covcols file of map dict d for pose_cols [k, m, 6, 6] as covariance_columns gives it for `poses`."""
+    stno = _c(d["stno"], np.int32)
+    q = _c(poses, np.int32)
+    pc = _c(pose_cols, np.float64)
+    rc = lib().lsfm_save_cov_columns(path.encode(), _ptr(stno, C.c_int), int(d["m"]), _ptr(q, C.c_int), len(q), _ptr(pc, C.c_double))
+    if rc != 0:
+        raise LsfmError(f"lsfm_save_cov_columns failed (rc={rc})")
+
+
+def read_cov_columns(path, cap=None):
+    """lsfm_read_cov_columns: a -covcols file as (ids_q [count], ids_p [count], blocks [count, 6, 6])."""
+    if cap is None:
+        with open(path) as f:
+            cap = sum(1 for line in f if line.strip())
+    iq = np.zeros(max(cap, 1), np.int32)
+    ip_ = np.zeros(max(cap, 1), np.int32)
+    blk = np.zeros((max(cap, 1), 6, 6))
+    cnt = C.c_int(0)
+    rc = lib().lsfm_read_cov_columns(path.encode(), _ptr(iq, C.c_int), _ptr(ip_, C.c_int), _ptr(blk, C.c_double), int(cap), C.byref(cnt))
+    if rc != 0:
+        raise LsfmError(f"lsfm_read_cov_columns({path}) failed (rc={rc})")
+    return iq[:cnt.value].copy(), ip_[:cnt.value].copy(), blk[:cnt.value].copy()

@@ -886,6 +886,22 @@ int lsfm_map_covariance(lsfm_context* ctx, const lsfm_map* map, int mono, double
 	return lsfm_map_covariance_timed(ctx, map, mono, pose_cov, feat_cov, pair_cov, cap_blocks, nnzb, nullptr);
 }
 
+int lsfm_map_covariance_columns_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* poses, int k, double* pose_cols, double* feat_cols,
+                                      double* joint, int* steps, double* last_corr, double* times)
+{
+	if (!map || (mono != 0 && mono != 1) || map->m <= 0 || map->n < 0 || map->nU < 0 || map->nW < 0 || !poses || k < 1 || (!pose_cols && !feat_cols && !joint))
+		return LSFM_ERR_ARG;
+	if ((map->nU && (!map->U || !map->Ui || !map->Uj)) || (map->nW && (!map->W || !map->photo || !map->feature)) || (map->n && !map->V) || (mono && !map->stno))
+		return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() { return map_covariance_columns(ctx, map, mono == 1, poses, k, pose_cols, feat_cols, joint, steps, last_corr, times); });
+}
+
+int lsfm_map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, int mono, const int* poses, int k, double* pose_cols, double* feat_cols, double* joint,
+                                int* steps, double* last_corr)
+{
+	return lsfm_map_covariance_columns_timed(ctx, map, mono, poses, k, pose_cols, feat_cols, joint, steps, last_corr, nullptr);
+}
+
 int lsfm_inverse_v(lsfm_context* ctx, double* V, int m, int n)
 {
 	(void)m;

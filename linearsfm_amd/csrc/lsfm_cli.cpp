@@ -10,6 +10,8 @@
 // were parsed otherwise), -fullbin <file> (final state as raw doubles), -json <file> (the run's lsfm_stats and phase times as one JSON object),
 // -gn <steps> (Gauss-Newton polish of the map-joining objective from the tree's result: lsfm_gn_polish; no reference counterpart),
 // -cov <file> / -covf <file> (marginal covariances of the final map's poses / features: lsfm_map_covariance; no reference counterpart),
+// -covcols <file> -covposes <id,id,...> (whole columns of the covariance for the poses with these labels: lsfm_map_covariance_columns; one
+// line per (requested pose, pose): "id_q id_p" and the 36 entries of Sigma_{p,q}; the two flags go together),
 // -robust huber|cauchy <c> (-gn uses lsfm_gn_polish_robust: whole local maps down-weighted by an M-estimator on chi2_k / dof_k),
 // -chi2 <file> (per local map, in input order, "index dof chi2 weight" at the final state: lsfm_map_chi2; no reference counterpart).
 #include <cmath>
@@ -43,7 +45,7 @@ static void print_help()
 
 int main(int argc, char** argv)
 {
-	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err;
+	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes;
 	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0;
 	double robust_c = 0.0;
 	bool has_path = false, has_num = false;
@@ -82,6 +84,8 @@ int main(int argc, char** argv)
 		else if (name == "cov") cov = next();
 		else if (name == "covf") covf = next();
 		else if (name == "chi2") chi2f = next();
+		else if (name == "covcols") covcols = next();
+		else if (name == "covposes") covposes = next();
 		else if (name == "robust")
 		{
 			const std::string k = next(), v = next();
@@ -98,6 +102,16 @@ int main(int argc, char** argv)
 	if (num <= 0) { fprintf(stderr, "LinearSFM: -num must be positive (got %d)\n", num); return 1; }
 	if ((levels > 0) != !nodes.empty() || levels < 0) { fprintf(stderr, "LinearSFM: -levels <L > 0> and -nodes <dir> go together\n"); return 1; }
 	if (!robust_err.empty()) { fprintf(stderr, "LinearSFM: %s\n", robust_err.c_str()); return 1; }
+	if (covcols.empty() != covposes.empty()) { fprintf(stderr, "LinearSFM: -covcols <file> and -covposes <id,id,...> go together\n"); return 1; }
+	std::vector<int> covids;
+	for (size_t p = 0; p < covposes.size();)
+	{
+		char* end = nullptr;
+		const long v = strtol(covposes.c_str() + p, &end, 10);
+		if (end == covposes.c_str() + p || (*end && *end != ',') || (*end == ',' && !end[1])) { fprintf(stderr, "LinearSFM: -covposes: '%s' is not a list of pose ids\n", covposes.c_str()); return 1; }
+		covids.push_back((int)v);
+		p = (size_t)(end - covposes.c_str()) + (*end ? 1 : 0);
+	}
 	if (robust && gn <= 0) { fprintf(stderr, "LinearSFM: -robust applies to -gn <steps>: give -gn too\n"); return 1; }
 
 	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -249,6 +263,16 @@ int main(int argc, char** argv)
 		fprintf(stderr, "lsfm: total %.3f ms (transform %.3f, join %.3f [schur %.3f, pcg %.3f, backsub %.3f]), pcg its %ld, max rel resid %.2e, not converged %d, attempts %d\n",
 		        stats.t_total_ms, stats.t_transform_ms, stats.t_join_ms, stats.t_schur_ms, stats.t_pcg_ms, stats.t_backsub_ms, stats.pcg_iterations,
 		        stats.max_rel_residual, stats.not_converged, stats.attempts);
+	// -covposes: labels to poses of the final map, before any file is written (an unknown id: nothing is written)
+	std::vector<int> q;
+	for (int id : covids)
+	{
+		int at = -1;
+		for (int p = 0; p < out.m; p++) if (-out.stno[6 * p] == id) at = p; // (the last state entry of an id, as the pose file)
+		if (at < 0) { fprintf(stderr, "LinearSFM: -covposes: the final map has no pose %d\n", id); return 3; }
+		for (int e : q) if (e == at) { fprintf(stderr, "LinearSFM: -covposes: pose %d is named twice\n", id); return 3; }
+		q.push_back(at);
+	}
 	const int r = 6 * out.m + 3 * out.n;
 	if (!st.empty()) lsfm_save_state(st.c_str(), out.stVal, out.stno, r);
 	if (!pose.empty() && !fea.empty()) lsfm_save_poses(pose.c_str(), fea.c_str(), out.stno, out.stVal, r); // only together (Imp.cpp:2078)
@@ -271,6 +295,20 @@ int main(int argc, char** argv)
 		}
 		if (lsfm_save_covariances(cov.empty() ? nullptr : cov.c_str(), covf.empty() ? nullptr : covf.c_str(), out.stno, out.m, out.n, pc.data(), fc.data()))
 			fprintf(stderr, "LinearSFM: cannot write the covariance files\n");
+	}
+	if (!covcols.empty())
+	{
+		// whole columns of the same map's covariance for the poses named by label
+		std::vector<double> pc((size_t)q.size() * out.m * 36);
+		int steps = 0; // (a positive status with no step taken: floored pivots, nothing written; with steps: the refinement ran out of them)
+		const int crc = lsfm_map_covariance_columns(ctx, &out, type, q.data(), (int)q.size(), pc.data(), nullptr, nullptr, &steps, nullptr);
+		if (crc < 0 || (crc > 0 && steps == 0))
+		{
+			fprintf(stderr, "LinearSFM: covariance columns: %s\n", crc < 0 ? lsfm_last_error(ctx) : "pivots had to be floored (the information matrix is too close to singular)");
+			return 3;
+		}
+		if (crc > 0) fprintf(stderr, "LinearSFM: covariance columns: the refinement took all %d steps and its last correction is still above the tolerance\n", steps);
+		if (lsfm_save_cov_columns(covcols.c_str(), out.stno, out.m, q.data(), (int)q.size(), pc.data())) fprintf(stderr, "LinearSFM: cannot write %s\n", covcols.c_str());
 	}
 	if (!json.empty())
 	{

@@ -13,12 +13,15 @@
 // at a time).  Every sum runs in a fixed order in one lane: the result is the same bits on every call.
 // Sigma = P^T D^-1/2 Z D^-1/2 P on S's upper pattern (k_cov_pairs), then per feature (k_cov_feat, one wave per feature)
 //     Sigma_ff = V_f^-1 + V_f^-1 (sum_{a,b} W_af^T Sigma_{p_a p_b} W_bf) V_f^-1.
+// The front end -- argument checks, upload, reduction, factorisation -- is cov_front (lsfm_cov.hpp), shared with the covariance columns
+// of chosen poses (lsfm_covcols.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "lsfm_chol.hpp"
+#include "lsfm_cov.hpp"
 #include "lsfm_device.hpp"
 #include "lsfm_internal.hpp"
 #include "lsfm_solve.hpp"
@@ -261,25 +264,14 @@ __global__ void __launch_bounds__(COV_FEAT_THREADS) k_cov_feat(int NF, const int
 	}
 }
 
-// device memory of one call beyond the context's arenas (Z is as large as the factor)
-struct DevBuf {
-	void* p = nullptr;
-	~DevBuf() { if (p) (void)hipFree(p); }
-	template <class T> T* get(size_t n)
-	{
-		LSFM_CHECK_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-		return static_cast<T*>(p);
-	}
-};
-
 } // namespace
 
-int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb_out,
-                   double* times)
+void cov_front(lsfm_context* ctx, const lsfm_map* map, bool mono, CovFront& fr)
 {
 	const int m = map->m, n = map->n, nU = map->nU, nW = map->nW;
 	// ---- arguments (host) ----
-	std::vector<int> fptr(n + 1);
+	std::vector<int>& fptr = fr.fptr;
+	fptr.assign(n + 1, 0);
 	{
 		int j = 0;
 		for (int f = 0; f < n; f++)
@@ -331,18 +323,18 @@ int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* po
 		dfx = ar.alloc<unsigned char>((size_t)m * 6);
 		h2d(ctx, dfx, fx.data(), fx.size());
 	}
-	SolveIO io;
+	SolveIO& io = fr.io;
 	io.M = m; io.NF = n; io.NU = nU; io.NW = nW; io.nseg = 1;
 	io.d_pose_seg = dseg; io.d_feat_seg = dseg + m;
 	io.U = dU; io.Ui = dUi; io.Uj = dUj; io.W = dW; io.photo = dph; io.fptr = dfp; io.V = dV; io.ea = dea; io.eb = deb;
 	io.d_fixed = dfx; io.d_pose_origin = dorg;
 	io.seg_rows.assign(1, m);
-	hipEvent_t ev[5];
-	for (int k = 0; k < 5; k++) ev[k] = ctx->pool_event();
+	hipEvent_t* ev = fr.ev;
+	for (int k = 0; k < 3; k++) ev[k] = ctx->pool_event();
 	LSFM_CHECK_HIP(hipEventRecord(ev[0], s));
 	// ---- reduce + factor: the tree level's own pieces, fp64, sparse path ----
-	SchurSystem sy;
-	CholDev ch;
+	SchurSystem& sy = fr.sy;
+	CholDev& ch = fr.ch;
 	CholHostIn hin;
 	ctx->pattern_dep = false;
 	schur_vinv(ctx, io, sy);
@@ -350,12 +342,9 @@ int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* po
 	chol_fetch(ctx, sy, io.d_pose_origin, hin);
 	build_schur_values(ctx, io, sy);
 	chol_analyse(ctx, sy, hin, ch);
-	const int nnzb = sy.nnzb;
-	*nnzb_out = nnzb;
-	if (pair_cov && nnzb > cap_blocks) LSFM_FAIL(LSFM_ERR_ARG, "pair_cov too small for the pattern (" + std::to_string(nnzb) + " blocks)");
 	LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
 	// the count of floored pivots goes to a record of this call's own (a tree's record stays as its run left it)
-	RunStatsDev* d_run = ctx->scratch.alloc<RunStatsDev>(1);
+	RunStatsDev* d_run = fr.d_run = ctx->scratch.alloc<RunStatsDev>(1);
 	dev_zero(ctx, d_run, sizeof(RunStatsDev));
 	{
 		struct Swap { lsfm_context* c; RunStatsDev* keep; ~Swap() { c->d_run = keep; } } swap{ ctx, ctx->d_run };
@@ -365,6 +354,33 @@ int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* po
 	}
 	chol_merge_groups(ctx, ch);
 	LSFM_CHECK_HIP(hipEventRecord(ev[2], s));
+}
+
+int cov_front_status(lsfm_context* ctx, const CovFront& fr)
+{
+	int chol_err = 0;
+	RunStatsDev rs;
+	d2h(ctx, &chol_err, fr.ch.d_err, sizeof(int));
+	d2h(ctx, &rs, fr.d_run, sizeof rs);
+	if (chol_err) LSFM_FAIL(LSFM_ERR_NOT_SPD, "the camera system is not positive definite (block column " + std::to_string(chol_err - 1) + " of the factor)");
+	return rs.floored;
+}
+
+int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb_out,
+                   double* times)
+{
+	CovFront fr;
+	cov_front(ctx, map, mono, fr);
+	const int m = map->m, n = map->n;
+	const SolveIO& io = fr.io;
+	const SchurSystem& sy = fr.sy;
+	CholDev& ch = fr.ch;
+	hipStream_t s = ctx->stream;
+	const double* dW = io.W; const int *dph = io.photo, *dfp = io.fptr;
+	const int nnzb = sy.nnzb;
+	*nnzb_out = nnzb;
+	if (pair_cov && nnzb > cap_blocks) LSFM_FAIL(LSFM_ERR_ARG, "pair_cov too small for the pattern (" + std::to_string(nnzb) + " blocks)");
+	hipEvent_t ev[5] = { fr.ev[0], fr.ev[1], fr.ev[2], ctx->pool_event(), ctx->pool_event() };
 	// ---- selected inversion ----
 	const int M = ch.M;
 	std::vector<int> hcolptr(M + 1), horder(M);
@@ -400,11 +416,8 @@ int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* po
 	LSFM_CHECK_HIP(hipEventRecord(ev[4], s));
 	LSFM_CHECK_HIP(hipGetLastError());
 	// ---- status: the factor's pivot word and the floored pivots, read once ----
-	int chol_err = 0, ferr = 0;
-	RunStatsDev rs;
-	d2h(ctx, &chol_err, ch.d_err, sizeof(int));
+	int ferr = 0;
 	d2h(ctx, &ferr, d_ferr, sizeof(int));
-	d2h(ctx, &rs, d_run, sizeof rs);
 	if (times)
 	{
 		for (int k = 0; k < 4; k++)
@@ -414,8 +427,8 @@ int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* po
 			times[k] = ms;
 		}
 	}
-	if (chol_err) LSFM_FAIL(LSFM_ERR_NOT_SPD, "the camera system is not positive definite (block column " + std::to_string(chol_err - 1) + " of the factor)");
-	if (rs.floored > 0) return rs.floored; // the factor is of a perturbed S: nothing is written
+	const int floored = cov_front_status(ctx, fr);
+	if (floored > 0) return floored; // the factor is of a perturbed S: nothing is written
 	if (ferr) LSFM_FAIL(LSFM_ERR_INTERNAL, ferr == 2 ? "a block of the selected inversion is not on the factor's pattern" : "a feature's pose pair is not in the camera system's pattern");
 	std::vector<double> hp((size_t)nnzb * 36);
 	d2h(ctx, hp.data(), dP, hp.size() * sizeof(double));

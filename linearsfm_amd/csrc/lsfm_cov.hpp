@@ -1,0 +1,48 @@
+// What the two covariance entry points share (lsfm_cov.hip: lsfm_map_covariance, lsfm_covcols.hip: lsfm_map_covariance_columns): the
+// front end that checks a map, uploads it, reduces it to the camera system and factors that, and the device memory of one call.
+#pragma once
+#include <algorithm>
+#include <vector>
+
+#include "lsfm_chol.hpp"
+#include "lsfm_internal.hpp"
+#include "lsfm_solve.hpp"
+
+namespace lsfm {
+
+// device memory of one call beyond the context's arenas (as large as the factor, or as the columns asked for); a refused
+// allocation is LSFM_ERR_OOM, and the device's error state is left clean for the calls that follow
+struct DevBuf {
+	void* p = nullptr;
+	~DevBuf() { if (p) (void)hipFree(p); }
+	template <class T> T* get(size_t n)
+	{
+		const hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
+		if (e == hipErrorOutOfMemory)
+		{
+			(void)hipGetLastError();
+			p = nullptr;
+			throw Error{ LSFM_ERR_OOM, "out of device memory: " + std::to_string(std::max<size_t>(n, 1) * sizeof(T)) + " bytes for the columns of one call" };
+		}
+		LSFM_CHECK_HIP(e);
+		return static_cast<T*>(p);
+	}
+};
+
+// The factored camera system of a map, in the context's arenas: A = D^-1/2 P S P^T D^-1/2 = L L^T, whole in ch.L / ch.Dinv.
+struct CovFront {
+	std::vector<int> fptr;   // host: W run of every feature
+	SolveIO io;              // the uploaded map (io.W / io.photo / io.fptr / io.d_fixed: device)
+	SchurSystem sy;
+	CholDev ch;
+	RunStatsDev* d_run = nullptr; // this call's own record (floored pivots)
+	hipEvent_t ev[3] = { nullptr, nullptr, nullptr }; // start | reduced + analysed | factored
+};
+// checks the map's arguments (throws LSFM_ERR_ARG), uploads it as lsfm_solve_* does and runs a tree level's own pieces on it, fp64,
+// sparse path: schur_vinv -> build_schur_pattern -> chol_fetch -> build_schur_values -> chol_analyse -> chol_scatter -> chol_factor ->
+// chol_merge_groups.  Resets arena 0 and the scratch arena.
+void cov_front(lsfm_context* ctx, const lsfm_map* map, bool mono, CovFront& fr);
+// the numerical status of the factorisation, read once: throws LSFM_ERR_NOT_SPD, returns the number of floored pivots
+int cov_front_status(lsfm_context* ctx, const CovFront& fr);
+
+} // namespace lsfm

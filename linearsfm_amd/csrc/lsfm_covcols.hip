@@ -1,0 +1,676 @@
+// Whole columns of Sigma = I^-1 for a chosen set Q of poses (C ABI: lsfm_map_covariance_columns): every block Sigma_{p,q} and
+// Sigma_{f,q}, q in Q, on and off the camera system's pattern.  No reference counterpart.
+//
+// The camera system is reduced and factored by lsfm_map_covariance's own front end (cov_front, lsfm_cov.hip): A = D^-1/2 P S P^T D^-1/2
+// = L L^T, fp64, sparse path.  The 6 |Q| unit right-hand sides are then solved SIDE BY SIDE against that factor and refined in fp64
+// against S itself:
+//     X = (L L^T)^-1 B,  B = D^-1/2 P E_Q;     Sigma_{.,Q} = P^T D^-1/2 X
+//     repeat:  Sigma_{.,Q} += P^T D^-1/2 (L L^T)^-1 D^-1/2 P (E_Q - S Sigma_{.,Q})
+// until the correction of every column is below the context's rel_tol relative to the column (or stops falling by half, or max_steps).
+// The stopping rule looks at the correction, not at the residual: the entries of S are 1e6..1e8, so the residual of a unit
+// right-hand side stalls around 1e-10 while the solution is already two orders better.
+//
+// Layout: a chunk of R = 6 k_c columns is one array X[6 M][R], the R values of one scalar row contiguous.  A lane owns a COLUMN: the
+// lanes of a wave load and store 512 contiguous bytes, the block of L (or S, or W) they multiply with is the same for all of them
+// -- its address is uniform -- and every such block is read once per
+// sweep for all R columns, where the single-vector kernels (k_chol_fwd/bwd_tasks, k_sn_fwd/bwd, k_spmv_gather) read the whole factor
+// per vector.  The sweeps run on CholDev's own schedule: the leaf tasks in one launch, then the supernode-group levels one after the
+// other.  A group's dense trapezoid below its run is a matrix product with N = R, in two versions (lsfm_set_covcols_panel): on
+// v_mfma_f64_16x16x4_f64 in a launch of its own (k_cc_fwd_panel / k_cc_bwd_panel), or lane per column inside the run's launch.
+//
+// k_c = CC_KC = 32: one work-group must hold all columns of the chunk (a block of L is then fetched by one work-group only), the
+// panel kernels run one wave per 16 columns, twelve waves = CC_MAXT lanes (the plain version: CC_MAXT / 192 = 4 row slices beside
+// each other), and the three arrays of a chunk ([6 M][192] doubles: 9 KB per pose each, 97 MB on a 3500-pose map) are what a call
+// allocates whatever k is.  Measured: the time of a chunk hardly grows with its columns, so a full chunk is
+// the cheapest way through a long list.  More poses go through in chunks.
+//
+// Not bit-reproducible: the rows of a column's ancestors collect their updates by fp64 atomics from whichever work-group comes
+// first.  The refinement takes the difference (a few ulps of the unrefined solve) far below what is asked of the result.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "lsfm_chol.hpp"
+#include "lsfm_cov.hpp"
+#include "lsfm_device.hpp"
+#include "lsfm_internal.hpp"
+#include "lsfm_solve.hpp"
+#include "lsfm_symbolic.hpp"
+
+namespace lsfm {
+
+namespace {
+
+#define CC_KC 32     /* poses per chunk (see above) */
+#define CC_MAXT 768  /* lanes of a supernode-group work-group: columns x row slices */
+#define CC_GK (6 * CHOL_GS) /* most scalar columns of a group's run */
+#define CC_PANEL_DEFAULT 2 /* a group's panel product when the context does not say (lsfm_set_covcols_panel): 1 plain, 2 MFMA */
+#define CC_GY 32     /* most work-groups that share one group's panel (k_cc_fwd_panel / k_cc_bwd_panel) */
+#define CC_EPW 16    /* entries of S's gather list per work-group of the product */
+#define CC_FB 8      /* features per work-group of the feature kernel */
+#define CC_ROWS 48   /* scalar rows per work-group of k_cc_perm_out */
+
+// a value another wave of the work-group has just added to by atomics (they are performed in L2): read it there
+__device__ __forceinline__ double ld_l2(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// The unit columns of the requested poses, column 6 a + c = scalar c of pose qpose[a] (a fixed scalar's column is zero).
+// perm == null: E_Q in the map's numbering.  perm != null: B = D^-1/2 P E_Q, written directly (block row i is pose perm[i]).
+__global__ void k_cc_unit(int M, int R, const int* __restrict__ perm, const double* __restrict__ dscale, const unsigned char* __restrict__ fixed,
+                          const int* __restrict__ qpose, double* __restrict__ out)
+{
+	const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (idx >= (size_t)M * 6 * R) return;
+	const int r = (int)(idx % R);
+	const size_t row = idx / R;
+	const int i = (int)(row / 6), q = (int)(row % 6);
+	const int p = perm ? perm[i] : i;
+	const bool one = p == qpose[r / 6] && q == r % 6 && !(fixed && fixed[(size_t)p * 6 + q]);
+	out[idx] = one ? (dscale ? dscale[row] : 1.0) : 0.0;
+}
+
+// V = D^-1/2 P Y (a residual into elimination order, scaled like the factor; fixed scalars zero)
+__global__ void k_cc_perm_in(int M, int R, const int* __restrict__ perm, const double* __restrict__ dscale, const unsigned char* __restrict__ fixed,
+                             const double* __restrict__ Y, double* __restrict__ V)
+{
+	const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (idx >= (size_t)M * 6 * R) return;
+	const int r = (int)(idx % R);
+	const size_t row = idx / R;
+	const size_t src = (size_t)perm[row / 6] * 6 + row % 6;
+	V[idx] = (fixed && fixed[src]) ? 0.0 : Y[src * R + r] * dscale[row];
+}
+
+// Xo (+)= P^T D^-1/2 V in the map's numbering (fixed scalars zero); ADD: the correction of a refinement step, with the largest
+// |delta| (norm[r]) and the largest |x| after it (norm[R + r]) of every column (non-negative doubles order like their bit patterns)
+template <bool ADD>
+__device__ __forceinline__ void cc_perm_out(int M, int R, const int* __restrict__ pinv, const double* __restrict__ dscale, const unsigned char* __restrict__ fixed,
+                                            const double* __restrict__ V, double* __restrict__ Xo, unsigned long long* __restrict__ norm)
+{
+	const int r = threadIdx.x;
+	if (r >= R) return;
+	const int row0 = blockIdx.x * CC_ROWS, row1 = min(row0 + CC_ROWS, 6 * M);
+	double md = 0.0, mx = 0.0;
+	for (int row = row0; row < row1; row++)
+	{
+		const size_t src = (size_t)pinv[row / 6] * 6 + row % 6;
+		const double d = (fixed && fixed[row]) ? 0.0 : V[src * R + r] * dscale[src];
+		double* o = Xo + (size_t)row * R + r;
+		if (ADD)
+		{
+			const double x = *o + d;
+			*o = x;
+			md = fmax(md, fabs(d)); mx = fmax(mx, fabs(x));
+		}
+		else *o = d;
+	}
+	if (ADD)
+	{
+		atomicMax(norm + r, (unsigned long long)__double_as_longlong(md));
+		atomicMax(norm + R + r, (unsigned long long)__double_as_longlong(mx));
+	}
+}
+__global__ void k_cc_perm_out(int M, int R, const int* __restrict__ pinv, const double* __restrict__ dscale, const unsigned char* __restrict__ fixed,
+                              const double* __restrict__ V, double* __restrict__ Xo)
+{
+	cc_perm_out<false>(M, R, pinv, dscale, fixed, V, Xo, nullptr);
+}
+__global__ void k_cc_perm_add(int M, int R, const int* __restrict__ pinv, const double* __restrict__ dscale, const unsigned char* __restrict__ fixed,
+                              const double* __restrict__ V, double* __restrict__ Xo, unsigned long long* __restrict__ norm)
+{
+	cc_perm_out<true>(M, R, pinv, dscale, fixed, V, Xo, norm);
+}
+
+// ---- the sweeps ---------------------------------------------------------------------------------------------------------------
+// One work-group walks a run of columns in elimination order: the columns of a leaf task (GROUP = false: a0 = task_ptr, a1 = task_cols)
+// (a2 = col_task) or of a supernode group (GROUP = true: a0 = grp_c0, a1 = grp_s, a2 = grp_nr of the level).  Lane x owns column x of X.
+// Forward, column j:   y_j = L_jj^-1 v_j;   v_i -= L_ij y_j for every block below the diagonal.
+// Rows inside the run are touched by this work-group alone (a leaf task is a whole sub-tree; the columns of a group's run follow each
+// other), and a lane only ever reads what it wrote itself: plain loads and stores, no barrier.  Rows outside (ancestors) collect the
+// sums of several work-groups: atomics.  A group's common rows -- the dense 6 nr x 6 s trapezoid below its run -- are a matrix
+// product X_rows -= Panel X_run.  own_panel (the plain version): once the run is solved, the row slices (threadIdx.y) take every
+// blockDim.y-th block row of the panel, sum over the run's columns in registers and add once per row.  Otherwise the launch has the
+// run's lanes only and k_cc_fwd_panel follows it.
+template <bool GROUP>
+__global__ void __launch_bounds__(CC_MAXT) k_cc_fwd(const int* __restrict__ a0, const int* __restrict__ a1, const int* __restrict__ a2, bool own_panel,
+                                                    int R, const int* __restrict__ colptr, const int* __restrict__ rowidx, const double* __restrict__ L,
+                                                    const double* __restrict__ Dinv, double* X)
+{
+	const int r = threadIdx.x;
+	const bool on = r < R;
+	const int slice = __builtin_amdgcn_readfirstlane((int)threadIdx.y), ns = blockDim.y;
+	const int me = blockIdx.x;
+	const int b = a0[me]; // first column (group) / first slot of task_cols (task)
+	const int nc = GROUP ? a1[me] : a0[me + 1] - b;
+	if (slice == 0 && on)
+		for (int k = 0; k < nc; k++)
+		{
+			const int j = GROUP ? b + k : a1[b + k];
+			double v[6], y[6];
+#pragma unroll
+			for (int q = 0; q < 6; q++) v[q] = X[((size_t)j * 6 + q) * R + r];
+			const double* D = Dinv + (size_t)j * 36;
+#pragma unroll
+			for (int c = 0; c < 6; c++)
+			{
+				double s = 0.0;
+#pragma unroll
+				for (int q = 0; q <= c; q++) s = fma(D[c * 6 + q], v[q], s);
+				y[c] = s;
+			}
+#pragma unroll
+			for (int q = 0; q < 6; q++) X[((size_t)j * 6 + q) * R + r] = y[q];
+			const int e0 = colptr[j] + 1, e1 = GROUP ? colptr[j] + (nc - k) : colptr[j + 1]; // (a group: the rows of its own run only)
+			for (int en = e0; en < e1; en++)
+			{
+				const int i = rowidx[en];
+				const double* blk = L + (size_t)en * 36;
+				double o[6];
+#pragma unroll
+				for (int rr = 0; rr < 6; rr++)
+				{
+					double s = 0.0;
+#pragma unroll
+					for (int q = 0; q < 6; q++) s = fma(blk[rr * 6 + q], y[q], s);
+					o[rr] = s;
+				}
+				double* dst = X + (size_t)i * 6 * R + r;
+				if (GROUP || a2[i] == me)
+				{
+#pragma unroll
+					for (int rr = 0; rr < 6; rr++) dst[(size_t)rr * R] -= o[rr];
+				}
+				else
+				{
+#pragma unroll
+					for (int rr = 0; rr < 6; rr++) atomic_add_f64(dst + (size_t)rr * R, -o[rr]);
+				}
+			}
+		}
+	if (!GROUP || !own_panel) return;
+	__syncthreads(); // y of the whole run is in X
+	if (!on) return;
+	const int nr = a2[me], rows0 = colptr[b + nc - 1] + 1;
+	for (int i = slice; i < nr; i += ns)
+	{
+		double o[6] = { 0, 0, 0, 0, 0, 0 };
+		for (int t = 0; t < nc; t++)
+		{
+			const double* blk = L + ((size_t)colptr[b + t] + (nc - t) + i) * 36;
+			double y[6];
+#pragma unroll
+			for (int q = 0; q < 6; q++) y[q] = X[((size_t)(b + t) * 6 + q) * R + r];
+#pragma unroll
+			for (int rr = 0; rr < 6; rr++)
+#pragma unroll
+				for (int q = 0; q < 6; q++) o[rr] = fma(blk[rr * 6 + q], y[q], o[rr]);
+		}
+		double* dst = X + (size_t)rowidx[rows0 + i] * 6 * R + r;
+#pragma unroll
+		for (int rr = 0; rr < 6; rr++) atomic_add_f64(dst + (size_t)rr * R, -o[rr]);
+	}
+}
+
+// Backward, column j from the last to the first:   z = y_j - sum_i L_ij^T x_i;   x_j = L_jj^-T z.
+// A group first takes the common rows off its whole run, z_run -= Panel^T X_rows: k_cc_bwd_panel in the launch before, or (own_panel)
+// the row slices split the panel's block rows and add their parts into the run's rows of X, which nobody else touches in this
+// launch; then one slice solves the run.  Every x_i read
+// is final: an ancestor's from an earlier launch, a row of the run from this lane itself.
+template <bool GROUP>
+__global__ void __launch_bounds__(CC_MAXT) k_cc_bwd(const int* __restrict__ a0, const int* __restrict__ a1, const int* __restrict__ a2, bool own_panel,
+                                                    int R, const int* __restrict__ colptr, const int* __restrict__ rowidx, const double* __restrict__ L,
+                                                    const double* __restrict__ Dinv, double* X)
+{
+	const int r = threadIdx.x;
+	const bool on = r < R;
+	const int slice = __builtin_amdgcn_readfirstlane((int)threadIdx.y), ns = blockDim.y;
+	const int me = blockIdx.x;
+	const int b = a0[me];
+	const int nc = GROUP ? a1[me] : a0[me + 1] - b;
+	if (GROUP && own_panel)
+	{
+		const int nr = a2[me], rows0 = colptr[b + nc - 1] + 1;
+		if (on && slice < nr)
+			for (int t = 0; t < nc; t++)
+			{
+				double acc[6] = { 0, 0, 0, 0, 0, 0 };
+				for (int i = slice; i < nr; i += ns)
+				{
+					const double* blk = L + ((size_t)colptr[b + t] + (nc - t) + i) * 36;
+					const double* src = X + (size_t)rowidx[rows0 + i] * 6 * R + r;
+					double x[6];
+#pragma unroll
+					for (int rr = 0; rr < 6; rr++) x[rr] = src[(size_t)rr * R];
+#pragma unroll
+					for (int c = 0; c < 6; c++)
+#pragma unroll
+						for (int rr = 0; rr < 6; rr++) acc[c] = fma(blk[rr * 6 + c], x[rr], acc[c]);
+				}
+				double* dst = X + (size_t)(b + t) * 6 * R + r;
+#pragma unroll
+				for (int c = 0; c < 6; c++) atomic_add_f64(dst + (size_t)c * R, -acc[c]);
+			}
+		__syncthreads();
+	}
+	if (slice != 0 || !on) return;
+	for (int k = nc - 1; k >= 0; k--)
+	{
+		const int j = GROUP ? b + k : a1[b + k];
+		double z[6];
+#pragma unroll
+		for (int c = 0; c < 6; c++) z[c] = GROUP ? ld_l2(X + ((size_t)j * 6 + c) * R + r) : X[((size_t)j * 6 + c) * R + r];
+		const int e0 = colptr[j] + 1, e1 = GROUP ? colptr[j] + (nc - k) : colptr[j + 1];
+		for (int en = e0; en < e1; en++)
+		{
+			const double* blk = L + (size_t)en * 36;
+			const double* src = X + (size_t)rowidx[en] * 6 * R + r;
+			double x[6];
+#pragma unroll
+			for (int rr = 0; rr < 6; rr++) x[rr] = src[(size_t)rr * R];
+#pragma unroll
+			for (int c = 0; c < 6; c++)
+#pragma unroll
+				for (int rr = 0; rr < 6; rr++) z[c] = fma(-blk[rr * 6 + c], x[rr], z[c]);
+		}
+		const double* D = Dinv + (size_t)j * 36;
+#pragma unroll
+		for (int c = 0; c < 6; c++)
+		{
+			double s = 0.0;
+#pragma unroll
+			for (int q = c; q < 6; q++) s = fma(D[q * 6 + c], z[q], s);
+			X[((size_t)j * 6 + c) * R + r] = s;
+		}
+	}
+}
+
+// ---- a group's trapezoid on the matrix cores ------------------------------------------------------------------------------------
+// X_rows -= Panel X_run as 16 x 16 tiles of v_mfma_f64_16x16x4_f64 (lane l feeds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15]
+// and holds C[row (l >> 4) + 4 reg][col l & 15]).  The contraction is over the run's 6 s <= CC_GK scalars: a wave owns 16 columns of
+// X and keeps its slice of X_run -- the B operand -- in registers for the whole launch; the work-groups of a group (blockIdx.y) deal
+// the panel's 16-row tiles among themselves, and a tile goes through LDS once for all waves.  The tile is full except in the last
+// rows of the panel and, for an odd s, the last k step.  Rows of X outside the run: atomics, as in the plain version.
+typedef double cc_v4d __attribute__((ext_vector_type(4)));
+
+__global__ void __launch_bounds__(CC_MAXT) k_cc_fwd_panel(const int* __restrict__ grp_c0, const int* __restrict__ grp_s, const int* __restrict__ grp_nr, int R,
+                                                          const int* __restrict__ colptr, const int* __restrict__ rowidx, const double* __restrict__ L, double* X)
+{
+	__shared__ double As[16][CC_GK + 1];
+	const int me = blockIdx.x, b = grp_c0[me], nc = grp_s[me];
+	const int K = 6 * nc, NR = 6 * grp_nr[me], ntile = (NR + 15) / 16;
+	if ((int)blockIdx.y >= ntile) return;
+	const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4;
+	const int col = (tid >> 6) * 16 + (lane & 15);
+	const bool cin = col < R;
+	double bq[CC_GK / 4];
+#pragma unroll
+	for (int ks = 0; ks < CC_GK / 4; ks++)
+	{
+		const int k = 4 * ks + kq;
+		bq[ks] = (k < K && cin) ? X[((size_t)b * 6 + k) * R + col] : 0.0;
+	}
+	const int rows0 = colptr[b + nc - 1] + 1;
+	for (int rt = blockIdx.y; rt < ntile; rt += gridDim.y)
+	{
+		__syncthreads(); // the tile of the round before has been read
+		for (int e = tid; e < 16 * CC_GK; e += blockDim.x)
+		{
+			const int rl = e / CC_GK, k = e - rl * CC_GK, rho = rt * 16 + rl;
+			double v = 0.0;
+			if (rho < NR && k < K)
+			{
+				const int i = rho / 6, t = k / 6;
+				v = L[((size_t)colptr[b + t] + (nc - t) + i) * 36 + (rho - 6 * i) * 6 + (k - 6 * t)];
+			}
+			As[rl][k] = v;
+		}
+		__syncthreads();
+		cc_v4d acc = { 0.0, 0.0, 0.0, 0.0 };
+#pragma unroll
+		for (int ks = 0; ks < CC_GK / 4; ks++)
+			if (4 * ks < K) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(As[lane & 15][4 * ks + kq], bq[ks], acc, 0, 0, 0);
+#pragma unroll
+		for (int reg = 0; reg < 4; reg++)
+		{
+			const int rho = rt * 16 + kq + 4 * reg;
+			if (rho < NR && cin) atomic_add_f64(X + ((size_t)rowidx[rows0 + rho / 6] * 6 + rho % 6) * R + col, -acc[reg]);
+		}
+	}
+}
+
+// z_run -= Panel^T X_rows: the contraction is over the panel's 6 nr rows, dealt among the work-groups of a group in chunks of CC_GK; the
+// chunk of the panel goes through LDS, the gathered rows of X (final: their groups ran in earlier launches) are the B operand, and
+// the up to three 16-row tiles of the run collect over all chunks in registers before they are added to the run's rows of X.
+__global__ void __launch_bounds__(CC_MAXT) k_cc_bwd_panel(const int* __restrict__ grp_c0, const int* __restrict__ grp_s, const int* __restrict__ grp_nr, int R,
+                                                          const int* __restrict__ colptr, const int* __restrict__ rowidx, const double* __restrict__ L, double* X)
+{
+	__shared__ double Ps[CC_GK][CC_GK + 1]; // [row of the chunk][scalar of the run]
+	const int me = blockIdx.x, b = grp_c0[me], nc = grp_s[me];
+	const int K = 6 * nc, NR = 6 * grp_nr[me], nchunk = (NR + CC_GK - 1) / CC_GK;
+	if ((int)blockIdx.y >= nchunk) return;
+	const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4;
+	const int col = (tid >> 6) * 16 + (lane & 15);
+	const bool cin = col < R;
+	const int rows0 = colptr[b + nc - 1] + 1;
+	cc_v4d acc[CC_GK / 16];
+#pragma unroll
+	for (int mt = 0; mt < CC_GK / 16; mt++) acc[mt] = (cc_v4d){ 0.0, 0.0, 0.0, 0.0 };
+	for (int c = blockIdx.y; c < nchunk; c += gridDim.y)
+	{
+		const int rho0 = c * CC_GK;
+		__syncthreads();
+		for (int e = tid; e < CC_GK * CC_GK; e += blockDim.x)
+		{
+			const int rl = e / CC_GK, k = e - rl * CC_GK, rho = rho0 + rl;
+			double v = 0.0;
+			if (rho < NR && k < K)
+			{
+				const int i = rho / 6, t = k / 6;
+				v = L[((size_t)colptr[b + t] + (nc - t) + i) * 36 + (rho - 6 * i) * 6 + (k - 6 * t)];
+			}
+			Ps[rl][k] = v;
+		}
+		double bq[CC_GK / 4];
+#pragma unroll
+		for (int ks = 0; ks < CC_GK / 4; ks++)
+		{
+			const int rho = rho0 + 4 * ks + kq;
+			bq[ks] = (rho < NR && cin) ? X[((size_t)rowidx[rows0 + rho / 6] * 6 + rho % 6) * R + col] : 0.0;
+		}
+		__syncthreads();
+#pragma unroll
+		for (int ks = 0; ks < CC_GK / 4; ks++)
+			if (rho0 + 4 * ks < NR)
+			{
+#pragma unroll
+				for (int mt = 0; mt < CC_GK / 16; mt++)
+					if (16 * mt < K) acc[mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(Ps[4 * ks + kq][16 * mt + (lane & 15)], bq[ks], acc[mt], 0, 0, 0);
+			}
+	}
+#pragma unroll
+	for (int mt = 0; mt < CC_GK / 16; mt++)
+#pragma unroll
+		for (int reg = 0; reg < 4; reg++)
+		{
+			const int k = 16 * mt + kq + 4 * reg;
+			if (k < K && cin) atomic_add_f64(X + ((size_t)b * 6 + k) * R + col, -acc[mt][reg]);
+		}
+}
+
+// ---- Y -= S Xo for all columns in one pass over S -------------------------------------------------------------------------------
+// The multi-column sibling of k_spmv_gather on the same list (both orientations of every block, sorted by the row they add to; the
+// holes of the diagonal blocks last): a work-group takes CC_EPW consecutive entries, a lane sums its column over the entries of one
+// target row in registers and adds once per row and work-group.  Fixed scalars as there: their rows receive nothing (and Xo is zero
+// in them, so their columns give nothing).
+__global__ void __launch_bounds__(CC_KC * 6) k_cc_resid(int nent, const unsigned long long* __restrict__ ent, const int* __restrict__ oth,
+                                                        const double* __restrict__ S, const unsigned char* __restrict__ fixed, int R,
+                                                        const double* __restrict__ Xo, double* __restrict__ Y)
+{
+	const int r = threadIdx.x;
+	if (r >= R) return;
+	const int e0 = blockIdx.x * CC_EPW, e1 = min(e0 + CC_EPW, nent);
+	int cur = -1;
+	double acc[6] = { 0, 0, 0, 0, 0, 0 };
+	auto flush = [&]() {
+		if (cur < 0) return;
+#pragma unroll
+		for (int rr = 0; rr < 6; rr++)
+			if (!(fixed && fixed[(size_t)cur * 6 + rr])) atomic_add_f64(Y + ((size_t)cur * 6 + rr) * R + r, -acc[rr]);
+	};
+	for (int e = e0; e < e1; e++)
+	{
+		const unsigned long long key = ent[e];
+		if (key == ~0ull) break; // (the holes are the tail of the list)
+		const int row = (int)(key >> 32);
+		const unsigned kk = (unsigned)(key & 0xffffffffull);
+		if (row != cur)
+		{
+			flush();
+			cur = row;
+#pragma unroll
+			for (int rr = 0; rr < 6; rr++) acc[rr] = 0.0;
+		}
+		const double* blk = S + (size_t)(kk >> 1) * 36;
+		const double* src = Xo + (size_t)oth[e] * 6 * R + r;
+		double x[6];
+#pragma unroll
+		for (int q = 0; q < 6; q++) x[q] = src[(size_t)q * R];
+		if (kk & 1u)
+		{
+#pragma unroll
+			for (int rr = 0; rr < 6; rr++)
+#pragma unroll
+				for (int q = 0; q < 6; q++) acc[rr] = fma(blk[q * 6 + rr], x[q], acc[rr]);
+		}
+		else
+		{
+#pragma unroll
+			for (int rr = 0; rr < 6; rr++)
+#pragma unroll
+				for (int q = 0; q < 6; q++) acc[rr] = fma(blk[rr * 6 + q], x[q], acc[rr]);
+		}
+	}
+	flush();
+}
+
+// ---- back to the caller's layouts -----------------------------------------------------------------------------------------------
+// pose_cols of the chunk: out[a][6 m rows][6] = Xo[row][6 a + c]
+__global__ void k_cc_pose_out(int M, int R, const double* __restrict__ Xo, double* __restrict__ out)
+{
+	const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const size_t per = (size_t)M * 36;
+	if (idx >= per * (R / 6)) return;
+	const int a = (int)(idx / per);
+	const size_t rem = idx - (size_t)a * per;
+	out[idx] = Xo[(rem / 6) * R + 6 * a + rem % 6];
+}
+// the rows of all k requested poses (for `joint`): out[6 b + q][R] = Xo[6 qall[b] + q][R]
+__global__ void k_cc_rows(int k, int R, const int* __restrict__ qall, const double* __restrict__ Xo, double* __restrict__ out)
+{
+	const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (idx >= (size_t)k * 6 * R) return;
+	const size_t row = idx / R;
+	out[idx] = Xo[((size_t)qall[row / 6] * 6 + row % 6) * R + idx % R];
+}
+
+// Sigma_{f,Q} = -V_f^-1 sum_a W_af^T Sigma_{p_a,Q}: one pass over W for all columns.  A work-group takes CC_FB features in turn; the
+// feature's run of W blocks and its V^-1 are uniform (broadcast), a lane sums its column.  out[a][n][3][6] (feat_cols of the chunk):
+// the 18 values of one (feature, requested pose) are contiguous and consecutive features follow each other.
+__global__ void __launch_bounds__(CC_KC * 6) k_cc_feat(int NF, const int* __restrict__ fptr, const int* __restrict__ photo, const double* __restrict__ W,
+                                                       const double* __restrict__ IV, int R, const double* __restrict__ Xo, double* __restrict__ out)
+{
+	const int r = threadIdx.x;
+	if (r >= R) return;
+	const int f0 = blockIdx.x * CC_FB, f1 = min(f0 + CC_FB, NF);
+	const int a = r / 6, c = r - 6 * a;
+	for (int f = f0; f < f1; f++)
+	{
+		const int w0 = fptr[f], w1 = fptr[f + 1];
+		double t[3] = { 0, 0, 0 };
+		for (int w = w0; w < w1; w++)
+		{
+			const double* wb = W + (size_t)w * 18;
+			const double* src = Xo + (size_t)photo[w] * 6 * R + r;
+#pragma unroll
+			for (int q = 0; q < 6; q++)
+			{
+				const double x = src[(size_t)q * R];
+#pragma unroll
+				for (int j = 0; j < 3; j++) t[j] = fma(wb[q * 3 + j], x, t[j]);
+			}
+		}
+		const double* iv = IV + (size_t)f * 9;
+		double* o = out + ((size_t)a * NF + f) * 18 + c;
+#pragma unroll
+		for (int i = 0; i < 3; i++) o[i * 6] = -(iv[i * 3] * t[0] + iv[i * 3 + 1] * t[1] + iv[i * 3 + 2] * t[2]);
+	}
+}
+
+inline unsigned blocks_of(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
+
+} // namespace
+
+int map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* poses, int k, double* pose_cols, double* feat_cols, double* joint,
+                           int* steps_out, double* last_corr, double* times)
+{
+	const int m = map->m, n = map->n;
+	{
+		std::vector<char> seen(m, 0);
+		for (int a = 0; a < k; a++)
+		{
+			if (poses[a] < 0 || poses[a] >= m) LSFM_FAIL(LSFM_ERR_ARG, "requested pose " + std::to_string(poses[a]) + " is not one of the map's " + std::to_string(m));
+			if (seen[poses[a]]) LSFM_FAIL(LSFM_ERR_ARG, "pose " + std::to_string(poses[a]) + " is requested twice");
+			seen[poses[a]] = 1;
+		}
+	}
+	if (steps_out) *steps_out = 0;
+	CovFront fr;
+	{
+		// the residual needs the row-sorted list of S's blocks whatever product the context's CG is set to (lsfm_set_spmv_variant)
+		struct Keep { lsfm_context* c; int v; ~Keep() { c->pcg.spmv_variant = v; } } keep{ ctx, ctx->pcg.spmv_variant };
+		ctx->pcg.spmv_variant = 2;
+		cov_front(ctx, map, mono, fr);
+	}
+	const SolveIO& io = fr.io;
+	const SchurSystem& sy = fr.sy;
+	const CholDev& ch = fr.ch;
+	hipStream_t s = ctx->stream;
+	LSFM_CHECK_HIP(hipGetLastError());
+	const int floored = cov_front_status(ctx, fr);
+	if (floored > 0) return floored; // the factor is of a perturbed S: nothing is written
+	if (!sy.gent) LSFM_FAIL(LSFM_ERR_INTERNAL, "the camera system has no row-sorted block list");
+	const int M = ch.M;
+	const int kc = std::min(k, CC_KC), Rmax = 6 * kc;
+	// ---- memory of the call ----
+	const size_t slab = (size_t)M * 6 * Rmax;
+	const bool want_feat = feat_cols && n;
+	{
+		const size_t need = (3 * slab + (want_feat ? (size_t)n * 18 * kc : 0) + (joint ? (size_t)k * 6 * Rmax : 0)) * sizeof(double);
+		size_t free_b = 0, total_b = 0;
+		if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b)
+			throw Error{ LSFM_ERR_OOM, "out of device memory: the columns of " + std::to_string(kc) + " poses need " + std::to_string(need) + " bytes, " + std::to_string(free_b) + " are free" };
+	}
+	DevBuf bV, bX, bY, bF, bN, bJ, bQ;
+	double* V = bV.get<double>(slab);   // elimination order, scaled: right-hand side in, solution out
+	double* Xo = bX.get<double>(slab);  // Sigma_{.,Q} of the chunk, [6 m][R]
+	double* Y = bY.get<double>(slab);   // residual [6 m][R]; at the end the chunk of pose_cols
+	double* F = want_feat ? bF.get<double>((size_t)n * 18 * kc) : nullptr;
+	unsigned long long* norm = bN.get<unsigned long long>(2 * (size_t)Rmax);
+	double* Jd = joint ? bJ.get<double>((size_t)k * 6 * Rmax) : nullptr;
+	int* dq = bQ.get<int>(k);
+	h2d(ctx, dq, poses, (size_t)k * sizeof(int));
+	hipEvent_t ev[3] = { ctx->pool_event(), ctx->pool_event(), ctx->pool_event() };
+	const int ngl = (int)ch.glevel_ptr.size() - 1;
+	const bool plain = (ctx->covcols_panel ? ctx->covcols_panel : CC_PANEL_DEFAULT) == 1;
+	// (L L^T)^-1 applied to V in place
+	auto sweep = [&](int R) {
+		const unsigned rp = (unsigned)((R + LSFM_WAVE - 1) / LSFM_WAVE * LSFM_WAVE);
+		const unsigned nsl = plain ? std::min(8u, CC_MAXT / rp) : 1u;
+		const unsigned pt = (unsigned)((R + 15) / 16) * LSFM_WAVE; // a wave per 16 columns (<= CC_MAXT: R <= 6 CC_KC)
+		if (ch.ntask0) hipLaunchKernelGGL(k_cc_fwd<false>, dim3(ch.ntask0), dim3(rp, 1), 0, s, ch.task_ptr, ch.task_cols, ch.col_task, false, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
+		for (int l = 0; l < ngl; l++)
+		{
+			const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0, mnr = ch.glevel_maxnr[l];
+			if (!ng) continue;
+			hipLaunchKernelGGL(k_cc_fwd<true>, dim3(ng), dim3(rp, nsl), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, plain, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
+			if (!plain && mnr > 0)
+				hipLaunchKernelGGL(k_cc_fwd_panel, dim3(ng, std::min(CC_GY, (6 * mnr + 15) / 16)), dim3(pt), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, R, ch.colptr, ch.rowidx, ch.L, V);
+		}
+		for (int l = ngl - 1; l >= 0; l--)
+		{
+			const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0, mnr = ch.glevel_maxnr[l];
+			if (!ng) continue;
+			if (!plain && mnr > 0)
+				hipLaunchKernelGGL(k_cc_bwd_panel, dim3(ng, std::min(CC_GY, (6 * mnr + CC_GK - 1) / CC_GK)), dim3(pt), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, R, ch.colptr, ch.rowidx, ch.L, V);
+			hipLaunchKernelGGL(k_cc_bwd<true>, dim3(ng), dim3(rp, nsl), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, plain, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
+		}
+		if (ch.ntask0) hipLaunchKernelGGL(k_cc_bwd<false>, dim3(ch.ntask0), dim3(rp, 1), 0, s, ch.task_ptr, ch.task_cols, (const int*)nullptr, false, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
+	};
+	const double tol = ctx->pcg.rel_tol;
+	const int max_steps = std::max(1, ctx->pcg.max_steps);
+	std::vector<double> hn(2 * (size_t)Rmax), hj(joint ? (size_t)k * 6 * Rmax : 0);
+	int most_steps = 0;
+	bool undone = false;
+	double t_solve = 0.0, t_feat = 0.0;
+	for (int c0 = 0; c0 < k; c0 += kc)
+	{
+		const int kcur = std::min(kc, k - c0), R = 6 * kcur;
+		const unsigned rp = (unsigned)((R + LSFM_WAVE - 1) / LSFM_WAVE * LSFM_WAVE);
+		const size_t cells = (size_t)M * 6 * R;
+		const int* qpose = dq + c0;
+		LSFM_CHECK_HIP(hipEventRecord(ev[0], s));
+		// ---- the unrefined solve ----
+		hipLaunchKernelGGL(k_cc_unit, dim3(blocks_of(cells, 256)), dim3(256), 0, s, M, R, ch.perm, ch.dscale, io.d_fixed, qpose, V);
+		sweep(R);
+		hipLaunchKernelGGL(k_cc_perm_out, dim3(blocks_of((size_t)M * 6, CC_ROWS)), dim3(rp), 0, s, M, R, ch.pinv, ch.dscale, io.d_fixed, V, Xo);
+		// ---- refinement: always one step, then while the corrections are above the tolerance and still halving ----
+		int steps = 0;
+		double prev = 0.0;
+		std::vector<double> ratio(R, 0.0);
+		for (;;)
+		{
+			hipLaunchKernelGGL(k_cc_unit, dim3(blocks_of(cells, 256)), dim3(256), 0, s, M, R, (const int*)nullptr, (const double*)nullptr, io.d_fixed, qpose, Y);
+			hipLaunchKernelGGL(k_cc_resid, dim3(blocks_of((size_t)2 * sy.nnzb, CC_EPW)), dim3(rp), 0, s, 2 * sy.nnzb, sy.gent, sy.goth, sy.S, io.d_fixed, R, Xo, Y);
+			hipLaunchKernelGGL(k_cc_perm_in, dim3(blocks_of(cells, 256)), dim3(256), 0, s, M, R, ch.perm, ch.dscale, io.d_fixed, Y, V);
+			sweep(R);
+			dev_zero(ctx, norm, 2 * (size_t)R * sizeof(unsigned long long));
+			hipLaunchKernelGGL(k_cc_perm_add, dim3(blocks_of((size_t)M * 6, CC_ROWS)), dim3(rp), 0, s, M, R, ch.pinv, ch.dscale, io.d_fixed, V, Xo, norm);
+			LSFM_CHECK_HIP(hipGetLastError());
+			d2h(ctx, hn.data(), norm, 2 * (size_t)R * sizeof(double)); // (the bit patterns of non-negative doubles)
+			steps++;
+			double worst = 0.0;
+			for (int r = 0; r < R; r++)
+			{
+				ratio[r] = hn[R + r] > 0.0 ? hn[r] / hn[R + r] : (hn[r] > 0.0 ? INFINITY : 0.0);
+				if (!(ratio[r] <= worst)) worst = ratio[r]; // (a NaN counts as the worst)
+			}
+			if (worst <= tol) break;
+			if (steps >= max_steps) { undone = true; break; }
+			if (steps > 1 && !(worst <= 0.5 * prev)) break; // as far as fp64 refinement against this factor goes
+			prev = worst;
+		}
+		most_steps = std::max(most_steps, steps);
+		if (last_corr)
+			for (int a = 0; a < kcur; a++) last_corr[c0 + a] = *std::max_element(ratio.begin() + 6 * a, ratio.begin() + 6 * a + 6);
+		// ---- the caller's layouts ----
+		if (pose_cols) hipLaunchKernelGGL(k_cc_pose_out, dim3(blocks_of(cells, 256)), dim3(256), 0, s, M, R, Xo, Y);
+		if (joint) hipLaunchKernelGGL(k_cc_rows, dim3(blocks_of((size_t)k * 6 * R, 256)), dim3(256), 0, s, k, R, dq, Xo, Jd);
+		LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
+		if (want_feat) hipLaunchKernelGGL(k_cc_feat, dim3(blocks_of(n, CC_FB)), dim3(rp), 0, s, n, io.fptr, io.photo, io.W, sy.IV, R, Xo, F);
+		LSFM_CHECK_HIP(hipEventRecord(ev[2], s));
+		LSFM_CHECK_HIP(hipGetLastError());
+		if (pose_cols) d2h(ctx, pose_cols + (size_t)c0 * m * 36, Y, cells * sizeof(double));
+		if (want_feat) d2h(ctx, feat_cols + (size_t)c0 * n * 18, F, (size_t)kcur * n * 18 * sizeof(double));
+		if (joint)
+		{
+			d2h(ctx, hj.data(), Jd, (size_t)k * 6 * R * sizeof(double));
+			for (int row = 0; row < 6 * k; row++) memcpy(&joint[(size_t)row * 6 * k + 6 * c0], &hj[(size_t)row * R], (size_t)R * sizeof(double));
+		}
+		LSFM_CHECK_HIP(hipStreamSynchronize(s));
+		float ms = 0.0f;
+		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); t_solve += ms;
+		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[1], ev[2])); t_feat += ms;
+	}
+	if (joint)
+	{
+		// the chunks' columns are in place; exactly symmetric: block (a, b), a < b, from column b and mirrored; the diagonal blocks (X + X^T) / 2
+		const size_t n6 = (size_t)k * 6;
+		for (size_t i = 0; i < n6; i++)
+			for (size_t j = i; j < n6; j++)
+			{
+				const double v = i / 6 == j / 6 ? 0.5 * (joint[i * n6 + j] + joint[j * n6 + i]) : joint[i * n6 + j];
+				joint[i * n6 + j] = joint[j * n6 + i] = v;
+			}
+	}
+	if (steps_out) *steps_out = most_steps;
+	if (times)
+	{
+		float ms = 0.0f;
+		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, fr.ev[0], fr.ev[1])); times[0] = ms;
+		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, fr.ev[1], fr.ev[2])); times[1] = ms;
+		times[2] = t_solve; times[3] = t_feat;
+	}
+	return undone ? LSFM_NOT_CONVERGED : LSFM_OK;
+}
+
+} // namespace lsfm

@@ -265,6 +265,7 @@ struct lsfm_context {
 	int cur = 0;
 	size_t arena_bytes = 0, arena_req = 0; // actual size of each arena / the request it answers (may have been capped)
 	lsfm::PcgOptions pcg;
+	int covcols_panel = 0; // lsfm_set_covcols_panel: 0 the default of lsfm_covcols.hip, 1 plain, 2 MFMA
 	// levels whose systems have at most this many poses take the one-launch dense path (lsfm_small.hip); 0: none.  The kernel holds 16;
 	// the default is where it beats the level pipeline on the NC3500-like set (per-level measurements).  lsfm_set_small_solve
 	int small_max = 5;
@@ -497,6 +498,10 @@ int map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const ls
 // Schur reduction + analysis, the factorisation, the selected inversion + pose gather, the feature part
 int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb,
                    double* times);
+// whole columns of Sigma for the poses poses[k], solved side by side against the same factor and refined in fp64 (lsfm_covcols.hip; C ABI:
+// lsfm_map_covariance_columns).  times (may be null): [4] ms of reduce + analyse, factorisation, all sweeps and products, the feature part
+int map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* poses, int k, double* pose_cols, double* feat_cols, double* joint,
+                           int* steps, double* last_corr, double* times);
 // the two feature-side pieces of the solve on their own (C ABI: lsfm_inverse_v / lsfm_solve_features); device pointers
 void vinv_only(lsfm_context* ctx, int NF, const double* V, double* IV);
 void backsub_only(lsfm_context* ctx, int NF, const int* fptr, const int* photo, const double* W, const double* IV, const double* eb, const double* xp, double* xf);

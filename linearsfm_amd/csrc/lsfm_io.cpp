@@ -549,4 +549,51 @@ int lsfm_read_covariances(const char* path, int k, int* ids, double* cov, int ca
 	return rc;
 }
 
+// the -covcols file (lsfm_map_covariance_columns): one line per (requested pose, pose), "id_q id_p" and the 36 entries of Sigma_{p,q}
+// row by row at %.17g; requested poses in the order given, within one the poses as in the pose file
+int lsfm_save_cov_columns(const char* path, const int* stno, int m, const int* poses, int k, const double* pose_cols)
+{
+	if (!path || !stno || m <= 0 || !poses || k < 1 || !pose_cols) return LSFM_ERR_ARG;
+	for (int a = 0; a < k; a++) if (poses[a] < 0 || poses[a] >= m) return LSFM_ERR_ARG;
+	std::vector<std::pair<int, int> > P;
+	for (int p = 0; p < m; p++) P.push_back(std::make_pair(-stno[6 * p], p));
+	std::stable_sort(P.begin(), P.end());
+	const std::string tmp = std::string(path) + ".tmp";
+	FILE* fp = fopen(tmp.c_str(), "w");
+	if (!fp) return LSFM_ERR_IO;
+	for (int a = 0; a < k; a++)
+		for (size_t i = 0; i < P.size(); i++)
+		{
+			if (i + 1 < P.size() && P[i + 1].first == P[i].first) continue;
+			const double* b = pose_cols + ((size_t)a * m + P[i].second) * 36;
+			fprintf(fp, "%d %d", -stno[6 * poses[a]], P[i].first);
+			for (int q = 0; q < 36; q++) fprintf(fp, " %.17g", b[q]);
+			fprintf(fp, "\n");
+		}
+	const bool bad = ferror(fp) != 0;
+	if (fclose(fp) != 0 || bad || rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); return LSFM_ERR_IO; }
+	return LSFM_OK;
+}
+
+int lsfm_read_cov_columns(const char* path, int* ids_q, int* ids_p, double* blocks, int cap, int* count)
+{
+	if (!path || cap < 0 || !count || (cap && (!ids_q || !ids_p || !blocks))) return LSFM_ERR_ARG;
+	FILE* fp = fopen(path, "r");
+	if (!fp) return LSFM_ERR_IO;
+	int cnt = 0, iq = 0, ip = 0, rc = LSFM_OK;
+	while (rc == LSFM_OK && fscanf(fp, "%d", &iq) == 1)
+	{
+		if (fscanf(fp, "%d", &ip) != 1) { rc = LSFM_ERR_IO; break; }
+		if (cnt >= cap) { rc = LSFM_ERR_ARG; break; }
+		double* b = blocks + (size_t)cnt * 36;
+		for (int q = 0; q < 36; q++)
+			if (fscanf(fp, "%lf", &b[q]) != 1) { rc = LSFM_ERR_IO; break; }
+		if (rc == LSFM_OK) { ids_q[cnt] = iq; ids_p[cnt] = ip; cnt++; }
+	}
+	if (rc == LSFM_OK && !feof(fp)) rc = LSFM_ERR_IO;
+	fclose(fp);
+	*count = cnt;
+	return rc;
+}
+
 } // extern "C"

@@ -1,6 +1,12 @@
 """lsfm_map_covariance on the final map of a named stand-in set: the HIP-event time of its parts (Schur reduction + symbolic analysis,
 numeric factorisation, selected inversion + gather onto the pattern, feature part) beside t_pcg_ms of the same set's tree run.
-usage: python tools/cov_bench.py <config> [maps] [reps]  -> one JSON object on stdout (profiles/cov_bench_<config>.json)."""
+usage: python tools/cov_bench.py <config> [maps] [reps]  -> one JSON object on stdout (profiles/cov_bench_<config>.json).
+
+  --columns K[,K...]   instead: lsfm_map_covariance_columns_timed for K requested poses each (pose columns only, then with the feature
+                       rows), warm, medians of `reps` calls (profiles/cov_columns_<config>.json); with --panel V the supernode-group
+                       panel product is set first (lsfm_set_covcols_panel: 1 lane per column, 2 MFMA; default 0 = the library's choice)
+  --parent-route       instead: the wall time of six Context.solve calls with unit right-hand sides -- one pose's six columns by the
+                       only route the library had before lsfm_map_covariance_columns (existing API only: runs on older commits too)"""
 import json
 import os
 import sys
@@ -12,14 +18,85 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 from linearsfm_amd import api, synth  # noqa: E402
 
-cfg = sys.argv[1]
-nmaps = int(sys.argv[2]) if len(sys.argv) > 2 and int(sys.argv[2]) > 0 else None
-reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+args = sys.argv[1:]
+columns, parent_route = None, False
+if "--columns" in args:
+    i = args.index("--columns")
+    columns = [int(v) for v in args[i + 1].split(",")]
+    del args[i: i + 2]
+panel = 0
+if "--panel" in args:
+    i = args.index("--panel")
+    panel = int(args[i + 1])
+    del args[i: i + 2]
+if "--parent-route" in args:
+    parent_route = True
+    args.remove("--parent-route")
+cfg = args[0]
+nmaps = int(args[1]) if len(args) > 1 and int(args[1]) > 0 else None
+reps = int(args[2]) if len(args) > 2 else 3
 typ, maps = synth.make_config(cfg, nmaps)
 mono = typ == "Monocular"
 d = [m.__dict__ for m in maps]
 ctx = api.Context(0)
 G, stats, rc = ctx.divide_conquer(d, mono)
+m_, n_ = int(G["m"]), int(G["n"])
+if parent_route:
+    # one pose's six columns as six whole solves: six uploads, Schur reductions and factorisations
+    j = m_ // 2
+    sa = None
+    if mono:
+        ids = -np.asarray(G["stno"])[: 6 * m_: 6]
+        pr, ps = int(np.nonzero(ids == G["Ref"])[0][0]), int(np.nonzero(ids == G["ScaP"])[0][0])
+        sa = [pr, 6 * pr, 6 * ps + int(G["Fix"]), 0, 0]
+        j = j if j != pr else (j + 1) % m_
+    walls = []
+    for rep in range(reps + 1):  # (the first round is a warm-up)
+        t0 = time.perf_counter()
+        for c in range(6):
+            eP = np.zeros(6 * m_)
+            eP[6 * j + c] = 1.0
+            ctx.solve(G, eP, np.zeros(3 * n_), mono, sa)
+        if rep:
+            walls.append(1e3 * (time.perf_counter() - t0))
+    print(json.dumps({"config": cfg, "type": typ, "maps": len(maps), "poses": m_, "features": n_, "leg": "parent-route", "pose": j,
+                      "six_solves_wall_ms": walls, "six_solves_wall_ms_median": float(np.median(walls)),
+                      "sixteen_poses_scaled_ms": 16 * float(np.median(walls)),
+                      "note": "wall time of six Context.solve calls (unit right-hand sides of one pose, eF = 0), each with its own upload, Schur "
+                              "reduction and factorisation; 16 poses = 96 such calls"}, indent=1))
+    ctx.close()
+    sys.exit(0)
+if columns:
+    ctx.set_covcols_panel(panel)
+    rng = np.random.default_rng(1)
+    legs = []
+    for K in columns:
+        q = rng.choice(m_, size=min(K, m_), replace=False)
+        for feats in (False, True):
+            walls, parts, steps = [], [], 0
+            for rep in range(reps + 1):  # (the first call is a warm-up)
+                t0 = time.perf_counter()
+                crc, pose, feat, _, steps, corr, t = ctx.covariance_columns_raw(G, mono, q, features=feats, times=True)
+                wall = 1e3 * (time.perf_counter() - t0)
+                if crc < 0:
+                    sys.exit(f"lsfm_map_covariance_columns: {api.lib().lsfm_last_error(ctx._h).decode()}")
+                if rep:
+                    walls.append(wall)
+                    parts.append(t.tolist())
+            med = np.median(np.array(parts), axis=0)
+            sweeps = 2 * (1 + steps)  # forward + backward of the unrefined solve and of every refinement step
+            legs.append({"K": int(len(q)), "features": feats, "status": crc, "steps": steps, "last_corr_max": float(corr.max()),
+                         "ms_median": {"reduce_analyse": med[0], "factor": med[1], "sweeps_products": med[2], "features": med[3]},
+                         "sweeps_products_ms_per_column": med[2] / (6 * len(q)), "ms_per_sweep_per_chunk": med[2] / sweeps / -(-len(q) // 32),
+                         "call_wall_ms_median": float(np.median(walls)), "call_wall_ms": walls,
+                         "feature_out_GBps": (18 * len(q) * n_ * 8 / (med[3] * 1e-3) / 1e9) if feats and med[3] > 0 else None})
+    print(json.dumps({"config": cfg, "type": typ, "maps": len(maps), "poses": m_, "features": n_, "leg": "columns", "panel": panel, "tree_t_total_ms": stats["t_total_ms"],
+                      "legs": legs,
+                      "note": "HIP events on the context's stream; sweeps_products covers the unrefined solve, every refinement step (product with S, "
+                              "both sweeps, update and its norms read back) and the gather into the caller's layout; call wall includes the upload "
+                              "of the map and the download of the columns"}, indent=1))
+    ctx.close()
+    sys.exit(0)
 calls, parts = [], []
 first = None
 status = 0
