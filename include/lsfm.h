@@ -215,6 +215,30 @@ int lsfm_map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, int type, cons
 int lsfm_gn_polish_robust(lsfm_context* ctx, const lsfm_map* maps, int N, int type, lsfm_map* x, int iters, int kind, double c,
                           double* obj, double* gnorm, int* halvings, double* chi2, double* weight);
 
+/* ---- the information matrix at a state: the joint map of the N local maps linearised at x ----
+ * H = sum_k w_k J_k^T I_k J_k and the state x as an lsfm_map (library-allocated: lsfm_map_release), the matrix a step of
+ * lsfm_gn_polish[_robust] solves with at x.  maps / N / type / x and every argument check: lsfm_gn_polish's; x is read only.
+ * weight[N] (may be NULL: all 1): finite, >= 0 (else LSFM_ERR_ARG) -- e.g. what lsfm_gn_polish_robust returned.
+ * obj (may be NULL): sum_k w_k chi2_k.  b[6m + 3n] (may be NULL): sum_k w_k J_k^T I_k r_k, poses then features, x's order.
+ * No reference counterpart: PARITY UNPINNED, as for lsfm_gn_polish.
+ * The map is canonical and its structure depends on the labels alone, never on values: m, n, stno, stVal, Ref, FRef, ScaP, Fix, Sign,
+ * FScaP, FFix are x's; pose_origin is x's if given, else the first local map holding the pose; U has exactly one block per pose pair
+ * (Ui <= Uj) that a local map or a hub role (a map's Ref / ScaP pose against its poses) produces, sorted by (Ui, Uj), diagonal blocks
+ * full; W is sorted by feature and within a feature by ascending pose, exactly one block per (pose, feature) -- a block whose value
+ * happens to be zero stays --, feature[] / FBlock[] to match; V one block per feature.  Mono: the rows and columns of the gauge
+ * scalars are kept (the gauge is applied by whoever inverts: lsfm_map_covariance(mono = 1) reads it from Ref / ScaP / Fix).  The
+ * result is an input like any other map to lsfm_map_covariance[_columns], lsfm_schur_pattern, lsfm_write_localmap / _mapset and
+ * lsfm_tree_upload.
+ * One assembly of the polish at x, then two kernels that sum the repeated blocks of its working form (one lane per output block, its
+ * sources in map order, no atomics).  The assembly in front of them adds with atomics: two calls agree to rounding, NOT bit for bit.
+ * Lifetime: works in the context's arenas like lsfm_gn_polish. */
+int lsfm_gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, const double* weight,
+                      lsfm_map* out, double* obj, double* b);
+/* measurement entry: the same, and times[3] (may be NULL) = HIP-event ms of the assembly, of the W and of the U coalescing launch;
+ * counts[4] (may be NULL) = blocks of the working form's W, of out's W, of the working form's U, of out's U */
+int lsfm_gn_linearise_timed(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, const double* weight,
+                            lsfm_map* out, double* obj, double* b, double* times, int* counts);
+
 /* ---- marginal covariances of a map (NO reference counterpart: the reference keeps the information matrix and never inverts it) ----
  * Sigma = I^-1 with I = [U W; W^T V] of `map` (any lsfm_map: a downloaded tree result, a checkpoint node, a local map).
  * mono = 0: Stereo, I is used as it is (the map's Ref pose is not in its state).  mono = 1: the gauge of lsfm_solve_mono /

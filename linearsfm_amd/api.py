@@ -120,6 +120,8 @@ def lib():
         L.lsfm_gn_polish.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), C.c_int, dp, dp, ip]
         L.lsfm_gn_polish_robust.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), C.c_int, C.c_int, C.c_double, dp, dp, ip, dp, dp]
         L.lsfm_map_chi2.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, ip]
+        L.lsfm_gn_linearise.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, P(LsfmMap), dp, dp]
+        L.lsfm_gn_linearise_timed.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, P(LsfmMap), dp, dp, dp, ip]
         L.lsfm_solve_features.argtypes = [vp, dp, dp, dp, dp, dp, dp, C.c_int, C.c_int, ip, ip]
         L.lsfm_map_covariance.argtypes = [vp, P(LsfmMap), C.c_int, dp, dp, dp, C.c_int, ip]
         L.lsfm_map_covariance_timed.argtypes = [vp, P(LsfmMap), C.c_int, dp, dp, dp, C.c_int, ip, dp]
@@ -142,7 +144,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_tree_download", "lsfm_tree_set_stop_level", "lsfm_tree_node_count", "lsfm_tree_download_node", "lsfm_tree_download_state", "lsfm_tree_set_plans", "lsfm_tree_export_size", "lsfm_tree_export_dev", "lsfm_packed_size",
            "lsfm_tree_upload_dev", "lsfm_tree_reload_dev", "lsfm_tree_set_comm", "lsfm_tree_set_comm_blocks", "lsfm_tree_export_slice_sizes", "lsfm_tree_export_slice_dev",
            "lsfm_tree_free", "lsfm_divide_conquer", "lsfm_read_localmap", "lsfm_read_localmaps", "lsfm_write_localmap", "lsfm_write_mapset", "lsfm_mapset_info", "lsfm_mapset_stamp", "lsfm_read_mapset", "lsfm_save_state_bin", "lsfm_save_state", "lsfm_save_poses", "lsfm_gn_polish",
-           "lsfm_gn_polish_robust", "lsfm_map_chi2",
+           "lsfm_gn_polish_robust", "lsfm_map_chi2", "lsfm_gn_linearise", "lsfm_gn_linearise_timed",
            "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
            "lsfm_map_covariance", "lsfm_map_covariance_timed",
            "lsfm_save_covariances", "lsfm_read_covariances",
@@ -213,6 +215,7 @@ def _gn_args(maps, G):
     st = np.array(np.asarray(G["stVal"], np.float64), copy=True)
     x.m, x.n, x.Ref, x.FRef = int(G["m"]), int(G["n"]), int(G["Ref"]), int(G.get("FRef", G["Ref"]))
     x.ScaP, x.Fix, x.Sign = int(G.get("ScaP", 0)), int(G.get("Fix", 0)), int(G.get("Sign", 1))
+    x.FScaP, x.FFix = int(G.get("FScaP", x.ScaP)), int(G.get("FFix", x.Fix))
     x.stno, x.stVal = _ptr(stno, C.c_int), _ptr(st, C.c_double)
     org = None
     if G.get("pose_origin") is not None:
@@ -451,6 +454,29 @@ class Context:
         if rc < 0:
             self._check(rc, "lsfm_gn_polish_robust")
         return st, obj, gn, hv[:iters], chi2, w, rc
+
+    def gn_linearise(self, maps, mono, G, weight=None, want_b=False, timed=False):
+        """lsfm_gn_linearise: the joint map of the local maps linearised at the global state G (as gn_polish takes it; read only) --
+        H = sum_k w_k J_k^T I_k J_k as U / W / V with every block once, the matrix a step of gn_polish[_robust] solves with at G.
+        weight [N] or None (all 1): e.g. what gn_polish_robust returned.  No reference counterpart.  Returns (map dict of the form
+        tree_download returns, F = sum_k w_k chi2_k, b = sum_k w_k J_k^T I_k r_k or None); timed: also ({"assembly_ms",
+        "coalesce_w_ms", "coalesce_u_ms"} by HIP events, {"NWJ", "nW", "NUJ", "nU"}: blocks of the working form / of the map)."""
+        hms, arr, x, keep = _gn_args(maps, G)
+        w = _c(weight, np.float64) if weight is not None else None
+        if w is not None and len(w) != len(hms):
+            raise LsfmError(f"gn_linearise: {len(w)} weights for {len(hms)} maps")
+        out = LsfmMap()
+        F = C.c_double(0.0)
+        b = np.zeros(6 * x.m + 3 * x.n) if want_b else None
+        t, cnt = np.zeros(3), np.zeros(4, np.int32)
+        rc = lib().lsfm_gn_linearise_timed(self._h, arr, len(hms), int(mono), C.byref(x), _ptr(w, C.c_double) if w is not None else None,
+                                           C.byref(out), C.byref(F), _ptr(b, C.c_double) if want_b else None,
+                                           _ptr(t, C.c_double) if timed else None, _ptr(cnt, C.c_int) if timed else None)
+        self._check(rc, "lsfm_gn_linearise")
+        d = map_to_dict(out)
+        if timed:
+            return d, F.value, b, dict(zip(("assembly_ms", "coalesce_w_ms", "coalesce_u_ms"), t.tolist())), dict(zip(("NWJ", "nW", "NUJ", "nU"), cnt.tolist()))
+        return d, F.value, b
 
     def inverse_v(self, V):
         """lsfm_inverse_v (the reference's pba_inverseV, Imp.cpp:3022): V^-1 of the 3x3 feature blocks, [n, 9]."""

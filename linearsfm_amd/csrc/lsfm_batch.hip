@@ -361,8 +361,6 @@ unsigned long long batch_structure_digest(lsfm_context* ctx, const DevBatch& b)
 	return h;
 }
 
-template <class T> static T* host_alloc(size_t n) { return static_cast<T*>(malloc((n ? n : 1) * sizeof(T))); }
-
 void batch_download_map(lsfm_context* ctx, const DevBatch& b, int k, bool mono, lsfm_map* g)
 {
 	memset(g, 0, sizeof *g);

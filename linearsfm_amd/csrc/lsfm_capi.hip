@@ -869,6 +869,23 @@ int lsfm_map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, int type, cons
 	return guarded(ctx, [&]() { return map_chi2(ctx, maps, N, type == 1, x, chi2, dof); });
 }
 
+int lsfm_gn_linearise_timed(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, const double* weight, lsfm_map* out, double* obj,
+                            double* b, double* times, int* counts)
+{
+	if (!maps || N <= 0 || !x || !out || (type != 0 && type != 1)) return LSFM_ERR_ARG;
+	if (weight)
+		for (int k = 0; k < N; k++)
+			if (!std::isfinite(weight[k]) || weight[k] < 0.0)
+				return guarded(ctx, [&]() -> int { LSFM_FAIL(LSFM_ERR_ARG, "gn linearise: weight " + std::to_string(k + 1) + " is negative or not finite"); });
+	return guarded(ctx, [&]() { return gn_linearise(ctx, maps, N, type == 1, x, weight, out, obj, b, times, counts); });
+}
+
+int lsfm_gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, const double* weight, lsfm_map* out, double* obj,
+                      double* b)
+{
+	return lsfm_gn_linearise_timed(ctx, maps, N, type, x, weight, out, obj, b, nullptr, nullptr);
+}
+
 int lsfm_map_covariance_timed(lsfm_context* ctx, const lsfm_map* map, int mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb,
                               double* times)
 {

@@ -13,7 +13,10 @@
 // -covcols <file> -covposes <id,id,...> (whole columns of the covariance for the poses with these labels: lsfm_map_covariance_columns; one
 // line per (requested pose, pose): "id_q id_p" and the 36 entries of Sigma_{p,q}; the two flags go together),
 // -robust huber|cauchy <c> (-gn uses lsfm_gn_polish_robust: whole local maps down-weighted by an M-estimator on chi2_k / dof_k),
-// -chi2 <file> (per local map, in input order, "index dof chi2 weight" at the final state: lsfm_map_chi2; no reference counterpart).
+// -chi2 <file> (per local map, in input order, "index dof chi2 weight" at the final state: lsfm_map_chi2; no reference counterpart),
+// -relin 1 (the final map's information matrix -- U / W / V and their index arrays -- is replaced by the local maps linearised at the final
+// state, after -gn if given and with the polish's weights under -robust: lsfm_gn_linearise; -info, -cov, -covf and -covcols then describe
+// the estimate the other files hold; no reference counterpart).
 #include <cmath>
 #include <chrono>
 #include <sys/stat.h>
@@ -40,13 +43,14 @@ static void print_help()
 	printf("			II : Stereo\n");
 	printf("-robust huber|cauchy <c>	With -gn: Down-Weight Inconsistent Local Maps (Threshold c On chi2 / dof)\n");
 	printf("-chi2 <file>		Save chi2 Of Every Local Map: index dof chi2 weight\n");
+	printf("-relin 1		Information Matrix (-info, -cov, -covf, -covcols) Of The Local Maps Linearised At The Final State\n");
 	printf("\n");
 }
 
 int main(int argc, char** argv)
 {
 	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes;
-	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0;
+	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0, relin = 0;
 	double robust_c = 0.0;
 	bool has_path = false, has_num = false;
 	double tol = 0;
@@ -84,6 +88,7 @@ int main(int argc, char** argv)
 		else if (name == "cov") cov = next();
 		else if (name == "covf") covf = next();
 		else if (name == "chi2") chi2f = next();
+		else if (name == "relin") relin = atoi(next());
 		else if (name == "covcols") covcols = next();
 		else if (name == "covposes") covposes = next();
 		else if (name == "robust")
@@ -259,6 +264,19 @@ int main(int argc, char** argv)
 			printf("Gauss-Newton Used Time:  %lf  sec\n\n", now() - g0);
 		}
 	}
+	if (relin)
+	{
+		// -relin 1: the information matrix of the state the files hold -- the local maps linearised at it (under -robust with the weights the
+		// polish ended at) instead of the tree's, whose joins linearised at states the estimate has since left
+		lsfm_map H;
+		if (lsfm_gn_linearise(ctx, maps.data(), num, type, &out, weightv.empty() ? nullptr : weightv.data(), &H, nullptr, nullptr) != LSFM_OK)
+		{
+			fprintf(stderr, "LinearSFM: relin: %s\n", lsfm_last_error(ctx));
+			return 3;
+		}
+		lsfm_map_release(&out);
+		out = H;
+	}
 	if (want_stats)
 		fprintf(stderr, "lsfm: total %.3f ms (transform %.3f, join %.3f [schur %.3f, pcg %.3f, backsub %.3f]), pcg its %ld, max rel resid %.2e, not converged %d, attempts %d\n",
 		        stats.t_total_ms, stats.t_transform_ms, stats.t_join_ms, stats.t_schur_ms, stats.t_pcg_ms, stats.t_backsub_ms, stats.pcg_iterations,
@@ -285,7 +303,7 @@ int main(int argc, char** argv)
 	if (!fullbin.empty() && lsfm_save_state_bin(fullbin.c_str(), out.stVal, out.stno, r)) fprintf(stderr, "LinearSFM: cannot write %s\n", fullbin.c_str());
 	if (!cov.empty() || !covf.empty())
 	{
-		// marginal covariances of the map the files above hold (after -gn its information matrix is still the tree's)
+		// marginal covariances of the map the files above hold (after -gn its information matrix is still the tree's, unless -relin 1)
 		std::vector<double> pc((size_t)out.m * 36), fc((size_t)out.n * 9);
 		const int crc = lsfm_map_covariance(ctx, &out, type, pc.data(), fc.data(), nullptr, 0, nullptr);
 		if (crc != LSFM_OK)

@@ -461,6 +461,39 @@ __global__ void k_gn_gather_pose(int M, const int* __restrict__ sptr, const int*
 	st<6>(ea + (size_t)g * 6, e);
 }
 
+// ---- the joint system as a map like any other (lsfm_gn_linearise) ----
+// UJ / WJ hold the solver's working form: entries with equal coordinates are repeated and add up.  Output block o is the sum of its
+// sources sidx[sptr[o] .. sptr[o + 1]) in that order (map order: the structure pass sorts stably).  One lane per output block,
+// consecutive lanes on consecutive output blocks; the sources of neighbouring output blocks lie in the same feature's run of WJ.  The
+// sum is held in registers and stored once.  No atomics: given UJ / WJ the result is the same bits every time.  HBM-bound: NWJ * 144 B
+// in, nW' * 144 B out (U: 288 B a block), no products.
+template <int N>
+__device__ __forceinline__ void gn_coalesce_block(int o, const int* __restrict__ sptr, const int* __restrict__ sidx, const double* __restrict__ src, double* __restrict__ dst)
+{
+	double acc[N], v[N];
+	const int q0 = sptr[o], q1 = sptr[o + 1];
+	ld<N>(acc, src + (size_t)sidx[q0] * N);
+	for (int q = q0 + 1; q < q1; q++)
+	{
+		ld<N>(v, src + (size_t)sidx[q] * N);
+#pragma unroll
+		for (int i = 0; i < N; i++) acc[i] += v[i];
+	}
+	st<N>(dst + (size_t)o * N, acc);
+}
+__global__ void __launch_bounds__(256)
+k_gn_coalesce_w(int nWo, const int* __restrict__ sptr, const int* __restrict__ sidx, const double* __restrict__ WJ, double* __restrict__ Wo)
+{
+	const int o = blockIdx.x * blockDim.x + threadIdx.x;
+	if (o < nWo) gn_coalesce_block<18>(o, sptr, sidx, WJ, Wo);
+}
+__global__ void __launch_bounds__(256)
+k_gn_coalesce_u(int nUo, const int* __restrict__ sptr, const int* __restrict__ sidx, const double* __restrict__ UJ, double* __restrict__ Uo)
+{
+	const int o = blockIdx.x * blockDim.x + threadIdx.x;
+	if (o < nUo) gn_coalesce_block<36>(o, sptr, sidx, UJ, Uo);
+}
+
 // ---- per-map chi^2 and the robust weights (lsfm_map_chi2, lsfm_gn_polish_robust) ----
 // chi2_k = r_k^T I_k r_k = sum_U (2 - delta_ab) r_a^T U_ab r_b + 2 sum_W r_a^T W_af r_f + sum_f r_f^T V_f r_f over map k's own blocks, at
 // the frames of k_gn_hubs and the pose residuals of k_gn_poses.  One work-group per map: its lanes stride over the map's U blocks and its
@@ -611,9 +644,20 @@ struct GnCall {
 	unsigned long long* d_max = nullptr;
 };
 
+// lsfm_gn_linearise only: the joint system with every block once.  Output W sorted by feature, within a feature by pose; output U sorted
+// by (i, j); per output block its sources in WJ / UJ as a CSR (wsp / wsi, usp / usi), in source (= map) order.  Index arrays on the host
+// (they go straight into the map handed out), the CSR and the output blocks on the device.
+struct GnCoalesce {
+	int nWo = 0, nUo = 0;
+	std::vector<int> photo, feature, FBlock, Ui, Uj, origin;
+	int *d_wsp = nullptr, *d_wsi = nullptr, *d_usp = nullptr, *d_usi = nullptr;
+	double *Wo = nullptr, *Uo = nullptr;
+};
+
 // the structure of a call, on the host from the labels, and the upload: which global variable every local one is, where every local
 // block lands in the joint system, the gauge (Mono); the state x goes to d_x.  Throws Error (LSFM_ERR_ARG) for what it cannot place.
-void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, GnCall& c)
+// weight (may be null: all 1): the maps' weights w_k.  co (may be null): the coalescing structure of lsfm_gn_linearise is built as well.
+void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, GnCall& c, const double* weight = nullptr, GnCoalesce* co = nullptr)
 {
 	const int M = c.M = x->m, NFG = c.NFG = x->n;
 	c.N = N; c.mono = mono;
@@ -629,6 +673,8 @@ void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const l
 		size_t P = 0, FI = 0, nW = 0, nU = 0;
 		for (int k = 0; k < N; k++) { P += maps[k].m; FI += maps[k].n; nW += maps[k].nW; nU += maps[k].nU; }
 		need += ((nW + 2 * FI) * 400 + (nU + 3 * P + 3 * (size_t)N) * 800 + (FI + NFG) * 500 + (P + M) * 6000) * 2 + (size_t)N * 64;
+		// (the coalesced blocks and their source lists: at most one output block and one source per joint block)
+		if (co) need += (nW + 2 * FI) * (144 + 16) + (nU + 2 * P + 3 * (size_t)N) * (288 + 16) + 1024;
 	}
 	ctx->ensure_arenas(need);
 	ctx->arena[0].reset(); ctx->arena[1].reset(); ctx->scratch.reset();
@@ -648,7 +694,7 @@ void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const l
 		memset(&t, 0, sizeof t);
 		t.p0 = X.pose_off[k]; t.m = L.m; t.f0 = X.feat_off[k]; t.n = L.n; t.u0 = X.u_off[k]; t.nu = L.nU;
 		t.hub[0] = t.hub[1] = -1;
-		t.w = 1.0;
+		t.w = weight ? weight[k] : 1.0;
 		if ((c.dof[k] = 6 * L.m + 3 * L.n) <= 0) LSFM_FAIL(LSFM_ERR_ARG, "gn polish: local map " + std::to_string(k + 1) + " is empty");
 		if (!mono && L.Ref == x->Ref) t.nh = 0;
 		else
@@ -773,7 +819,44 @@ void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const l
 	h2d(ctx, c.d_dof, c.dof.data(), c.dof.size() * sizeof(int));
 	h2d(ctx, c.d_x, x->stVal, RS * sizeof(double));
 	dev_zero(ctx, d_seg, (size_t)(M + NFG + 1) * sizeof(int));
-
+	if (co)
+	{
+		// W: every feature's joint run sorted stably by pose, equal poses merged
+		std::vector<int> wsp(1, 0), wsi(NWJ), usp(1, 0), usi(NUJ);
+		co->photo.clear(); co->feature.clear(); co->FBlock.assign(NFG, 0);
+		for (int q = 0; q < NWJ; q++) wsi[q] = q;
+		for (int g = 0; g < NFG; g++)
+		{
+			std::stable_sort(wsi.begin() + fptrJ[g], wsi.begin() + fptrJ[g + 1], [&](int a, int b) { return photoJ[a] < photoJ[b]; });
+			co->FBlock[g] = (int)co->photo.size();
+			for (int q = fptrJ[g]; q < fptrJ[g + 1]; q++)
+			{
+				if (q > fptrJ[g] && photoJ[wsi[q]] == photoJ[wsi[q - 1]]) continue;
+				if (q > 0) wsp.push_back(q);
+				co->photo.push_back(photoJ[wsi[q]]); co->feature.push_back(g);
+			}
+		}
+		wsp.push_back(NWJ);
+		if (NWJ == 0) wsp.assign(1, 0);
+		// U: the joint keys sorted stably by (i, j), equal keys merged
+		for (int q = 0; q < NUJ; q++) usi[q] = q;
+		std::stable_sort(usi.begin(), usi.end(), [&](int a, int b) { return UiJ[a] != UiJ[b] ? UiJ[a] < UiJ[b] : UjJ[a] < UjJ[b]; });
+		co->Ui.clear(); co->Uj.clear();
+		for (int q = 0; q < NUJ; q++)
+		{
+			if (q > 0 && UiJ[usi[q]] == UiJ[usi[q - 1]] && UjJ[usi[q]] == UjJ[usi[q - 1]]) continue;
+			if (q > 0) usp.push_back(q);
+			co->Ui.push_back(UiJ[usi[q]]); co->Uj.push_back(UjJ[usi[q]]);
+		}
+		usp.push_back(NUJ);
+		if (NUJ == 0) usp.assign(1, 0);
+		co->nWo = (int)co->photo.size(); co->nUo = (int)co->Ui.size();
+		co->origin = origin;
+		co->d_wsp = ar.alloc<int>(wsp.size()); co->d_wsi = ar.alloc<int>(NWJ); co->d_usp = ar.alloc<int>(usp.size()); co->d_usi = ar.alloc<int>(NUJ);
+		co->Wo = ar.alloc<double>((size_t)co->nWo * 18); co->Uo = ar.alloc<double>((size_t)co->nUo * 36);
+		h2d(ctx, co->d_wsp, wsp.data(), wsp.size() * sizeof(int)); h2d(ctx, co->d_wsi, wsi.data(), wsi.size() * sizeof(int));
+		h2d(ctx, co->d_usp, usp.data(), usp.size() * sizeof(int)); h2d(ctx, co->d_usi, usi.data(), usi.size() * sizeof(int));
+	}
 }
 
 // the frames of the maps at the state in d_x, the pose residuals r_a with their D_a and C_s,a
@@ -789,6 +872,34 @@ void gn_chi2(lsfm_context* ctx, const GnCall& c)
 {
 	hipLaunchKernelGGL(k_gn_map_chi2, dim3(c.N), dim3(GN_CHI2_LANES), 0, ctx->stream, c.d_gm, c.X.U, c.X.Ui, c.X.Uj, c.rp, c.d_gf,
 	                   c.d_x + (size_t)c.M * 6, c.X.feat, c.X.fptr, c.X.photo, c.X.W, c.X.V, c.d_chi2);
+}
+// the launches of one assembly at the state in d_x: F into Fsum (kind != 0: the robust weights first, G into d_G), the joint system
+// UJ / WJ / VJ and the right-hand sides ea / eb.  bracket_chi2: ev0 / ev1 of the context around the chi2 + weights kernels.
+void gn_assemble(lsfm_context* ctx, const GnCall& c, int kind, double cth, bool bracket_chi2)
+{
+	hipStream_t s = ctx->stream;
+	const DevBatch& X = c.X;
+	const int N = c.N, M = c.M, NFG = c.NFG, P = c.P, FI = c.FI;
+	const bool mono = c.mono;
+	dev_zero(ctx, c.Gacc, ((size_t)P * GN_GW + (size_t)N * GN_HW + 2) * sizeof(double));
+	gn_frames(ctx, c);
+	if (kind != 0)
+	{
+		if (bracket_chi2) LSFM_CHECK_HIP(hipEventRecord(ctx->ev0, s));
+		gn_chi2(ctx, c);
+		hipLaunchKernelGGL(k_gn_robust_weights, dim3(1), dim3(GN_WEIGHT_LANES), 0, s, N, kind, cth, c.d_dof, c.d_chi2, c.d_gm, c.d_w, c.d_G);
+		if (bracket_chi2) LSFM_CHECK_HIP(hipEventRecord(ctx->ev1, s));
+	}
+	if (X.NU) hipLaunchKernelGGL(k_gn_ublocks, grid_for(X.NU, 128), dim3(128), 0, s, X.NU, P, X.Ui, X.Uj, X.U, X.pose_map, c.d_gm, c.d_gp, c.Dp, c.Cp, c.rp, c.Gacc, c.UJ);
+	if (FI)
+	{
+		if (mono) hipLaunchKernelGGL((k_gn_features<2>), grid_for(FI, 256), dim3(256), 0, s, FI, P, X.feat_map, c.d_gm, c.d_gf, c.d_x + (size_t)M * 6, X.feat, X.fptr, X.photo, X.W, X.V, c.Dp, c.Cp, c.rp, c.d_wdst, c.WJ, c.Vinst, c.eFinst, c.Gacc, c.Hacc);
+		else hipLaunchKernelGGL((k_gn_features<1>), grid_for(FI, 256), dim3(256), 0, s, FI, P, X.feat_map, c.d_gm, c.d_gf, c.d_x + (size_t)M * 6, X.feat, X.fptr, X.photo, X.W, X.V, c.Dp, c.Cp, c.rp, c.d_wdst, c.WJ, c.Vinst, c.eFinst, c.Gacc, c.Hacc);
+	}
+	hipLaunchKernelGGL(k_gn_pose_post, grid_for(P, 128), dim3(128), 0, s, P, X.pose_map, c.d_gm, c.d_gp, c.Dp, c.Cp, c.rp, c.Gacc, c.UJ, c.ePinst, c.Hacc);
+	hipLaunchKernelGGL(k_gn_hubhub, grid_for(N, 128), dim3(128), 0, s, N, c.d_gm, c.Hacc, c.UJ, c.Fsum);
+	if (NFG) hipLaunchKernelGGL(k_gn_gather_feat, grid_for(NFG, 256), dim3(256), 0, s, NFG, c.d_fsp, c.d_fsi, c.Vinst, c.eFinst, c.VJ, c.eb);
+	hipLaunchKernelGGL(k_gn_gather_pose, grid_for(M, 128), dim3(128), 0, s, M, c.d_psp, c.d_psi, c.ePinst, c.Hacc, c.ea);
 }
 } // namespace
 
@@ -809,33 +920,14 @@ int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_ma
 	int n_asm = 0, n_solve = 0;
 	GnCall c;
 	gn_setup(ctx, maps, N, mono, x, c);
-	const int M = c.M, NFG = c.NFG, P = c.P, FI = c.FI;
+	const int M = c.M, NFG = c.NFG;
 	const size_t RS = c.RS;
-	const DevBatch& X = c.X;
 	const bool robust = kind != 0;
 
 	// F (robust: G) and the step's system at the state in d_x
 	auto assemble = [&]() -> double {
 		const double ta = wall();
-		dev_zero(ctx, c.Gacc, ((size_t)P * GN_GW + (size_t)N * GN_HW + 2) * sizeof(double));
-		gn_frames(ctx, c);
-		if (robust)
-		{
-			if (timing) LSFM_CHECK_HIP(hipEventRecord(ctx->ev0, s));
-			gn_chi2(ctx, c);
-			hipLaunchKernelGGL(k_gn_robust_weights, dim3(1), dim3(GN_WEIGHT_LANES), 0, s, N, kind, cth, c.d_dof, c.d_chi2, c.d_gm, c.d_w, c.d_G);
-			if (timing) LSFM_CHECK_HIP(hipEventRecord(ctx->ev1, s));
-		}
-		if (X.NU) hipLaunchKernelGGL(k_gn_ublocks, grid_for(X.NU, 128), dim3(128), 0, s, X.NU, P, X.Ui, X.Uj, X.U, X.pose_map, c.d_gm, c.d_gp, c.Dp, c.Cp, c.rp, c.Gacc, c.UJ);
-		if (FI)
-		{
-			if (mono) hipLaunchKernelGGL((k_gn_features<2>), grid_for(FI, 256), dim3(256), 0, s, FI, P, X.feat_map, c.d_gm, c.d_gf, c.d_x + (size_t)M * 6, X.feat, X.fptr, X.photo, X.W, X.V, c.Dp, c.Cp, c.rp, c.d_wdst, c.WJ, c.Vinst, c.eFinst, c.Gacc, c.Hacc);
-			else hipLaunchKernelGGL((k_gn_features<1>), grid_for(FI, 256), dim3(256), 0, s, FI, P, X.feat_map, c.d_gm, c.d_gf, c.d_x + (size_t)M * 6, X.feat, X.fptr, X.photo, X.W, X.V, c.Dp, c.Cp, c.rp, c.d_wdst, c.WJ, c.Vinst, c.eFinst, c.Gacc, c.Hacc);
-		}
-		hipLaunchKernelGGL(k_gn_pose_post, grid_for(P, 128), dim3(128), 0, s, P, X.pose_map, c.d_gm, c.d_gp, c.Dp, c.Cp, c.rp, c.Gacc, c.UJ, c.ePinst, c.Hacc);
-		hipLaunchKernelGGL(k_gn_hubhub, grid_for(N, 128), dim3(128), 0, s, N, c.d_gm, c.Hacc, c.UJ, c.Fsum);
-		if (NFG) hipLaunchKernelGGL(k_gn_gather_feat, grid_for(NFG, 256), dim3(256), 0, s, NFG, c.d_fsp, c.d_fsi, c.Vinst, c.eFinst, c.VJ, c.eb);
-		hipLaunchKernelGGL(k_gn_gather_pose, grid_for(M, 128), dim3(128), 0, s, M, c.d_psp, c.d_psi, c.ePinst, c.Hacc, c.ea);
+		gn_assemble(ctx, c, kind, cth, robust && timing);
 		double F = 0.0;
 		d2h(ctx, &F, robust ? c.d_G : c.Fsum, sizeof(double));
 		if (robust && timing)
@@ -929,6 +1021,86 @@ int map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const ls
 	gn_chi2(ctx, c);
 	d2h(ctx, chi2, c.d_chi2, (size_t)N * sizeof(double));
 	if (dof) std::copy(c.dof.begin(), c.dof.end(), dof);
+	return LSFM_OK;
+}
+
+// The joint system of the N local maps linearised at x, as a map like any other (C ABI: lsfm_gn_linearise).  One assembly at x with the
+// maps' weights, then every block of UJ / WJ summed once into its place (k_gn_coalesce_u / _w), then the download into arrays of the
+// library's own allocator (lsfm_map_release frees them).  x is read only.  The assembly sums with atomics: two calls agree to rounding,
+// not bit for bit; the structure of `out` depends on the labels alone.
+// times (may be null): [3] HIP-event ms of the assembly, k_gn_coalesce_w, k_gn_coalesce_u; counts (may be null): [4] NWJ, nW', NUJ, nU'.
+int gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, const double* weight, lsfm_map* out, double* obj,
+                 double* b, double* times, int* counts)
+{
+	hipStream_t s = ctx->stream;
+	// LSFM_GN_TIMING=1: wall clock of the call's parts on stderr, as lsfm_gn_polish
+	static const bool timing = getenv("LSFM_GN_TIMING") != nullptr;
+	auto wall = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+	const double tw0 = wall();
+	GnCall c;
+	GnCoalesce co;
+	gn_setup(ctx, maps, N, mono, x, c, weight, &co);
+	const int M = c.M, NFG = c.NFG;
+	if (timing) LSFM_CHECK_HIP(hipStreamSynchronize(s));
+	const double tw1 = wall();
+	if (times) LSFM_CHECK_HIP(hipEventRecord(ctx->ev0, s));
+	gn_assemble(ctx, c, 0, 1.0, false);
+	if (times) LSFM_CHECK_HIP(hipEventRecord(ctx->ev1, s));
+	if (co.nWo) hipLaunchKernelGGL(k_gn_coalesce_w, grid_for(co.nWo, 256), dim3(256), 0, s, co.nWo, co.d_wsp, co.d_wsi, c.WJ, co.Wo);
+	if (times) LSFM_CHECK_HIP(hipEventRecord(ctx->ev2, s));
+	if (co.nUo) hipLaunchKernelGGL(k_gn_coalesce_u, grid_for(co.nUo, 256), dim3(256), 0, s, co.nUo, co.d_usp, co.d_usi, c.UJ, co.Uo);
+	if (times) LSFM_CHECK_HIP(hipEventRecord(ctx->ev3, s));
+	if (timing) LSFM_CHECK_HIP(hipStreamSynchronize(s));
+	const double tw2 = wall();
+	lsfm_map g;
+	memset(&g, 0, sizeof g);
+	g.m = M; g.n = NFG; g.nU = co.nUo; g.nW = co.nWo;
+	g.Ref = x->Ref; g.FRef = x->FRef; g.ScaP = x->ScaP; g.Fix = x->Fix; g.Sign = x->Sign; g.FScaP = x->FScaP; g.FFix = x->FFix;
+	g.stno = host_alloc<int>(c.RS); g.stVal = host_alloc<double>(c.RS);
+	g.U = host_alloc<double>((size_t)g.nU * 36); g.Ui = host_alloc<int>(g.nU); g.Uj = host_alloc<int>(g.nU);
+	g.W = host_alloc<double>((size_t)g.nW * 18); g.photo = host_alloc<int>(g.nW); g.feature = host_alloc<int>(g.nW);
+	g.V = host_alloc<double>((size_t)NFG * 9); g.FBlock = host_alloc<int>(NFG);
+	g.pose_origin = host_alloc<int>(M);
+	if (!g.stno || !g.stVal || !g.U || !g.Ui || !g.Uj || !g.W || !g.photo || !g.feature || !g.V || !g.FBlock || !g.pose_origin)
+	{
+		lsfm_map_release(&g);
+		LSFM_FAIL(LSFM_ERR_OOM, "gn linearise: out of host memory for the map");
+	}
+	try
+	{
+		std::copy(x->stno, x->stno + c.RS, g.stno); std::copy(x->stVal, x->stVal + c.RS, g.stVal);
+		std::copy(co.Ui.begin(), co.Ui.end(), g.Ui); std::copy(co.Uj.begin(), co.Uj.end(), g.Uj);
+		std::copy(co.photo.begin(), co.photo.end(), g.photo); std::copy(co.feature.begin(), co.feature.end(), g.feature);
+		std::copy(co.FBlock.begin(), co.FBlock.end(), g.FBlock); std::copy(co.origin.begin(), co.origin.end(), g.pose_origin);
+		if (g.nU) d2h(ctx, g.U, co.Uo, (size_t)g.nU * 36 * sizeof(double));
+		if (g.nW) d2h(ctx, g.W, co.Wo, (size_t)g.nW * 18 * sizeof(double));
+		if (NFG) d2h(ctx, g.V, c.VJ, (size_t)NFG * 9 * sizeof(double));
+		if (obj) d2h(ctx, obj, c.Fsum, sizeof(double));
+		if (b)
+		{
+			d2h(ctx, b, c.ea, (size_t)M * 6 * sizeof(double));
+			if (NFG) d2h(ctx, b + (size_t)M * 6, c.eb, (size_t)NFG * 3 * sizeof(double));
+		}
+		LSFM_CHECK_HIP(hipStreamSynchronize(s));
+		if (times)
+		{
+			float ms[3] = { 0.0f, 0.0f, 0.0f };
+			LSFM_CHECK_HIP(hipEventElapsedTime(&ms[0], ctx->ev0, ctx->ev1));
+			LSFM_CHECK_HIP(hipEventElapsedTime(&ms[1], ctx->ev1, ctx->ev2));
+			LSFM_CHECK_HIP(hipEventElapsedTime(&ms[2], ctx->ev2, ctx->ev3));
+			for (int i = 0; i < 3; i++) times[i] = ms[i];
+		}
+	}
+	catch (...)
+	{
+		lsfm_map_release(&g);
+		throw;
+	}
+	if (counts) { counts[0] = c.NWJ; counts[1] = co.nWo; counts[2] = c.NUJ; counts[3] = co.nUo; }
+	if (timing)
+		fprintf(stderr, "lsfm_gn_linearise: %d maps, %d poses, %d features, W %d -> %d blocks, U %d -> %d blocks; structure + upload %.2f ms, assembly + coalescing "
+		                "%.2f ms, download %.2f ms, call %.2f ms\n", N, M, NFG, c.NWJ, co.nWo, c.NUJ, co.nUo, tw1 - tw0, tw2 - tw1, wall() - tw2, wall() - tw0);
+	*out = g;
 	return LSFM_OK;
 }
 

@@ -396,6 +396,8 @@ void fill_async(hipStream_t s, void* d, int byte, size_t bytes); // (a kernel of
 // ---- batches (lsfm_batch.hip) -------------------------------------------------------------------------------
 void batch_upload(lsfm_context* ctx, Arena& ar, const lsfm_map* maps, int N, bool mono, DevBatch& out);
 void batch_download_map(lsfm_context* ctx, const DevBatch& b, int k, bool mono, lsfm_map* out);
+// the allocator of every map the library hands out (lsfm_map_release frees with free())
+template <class T> inline T* host_alloc(size_t n) { return static_cast<T*>(malloc((n ? n : 1) * sizeof(T))); }
 struct CopyBatch;
 // uploads pose_off / feat_off, fills pose_map / feat_map (cb != null: the uploads join the caller's batch, which then calls batch_fill_maps)
 void batch_set_offsets(lsfm_context* ctx, Arena& ar, DevBatch& b, CopyBatch* cb = nullptr);
@@ -494,6 +496,10 @@ int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_ma
               int* halvings, double* chi2, double* weight);
 // per-map chi^2 of the map-joining objective at a global state (lsfm_gn.hip; C ABI: lsfm_map_chi2)
 int map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, double* chi2, int* dof);
+// the joint system of the local maps linearised at x as a map of its own, every block once (lsfm_gn.hip; C ABI: lsfm_gn_linearise).
+// times (may be null): [3] ms of the assembly, the W and the U coalescing launch; counts (may be null): [4] NWJ, nW', NUJ, nU'
+int gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, const double* weight, lsfm_map* out, double* obj,
+                 double* b, double* times, int* counts);
 // marginal covariances of a map's information matrix (lsfm_cov.hip; C ABI: lsfm_map_covariance).  times (may be null): [4] ms of the
 // Schur reduction + analysis, the factorisation, the selected inversion + pose gather, the feature part
 int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb,

@@ -1,8 +1,12 @@
 """lsfm_gn_polish on a named stand-in set, from the device's own tree result: the objective / gradient trace and the wall clock of the
 call's parts (LSFM_GN_TIMING=1: structure + upload, per assembly (with the chi2 + weights kernels' HIP-event time when robust), per
-solve).  usage: python tools/gn_bench.py <config> [steps] [maps] [--robust huber|cauchy --c <c>]
+solve).  usage: python tools/gn_bench.py <config> [steps] [maps] [--robust huber|cauchy --c <c>] [--linearise]
 -> one JSON object per call on stdout (profiles/r06_gn_polish_<config>.json).  --robust: lsfm_gn_polish_robust instead, and the same
-steps of the plain polish beside it (wall clock per step of each, the chi2 kernel's share of an assembly)."""
+steps of the plain polish beside it (wall clock per step of each, the chi2 kernel's share of an assembly).  --linearise: after the
+polish, lsfm_gn_linearise at the polished state (profiles/gn_linearise_<config>.json), one warm-up and the medians of 3 calls: HIP-event ms
+of the assembly and of the two coalescing launches, the block counts of the working form and of the map, the GB/s of k_gn_coalesce_w
+against (NWJ + nW') * 144 bytes, the call's wall ms with the library's own split (structure + upload, device, download), and the wall ms
+of lsfm_map_covariance on the result beside the same call on the tree's own map."""
 import json
 import os
 import re
@@ -22,6 +26,14 @@ if len(sys.argv) > 1 and sys.argv[1] != "--child":
         sys.exit(p.stdout + p.stderr)
     d = json.loads(line[0])
     d["library_timing"] = tim
+    lin = [l for l in p.stderr.splitlines() if l.startswith("lsfm_gn_linearise:")]
+    if lin:
+        # the library's own split of the calls after the warm-up: medians
+        pat = r"structure \+ upload ([0-9.]+) ms, assembly \+ coalescing ([0-9.]+) ms, download ([0-9.]+) ms, call ([0-9.]+) ms"
+        rows = sorted(tuple(float(v) for v in re.search(pat, l).groups()) for l in lin[1:])
+        up, dev, down, call = (sorted(r[i] for r in rows)[len(rows) // 2] for i in range(4))
+        d["linearise"]["library_wall_ms"] = {"structure_upload": up, "device": dev, "download": down, "call": call,
+                                             "upload_download_share": (up + down) / call}
     if "robust" in d and len(tim) >= 4:
         # per step = one solve + the assemblies of the line search; from the warm call of each kind
         def parse(t):
@@ -49,6 +61,7 @@ ap.add_argument("steps", nargs="?", type=int, default=3)
 ap.add_argument("maps", nargs="?", type=int, default=0)
 ap.add_argument("--robust", choices=["huber", "cauchy"])
 ap.add_argument("--c", type=float, default=1.0)
+ap.add_argument("--linearise", action="store_true")
 a = ap.parse_args(sys.argv[2:])
 cfg, steps, nmaps = a.config, a.steps, a.maps
 typ, maps = synth.make_config(cfg, nmaps or None)
@@ -75,7 +88,32 @@ if a.robust:
                       "note": "plain = lsfm_gn_polish, robust_run = lsfm_gn_polish_robust, same steps from the device's tree result; library_timing: "
                               "the library's own clocks, in call order plain, plain, robust, robust (the second of each warm)"}))
     sys.exit(0)
+lin = None
+if a.linearise:
+    med = lambda v: float(np.median(v))
+    Gp = dict(G, stVal=st)
+    rows, walls = [], []
+    for rep in range(4):
+        t0 = time.perf_counter()
+        H, F, _, tm, cnt = ctx.gn_linearise(d, mono, Gp, timed=True)
+        walls.append(1e3 * (time.perf_counter() - t0))
+        rows.append(tm)
+    ev = {k: med([r[k] for r in rows[1:]]) for k in rows[0]}
+    cov = {}
+    for name, mp in (("linearised", H), ("tree", G)):
+        t = []
+        for rep in range(4):
+            t0 = time.perf_counter()
+            crc = ctx.covariance_raw(mp, mono)[0]
+            t.append(1e3 * (time.perf_counter() - t0))
+        cov[name] = {"wall_ms": med(t[1:]), "rc": crc, "U_blocks": int(mp["nU"]), "W_blocks": int(mp["nW"])}
+    lin = {"events_ms": ev, "coalescing_over_assembly": (ev["coalesce_w_ms"] + ev["coalesce_u_ms"]) / ev["assembly_ms"], "blocks": cnt,
+           "coalesce_w_GBps": (cnt["NWJ"] + cnt["nW"]) * 144 / (ev["coalesce_w_ms"] * 1e6) if ev["coalesce_w_ms"] > 0 else None,
+           "python_call_wall_ms": med(walls[1:]), "objective": F, "map_covariance": cov,
+           "note": "at the polished state; medians of 3 calls after one warm-up; python_call_wall_ms includes building the lsfm_map views and copying "
+                   "the result into numpy arrays; library_wall_ms: the library's own clocks"}
 print(json.dumps({"config": cfg, "type": typ, "maps": len(maps), "poses": int(G["m"]), "features": int(G["n"]), "steps": steps, "tree_ms": stats["t_total_ms"], "tree_rc": rc,
+                  **({"linearise": lin} if lin else {}),
                   "gn_rc": rc2, "objective": obj.tolist(), "gradient_max": gn.tolist(), "halvings": hv.tolist(), "call_wall_ms": calls,
                   "max_state_change": float(np.max(np.abs(st - G["stVal"]))),
                   "note": "lsfm_gn_polish from the device's own tree result; call_wall_ms includes building the lsfm_map views in Python, the upload of the "
