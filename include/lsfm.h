@@ -297,6 +297,29 @@ int lsfm_map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, int mono
 int lsfm_map_covariance_columns_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* poses, int k, double* pose_cols, double* feat_cols,
                                       double* joint, int* steps, double* last_corr, double* times);
 
+/* ---- marginalising features out of a map (NO reference counterpart: the reference keeps every feature to the end) ----
+ * out = `map` with every feature f that has drop[f] != 0 (drop[n], one flag per feature in the map's order) marginalised out:
+ *     U' = U - sum_{f dropped} W_f V_f^-1 W_f^T
+ * exact for a Gaussian, and again a map: V stays block diagonal, the fill lands in U.  The sum is taken by the pieces a tree level
+ * reduces its camera system with (V^-1, the pattern of S, K9: fixed-point sums), over the dropped features alone; a kept feature's V
+ * is never inverted.  Mono: the rows and columns of the gauge scalars (zero in the map) stay exactly zero; no gauge is applied.
+ * The result is canonical and its structure depends on the labels and the flags alone, never on values: poses, their estimates, Ref,
+ * FRef, ScaP, Fix, Sign, FScaP, FFix and pose_origin are the input's; the kept features stay in their order with V, W, photo and their
+ * estimates bit for bit the input's (repeated (pose, feature) blocks stay as they are), feature[] and FBlock[] renumbered; U' has
+ * exactly one block per pose pair (Ui <= Uj), sorted by (Ui, Uj), the diagonal block first and full -- the pairs of U's pattern, the
+ * pairs that observe a common dropped feature and every diagonal; a block whose value happens to be zero stays.
+ * Dropping nothing gives the canonical form of the same matrix; dropping everything gives n = 0, nW = 0: the pose graph.
+ * Entries of U with the same coordinates are summed by atomics: two calls agree to rounding where the input has such duplicates and
+ * bit for bit where it has none (the sums over the features are in fixed point and do not depend on their order).
+ * Returns LSFM_OK; LSFM_ERR_NOT_SPD when the V block of a dropped feature is not positive definite (out is not touched);
+ * LSFM_ERR_ARG for drop == NULL and for what lsfm_map_covariance refuses (W not sorted by feature, a feature without a W block, an
+ * index out of range).  out: library-allocated (lsfm_map_release).
+ * Lifetime: works in the context's arenas like lsfm_map_covariance -- a tree's result must be downloaded first. */
+int lsfm_map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned char* drop, lsfm_map* out);
+/* measurement entry: the same, and times[3] (may be NULL) = HIP-event ms of flags + partition of W + V^-1 + pattern, of K9's values,
+ * of the emission of U' with the download */
+int lsfm_map_marginalise_timed(lsfm_context* ctx, const lsfm_map* map, const unsigned char* drop, lsfm_map* out, double* times);
+
 /* replaces pba_inverseV (Imp.h:213, Imp.cpp:3022-3042): V^-1 of the n 3x3 feature blocks, IN PLACE like the reference's (which
  * inverts V in place and restores it afterwards, Imp.cpp:2210-2212, 2365): the upper triangle of the computed inverse, mirrored.
  * m is unused, as in the reference. */
@@ -385,6 +408,22 @@ int lsfm_tree_export_dev(lsfm_context* ctx, lsfm_tree* tree, void* dst, size_t c
 #define LSFM_PACK_HEADER_BYTES 256
 size_t lsfm_packed_size(const void* host_header256);
 int lsfm_tree_upload_dev(lsfm_context* ctx, const void* const* packed, int N, int mono, lsfm_tree** out);
+/* A REDUCED pack of a finished tree's final map: every feature whose label is not in keep_ids[0..nkeep) marginalised out
+ * (lsfm_map_marginalise has the arithmetic and the canonical form), in the format of lsfm_tree_export_dev -- lsfm_packed_size and
+ * lsfm_tree_upload_dev take it unchanged.  A node handed on this way no longer carries the features that nothing above it will
+ * meet again.  keep_ids: host array, any order, may repeat; ids the map does not hold are ignored; nkeep = 0 (keep_ids may then be
+ * NULL) drops every feature.  Device to device: the keep list goes up, the counts come back (one synchronisation for the features
+ * and W blocks, one for the pattern of U'), nothing else crosses.  Works in the arenas the result does not occupy and in the scratch
+ * arena: the result stays intact -- an lsfm_tree_export_dev or lsfm_tree_download afterwards still gives the full map.
+ *   lsfm_tree_export_reduced_size  *bytes = what lsfm_tree_export_reduced_dev will write for the same keep list
+ *   lsfm_tree_export_reduced_dev   dst: device memory of >= cap bytes; cap too small: LSFM_ERR_ARG, lsfm_last_error names the size
+ * LSFM_ERR_ARG also for a tree that has not been run or whose result was overwritten; LSFM_ERR_NOT_SPD as lsfm_map_marginalise
+ * (dst then holds no pack). */
+int lsfm_tree_export_reduced_size(lsfm_context* ctx, lsfm_tree* tree, const int* keep_ids, int nkeep, size_t* bytes);
+int lsfm_tree_export_reduced_dev(lsfm_context* ctx, lsfm_tree* tree, const int* keep_ids, int nkeep, void* dst, size_t cap);
+/* measurement entry: the same, and times[5] (may be NULL) = HIP-event ms of flags + scans + the pattern of U' (with its two read-backs),
+ * of the partition pass over W alone, of the per-feature gather + V^-1, of K9's values, of the emission of U' */
+int lsfm_tree_export_reduced_dev_timed(lsfm_context* ctx, lsfm_tree* tree, const int* keep_ids, int nkeep, void* dst, size_t cap, double* times);
 /* new VALUES for the resident inputs of a tree made by lsfm_tree_upload_dev: N packed maps with the same sizes as the ones
  * it was built from -- the next step of a scheduler that joins the same sub-tree roots again.  Keeps the tree's
  * allocations; its plans (lsfm_tree_set_plans) are kept when the labels and index arrays are the same too (a digest of

@@ -131,6 +131,11 @@ def lib():
         L.lsfm_map_covariance_columns_timed.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, dp, ip, dp, dp]
         L.lsfm_save_cov_columns.argtypes = [C.c_char_p, ip, C.c_int, ip, C.c_int, dp]
         L.lsfm_read_cov_columns.argtypes = [C.c_char_p, ip, ip, dp, C.c_int, ip]
+        L.lsfm_map_marginalise.argtypes = [vp, P(LsfmMap), P(C.c_ubyte), P(LsfmMap)]
+        L.lsfm_map_marginalise_timed.argtypes = [vp, P(LsfmMap), P(C.c_ubyte), P(LsfmMap), dp]
+        L.lsfm_tree_export_reduced_size.argtypes = [vp, vp, ip, C.c_int, P(C.c_size_t)]
+        L.lsfm_tree_export_reduced_dev.argtypes = [vp, vp, ip, C.c_int, vp, C.c_size_t]
+        L.lsfm_tree_export_reduced_dev_timed.argtypes = [vp, vp, ip, C.c_int, vp, C.c_size_t, dp]
         L.lsfm_spmv_bench.argtypes = [vp, C.c_int, ip, ip, dp, dp, dp, C.c_int, dp, dp]
         L.lsfm_wstream_bench.argtypes = [vp, C.c_longlong, C.c_int, C.c_int, dp]
         L.lsfm_selftest_prims.argtypes = [vp, C.c_int, C.c_uint]
@@ -148,7 +153,9 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
            "lsfm_map_covariance", "lsfm_map_covariance_timed",
            "lsfm_save_covariances", "lsfm_read_covariances",
-           "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns"]
+           "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns",
+           "lsfm_map_marginalise", "lsfm_map_marginalise_timed", "lsfm_tree_export_reduced_size", "lsfm_tree_export_reduced_dev",
+           "lsfm_tree_export_reduced_dev_timed"]
 
 
 def _c(a, dtype):
@@ -388,6 +395,26 @@ class Context:
         self._check(lib().lsfm_tree_upload_dev(self._h, arr, len(dev_ptrs), int(mono), C.byref(t)), "lsfm_tree_upload_dev")
         return t
 
+    def tree_export_reduced_size(self, tree, keep_ids):
+        """Bytes of the reduced pack of a finished tree's final map: every feature whose label is not in keep_ids marginalised out."""
+        ids = _c(keep_ids, np.int32)
+        n = C.c_size_t(0)
+        self._check(lib().lsfm_tree_export_reduced_size(self._h, tree, _ptr(ids, C.c_int) if len(ids) else None, len(ids), C.byref(n)),
+                    "lsfm_tree_export_reduced_size")
+        return int(n.value)
+
+    def tree_export_reduced_dev(self, tree, keep_ids, dev_ptr, cap, times=False):
+        """Packs the final map of a finished tree, reduced to the features in keep_ids (any order; unknown ids are ignored), into
+        caller-owned device memory: the format of tree_export_dev, taken by tree_upload_dev unchanged.  The result stays intact.
+        times: returns {"structure_ms", "partition_ms", "vinv_ms", "values_ms", "emit_ms"} by HIP events."""
+        ids = _c(keep_ids, np.int32)
+        t = np.zeros(5)
+        self._check(lib().lsfm_tree_export_reduced_dev_timed(self._h, tree, _ptr(ids, C.c_int) if len(ids) else None, len(ids),
+                                                             C.c_void_p(int(dev_ptr)), int(cap), _ptr(t, C.c_double) if times else None),
+                    "lsfm_tree_export_reduced_dev")
+        if times:
+            return dict(zip(("structure_ms", "partition_ms", "vinv_ms", "values_ms", "emit_ms"), t.tolist()))
+
     # ---- feature-sharded joins (the top of the tree over several GPUs) -----------------------------------
     def tree_export_slice_sizes(self, tree, nslices):
         sizes = (C.c_size_t * nslices)()
@@ -576,6 +603,24 @@ class Context:
         if rc > 0 and steps == 0:
             raise LsfmError(f"lsfm_map_covariance_columns: {rc} pivot(s) floored -- the information matrix is too close to singular")
         return {"pose": pose, "feature": feat, "joint": jt, "steps": steps, "last_corr": corr, "converged": rc == 0}
+
+    def marginalise(self, d, drop, times=False):
+        """lsfm_map_marginalise: the map dict d with every feature f that has drop[f] != 0 marginalised out (U' = U - sum W_f V_f^-1
+        W_f^T over the dropped features), in canonical form: kept features in their order with V / W / photo unchanged, one U block
+        per pose pair sorted by (Ui, Uj).  No reference counterpart.  Returns a map dict of the form tree_download returns; times:
+        also {"structure_ms", "values_ms", "emit_ms"} by HIP events."""
+        h = HostMap(d)
+        fl = np.ascontiguousarray(np.asarray(drop).astype(bool), dtype=np.uint8).reshape(-1)
+        if len(fl) != h.c.n:
+            raise LsfmError(f"marginalise: {len(fl)} flags for {h.c.n} features")
+        out = LsfmMap()
+        t = np.zeros(3)
+        self._check(lib().lsfm_map_marginalise_timed(self._h, C.byref(h.c), _ptr(fl, C.c_ubyte), C.byref(out), _ptr(t, C.c_double) if times else None),
+                    "lsfm_map_marginalise")
+        g = map_to_dict(out)
+        if times:
+            return g, dict(zip(("structure_ms", "values_ms", "emit_ms"), t.tolist()))
+        return g
 
     def spmv_bench(self, rowptr, colidx, val, x, reps=20):
         rowptr = _c(rowptr, np.int32); colidx = _c(colidx, np.int32); val = _c(val, np.float64); x = _c(x, np.float64)

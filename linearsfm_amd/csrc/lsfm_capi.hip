@@ -1,5 +1,6 @@
 // C ABI (include/lsfm.h) and the tree scheduler that replaces lmj_PF3D_Divide_Conquer{Stereo,Mono}
 // (Imp.cpp:1926-2063 / 6511-6630): every level of the reference's binary join tree runs as ONE batch.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -7,6 +8,7 @@
 
 #include "lsfm_internal.hpp"
 #include "lsfm_join.hpp"
+#include "lsfm_marg.hpp"
 #include "lsfm_solve.hpp"
 
 using namespace lsfm;
@@ -652,6 +654,92 @@ int lsfm_tree_export_slice_dev(lsfm_context* ctx, lsfm_tree* t, int nslices, int
 	});
 }
 
+// The reduced pack of a finished tree's final map (include/lsfm.h; lsfm_marg.hip has the reduction): dst == null: the size alone.
+static void tree_export_reduced(lsfm_context* ctx, lsfm_tree* t, const int* keep_ids, int nkeep, void* dst, size_t cap, size_t* bytes, double* times = nullptr)
+{
+	if (!t->done || t->level.B != 1) LSFM_FAIL(LSFM_ERR_ARG, "tree has not been run");
+	if (t->generation != ctx->generation) LSFM_FAIL(LSFM_ERR_ARG, "the result of this tree was overwritten by a later call on the same context");
+	const DevBatch& b = t->level;
+	if (b.W_alias) LSFM_FAIL(LSFM_ERR_INTERNAL, "cannot pack a batch whose W blocks are aliased");
+	// work space: an arena the result does not live in, and the scratch arena above what is there
+	struct Scratch { Arena& a; size_t mk; ~Scratch() { a.release(mk); } } hold{ ctx->scratch, ctx->scratch.mark() };
+	Arena& ar = ctx->arena[t->slot < 0 ? 0 : (t->slot + 1) % 3];
+	ar.reset();
+	hipStream_t s = ctx->stream;
+	std::vector<int> keep(keep_ids, keep_ids + nkeep);
+	std::sort(keep.begin(), keep.end());
+	int* d_keep = ar.alloc<int>((size_t)nkeep + 1);
+	h2d(ctx, d_keep, keep.data(), (size_t)nkeep * sizeof(int));
+	hipEvent_t ev[6]; // start | structure | partition pass | gather + V^-1 | K9 values | emitted
+	if (times) { for (int k = 0; k < 6; k++) ev[k] = ctx->pool_event(); LSFM_CHECK_HIP(hipEventRecord(ev[0], s)); }
+	int* drop = ar.alloc<int>((size_t)b.NF + 2);
+	marg_flags_from_keep(ctx, b.NF, b.feat_id, d_keep, nkeep, drop);
+	MargView in; // (a single map: its indices are local already)
+	in.M = b.M; in.NF = b.NF; in.NU = b.NU; in.NW = b.NW;
+	in.U = b.U; in.Ui = b.Ui; in.Uj = b.Uj; in.W = b.W; in.photo = b.photo; in.feature = b.feature; in.fptr = b.fptr; in.V = b.V;
+	in.feat = b.feat; in.feat_id = b.feat_id;
+	MargWork w;
+	marg_structure(ctx, ar, in, drop, -1, -1, w);
+	PackHeader h;
+	memset(&h, 0, sizeof h);
+	h.magic = LSFM_PACK_MAGIC; h.version = 1; h.mono = t->mono;
+	h.m = b.M; h.n = w.nkeep; h.nU = w.sy.nnzb; h.nW = w.nWkeep;
+	h.Ref = b.Ref[0]; h.FRef = b.FRef[0]; h.ScaP = b.ScaP[0]; h.Fix = b.Fix[0]; h.Sign = b.Sign[0]; h.FScaP = b.FScaP[0]; h.FFix = b.FFix[0];
+	const size_t total = pack_layout(h);
+	if (bytes) *bytes = total;
+	if (!dst) return;
+	if (total > cap) LSFM_FAIL(LSFM_ERR_ARG, "export buffer too small: " + std::to_string(total) + " bytes needed");
+	char* d = static_cast<char*>(dst);
+	h2d(ctx, d, &h, sizeof h);
+	auto cp = [&](int slot, const void* src, size_t n) {
+		if (n) LSFM_CHECK_HIP(hipMemcpyAsync(d + h.off[slot], src, n, hipMemcpyDeviceToDevice, s));
+	};
+	cp(0, b.pose, (size_t)h.m * 48); cp(5, b.pose_id, (size_t)h.m * 4); cp(6, b.pose_origin, (size_t)h.m * 4);
+	MargKept kept;
+	kept.feat = reinterpret_cast<double*>(d + h.off[1]); kept.W = reinterpret_cast<double*>(d + h.off[3]); kept.V = reinterpret_cast<double*>(d + h.off[4]);
+	kept.feat_id = reinterpret_cast<int*>(d + h.off[7]); kept.photo = reinterpret_cast<int*>(d + h.off[10]); kept.fptr = reinterpret_cast<int*>(d + h.off[11]);
+	int* d_err = ar.alloc<int>(1);
+	dev_zero(ctx, d_err, sizeof(int));
+	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
+	marg_values(ctx, ar, w, kept, reinterpret_cast<double*>(d + h.off[2]), reinterpret_cast<int*>(d + h.off[8]), reinterpret_cast<int*>(d + h.off[9]), d_err,
+	            times ? ev + 2 : nullptr);
+	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[5], s));
+	int err = 0;
+	d2h(ctx, &err, d_err, sizeof(int)); // (synchronises: the caller hands dst to another library / stream next)
+	if (times)
+		for (int k = 0; k < 5; k++)
+		{
+			float ms = 0.0f;
+			LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+			times[k] = ms;
+		}
+	if (err) LSFM_FAIL(LSFM_ERR_NOT_SPD, "the V block of a feature to be marginalised out is not positive definite");
+}
+
+int lsfm_tree_export_reduced_size(lsfm_context* ctx, lsfm_tree* t, const int* keep_ids, int nkeep, size_t* bytes)
+{
+	if (!t || !bytes || nkeep < 0 || (nkeep > 0 && !keep_ids)) return LSFM_ERR_ARG;
+	*bytes = 0;
+	return guarded(ctx, [&]() {
+		tree_export_reduced(ctx, t, keep_ids, nkeep, nullptr, 0, bytes);
+		return LSFM_OK;
+	});
+}
+
+int lsfm_tree_export_reduced_dev_timed(lsfm_context* ctx, lsfm_tree* t, const int* keep_ids, int nkeep, void* dst, size_t cap, double* times)
+{
+	if (!t || !dst || nkeep < 0 || (nkeep > 0 && !keep_ids)) return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() {
+		tree_export_reduced(ctx, t, keep_ids, nkeep, dst, cap, nullptr, times);
+		return LSFM_OK;
+	});
+}
+
+int lsfm_tree_export_reduced_dev(lsfm_context* ctx, lsfm_tree* t, const int* keep_ids, int nkeep, void* dst, size_t cap)
+{
+	return lsfm_tree_export_reduced_dev_timed(ctx, t, keep_ids, nkeep, dst, cap, nullptr);
+}
+
 int lsfm_tree_set_stop_level(lsfm_tree* t, int levels)
 {
 	if (!t || levels < 0) return LSFM_ERR_ARG;
@@ -901,6 +989,17 @@ int lsfm_map_covariance_timed(lsfm_context* ctx, const lsfm_map* map, int mono, 
 int lsfm_map_covariance(lsfm_context* ctx, const lsfm_map* map, int mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb)
 {
 	return lsfm_map_covariance_timed(ctx, map, mono, pose_cov, feat_cov, pair_cov, cap_blocks, nnzb, nullptr);
+}
+
+int lsfm_map_marginalise_timed(lsfm_context* ctx, const lsfm_map* map, const unsigned char* drop, lsfm_map* out, double* times)
+{
+	if (!map || !drop || !out) return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() { return map_marginalise(ctx, map, drop, out, times); });
+}
+
+int lsfm_map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned char* drop, lsfm_map* out)
+{
+	return lsfm_map_marginalise_timed(ctx, map, drop, out, nullptr);
 }
 
 int lsfm_map_covariance_columns_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* poses, int k, double* pose_cols, double* feat_cols,

@@ -16,13 +16,17 @@
 // -chi2 <file> (per local map, in input order, "index dof chi2 weight" at the final state: lsfm_map_chi2; no reference counterpart),
 // -relin 1 (the final map's information matrix -- U / W / V and their index arrays -- is replaced by the local maps linearised at the final
 // state, after -gn if given and with the polish's weights under -robust: lsfm_gn_linearise; -info, -cov, -covf and -covcols then describe
-// the estimate the other files hold; no reference counterpart).
+// the estimate the other files hold; no reference counterpart),
+// -keepf <file> (whitespace-separated feature ids, unknown ones ignored: after -gn / -relin and before any file is written the final map is
+// replaced by its reduction to these features -- every other feature marginalised out, lsfm_map_marginalise; -st, -p, -f, -full, -fullbin,
+// -info, -cov, -covf and -covcols describe the reduced map, -chi2 is evaluated on the full state first; no reference counterpart).
 #include <cmath>
 #include <chrono>
 #include <sys/stat.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -44,15 +48,16 @@ static void print_help()
 	printf("-robust huber|cauchy <c>	With -gn: Down-Weight Inconsistent Local Maps (Threshold c On chi2 / dof)\n");
 	printf("-chi2 <file>		Save chi2 Of Every Local Map: index dof chi2 weight\n");
 	printf("-relin 1		Information Matrix (-info, -cov, -covf, -covcols) Of The Local Maps Linearised At The Final State\n");
+	printf("-keepf <file>		Keep Only The Features Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
 	printf("\n");
 }
 
 int main(int argc, char** argv)
 {
-	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes;
+	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf;
 	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0, relin = 0;
 	double robust_c = 0.0;
-	bool has_path = false, has_num = false;
+	bool has_path = false, has_num = false, has_keepf = false;
 	double tol = 0;
 	for (int i = 1; i < argc; i++)
 	{
@@ -91,6 +96,7 @@ int main(int argc, char** argv)
 		else if (name == "relin") relin = atoi(next());
 		else if (name == "covcols") covcols = next();
 		else if (name == "covposes") covposes = next();
+		else if (name == "keepf") { keepf = next(); has_keepf = true; }
 		else if (name == "robust")
 		{
 			const std::string k = next(), v = next();
@@ -116,6 +122,19 @@ int main(int argc, char** argv)
 		if (end == covposes.c_str() + p || (*end && *end != ',') || (*end == ',' && !end[1])) { fprintf(stderr, "LinearSFM: -covposes: '%s' is not a list of pose ids\n", covposes.c_str()); return 1; }
 		covids.push_back((int)v);
 		p = (size_t)(end - covposes.c_str()) + (*end ? 1 : 0);
+	}
+	// -keepf: the ids to keep, sorted; an unreadable file ends the run before anything is computed or written
+	std::vector<int> keepids;
+	if (has_keepf)
+	{
+		FILE* f = fopen(keepf.c_str(), "r");
+		if (!f) { fprintf(stderr, "LinearSFM: -keepf: cannot read %s\n", keepf.c_str()); return 1; }
+		int v = 0, got = 0;
+		while ((got = fscanf(f, "%d", &v)) == 1) keepids.push_back(v);
+		const bool junk = got != EOF;
+		fclose(f);
+		if (junk) { fprintf(stderr, "LinearSFM: -keepf: %s is not a list of feature ids\n", keepf.c_str()); return 1; }
+		std::sort(keepids.begin(), keepids.end());
 	}
 	if (robust && gn <= 0) { fprintf(stderr, "LinearSFM: -robust applies to -gn <steps>: give -gn too\n"); return 1; }
 
@@ -277,6 +296,27 @@ int main(int argc, char** argv)
 		lsfm_map_release(&out);
 		out = H;
 	}
+	std::vector<int> chi2dof; // -keepf with -chi2: filled before the reduction
+	if (has_keepf)
+	{
+		// -chi2 needs the full state: evaluated now, its file is still written last
+		if (!chi2f.empty() && chi2v.empty())
+		{
+			chi2v.resize(num); weightv.assign(num, 1.0); chi2dof.resize(num);
+			if (lsfm_map_chi2(ctx, maps.data(), num, type, &out, chi2v.data(), chi2dof.data()) < 0) { fprintf(stderr, "LinearSFM: chi2: %s\n", lsfm_last_error(ctx)); return 3; }
+		}
+		// the final map reduced to the features of -keepf: every other one marginalised out (lsfm_map_marginalise)
+		std::vector<unsigned char> drop(out.n > 0 ? out.n : 1);
+		for (int f = 0; f < out.n; f++) drop[f] = std::binary_search(keepids.begin(), keepids.end(), out.stno[6 * out.m + 3 * f]) ? 0 : 1;
+		lsfm_map R;
+		if (lsfm_map_marginalise(ctx, &out, drop.data(), &R) != LSFM_OK)
+		{
+			fprintf(stderr, "LinearSFM: keepf: %s\n", lsfm_last_error(ctx));
+			return 3;
+		}
+		lsfm_map_release(&out);
+		out = R;
+	}
 	if (want_stats)
 		fprintf(stderr, "lsfm: total %.3f ms (transform %.3f, join %.3f [schur %.3f, pcg %.3f, backsub %.3f]), pcg its %ld, max rel resid %.2e, not converged %d, attempts %d\n",
 		        stats.t_total_ms, stats.t_transform_ms, stats.t_join_ms, stats.t_schur_ms, stats.t_pcg_ms, stats.t_backsub_ms, stats.pcg_iterations,
@@ -348,7 +388,8 @@ int main(int argc, char** argv)
 	{
 		// per-map chi2 of the state the files above hold (-robust: the polish's own, with its weights; otherwise weight 1)
 		std::vector<int> dof(num);
-		if (chi2v.empty())
+		if (!chi2dof.empty()) dof = chi2dof;
+		else if (chi2v.empty())
 		{
 			chi2v.resize(num);
 			weightv.assign(num, 1.0);

@@ -1,0 +1,45 @@
+// Marginalising features out of a map on the device (lsfm_marg.hip): what the host entry (lsfm_map_marginalise) and the reduced pack of
+// a resident result (lsfm_tree_export_reduced_*, lsfm_capi.hip) share.
+#pragma once
+#include "lsfm_internal.hpp"
+#include "lsfm_solve.hpp"
+
+namespace lsfm {
+
+// a map resident on the device, indices local to it (a SolveIO-style view plus feature[] of every W block)
+struct MargView {
+	int M = 0, NF = 0, NU = 0, NW = 0;
+	const double* U = nullptr; const int *Ui = nullptr, *Uj = nullptr;
+	const double* W = nullptr; const int *photo = nullptr, *feature = nullptr, *fptr = nullptr;
+	const double* V = nullptr;
+	const double* feat = nullptr; // [NF * 3] estimates and [NF] labels of the features (null: the kept features are not gathered)
+	const int* feat_id = nullptr;
+};
+// where the kept features go (device; all null: the caller compacts them itself and only the dropped blocks move)
+struct MargKept {
+	double *W = nullptr, *V = nullptr, *feat = nullptr;
+	int *photo = nullptr, *feature = nullptr, *fptr = nullptr, *feat_id = nullptr;
+};
+// the state of one reduction between its two halves; everything lives in `ar` and the scratch arena
+struct MargWork {
+	MargView in;
+	const int* drop = nullptr;     // [NF + 1] 1: marginalised out (entry NF: 0)
+	int *kpos = nullptr, *kwpos = nullptr; // [NF + 1] exclusive scans of the kept flags / the kept run lengths
+	int nkeep = 0, nWkeep = 0, ndrop = 0, nWdrop = 0;
+	int *dfp = nullptr, *dph = nullptr; // run pointers [ndrop + 1] and poses [nWdrop] of the dropped features, made contiguous
+	SolveIO io;                    // K9's input: U and the dropped features
+	SchurSystem sy;                // sy.nnzb / sy.upper_keys: the pattern of U'
+};
+// drop[f] = 1 unless feat_id[f] is in the sorted list keep[0..nkeep)
+void marg_flags_from_keep(lsfm_context* ctx, int NF, const int* feat_id, const int* keep_sorted, int nkeep, int* drop);
+// first half: positions from the flags, the dropped runs' index arrays, the pattern of U'.  nkeep / nWkeep < 0: counted on the device
+// and read back (one synchronisation); the pattern build synchronises once more.
+void marg_structure(lsfm_context* ctx, Arena& ar, const MargView& in, const int* drop, int nkeep, int nWkeep, MargWork& w);
+// second half: the one partition pass over W, the per-feature gather, V^-1 of the dropped features, K9, and U' / Ui / Uj (device,
+// sy.nnzb blocks).  d_err (device int, zeroed by the caller): != 0 afterwards = a dropped V block was not positive definite.
+// ev (may be null): [3] events recorded behind the partition pass, behind the gather + V^-1 and behind K9's values.
+void marg_values(lsfm_context* ctx, Arena& ar, MargWork& w, const MargKept& kept, double* oU, int* oUi, int* oUj, int* d_err, hipEvent_t* ev);
+// lsfm_map_marginalise
+int map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned char* drop, lsfm_map* out, double* times);
+
+} // namespace lsfm
