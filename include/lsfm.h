@@ -537,6 +537,35 @@ int lsfm_wstream_bench(lsfm_context* ctx, long long nblocks, int mode, int reps,
  * mismatch in lsfm_last_error. */
 int lsfm_selftest_prims(lsfm_context* ctx, int cases, unsigned seed);
 
+/* Test entry: the device Cholesky factorisation of a camera system (the preconditioner of every level solve, the factor the
+ * covariance calls invert; it stands for cholmod_analyze / factorize / solve, Imp.cpp:2380-2449 / 7043-7121) on a matrix of the
+ * caller's, and UNREFINED applications of it.  Inside a level solve the refinement tests the true residual and goes on until it
+ * passes, so a factor or a triangular sweep that is slightly wrong only costs steps there; here nothing corrects it.  The call runs
+ * the solver's own host steps and nothing else: ordering + symbolic analysis, scatter with the power-of-four scaling, numeric
+ * factorisation, one application z = (L L^T)^-1 r per right-hand side in the order given; no product with S, no refinement.
+ *   m, rowptr[m + 1], colidx, val[36 nnzb]   symmetric positive definite matrix, upper block CSR, every block row starting with its
+ *                   diagonal block, stored full (as lsfm_spmv_bench; LSFM_ERR_ARG otherwise)
+ *   origin[m]       local map that brought each pose, as lsfm_symbolic_analyse (NULL: its position)
+ *   fixed[6 m]      != 0: a scalar held at zero -- its row and column leave the system, z is 0 there (NULL: none)
+ *   pose_seg[m], nseg   independent system each pose belongs to, 0 .. nseg - 1
+ *   r[nrhs][6 m]    right-hand sides
+ *   mode            bit 0: the first right-hand side takes the level solve's route -- its forward substitution rides on the
+ *                   factorisation, the application starts behind it; bit 1: the factor is rounded to fp32 before the applications
+ *                   (lsfm_set_precision(ctx, 1)'s sweeps)
+ * Outputs: z[nrhs][6 m]; dot[nrhs][nseg] = r . z per system; the whole factor in the new numbering (each optional) -- perm[m]
+ * (new -> old), colptr[m + 1], rowidx[cap_blocks] (block CSC, rows ascending, diagonal first), L[36 cap_blocks] (row-major 6x6
+ * blocks of the factor of the SCALED matrix D P S P^T D), Dinv[36 m] (inverses of the diagonal blocks of L), dscale[6 m] (the
+ * diagonal of D, powers of two) --; info[LSFM_SELFTEST_CHOL_INFO] = { blocks of L, leaf tasks, columns in leaf tasks, most deferred
+ * update pairs of a leaf column, supernode groups, group levels, group levels launched as the fused panel kernel, group levels
+ * launched as panel + rank-update kernels, most rows below a group, the factorisation's error word (1 + block column of a
+ * non-positive pivot), pivots held at their lower bound, 0 ... }.
+ * Returns LSFM_ERR_ARG when cap_blocks is too small (info[0] still holds the size needed), LSFM_ERR_NOT_SPD for a non-positive
+ * pivot (info is complete, the other outputs are what the device left). */
+#define LSFM_SELFTEST_CHOL_INFO 16
+int lsfm_selftest_chol(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin, const unsigned char* fixed,
+                       const int* pose_seg, int nseg, const double* r, int nrhs, int mode, double* z, double* dot, int* perm, int* colptr, int* rowidx,
+                       double* L, double* Dinv, double* dscale, int cap_blocks, int* info);
+
 #ifdef __cplusplus
 }
 #endif

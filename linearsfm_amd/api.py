@@ -139,6 +139,8 @@ def lib():
         L.lsfm_spmv_bench.argtypes = [vp, C.c_int, ip, ip, dp, dp, dp, C.c_int, dp, dp]
         L.lsfm_wstream_bench.argtypes = [vp, C.c_longlong, C.c_int, C.c_int, dp]
         L.lsfm_selftest_prims.argtypes = [vp, C.c_int, C.c_uint]
+        L.lsfm_selftest_chol.argtypes = [vp, C.c_int, ip, ip, dp, ip, P(C.c_ubyte), ip, C.c_int, dp, C.c_int, C.c_int, dp, dp, ip, ip, ip, dp, dp, dp,
+                                         C.c_int, ip]
         _LIB = L
     return _LIB
 
@@ -150,7 +152,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_tree_upload_dev", "lsfm_tree_reload_dev", "lsfm_tree_set_comm", "lsfm_tree_set_comm_blocks", "lsfm_tree_export_slice_sizes", "lsfm_tree_export_slice_dev",
            "lsfm_tree_free", "lsfm_divide_conquer", "lsfm_read_localmap", "lsfm_read_localmaps", "lsfm_write_localmap", "lsfm_write_mapset", "lsfm_mapset_info", "lsfm_mapset_stamp", "lsfm_read_mapset", "lsfm_save_state_bin", "lsfm_save_state", "lsfm_save_poses", "lsfm_gn_polish",
            "lsfm_gn_polish_robust", "lsfm_map_chi2", "lsfm_gn_linearise", "lsfm_gn_linearise_timed",
-           "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
+           "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_selftest_chol", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
            "lsfm_map_covariance", "lsfm_map_covariance_timed",
            "lsfm_save_covariances", "lsfm_read_covariances",
            "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns",
@@ -649,6 +651,44 @@ def _selftest_prims(self, cases=64, seed=1):
 
 
 Context.selftest_prims = _selftest_prims
+
+SELFTEST_CHOL_INFO = ("blocks", "leaf_tasks", "leaf_columns", "task0_outer", "groups", "group_levels", "fused_levels", "split_levels", "max_rows_below",
+                      "d_err", "floored")
+
+
+def _selftest_chol(self, rowptr, colidx, val, r, origin=None, fixed=None, pose_seg=None, nseg=1, mode=0):
+    """lsfm_selftest_chol: the device Cholesky factor of the symmetric positive definite block matrix (rowptr, colidx, val: upper
+    block CSR, diagonal block first and full) and one unrefined application of it per right-hand side r[nrhs, 6 m], in order.
+    mode bit 0: the first right-hand side's forward substitution rides on the factorisation; bit 1: fp32 sweeps.  Returns dict(z
+    [nrhs, 6 m], dot [nrhs, nseg], perm, colptr, rowidx, L [blocks, 6, 6], Dinv [m, 6, 6], dscale [6 m], info: dict by
+    SELFTEST_CHOL_INFO)."""
+    rowptr = _c(rowptr, np.int32); colidx = _c(colidx, np.int32); val = _c(val, np.float64)
+    m = len(rowptr) - 1
+    if m < 1 or len(colidx) != rowptr[-1] or len(val) != 36 * len(colidx):
+        raise LsfmError("selftest_chol: rowptr / colidx / val do not fit together")
+    r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 6 * m)
+    nrhs = r.shape[0]
+    org = _c(origin, np.int32) if origin is not None else None
+    fx = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.uint8).reshape(-1) if fixed is not None else None
+    seg = _c(pose_seg, np.int32) if pose_seg is not None else np.zeros(m, np.int32)
+    if (org is not None and len(org) != m) or (fx is not None and len(fx) != 6 * m) or len(seg) != m:
+        raise LsfmError("selftest_chol: origin / fixed / pose_seg do not fit m")
+    cap = int(symbolic_analyse(rowptr, colidx, org)["info"][0])
+    z = np.zeros((nrhs, 6 * m)); dot = np.zeros((nrhs, int(nseg)))
+    perm = np.zeros(m, np.int32); colptr = np.zeros(m + 1, np.int32); rowidx = np.zeros(cap, np.int32)
+    Lb = np.zeros((cap, 6, 6)); Dinv = np.zeros((m, 6, 6)); dscale = np.zeros(6 * m)
+    info = np.zeros(16, np.int32)
+    rc = lib().lsfm_selftest_chol(self._h, m, _ptr(rowptr, C.c_int), _ptr(colidx, C.c_int), _ptr(val, C.c_double),
+                                  _ptr(org, C.c_int) if org is not None else None, _ptr(fx, C.c_ubyte) if fx is not None else None,
+                                  _ptr(seg, C.c_int), int(nseg), _ptr(r, C.c_double), nrhs, int(mode), _ptr(z, C.c_double), _ptr(dot, C.c_double),
+                                  _ptr(perm, C.c_int), _ptr(colptr, C.c_int), _ptr(rowidx, C.c_int), _ptr(Lb, C.c_double), _ptr(Dinv, C.c_double),
+                                  _ptr(dscale, C.c_double), cap, _ptr(info, C.c_int))
+    self._check(rc, "lsfm_selftest_chol")
+    return dict(z=z, dot=dot, perm=perm, colptr=colptr, rowidx=rowidx, L=Lb, Dinv=Dinv, dscale=dscale,
+                info=dict(zip(SELFTEST_CHOL_INFO, (int(v) for v in info))))
+
+
+Context.selftest_chol = _selftest_chol
 
 
 def symbolic_analyse(rowptr, colidx, origin=None, reps=1):

@@ -1113,6 +1113,25 @@ int lsfm_spmv_bench(lsfm_context* ctx, int m, const int* rowptr, const int* coli
 	});
 }
 
+int lsfm_selftest_chol(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin, const unsigned char* fixed,
+                       const int* pose_seg, int nseg, const double* r, int nrhs, int mode, double* z, double* dot, int* perm, int* colptr, int* rowidx,
+                       double* L, double* Dinv, double* dscale, int cap_blocks, int* info)
+{
+	if (m <= 0 || !rowptr || !colidx || !val || !pose_seg || nseg <= 0 || !r || nrhs <= 0 || mode < 0 || mode > 3 || !z || !dot || !info || cap_blocks < 0 ||
+	    rowptr[0] != 0)
+		return LSFM_ERR_ARG;
+	for (int p = 0; p < m; p++)
+	{
+		if (rowptr[p + 1] <= rowptr[p] || colidx[rowptr[p]] != p || pose_seg[p] < 0 || pose_seg[p] >= nseg) return LSFM_ERR_ARG; // every block row starts with its diagonal block
+		for (int k = rowptr[p] + 1; k < rowptr[p + 1]; k++)
+			if (colidx[k] <= colidx[k - 1] || colidx[k] >= m) return LSFM_ERR_ARG;
+	}
+	for (int i = 0; i < LSFM_SELFTEST_CHOL_INFO; i++) info[i] = 0;
+	return guarded(ctx, [&]() {
+		return chol_selftest(ctx, m, rowptr, colidx, val, origin, fixed, pose_seg, nseg, r, nrhs, mode, z, dot, perm, colptr, rowidx, L, Dinv, dscale, cap_blocks, info);
+	});
+}
+
 int lsfm_wstream_bench(lsfm_context* ctx, long long nblocks, int mode, int reps, double* avg_ms)
 {
 	if (nblocks <= 0 || mode < 0 || mode > 2 || reps <= 0 || !avg_ms) return LSFM_ERR_ARG;

@@ -1509,6 +1509,7 @@ void chol_factor(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* 
 	hipStream_t s = ctx->stream;
 	const bool dist = chol_distributed(ctx, ch);
 	const OwnFilter mine{ dist ? ch.col_owner : nullptr, dist ? ctx->comm->rank : 0 }, shared{ dist ? ch.col_owner : nullptr, -1 };
+	ch.sn_fused_levels = ch.sn_split_levels = 0;
 	if (ch.ntask0)
 	{
 		hipLaunchKernelGGL(k_chol_factor_level, dim3(ch.ntask0), dim3(128), (size_t)ch.task0_lds, s, ch.task_ptr, ch.task_cols, ch.col_nin, ch.colptr, ch.rowidx,
@@ -1556,6 +1557,7 @@ void chol_factor(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* 
 				const int nch = (mnr + SN_RB / 2 - 1) / (SN_RB / 2);
 				hipLaunchKernelGGL(k_sn_panel<true>, dim3(ng, std::max(1, nch * (nch + 1) / 2)), dim3(SN_PT), sn_panel_lds(smax), s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0,
 				                   ch.colptr, ch.L, ch.Lg, ch.Dinv, ch.d_err, ch.rowidx, fwd_v, ch.wv, smax, ch.diag0, piv_floor, ctx->d_run ? &ctx->d_run->floored : nullptr, of);
+				ch.sn_fused_levels++;
 				continue;
 			}
 			hipLaunchKernelGGL(k_sn_panel<false>, dim3(ng, std::max(1, (mnr + SN_RB - 1) / SN_RB)), dim3(SN_PT), sn_panel_lds(smax), s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0,
@@ -1563,6 +1565,7 @@ void chol_factor(lsfm_context* ctx, const SchurSystem& sy, const unsigned char* 
 			const long nch = (mnr + SN_RB / 2 - 1) / (SN_RB / 2), npair = nch * (nch + 1) / 2;
 			hipLaunchKernelGGL(k_sn_syrk, dim3(ng, (unsigned)std::max<long>(1, std::min<long>(npair, 8192))), dim3(SN_THREADS), sn_syrk_lds(smax), s,
 			                   ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, ch.colptr, ch.rowidx, ch.L, ch.Lg, smax, of);
+			ch.sn_split_levels++;
 		}
 	}
 }
@@ -1648,6 +1651,91 @@ void chol_apply(lsfm_context* ctx, const CholDev& ch, const double* r, double* v
 	}
 	else
 		hipLaunchKernelGGL(k_perm_out_dot, dim3((ch.M + 127) / 128), dim3(128), 0, s, ch.M, ch.pinv, v, r, fixed, ch.dscale, pose_seg, z, dot, dot_stride, (const int*)nullptr, 0);
+}
+
+// Test entry of the C ABI (lsfm_selftest_chol, include/lsfm.h has the arguments): the factor of a caller's matrix and UNREFINED
+// applications of it, by the host steps above and nothing else -- chol_analyse, chol_scatter, chol_factor, chol_round_to_float
+// (mode bit 1), chol_apply once per right-hand side in order, chol_merge_groups.  Inside a level solve the refinement corrects
+// whatever a wrong factor or sweep leaves (it only takes more steps); here nothing does.  The caller has checked the arguments.
+int chol_selftest(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin, const unsigned char* fixed,
+                  const int* pose_seg, int nseg, const double* r, int nrhs, int mode, double* z, double* dot, int* perm, int* colptr, int* rowidx,
+                  double* L, double* Dinv, double* dscale, int cap_blocks, int* info)
+{
+	const int nnzb = rowptr[m];
+	const size_t ns = (size_t)m * 6;
+	CholHostIn hin;
+	hin.keys.resize(nnzb);
+	hin.origin.resize(m);
+	for (int p = 0; p < m; p++)
+	{
+		hin.origin[p] = origin ? origin[p] : p;
+		for (int k = rowptr[p]; k < rowptr[p + 1]; k++) hin.keys[k] = ((unsigned long long)(unsigned)p << 32) | (unsigned)colidx[k];
+	}
+	{
+		// (the size of the factor first, on the host: the arenas are made for it, and a caller whose arrays are too small learns it here)
+		CholSymbolic sym;
+		chol_symbolic(hin.keys.data(), nnzb, hin.origin.data(), m, sym);
+		info[0] = sym.nnzL;
+		if (cap_blocks < sym.nnzL) LSFM_FAIL(LSFM_ERR_ARG, "rowidx / L too small for the factor (" + std::to_string(sym.nnzL) + " blocks)");
+		// (L, Lg and their fp32 copies; S, keys; a dozen vectors and the right-hand sides)
+		ctx->ensure_arenas((size_t)sym.nnzL * 36 * 32 + (size_t)nnzb * 320 + ns * 8 * (16 + 2 * (size_t)nrhs) + ((size_t)64 << 20));
+	}
+	ctx->scratch.reset();
+	Arena& sc = ctx->scratch;
+	SchurSystem sy;
+	sy.M = m; sy.nnzb = nnzb;
+	unsigned long long* dk = sc.alloc<unsigned long long>(nnzb + 1);
+	sy.S = sc.alloc<double>((size_t)nnzb * 36);
+	sy.rowptr = sc.alloc<int>(m + 1);
+	h2d(ctx, dk, hin.keys.data(), (size_t)nnzb * sizeof(unsigned long long));
+	h2d(ctx, sy.S, val, (size_t)nnzb * 36 * sizeof(double));
+	h2d(ctx, sy.rowptr, rowptr, (size_t)(m + 1) * sizeof(int));
+	sy.upper_keys = dk;
+	unsigned char* dfx = nullptr;
+	if (fixed) { dfx = sc.alloc<unsigned char>(ns); h2d(ctx, dfx, fixed, ns); }
+	int* dseg = sc.alloc<int>(m);
+	h2d(ctx, dseg, pose_seg, (size_t)m * sizeof(int));
+	double* dr = sc.alloc<double>(ns * nrhs);
+	double* dz = sc.alloc<double>(ns * nrhs);
+	double* ddot = sc.alloc<double>((size_t)nseg * nrhs);
+	double* dv = sc.alloc<double>(ns);
+	h2d(ctx, dr, r, ns * nrhs * sizeof(double));
+	dev_zero(ctx, ddot, (size_t)nseg * nrhs * sizeof(double));
+	CholDev ch;
+	chol_analyse(ctx, sy, hin, ch);
+	// (the count of floored pivots goes to a record of this call's own, as in lsfm_cov.hip)
+	RunStatsDev* d_run = sc.alloc<RunStatsDev>(1);
+	dev_zero(ctx, d_run, sizeof(RunStatsDev));
+	const bool fused = (mode & 1) != 0;
+	{
+		struct Swap { lsfm_context* c; RunStatsDev* keep; ~Swap() { c->d_run = keep; } } swap{ ctx, ctx->d_run };
+		ctx->d_run = d_run;
+		chol_scatter(ctx, sy, dfx, ch);
+		if (fused) chol_perm_in(ctx, ch, dr, dfx, dv);
+		chol_factor(ctx, sy, dfx, ch, fused ? dv : nullptr);
+	}
+	if (mode & 2) chol_round_to_float(ctx, ch);
+	for (int k = 0; k < nrhs; k++) chol_apply(ctx, ch, dr + ns * k, dv, dz + ns * k, dfx, dseg, ddot + (size_t)nseg * k, 1, fused && k == 0);
+	chol_merge_groups(ctx, ch);
+	LSFM_CHECK_HIP(hipGetLastError());
+	RunStatsDev rs;
+	d2h(ctx, &rs, d_run, sizeof rs);
+	const int chol_err = d2h_int(ctx, ch.d_err);
+	const int ngl = (int)ch.glevel_ptr.size() - 1;
+	info[1] = ch.ntask0; info[2] = ch.ncol0; info[3] = ch.task0_outer; info[4] = ch.ngroups; info[5] = std::max(ngl, 0);
+	info[6] = ch.sn_fused_levels; info[7] = ch.sn_split_levels;
+	info[8] = ch.glevel_maxnr.empty() ? 0 : *std::max_element(ch.glevel_maxnr.begin(), ch.glevel_maxnr.end());
+	info[9] = chol_err; info[10] = rs.floored;
+	d2h(ctx, z, dz, ns * nrhs * sizeof(double));
+	d2h(ctx, dot, ddot, (size_t)nseg * nrhs * sizeof(double));
+	if (perm) d2h(ctx, perm, ch.perm, (size_t)m * sizeof(int));
+	if (colptr) d2h(ctx, colptr, ch.colptr, (size_t)(m + 1) * sizeof(int));
+	if (rowidx) d2h(ctx, rowidx, ch.rowidx, (size_t)ch.nnzL * sizeof(int));
+	if (L) d2h(ctx, L, ch.L, (size_t)ch.nnzL * 36 * sizeof(double));
+	if (Dinv) d2h(ctx, Dinv, ch.Dinv, (size_t)m * 36 * sizeof(double));
+	if (dscale) d2h(ctx, dscale, ch.dscale, ns * sizeof(double));
+	if (chol_err) LSFM_FAIL(LSFM_ERR_NOT_SPD, "the matrix is not positive definite (block column " + std::to_string(chol_err - 1) + " of the factor)");
+	return LSFM_OK;
 }
 
 } // namespace lsfm

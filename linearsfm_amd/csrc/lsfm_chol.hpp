@@ -39,6 +39,7 @@ struct CholDev {
 	std::vector<int> glevel_ptr;    // host: groups of level l = [glevel_ptr[l], glevel_ptr[l+1])
 	std::vector<int> glevel_maxnr;  // host: most rows below a run of the level
 	std::vector<int> glevel_maxs;   // host: most block columns of a run of the level (LDS of k_sn_panel)
+	int sn_fused_levels = 0, sn_split_levels = 0; // what the last chol_factor launched: group levels as k_sn_panel<true> / as k_sn_panel<false> + k_sn_syrk
 	// distributed factorisation (lsfm_symbolic.hpp): owner of every column (-1: shared), null when off; the shared columns are the
 	// last ones, from first_shared on (their blocks: from block shared_blk0 of L on)
 	int* col_owner = nullptr;
@@ -104,5 +105,6 @@ void chol_apply(lsfm_context* ctx, const CholDev& ch, const double* r, double* v
 bool chol_distributed(const lsfm_context* ctx, const CholDev& ch);
 // feature-sharded run: one or two host numbers summed over the ranks, in place (a synchronisation)
 void comm_sum_host(lsfm_context* ctx, long long* h, int n);
+// chol_selftest (test entry lsfm_selftest_chol: the factor of a caller's matrix and unrefined applications of it): lsfm_internal.hpp
 
 } // namespace lsfm

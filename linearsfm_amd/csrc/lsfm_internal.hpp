@@ -518,6 +518,10 @@ unsigned order_event_flags();
 void prefetch_next_level(lsfm_context* ctx, const DevBatch& Y, const std::vector<int>& target_ref, int next_level, int step_hint);
 int spmv_external(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const double* x, double* y, int reps,
                   double* avg_ms, double* bytes);
+// the device Cholesky on a caller's matrix, without refinement (lsfm_chol.hip; C ABI: lsfm_selftest_chol); arguments checked by the caller
+int chol_selftest(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin, const unsigned char* fixed,
+                  const int* pose_seg, int nseg, const double* r, int nrhs, int mode, double* z, double* dot, int* perm, int* colptr, int* rowidx,
+                  double* L, double* Dinv, double* dscale, int cap_blocks, int* info);
 
 int wstream_bench(lsfm_context* ctx, long long nblocks, int mode, int reps, double* avg_ms); // measurement: W access patterns vs stream copy
 } // namespace lsfm
