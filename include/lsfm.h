@@ -167,7 +167,9 @@ int lsfm_join_mono(lsfm_context* ctx, const lsfm_map* End, const lsfm_map* Cur, 
 /* replaces lmj_solveLinearSFMStereo (Imp.h:209, Imp.cpp:2119-2378), same argument list + context.
  * Schur complement on the features, preconditioned CG on the camera system (instead of CHOLMOD),
  * back-substitution.  Writes stVal[0..6m+3n).  x0 (optional, may be NULL): initial guess for the 6m pose
- * scalars.  V is read only (the reference inverts it in place and restores it). */
+ * scalars.  V is read only (the reference inverts it in place and restores it).
+ * LSFM_ERR_ARG for W not sorted by feature, a feature without a W block, a photo index outside [0, m) and a U block that does not
+ * satisfy 0 <= Ui <= Uj < m (lsfm_solve_mono alike). */
 int lsfm_solve_stereo(lsfm_context* ctx, double* stVal, const double* eb, const double* ea, const double* U,
                       const double* W, const double* V, const int* Ui, const int* Uj, const int* photo,
                       const int* feature, int m, int n, int nU, int nW, const double* x0);

@@ -13,8 +13,8 @@
 // at a time).  Every sum runs in a fixed order in one lane: the result is the same bits on every call.
 // Sigma = P^T D^-1/2 Z D^-1/2 P on S's upper pattern (k_cov_pairs), then per feature (k_cov_feat, one wave per feature)
 //     Sigma_ff = V_f^-1 + V_f^-1 (sum_{a,b} W_af^T Sigma_{p_a p_b} W_bf) V_f^-1.
-// The front end -- argument checks, upload, reduction, factorisation -- is cov_front (lsfm_cov.hpp), shared with the covariance columns
-// of chosen poses (lsfm_covcols.hip).
+// The front end -- argument checks and upload (lsfm_system.hpp), reduction, factorisation -- is cov_front (lsfm_cov.hpp), shared with the
+// covariance columns of chosen poses (lsfm_covcols.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -25,6 +25,7 @@
 #include "lsfm_device.hpp"
 #include "lsfm_internal.hpp"
 #include "lsfm_solve.hpp"
+#include "lsfm_system.hpp"
 
 namespace lsfm {
 
@@ -268,23 +269,13 @@ __global__ void __launch_bounds__(COV_FEAT_THREADS) k_cov_feat(int NF, const int
 
 void cov_front(lsfm_context* ctx, const lsfm_map* map, bool mono, CovFront& fr)
 {
-	const int m = map->m, n = map->n, nU = map->nU, nW = map->nW;
+	const int m = map->m;
 	// ---- arguments (host) ----
-	std::vector<int>& fptr = fr.fptr;
-	fptr.assign(n + 1, 0);
-	{
-		int j = 0;
-		for (int f = 0; f < n; f++)
-		{
-			fptr[f] = j;
-			while (j < nW && map->feature[j] == f) j++;
-			if (j == fptr[f]) LSFM_FAIL(LSFM_ERR_ARG, "every feature needs at least one W block, W sorted by feature");
-		}
-		if (j != nW) LSFM_FAIL(LSFM_ERR_ARG, "W is not sorted by feature");
-		fptr[n] = nW;
-	}
-	for (int i = 0; i < nU; i++) if (map->Ui[i] < 0 || map->Uj[i] >= m || map->Ui[i] > map->Uj[i]) LSFM_FAIL(LSFM_ERR_ARG, "U block coordinates must satisfy 0 <= Ui <= Uj < m");
-	for (int j = 0; j < nW; j++) if (map->photo[j] < 0 || map->photo[j] >= m) LSFM_FAIL(LSFM_ERR_ARG, "photo index out of range");
+	HostSystem h;
+	h.m = m; h.n = map->n; h.nU = map->nU; h.nW = map->nW;
+	h.Ui = map->Ui; h.Uj = map->Uj; h.photo = map->photo; h.feature = map->feature;
+	h.U = map->U; h.W = map->W; h.V = map->V; h.pose_origin = map->pose_origin;
+	const std::vector<int> fptr = system_fptr(h);
 	std::vector<unsigned char> fx;
 	if (mono)
 	{
@@ -296,39 +287,12 @@ void cov_front(lsfm_context* ctx, const lsfm_map* map, bool mono, CovFront& fr)
 			if (-map->stno[6 * p] == map->ScaP) ps = p;
 		}
 		if (pr < 0 || ps < 0 || map->Fix < 0 || map->Fix > 2) LSFM_FAIL(LSFM_ERR_ARG, "Mono map: its Ref / ScaP pose is not in its state or Fix is not 0..2");
-		fx.assign((size_t)m * 6, 0);
-		for (int i = 0; i < 6; i++) fx[(size_t)pr * 6 + i] = 1;
-		fx[(size_t)ps * 6 + map->Fix] = 1;
+		fx = gauge_mask(m, pr, ps * 6 + map->Fix);
 	}
-	// ---- upload (as lsfm_solve_*) ----
-	size_t need = ((size_t)nW * 200 + (size_t)nU * 400 + (size_t)n * 300 + (size_t)m * 4000) * 3 + ((size_t)128 << 20);
-	ctx->ensure_arenas(need);
-	ctx->arena[0].reset(); ctx->scratch.reset();
-	Arena& ar = ctx->arena[0];
-	hipStream_t s = ctx->stream;
-	double* dU = ar.alloc<double>((size_t)nU * 36); int* dUi = ar.alloc<int>(nU); int* dUj = ar.alloc<int>(nU);
-	double* dW = ar.alloc<double>((size_t)nW * 18); int* dph = ar.alloc<int>(nW); int* dfp = ar.alloc<int>(n + 1);
-	double* dV = ar.alloc<double>((size_t)n * 9); double* dea = ar.alloc<double>((size_t)m * 6); double* deb = ar.alloc<double>((size_t)n * 3);
-	int* dseg = ar.alloc<int>(m + n + 1);
-	int* dorg = map->pose_origin ? ar.alloc<int>(m) : nullptr;
-	h2d(ctx, dU, map->U, (size_t)nU * 36 * sizeof(double)); h2d(ctx, dUi, map->Ui, nU * sizeof(int)); h2d(ctx, dUj, map->Uj, nU * sizeof(int));
-	h2d(ctx, dW, map->W, (size_t)nW * 18 * sizeof(double)); h2d(ctx, dph, map->photo, nW * sizeof(int)); h2d(ctx, dfp, fptr.data(), (n + 1) * sizeof(int));
-	h2d(ctx, dV, map->V, (size_t)n * 9 * sizeof(double));
-	if (dorg) h2d(ctx, dorg, map->pose_origin, (size_t)m * sizeof(int));
-	dev_zero(ctx, dea, (size_t)m * 6 * sizeof(double)); dev_zero(ctx, deb, (size_t)n * 3 * sizeof(double)); // (the right-hand side is not used)
-	dev_zero(ctx, dseg, (m + n + 1) * sizeof(int));
-	unsigned char* dfx = nullptr;
-	if (mono)
-	{
-		dfx = ar.alloc<unsigned char>((size_t)m * 6);
-		h2d(ctx, dfx, fx.data(), fx.size());
-	}
+	// ---- upload (lsfm_system.hip; the right-hand side is not used) ----
 	SolveIO& io = fr.io;
-	io.M = m; io.NF = n; io.NU = nU; io.NW = nW; io.nseg = 1;
-	io.d_pose_seg = dseg; io.d_feat_seg = dseg + m;
-	io.U = dU; io.Ui = dUi; io.Uj = dUj; io.W = dW; io.photo = dph; io.fptr = dfp; io.V = dV; io.ea = dea; io.eb = deb;
-	io.d_fixed = dfx; io.d_pose_origin = dorg;
-	io.seg_rows.assign(1, m);
+	system_upload(ctx, h, SYS_VALUES | SYS_RHS_0, fptr, mono ? &fx : nullptr, io);
+	hipStream_t s = ctx->stream;
 	hipEvent_t* ev = fr.ev;
 	for (int k = 0; k < 3; k++) ev[k] = ctx->pool_event();
 	LSFM_CHECK_HIP(hipEventRecord(ev[0], s));

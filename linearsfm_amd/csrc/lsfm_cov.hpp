@@ -31,15 +31,14 @@ struct DevBuf {
 
 // The factored camera system of a map, in the context's arenas: A = D^-1/2 P S P^T D^-1/2 = L L^T, whole in ch.L / ch.Dinv.
 struct CovFront {
-	std::vector<int> fptr;   // host: W run of every feature
 	SolveIO io;              // the uploaded map (io.W / io.photo / io.fptr / io.d_fixed: device)
 	SchurSystem sy;
 	CholDev ch;
 	RunStatsDev* d_run = nullptr; // this call's own record (floored pivots)
 	hipEvent_t ev[3] = { nullptr, nullptr, nullptr }; // start | reduced + analysed | factored
 };
-// checks the map's arguments (throws LSFM_ERR_ARG), uploads it as lsfm_solve_* does and runs a tree level's own pieces on it, fp64,
-// sparse path: schur_vinv -> build_schur_pattern -> chol_fetch -> build_schur_values -> chol_analyse -> chol_scatter -> chol_factor ->
+// checks the map's arguments (throws LSFM_ERR_ARG), uploads it (system_fptr / system_upload, lsfm_system.hpp) and runs a tree level's own
+// pieces on it, fp64, sparse path: schur_vinv -> build_schur_pattern -> chol_fetch -> build_schur_values -> chol_analyse -> chol_scatter -> chol_factor ->
 // chol_merge_groups.  Resets arena 0 and the scratch arena.
 void cov_front(lsfm_context* ctx, const lsfm_map* map, bool mono, CovFront& fr);
 // the numerical status of the factorisation, read once: throws LSFM_ERR_NOT_SPD, returns the number of floored pivots

@@ -323,7 +323,7 @@ struct lsfm_context {
 	bool timeline_on = false;
 	void mark(const char* what);
 	bool in_tree_run = false;
-	int inject_level = -1; // tests: the level in which this rank's pass fails (LSFM_TEST_FAIL_RANK, lsfm_capi.hip), -1: none
+	int inject_level = -1; // tests: the level in which this rank's pass fails (LSFM_TEST_FAIL_RANK, lsfm_tree.hip), -1: none
 	// refinement steps of the level being run: step_hint > 0 = what an earlier run of this tree needed here (the steps are then
 	// enqueued without asking the device after each one; whether they sufficed is read at the end of the run), steps_used = what
 	// a level that did ask needed
@@ -508,9 +508,11 @@ int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* po
 // lsfm_map_covariance_columns).  times (may be null): [4] ms of reduce + analyse, factorisation, all sweeps and products, the feature part
 int map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* poses, int k, double* pose_cols, double* feat_cols, double* joint,
                            int* steps, double* last_corr, double* times);
-// the two feature-side pieces of the solve on their own (C ABI: lsfm_inverse_v / lsfm_solve_features); device pointers
-void vinv_only(lsfm_context* ctx, int NF, const double* V, double* IV);
-void backsub_only(lsfm_context* ctx, int NF, const int* fptr, const int* photo, const double* W, const double* IV, const double* eb, const double* xp, double* xf);
+// the two feature-side pieces of the solve on their own (lsfm_solve.hip; C ABI: lsfm_inverse_v / lsfm_solve_features); host pointers,
+// arguments checked by the caller
+int inverse_v(lsfm_context* ctx, double* V, int n);
+int solve_features(lsfm_context* ctx, const double* W, const double* IV, const double* eb, const double* dpa, double* dpb, int m, int n, const int* mapCor,
+                   const int* photo);
 bool no_timing_events(); // (LSFM_NO_TIMING_EVENTS=1: the phase brackets are not recorded -- the stage times of lsfm_stats stay zero)
 #define LSFM_REC_T(e, s) do { if (!lsfm::no_timing_events()) LSFM_CHECK_HIP(hipEventRecord(e, s)); } while (0)
 unsigned timing_event_flags(); // (lsfm_prims.hip: events without the system-scope fence)
@@ -524,4 +526,6 @@ int chol_selftest(lsfm_context* ctx, int m, const int* rowptr, const int* colidx
                   double* L, double* Dinv, double* dscale, int cap_blocks, int* info);
 
 int wstream_bench(lsfm_context* ctx, long long nblocks, int mode, int reps, double* avg_ms); // measurement: W access patterns vs stream copy
+// fills, word copies and CopyBatch against a host mirror (lsfm_prims.hip; C ABI: lsfm_selftest_prims)
+int prims_selftest(lsfm_context* ctx, int cases, unsigned seed);
 } // namespace lsfm

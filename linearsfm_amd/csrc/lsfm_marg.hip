@@ -28,6 +28,7 @@
 
 #include "lsfm_device.hpp"
 #include "lsfm_marg.hpp"
+#include "lsfm_system.hpp"
 
 namespace lsfm {
 
@@ -207,42 +208,30 @@ void marg_values(lsfm_context* ctx, Arena& ar, MargWork& w, const MargKept& kept
 
 int map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned char* drop, lsfm_map* out, double* times)
 {
-	const int m = map->m, n = map->n, nU = map->nU, nW = map->nW;
-	if (m < 0 || n < 0 || nU < 0 || nW < 0) LSFM_FAIL(LSFM_ERR_ARG, "negative map size");
-	// ---- arguments (host): those of lsfm_map_covariance ----
-	std::vector<int> fptr(n + 1, 0), hdrop(n + 1, 0);
+	const int m = map->m, n = map->n;
+	// ---- arguments (host) ----
+	HostSystem h;
+	h.m = m; h.n = n; h.nU = map->nU; h.nW = map->nW;
+	h.Ui = map->Ui; h.Uj = map->Uj; h.photo = map->photo; h.feature = map->feature;
+	h.U = map->U; h.W = map->W; h.V = map->V;
+	const std::vector<int> fptr = system_fptr(h);
+	std::vector<int> hdrop(n + 1, 0);
 	int nkeep = 0, nWkeep = 0;
+	for (int f = 0; f < n; f++)
 	{
-		int j = 0;
-		for (int f = 0; f < n; f++)
-		{
-			fptr[f] = j;
-			while (j < nW && map->feature[j] == f) j++;
-			if (j == fptr[f]) LSFM_FAIL(LSFM_ERR_ARG, "every feature needs at least one W block, W sorted by feature");
-			hdrop[f] = drop[f] ? 1 : 0;
-			if (!drop[f]) { nkeep++; nWkeep += j - fptr[f]; }
-		}
-		if (j != nW) LSFM_FAIL(LSFM_ERR_ARG, "W is not sorted by feature");
-		fptr[n] = nW;
+		hdrop[f] = drop[f] ? 1 : 0;
+		if (!drop[f]) { nkeep++; nWkeep += fptr[f + 1] - fptr[f]; }
 	}
-	for (int i = 0; i < nU; i++) if (map->Ui[i] < 0 || map->Uj[i] >= m || map->Ui[i] > map->Uj[i]) LSFM_FAIL(LSFM_ERR_ARG, "U block coordinates must satisfy 0 <= Ui <= Uj < m");
-	for (int j = 0; j < nW; j++) if (map->photo[j] < 0 || map->photo[j] >= m) LSFM_FAIL(LSFM_ERR_ARG, "photo index out of range");
-	// ---- upload (as lsfm_map_covariance) ----
-	const size_t need = ((size_t)nW * 200 + (size_t)nU * 400 + (size_t)n * 300 + (size_t)m * 4000) * 3 + ((size_t)128 << 20);
-	ctx->ensure_arenas(need);
-	ctx->arena[0].reset(); ctx->scratch.reset();
+	// ---- upload (lsfm_system.hip) ----
+	SolveIO up;
+	MargView in;
+	system_upload(ctx, h, SYS_VALUES | SYS_FEATURE, fptr, nullptr, up, &in.feature);
 	Arena& ar = ctx->arena[0];
 	hipStream_t s = ctx->stream;
-	double* dU = ar.alloc<double>((size_t)nU * 36); int* dUi = ar.alloc<int>(nU); int* dUj = ar.alloc<int>(nU);
-	double* dW = ar.alloc<double>((size_t)nW * 18); int* dph = ar.alloc<int>(nW); int* dft = ar.alloc<int>(nW); int* dfp = ar.alloc<int>(n + 1);
-	double* dV = ar.alloc<double>((size_t)n * 9); int* ddrop = ar.alloc<int>(n + 1);
-	h2d(ctx, dU, map->U, (size_t)nU * 36 * sizeof(double)); h2d(ctx, dUi, map->Ui, nU * sizeof(int)); h2d(ctx, dUj, map->Uj, nU * sizeof(int));
-	h2d(ctx, dW, map->W, (size_t)nW * 18 * sizeof(double)); h2d(ctx, dph, map->photo, nW * sizeof(int)); h2d(ctx, dft, map->feature, nW * sizeof(int));
-	h2d(ctx, dfp, fptr.data(), (n + 1) * sizeof(int)); h2d(ctx, dV, map->V, (size_t)n * 9 * sizeof(double));
+	int* ddrop = ar.alloc<int>(n + 1);
 	h2d(ctx, ddrop, hdrop.data(), (n + 1) * sizeof(int));
-	MargView in;
-	in.M = m; in.NF = n; in.NU = nU; in.NW = nW;
-	in.U = dU; in.Ui = dUi; in.Uj = dUj; in.W = dW; in.photo = dph; in.feature = dft; in.fptr = dfp; in.V = dV;
+	in.M = m; in.NF = n; in.NU = up.NU; in.NW = up.NW;
+	in.U = up.U; in.Ui = up.Ui; in.Uj = up.Uj; in.W = up.W; in.photo = up.photo; in.fptr = up.fptr; in.V = up.V;
 	hipEvent_t ev[5]; // start | partition pass | V^-1 | K9 values | downloaded
 	for (int k = 0; k < 5; k++) ev[k] = ctx->pool_event();
 	LSFM_CHECK_HIP(hipEventRecord(ev[0], s));
@@ -305,6 +294,64 @@ int map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned char*
 	}
 	*out = g;
 	return LSFM_OK;
+}
+
+void marg_export_reduced(lsfm_context* ctx, const DevBatch& b, bool mono, Arena& ar, const int* keep_ids, int nkeep, void* dst, size_t cap, size_t* bytes,
+                         double* times)
+{
+	if (b.W_alias) LSFM_FAIL(LSFM_ERR_INTERNAL, "cannot pack a batch whose W blocks are aliased");
+	// work space: `ar`, and the scratch arena above what is there
+	struct Scratch { Arena& a; size_t mk; ~Scratch() { a.release(mk); } } hold{ ctx->scratch, ctx->scratch.mark() };
+	ar.reset();
+	hipStream_t s = ctx->stream;
+	std::vector<int> keep(keep_ids, keep_ids + nkeep);
+	std::sort(keep.begin(), keep.end());
+	int* d_keep = ar.alloc<int>((size_t)nkeep + 1);
+	h2d(ctx, d_keep, keep.data(), (size_t)nkeep * sizeof(int));
+	hipEvent_t ev[6]; // start | structure | partition pass | gather + V^-1 | K9 values | emitted
+	if (times) { for (int k = 0; k < 6; k++) ev[k] = ctx->pool_event(); LSFM_CHECK_HIP(hipEventRecord(ev[0], s)); }
+	int* drop = ar.alloc<int>((size_t)b.NF + 2);
+	marg_flags_from_keep(ctx, b.NF, b.feat_id, d_keep, nkeep, drop);
+	MargView in; // (a single map: its indices are local already)
+	in.M = b.M; in.NF = b.NF; in.NU = b.NU; in.NW = b.NW;
+	in.U = b.U; in.Ui = b.Ui; in.Uj = b.Uj; in.W = b.W; in.photo = b.photo; in.feature = b.feature; in.fptr = b.fptr; in.V = b.V;
+	in.feat = b.feat; in.feat_id = b.feat_id;
+	MargWork w;
+	marg_structure(ctx, ar, in, drop, -1, -1, w);
+	PackHeader h;
+	memset(&h, 0, sizeof h);
+	h.magic = LSFM_PACK_MAGIC; h.version = 1; h.mono = mono;
+	h.m = b.M; h.n = w.nkeep; h.nU = w.sy.nnzb; h.nW = w.nWkeep;
+	h.Ref = b.Ref[0]; h.FRef = b.FRef[0]; h.ScaP = b.ScaP[0]; h.Fix = b.Fix[0]; h.Sign = b.Sign[0]; h.FScaP = b.FScaP[0]; h.FFix = b.FFix[0];
+	const size_t total = pack_layout(h);
+	if (bytes) *bytes = total;
+	if (!dst) return;
+	if (total > cap) LSFM_FAIL(LSFM_ERR_ARG, "export buffer too small: " + std::to_string(total) + " bytes needed");
+	char* d = static_cast<char*>(dst);
+	h2d(ctx, d, &h, sizeof h);
+	auto cp = [&](int slot, const void* src, size_t n) {
+		if (n) LSFM_CHECK_HIP(hipMemcpyAsync(d + h.off[slot], src, n, hipMemcpyDeviceToDevice, s));
+	};
+	cp(0, b.pose, (size_t)h.m * 48); cp(5, b.pose_id, (size_t)h.m * 4); cp(6, b.pose_origin, (size_t)h.m * 4);
+	MargKept kept;
+	kept.feat = reinterpret_cast<double*>(d + h.off[1]); kept.W = reinterpret_cast<double*>(d + h.off[3]); kept.V = reinterpret_cast<double*>(d + h.off[4]);
+	kept.feat_id = reinterpret_cast<int*>(d + h.off[7]); kept.photo = reinterpret_cast<int*>(d + h.off[10]); kept.fptr = reinterpret_cast<int*>(d + h.off[11]);
+	int* d_err = ar.alloc<int>(1);
+	dev_zero(ctx, d_err, sizeof(int));
+	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
+	marg_values(ctx, ar, w, kept, reinterpret_cast<double*>(d + h.off[2]), reinterpret_cast<int*>(d + h.off[8]), reinterpret_cast<int*>(d + h.off[9]), d_err,
+	            times ? ev + 2 : nullptr);
+	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[5], s));
+	int err = 0;
+	d2h(ctx, &err, d_err, sizeof(int)); // (synchronises: the caller hands dst to another library / stream next)
+	if (times)
+		for (int k = 0; k < 5; k++)
+		{
+			float ms = 0.0f;
+			LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+			times[k] = ms;
+		}
+	if (err) LSFM_FAIL(LSFM_ERR_NOT_SPD, "the V block of a feature to be marginalised out is not positive definite");
 }
 
 } // namespace lsfm

@@ -1,5 +1,5 @@
 // Marginalising features out of a map on the device (lsfm_marg.hip): what the host entry (lsfm_map_marginalise) and the reduced pack of
-// a resident result (lsfm_tree_export_reduced_*, lsfm_capi.hip) share.
+// a resident result (lsfm_tree_export_reduced_*) share.
 #pragma once
 #include "lsfm_internal.hpp"
 #include "lsfm_solve.hpp"
@@ -39,6 +39,11 @@ void marg_structure(lsfm_context* ctx, Arena& ar, const MargView& in, const int*
 // sy.nnzb blocks).  d_err (device int, zeroed by the caller): != 0 afterwards = a dropped V block was not positive definite.
 // ev (may be null): [3] events recorded behind the partition pass, behind the gather + V^-1 and behind K9's values.
 void marg_values(lsfm_context* ctx, Arena& ar, MargWork& w, const MargKept& kept, double* oU, int* oUi, int* oUj, int* d_err, hipEvent_t* ev);
+// lsfm_tree_export_reduced_*: the reduced pack of the single map of `b` (a finished tree's final map), its features cut down to the
+// labels keep_ids[0..nkeep).  ar: work space, an arena the map does not live in (reset here).  dst == null: the size alone, to *bytes.
+// times (may be null): [5] ms of structure | partition pass | gather + V^-1 | K9 values | emit
+void marg_export_reduced(lsfm_context* ctx, const DevBatch& b, bool mono, Arena& ar, const int* keep_ids, int nkeep, void* dst, size_t cap, size_t* bytes,
+                         double* times);
 // lsfm_map_marginalise
 int map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned char* drop, lsfm_map* out, double* times);
 

@@ -829,22 +829,50 @@ void launch_backsub(lsfm_context* ctx, const SolveIO& io, const SchurSystem& sy,
 		                   io.d_feat_seg, io.d_seg_active, io.x_feat, sy.LY, io.rhs ? io.rhs->pose_src : (const double*)nullptr);
 }
 
-void vinv_only(lsfm_context* ctx, int NF, const double* V, double* IV)
+// the two feature-side pieces of the solve on their own, from and to host arrays (C ABI: lsfm_inverse_v / lsfm_solve_features)
+int inverse_v(lsfm_context* ctx, double* V, int n)
 {
-	if (!NF) return;
-	const size_t mk = ctx->scratch.mark();
-	double* LY = ctx->scratch.alloc<double>((size_t)NF * 9);
-	double* eb = ctx->scratch.alloc<double>((size_t)NF * 3);
-	dev_zero(ctx, eb, (size_t)NF * 3 * sizeof(double));
-	hipLaunchKernelGGL(k_vinv, dim3((NF + 255) / 256), dim3(256), 0, ctx->stream, NF, V, eb, IV, LY, (double*)nullptr, RhsFused(), (double*)nullptr);
-	LSFM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-	ctx->scratch.release(mk);
+	ctx->ensure_arenas((size_t)n * 400 + ((size_t)64 << 20));
+	ctx->arena[0].reset(); ctx->scratch.reset();
+	double* dV = ctx->arena[0].alloc<double>((size_t)n * 9);
+	double* dIV = ctx->arena[0].alloc<double>((size_t)n * 9);
+	h2d(ctx, dV, V, (size_t)n * 9 * sizeof(double));
+	if (n)
+	{
+		double* LY = ctx->scratch.alloc<double>((size_t)n * 9);
+		double* eb = ctx->scratch.alloc<double>((size_t)n * 3);
+		dev_zero(ctx, eb, (size_t)n * 3 * sizeof(double));
+		hipLaunchKernelGGL(k_vinv, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, dV, eb, dIV, LY, (double*)nullptr, RhsFused(), (double*)nullptr);
+		LSFM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+	}
+	d2h(ctx, V, dIV, (size_t)n * 9 * sizeof(double));
+	return LSFM_OK;
 }
-void backsub_only(lsfm_context* ctx, int NF, const int* fptr, const int* photo, const double* W, const double* IV, const double* eb, const double* xp, double* xf)
+int solve_features(lsfm_context* ctx, const double* W, const double* IV, const double* eb, const double* dpa, double* dpb, int m, int n, const int* mapCor,
+                   const int* photo)
 {
-	if (NF)
-		hipLaunchKernelGGL(k_backsub, dim3((NF + BSUB_TILE - 1) / BSUB_TILE), dim3(256), 0, ctx->stream, NF, fptr, photo, W, IV, eb, xp,
-		                   (const int*)nullptr, (const unsigned char*)nullptr, xf, (const double*)nullptr, (const double*)nullptr);
+	std::vector<int> fptr((size_t)n + 1, 0);
+	for (int f = 0; f < n; f++)
+	{
+		if (mapCor[f] < 0) LSFM_FAIL(LSFM_ERR_ARG, "negative block count of a feature");
+		fptr[f + 1] = fptr[f] + mapCor[f];
+	}
+	const int nW = fptr[n];
+	for (int j = 0; j < nW; j++) if (photo[j] < 0 || photo[j] >= m) LSFM_FAIL(LSFM_ERR_ARG, "photo index out of range");
+	ctx->ensure_arenas((size_t)nW * 200 + (size_t)n * 300 + (size_t)m * 100 + ((size_t)64 << 20));
+	ctx->arena[0].reset(); ctx->scratch.reset();
+	Arena& ar = ctx->arena[0];
+	double* dW = ar.alloc<double>((size_t)nW * 18); int* dph = ar.alloc<int>(nW); int* dfp = ar.alloc<int>((size_t)n + 1);
+	double* dIV = ar.alloc<double>((size_t)n * 9); double* deb = ar.alloc<double>((size_t)n * 3);
+	double* dxp = ar.alloc<double>((size_t)m * 6); double* dxf = ar.alloc<double>((size_t)n * 3);
+	h2d(ctx, dW, W, (size_t)nW * 18 * sizeof(double)); h2d(ctx, dph, photo, (size_t)nW * sizeof(int));
+	h2d(ctx, dfp, fptr.data(), ((size_t)n + 1) * sizeof(int)); h2d(ctx, dIV, IV, (size_t)n * 9 * sizeof(double));
+	h2d(ctx, deb, eb, (size_t)n * 3 * sizeof(double)); h2d(ctx, dxp, dpa, (size_t)m * 6 * sizeof(double));
+	if (n)
+		hipLaunchKernelGGL(k_backsub, dim3((n + BSUB_TILE - 1) / BSUB_TILE), dim3(256), 0, ctx->stream, n, dfp, dph, dW, dIV, deb, dxp,
+		                   (const int*)nullptr, (const unsigned char*)nullptr, dxf, (const double*)nullptr, (const double*)nullptr);
+	d2h(ctx, dpb, dxf, (size_t)n * 3 * sizeof(double));
+	return LSFM_OK;
 }
 
 // y = S x for an externally supplied symmetric block matrix (upper block CSR): measurement entry of the C ABI

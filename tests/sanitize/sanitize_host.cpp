@@ -1,10 +1,11 @@
 // Sanitizer driver (CPU only, test infrastructure): the host-side code of the library that runs without a device --
-// lsfm_io.cpp (reader, writers) and lsfm_symbolic.cpp (ordering + symbolic factorisation) -- and the oracle (oracle/lsfm_oracle.c,
+// lsfm_io.cpp (reader, writers), lsfm_symbolic.cpp (ordering + symbolic factorisation), lsfm_system.cpp (argument checks) -- and the oracle (oracle/lsfm_oracle.c,
 // lsfm_chol.c), all compiled with -fsanitize=address,undefined by tests/test_sanitize_cpu.py and run over a small join tree:
 //   sanitize_host <dir> <N> <Monocular|Stereo>
 // reads <dir>/localmap_1..N.txt with the library's reader (one by one and as a threaded set) and with the oracle's, compares
 // them, joins the tree with the oracle (serial and threaded), writes / re-reads the result with lsfm_write_localmap and the
-// state / pose writers, and runs lsfm_symbolic_analyse on the final map's camera-system pattern (with and without origins).
+// state / pose writers, runs lsfm_symbolic_analyse on the final map's camera-system pattern (with and without origins), and hands the
+// final map and malformed copies of it to the host checks of a system from host arrays (lsfm_system.cpp).
 // Any sanitizer report aborts the process (-fno-sanitize-recover): exit code != 0.
 #include <cmath>
 #include <cstdio>
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "../../include/lsfm.h"
+#include "../../linearsfm_amd/csrc/lsfm_system.hpp"
 extern "C" {
 #include "../../oracle/lsfm_oracle.h"
 }
@@ -162,6 +164,67 @@ int main(int argc, char** argv)
 			for (int j = 0; j < m; j++) CHECK(rowidx[colptr[j]] == j);
 		}
 		CHECK(lsfm_symbolic_analyse(m, rowptr.data(), colidx.data(), nullptr, 1, nullptr, nullptr, rowidx.data(), 1, info, nullptr) != 0 || info[0] <= 1); // too small a buffer is refused
+	}
+	// the index arrays of a system from host arrays (lsfm_system.cpp): the final map passes and its W runs are a plain recount; malformed
+	// copies are refused with LSFM_ERR_ARG, nothing of them is read out of bounds
+	{
+		using lsfm::HostSystem;
+		HostSystem h;
+		h.m = fin.m; h.n = fin.n; h.nU = fin.nU; h.nW = fin.nW;
+		h.Ui = fin.Ui; h.Uj = fin.Uj; h.photo = fin.photo; h.feature = fin.feature;
+		CHECK(fin.m > 0 && fin.n > 2 && fin.nU > 0 && fin.nW > 3);
+		std::vector<int> fptr, count(fin.n + 1, 0);
+		const char* why = nullptr;
+		CHECK(lsfm::system_check(h, false, fptr, &why) == LSFM_OK);
+		for (int j = 0; j < fin.nW; j++) count[fin.feature[j] + 1]++;
+		for (int f = 0; f < fin.n; f++) count[f + 1] += count[f];
+		CHECK(fptr == count);
+		auto refused = [&](const HostSystem& x, bool empty_ok) {
+			std::vector<int> fp;
+			const char* msg = nullptr;
+			return lsfm::system_check(x, empty_ok, fp, &msg) == LSFM_ERR_ARG && msg != nullptr;
+		};
+		std::vector<int> Ui(fin.Ui, fin.Ui + fin.nU), Uj(fin.Uj, fin.Uj + fin.nU), ph(fin.photo, fin.photo + fin.nW), fe(fin.feature, fin.feature + fin.nW);
+		HostSystem x = h;
+		std::vector<int> rev(fe.rbegin(), fe.rend());
+		x.feature = rev.data();
+		CHECK(refused(x, false) && refused(x, true)); // W runs reversed
+		std::vector<int> gap = fe; // feature fin.n / 2 without a block: the ones behind it move up, n + 1 features
+		for (int& f : gap) if (f >= fin.n / 2) f++;
+		x = h; x.feature = gap.data(); x.n = fin.n + 1;
+		CHECK(refused(x, false));
+		CHECK(lsfm::system_check(x, true, fptr, &why) == LSFM_OK && (int)fptr.size() == fin.n + 2 && fptr[fin.n / 2] == fptr[fin.n / 2 + 1] && fptr[fin.n + 1] == fin.nW);
+		for (int bad : { -1, fin.m })
+		{
+			std::vector<int> p2 = ph;
+			p2[bad < 0 ? 3 : fin.nW - 1] = bad;
+			x = h; x.photo = p2.data();
+			CHECK(refused(x, false) && refused(x, true));
+		}
+		{
+			std::vector<int> i2 = Ui, j2 = Uj;
+			int k = 0;
+			while (k < fin.nU && Ui[k] == Uj[k]) k++;
+			if (k < fin.nU) std::swap(i2[k], j2[k]); else i2[0] = Uj[0] + 1;
+			x = h; x.Ui = i2.data(); x.Uj = j2.data();
+			CHECK(refused(x, false)); // Ui > Uj
+			j2 = Uj; j2[fin.nU - 1] = fin.m;
+			x = h; x.Uj = j2.data();
+			CHECK(refused(x, false)); // Uj = m
+		}
+		x = h; x.n = 0;
+		CHECK(refused(x, false) && refused(x, true));
+		x = h; x.nW = 0;
+		CHECK(refused(x, false));
+		CHECK(lsfm::system_check(x, true, fptr, &why) == LSFM_OK && fptr == std::vector<int>(fin.n + 1, 0));
+		x = h; x.m = 1;
+		CHECK(fin.m == 1 || refused(x, false)); // (a map of one pose is that system already)
+		// the gauge mask: a pose's six scalars and one more; indices out of range mark nothing
+		const std::vector<unsigned char> fx = lsfm::gauge_mask(fin.m, fin.m - 1, 2), none = lsfm::gauge_mask(fin.m, -1, -1), out2 = lsfm::gauge_mask(1, 1, 6);
+		int marked = 0;
+		for (unsigned char b : fx) marked += b;
+		CHECK((int)fx.size() == 6 * fin.m && marked == (fin.m > 1 ? 7 : 6) && fx[2] == 1 && fx[6 * (size_t)fin.m - 1] == 1);
+		CHECK(none == std::vector<unsigned char>(6 * (size_t)fin.m, 0) && out2 == std::vector<unsigned char>(6, 0));
 	}
 	lsfm_map_release(&back);
 	for (int k = 0; k < N; k++) { lsfm_map_release(&one[k]); lsfm_map_release(&set[k]); orc_map_free(&om[k]); }
