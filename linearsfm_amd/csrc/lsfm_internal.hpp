@@ -367,7 +367,7 @@ struct OnStream {
 // ---- primitives (lsfm_prims.hip; rocPRIM scan / radix sort on the context stream) ------------------------
 void dev_exclusive_scan(lsfm_context* ctx, const int* in, int* out, size_t n); // out[n] = total (n+1 entries written)
 void dev_sort_pairs_u64(lsfm_context* ctx, unsigned long long* keys, int* vals, size_t n, int end_bit, int begin_bit = 0); // stable, bits [begin, end)
-void dev_sort_keys_u64(lsfm_context* ctx, unsigned long long* keys, size_t n, int begin_bit, int end_bit);
+void dev_sort_keys_u64(lsfm_context* ctx, const unsigned long long* keys, unsigned long long* sorted, size_t n, int begin_bit, int end_bit);
 int d2h_int(lsfm_context* ctx, const int* dptr);
 void d2h_ints(lsfm_context* ctx, const int* dptr, int* h, size_t n);
 void h2d(lsfm_context* ctx, void* d, const void* h, size_t bytes);

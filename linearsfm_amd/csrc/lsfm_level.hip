@@ -349,7 +349,7 @@ static LevelStructure level_structure(lsfm_context* ctx, const SolveIO& io, Solv
 
 // A level of small systems (at most 16 poses each): assembled, factored and solved by one launch (lsfm_small.hip) -- no pattern of S,
 // no symbolic factorisation; the level above builds its pattern from its own joint maps when this one leaves none
-// (schur_pattern_prefetch / k_pat_insert_w_early).  warm: the level has a recorded plan (SolvePlan::small)
+// (schur_pattern_prefetch / schur_pattern_early_issue).  warm: the level has a recorded plan (SolvePlan::small)
 static int solve_level_dense(lsfm_context* ctx, const SolveIO& io, int strips, bool warm, hipEvent_t eb, hipEvent_t ec, hipEvent_t ed)
 {
 	hipStream_t s = ctx->stream;

@@ -1,7 +1,7 @@
 // K8: the block pattern of the camera system S = U - W V^-1 W^T of a level -- a hash set of the pose pairs that share a feature plus
 // U's pattern (replaces the dense byte mask smask, Imp.cpp:2131-2205), compacted and sorted into block CSR.  It depends on index
 // arrays only, so it can be made from more than one place:
-//   build_schur_pattern           from the joint map (k_pat_insert_w); a Mono level: seeded from the level below (PatternSeed); a
+//   build_schur_pattern           from the joint map (pat_insert_w); a Mono level: seeded from the level below (PatternSeed); a
 //                                 feature-sharded run: the union over the ranks
 //   schur_pattern_early_*         earlier, from the inputs of a Stereo level, while its transform runs
 //   schur_pattern_prefetch        one level ahead, from this level's joint maps, with what the next level's transform and join count
@@ -45,29 +45,6 @@ __global__ void k_pat_insert_u(int NU, int M, const int* __restrict__ Ui, const 
 	}
 }
 
-// one lane per feature; all pose pairs of its W run (Imp.cpp:2155-2173), the wave in step (hash_insert_wave)
-__global__ void __launch_bounds__(256)
-k_pat_insert_w(int NF, const int* __restrict__ fptr, const int* __restrict__ photo, unsigned long long* tab, unsigned long long mask,
-               int* overflow)
-{
-	int f = blockIdx.x * blockDim.x + threadIdx.x;
-	const bool inb = f < NF;
-	int j0 = 0, len = 0;
-	if (inb) { j0 = fptr[f]; len = fptr[f + 1] - j0; }
-	int maxlen = len;
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) maxlen = max(maxlen, __shfl_xor(maxlen, off, LSFM_WAVE));
-	for (int a = 0; a < maxlen; a++)
-	{
-		const int pa = (inb && a < len) ? photo[j0 + a] : -1;
-		for (int b = a + 1; b < maxlen; b++)
-		{
-			const bool v = inb && b < len;
-			hash_insert_wave(tab, mask, v, v ? pair_key(pa, photo[j0 + b]) : 0ull, overflow);
-		}
-	}
-}
-
 // the pattern of the level below through the join's pose renumbering (PatternSeed)
 __global__ void k_pat_insert_keys_remap(int n, const unsigned long long* __restrict__ keys, const int* __restrict__ pnew, const unsigned char* __restrict__ dropped,
                                         unsigned long long* tab, unsigned long long mask, int* overflow)
@@ -78,108 +55,167 @@ __global__ void k_pat_insert_keys_remap(int n, const unsigned long long* __restr
 	if (dropped[a] || dropped[b]) return;
 	hash_insert(tab, mask, pair_key(pnew[a], pnew[b]), overflow);
 }
-// ... and the pairs across the two sources of a matched joint feature (neighbouring features are seen by the same poses: the wave in step)
-__global__ void __launch_bounds__(256)
-k_pat_insert_cross_remap(PatternSeed sd, unsigned long long* tab, unsigned long long mask, int* overflow)
+// ---- pose pairs of features -------------------------------------------------------------------------------------------------------
+// A feature is seen by the poses of up to two W runs (E: photo[jE .. jE + lenE), C likewise), each with the hub pose of its map behind it
+// where the map is transformed on the way (hE / hC >= 0).  ALL: every pair of that list; CROSS: every pair of an E pose with a C pose.
+// How the runs of feature f are found:
+//   the joint map itself (pat_insert_w, Imp.cpp:2155-2173)        E = f, no C                                        ALL
+//   the inputs of a Stereo level (schur_pattern_early_issue)      E = srcE[f], C = srcC[f], either may be missing, hubs ALL
+//     The joint map of a Stereo join is the two input maps side by side: a joint feature is seen by the poses of its End source,
+//     the poses of its Cur source, and the hub pose of either map that is transformed on the way (the transform gives every feature
+//     of the map a block to the hub pose, Imp.cpp:1303-1309, and folds old blocks to it into that one).  All of that is known from the
+//     level's INPUT index arrays once the features are matched -- before the transform's block kernels have run.
+//   one level ahead (schur_pattern_prefetch)                      C = f (second map of a pair), E = match[f], hubs   CROSS
+//   a Mono level seeded from the level below (PatternSeed)        E = srcE[f], C = srcC[f], poses renumbered by the join (pnew, dropped)  CROSS
+// The two CROSS callers first make the features that have both runs dense (k_pat_dense_matched: `list`, `count` on the device), so
+// that no work-group is mostly idle lanes.
+// A work-group of PAT_WG lanes takes PAT_RUN consecutive features of the (dense) list at a time and spreads ALL their pairs over its
+// lanes (a prefix sum of the pair counts; a lane finds its feature by bisection), so long and short runs fill the lanes alike; the
+// pairs go through the work-group's own set (pairset_insert, lsfm_solve.hpp), which is emptied for every run of features.
+constexpr int PAT_RUN = 32;
+constexpr int PAT_WG = 256;
+struct PatFeat { int jE, lenE, hE, jC, lenC, hC; };
+struct PatPairsIn {
+	int n = 0;                                    // features (an upper bound where count is given)
+	const int *count = nullptr, *list = nullptr;  // the dense list and its length on the device; null: the features 0 .. n-1
+	const int *srcE = nullptr, *srcC = nullptr, *match = nullptr;
+	const int *fptr = nullptr, *photo = nullptr;
+	const int *feat_map = nullptr, *hub = nullptr; // hub pose of the map of a feature; null: none
+	const int* pnew = nullptr;                     // renumbering of the poses; null: none
+	const unsigned char* dropped = nullptr;
+};
+template <bool CROSS>
+__global__ void __launch_bounds__(PAT_WG)
+k_pat_insert_pairs(PatPairsIn in, unsigned long long* tab, unsigned long long mask, int* overflow)
 {
-	const int nf = blockIdx.x * blockDim.x + threadIdx.x;
-	int jE = 0, lenE = 0, jC = 0, lenC = 0;
-	if (nf < sd.NFY)
+	__shared__ unsigned long long set[PAIRSET_SLOTS];
+	__shared__ PatFeat feats[PAT_RUN];
+	__shared__ unsigned long long pre[PAT_RUN + 1]; // pre[i]: pairs of the features before i of this run
+	static_assert(PAT_RUN <= LSFM_WAVE && (PAT_RUN & (PAT_RUN - 1)) == 0, "one wave loads a run of features");
+	const int n = in.count ? min(*in.count, in.n) : in.n;
+	const int tid = threadIdx.x;
+	for (int r0 = blockIdx.x * PAT_RUN; r0 < n; r0 += gridDim.x * PAT_RUN)
 	{
-		const int fe = sd.srcE[nf], fc = sd.srcC[nf];
-		if (fe >= 0 && fc >= 0) { jE = sd.fptr_in[fe]; lenE = sd.fptr_in[fe + 1] - jE; jC = sd.fptr_in[fc]; lenC = sd.fptr_in[fc + 1] - jC; }
-	}
-	int maxE = lenE, maxC = lenC;
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) { maxE = max(maxE, __shfl_xor(maxE, off, LSFM_WAVE)); maxC = max(maxC, __shfl_xor(maxC, off, LSFM_WAVE)); }
-	for (int a = 0; a < maxE; a++)
-	{
-		int na = -1;
-		if (a < lenE) { const int pa = sd.photo_in[jE + a]; if (!sd.dropped[pa]) na = sd.pnew[pa]; }
-		for (int b = 0; b < maxC; b++)
+		pairset_clear(set);
+		if (tid < LSFM_WAVE)
 		{
-			int nb = -1;
-			if (na >= 0 && b < lenC) { const int pb = sd.photo_in[jC + b]; if (!sd.dropped[pb]) nb = sd.pnew[pb]; }
-			hash_insert_wave(tab, mask, nb >= 0, nb >= 0 ? pair_key(na, nb) : 0ull, overflow);
+			PatFeat f = { 0, 0, -1, 0, 0, -1 };
+			unsigned long long np = 0;
+			if (tid < PAT_RUN && r0 + tid < n)
+			{
+				const int x = in.list ? in.list[r0 + tid] : r0 + tid;
+				const int fe = in.srcE ? in.srcE[x] : (in.match ? in.match[x] : x);
+				const int fc = in.srcC ? in.srcC[x] : (in.match ? x : -1);
+				if (fe >= 0) { f.jE = in.fptr[fe]; f.lenE = in.fptr[fe + 1] - f.jE; if (in.hub) f.hE = in.hub[in.feat_map[fe]]; }
+				if (fc >= 0) { f.jC = in.fptr[fc]; f.lenC = in.fptr[fc + 1] - f.jC; if (in.hub) f.hC = in.hub[in.feat_map[fc]]; }
+				const unsigned long long LE = f.lenE + (f.hE >= 0 ? 1 : 0), LC = f.lenC + (f.hC >= 0 ? 1 : 0);
+				// ALL: pair (a, a + d) of the list taken as a ring, d = 1 .. L / 2 -- every pair once (twice at d = L / 2 of an even L)
+				np = CROSS ? LE * LC : (LE + LC) * ((LE + LC) / 2);
+			}
+			unsigned long long sum = np;
+#pragma unroll
+			for (int off = 1; off < PAT_RUN; off <<= 1)
+			{
+				const unsigned long long v = (unsigned long long)__shfl_up((long long)sum, off, LSFM_WAVE);
+				if (tid >= off) sum += v;
+			}
+			if (tid < PAT_RUN) { feats[tid] = f; pre[tid + 1] = sum; }
+			if (tid == 0) pre[0] = 0;
 		}
+		__syncthreads();
+		const unsigned long long P = pre[PAT_RUN];
+		for (unsigned long long g = tid; g < P; g += PAT_WG)
+		{
+			int lo = 0, hi = PAT_RUN; // pre[lo] <= g < pre[hi]
+			while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (pre[mid] <= g) lo = mid; else hi = mid; }
+			const PatFeat f = feats[lo];
+			const unsigned idx = (unsigned)(g - pre[lo]);
+			const int LE = f.lenE + (f.hE >= 0 ? 1 : 0), LC = f.lenC + (f.hC >= 0 ? 1 : 0);
+			int a, b;
+			if (CROSS) { a = (int)(idx / (unsigned)LC); b = LE + (int)(idx - (unsigned)a * (unsigned)LC); }
+			else
+			{
+				const int L = LE + LC, half = L / 2;
+				a = (int)(idx / (unsigned)half);
+				b = a + 1 + (int)(idx - (unsigned)a * (unsigned)half);
+				if (b >= L) b -= L;
+			}
+			auto pose_at = [&](int i) -> int {
+				int p;
+				if (i < LE) p = i < f.lenE ? in.photo[f.jE + i] : f.hE;
+				else { i -= LE; p = i < f.lenC ? in.photo[f.jC + i] : f.hC; }
+				if (in.pnew) p = in.dropped[p] ? -1 : in.pnew[p];
+				return p;
+			};
+			const int pa = pose_at(a), pb = pose_at(b);
+			if (pa >= 0 && pb >= 0) pairset_insert(set, tab, mask, pair_key(pa, pb), overflow);
+		}
+		__syncthreads(); // (the next run overwrites feats, pre and the set)
 	}
+}
+template <bool CROSS>
+static void pat_insert_pairs(hipStream_t s, const PatPairsIn& in, unsigned long long* tab, unsigned long long mask, int* overflow)
+{
+	if (in.n <= 0) return;
+	const unsigned grid = (unsigned)std::min(2048, (in.n + PAT_RUN - 1) / PAT_RUN);
+	hipLaunchKernelGGL(k_pat_insert_pairs<CROSS>, dim3(grid), dim3(PAT_WG), 0, s, in, tab, mask, overflow);
 }
 
-// The joint map of a Stereo join is the two input maps side by side: a joint feature is seen by the poses of its End source,
-// the poses of its Cur source, and the hub pose of either map that is transformed on the way (the transform gives every feature
-// of the map a block to the hub pose, Imp.cpp:1303-1309, and folds old blocks to it into that one).  All of that is known from the
-// level's INPUT index arrays once the features are matched -- before the transform's block kernels have run.
-__global__ void __launch_bounds__(256)
-k_pat_insert_w_early(int NFY, const int* __restrict__ srcE, const int* __restrict__ srcC, const int* __restrict__ fptr, const int* __restrict__ photo,
-                     const int* __restrict__ feat_map, const int* __restrict__ hub, unsigned long long* tab, unsigned long long mask, int* overflow)
+// the slot of every lane that has something to append to a list whose length is *count: one atomic per work-group (256 lanes, all call)
+__device__ __forceinline__ int wg_append_slot(bool have, int* count)
 {
-	const int nf = blockIdx.x * blockDim.x + threadIdx.x;
-	const bool inb = nf < NFY;
-	int jE = 0, lenE = 0, hE = -1, jC = 0, lenC = 0, hC = -1;
-	if (inb)
+	__shared__ int wave_n[256 / LSFM_WAVE], base;
+	const unsigned long long m = __ballot(have);
+	const int lane = threadIdx.x & (LSFM_WAVE - 1), w = threadIdx.x / LSFM_WAVE;
+	if (lane == 0) wave_n[w] = __popcll(m);
+	__syncthreads();
+	if (threadIdx.x == 0)
 	{
-		const int fe = srcE[nf], fc = srcC[nf];
-		if (fe >= 0) { jE = fptr[fe]; lenE = fptr[fe + 1] - jE; hE = hub[feat_map[fe]]; }
-		if (fc >= 0) { jC = fptr[fc]; lenC = fptr[fc + 1] - jC; hC = hub[feat_map[fc]]; }
+		int total = 0;
+		for (int k = 0; k < 256 / LSFM_WAVE; k++) total += wave_n[k];
+		base = total ? atomicAdd(count, total) : 0;
 	}
-	const int nE = lenE + (hE >= 0 ? 1 : 0), len = nE + lenC + (hC >= 0 ? 1 : 0);
-	auto pose_at = [&](int i) -> int {
-		if (i < lenE) return photo[jE + i];
-		if (i < nE) return hE;
-		i -= nE;
-		return i < lenC ? photo[jC + i] : hC;
-	};
-	int maxlen = len;
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) maxlen = max(maxlen, __shfl_xor(maxlen, off, LSFM_WAVE));
-	for (int a = 0; a < maxlen; a++)
-	{
-		const int pa = (inb && a < len) ? pose_at(a) : -1;
-		for (int b = a + 1; b < maxlen; b++)
-		{
-			const bool v = inb && b < len;
-			hash_insert_wave(tab, mask, v, v ? pair_key(pa, pose_at(b)) : 0ull, overflow);
-		}
-	}
+	__syncthreads();
+	int slot = base + __popcll(m & ((1ull << lane) - 1ull));
+	for (int k = 0; k < w; k++) slot += wave_n[k];
+	return slot;
 }
-// pairs across the two maps of a pair, one lane per feature of the second map that has a match in the first
+// the features that have both runs (a[i] >= 0, b[i] >= 0 where given), of the second map of a pair (odd_of[i] odd, where given)
 __global__ void __launch_bounds__(256)
-k_pat_insert_w_cross_match(int NF, const int* __restrict__ feat_map, const int* __restrict__ match, const int* __restrict__ fptr,
-                           const int* __restrict__ photo, const int* __restrict__ hub, unsigned long long* tab, unsigned long long mask, int* overflow)
+k_pat_dense_matched(int n, const int* __restrict__ a, const int* __restrict__ b, const int* __restrict__ odd_of, int* __restrict__ list, int* __restrict__ count)
 {
-	const int fc = blockIdx.x * blockDim.x + threadIdx.x;
-	if (fc >= NF || !(feat_map[fc] & 1)) return;
-	const int fe = match[fc];
-	if (fe < 0) return;
-	const int jE = fptr[fe], lenE = fptr[fe + 1] - jE, hE = hub[feat_map[fe]];
-	const int jC = fptr[fc], lenC = fptr[fc + 1] - jC, hC = hub[feat_map[fc]];
-	for (int a = 0; a <= lenE; a++)
-	{
-		const int pa = a < lenE ? photo[jE + a] : hE;
-		if (pa < 0) continue;
-		for (int b = 0; b <= lenC; b++)
-		{
-			const int pb = b < lenC ? photo[jC + b] : hC;
-			if (pb >= 0) hash_insert(tab, mask, pair_key(pa, pb), overflow);
-		}
-	}
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	const bool have = i < n && a[i] >= 0 && (!b || b[i] >= 0) && (!odd_of || (odd_of[i] & 1));
+	const int slot = wg_append_slot(have, count);
+	if (have) list[slot] = i;
 }
 
 // ---- table -> sorted key list -> block CSR ----------------------------------------------------------------------------------------
-__global__ void k_pat_compact(size_t cap, const unsigned long long* __restrict__ tab, unsigned long long* __restrict__ list, int* __restrict__ count)
+// (the order of `list` is free -- it is sorted next --, the count exact)
+__global__ void __launch_bounds__(256)
+k_pat_compact(size_t cap, const unsigned long long* __restrict__ tab, unsigned long long* __restrict__ list, int* __restrict__ count)
 {
-	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= cap) return;
-	unsigned long long k = tab[i];
-	if (k != HEMPTY) list[atomicAdd(count, 1)] = k;
+	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const unsigned long long k = i < cap ? tab[i] : HEMPTY;
+	const int slot = wg_append_slot(k != HEMPTY, count);
+	if (k != HEMPTY) list[slot] = k;
 }
 
-__global__ void k_pat_assign(int nnzb, const unsigned long long* __restrict__ sorted, const unsigned long long* __restrict__ tab,
-                             int* __restrict__ val, unsigned long long mask, int* __restrict__ colidx)
+// (row << 32 | column) -> (row << rb | column), both below 2^rb: the bits the sort has to look at, next to each other
+__global__ void k_pat_pack(int n, unsigned long long* __restrict__ keys, int rb)
+{
+	int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) keys[i] = ((keys[i] >> 32) << rb) | (keys[i] & 0xffffffffull);
+}
+// packed: the sorted packed keys; sorted: the same as (row << 32 | column)
+__global__ void k_pat_assign(int nnzb, const unsigned long long* __restrict__ packed, int rb, unsigned long long* __restrict__ sorted,
+                             const unsigned long long* __restrict__ tab, int* __restrict__ val, unsigned long long mask, int* __restrict__ colidx)
 {
 	int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= nnzb) return;
-	unsigned long long key = sorted[i];
+	const unsigned long long pk = packed[i];
+	const unsigned long long key = ((pk >> rb) << 32) | (pk & ((1ull << rb) - 1ull));
+	sorted[i] = key;
 	unsigned long long h = mix64(key) & mask;
 	while (tab[h] != key) h = (h + 1) & mask;
 	val[h] = i;
@@ -203,7 +239,7 @@ void rowptr_from_keys(lsfm_context* ctx, int M, int cnt, const unsigned long lon
 
 struct PatternBuild {
 	unsigned long long *tab = nullptr, *list = nullptr;
-	int *hval = nullptr, *d_flags = nullptr; // [0] overflow, [1] count
+	int *hval = nullptr, *d_flags = nullptr; // [0] overflow, [1] count, [2] length of the dense feature list of the cross pairs
 	size_t cap = 0;
 	unsigned long long mask() const { return (unsigned long long)(cap - 1); }
 };
@@ -225,6 +261,21 @@ static void pattern_begin(lsfm_context* ctx, size_t cap, PatternBuild& pb)
 	pb.d_flags = sc.alloc<int>(4);
 	dev_zero(ctx, pb.d_flags, 4 * sizeof(int));
 	hipLaunchKernelGGL(k_fill_u64, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, pb.tab, cap, HEMPTY);
+}
+// all pose pairs of every feature's W run
+static void pat_insert_w(hipStream_t s, int NF, const int* fptr, const int* photo, const PatternBuild& pb)
+{
+	PatPairsIn in;
+	in.n = NF; in.fptr = fptr; in.photo = photo;
+	pat_insert_pairs<false>(s, in, pb.tab, pb.mask(), pb.d_flags);
+}
+// the cross pairs of the features that have both runs (k_pat_dense_matched), on ctx->stream; once per table
+static void pat_insert_matched_pairs(lsfm_context* ctx, PatPairsIn in, const int* a, const int* b, const int* odd_of, const PatternBuild& pb)
+{
+	int* dense = ctx->scratch.alloc<int>(in.n);
+	hipLaunchKernelGGL(k_pat_dense_matched, dim3((in.n + 255) / 256), dim3(256), 0, ctx->stream, in.n, a, b, odd_of, dense, pb.d_flags + 2);
+	in.list = dense; in.count = pb.d_flags + 2;
+	pat_insert_pairs<true>(ctx->stream, in, pb.tab, pb.mask(), pb.d_flags);
 }
 static void pattern_compact(lsfm_context* ctx, PatternBuild& pb)
 {
@@ -273,15 +324,18 @@ static void pattern_finish(lsfm_context* ctx, int M, const PatternBuild& pb, int
 	Arena& sc = ctx->scratch;
 	sy.M = M;
 	sy.nnzb = cnt;
-	// keys are (row << 32 | column) with both below M: two stable sorts over the bits in use (columns, then rows) instead of
-	// one over all 64 -- a third of the passes
+	// keys are (row << 32 | column) with both below M < 2^rb: ONE sort, of the keys packed to (row << rb | column), over their 2 rb
+	// bits, out of place; k_pat_assign unpacks them into the list again.  That is the one path for every size: a list of some 10^5
+	// keys or fewer rocPRIM merge-sorts whatever the bit range (one block sort + a few merges; two sorts over rb bits each were two of
+	// those and two runtime copies), a larger one it radix-sorts, and 2 rb bits in one sort are never more passes than rb bits twice.
 	int rb = 1;
 	while ((1 << rb) <= M) rb++;
-	dev_sort_keys_u64(ctx, pb.list, cnt, 0, rb);
-	dev_sort_keys_u64(ctx, pb.list, cnt, 32, 32 + rb);
+	unsigned long long* packed = sc.alloc<unsigned long long>(cnt + 1);
+	if (cnt) hipLaunchKernelGGL(k_pat_pack, dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, cnt, pb.list, rb);
+	dev_sort_keys_u64(ctx, pb.list, packed, cnt, 0, 2 * rb);
 	sy.rowptr = sc.alloc<int>(M + 1);
 	sy.colidx = sc.alloc<int>(cnt + 1);
-	if (cnt) hipLaunchKernelGGL(k_pat_assign, dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, cnt, pb.list, pb.tab, pb.hval, pb.mask(), sy.colidx);
+	if (cnt) hipLaunchKernelGGL(k_pat_assign, dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, cnt, packed, rb, pb.list, pb.tab, pb.hval, pb.mask(), sy.colidx);
 	rowptr_from_keys(ctx, M, cnt, pb.list, sy.rowptr);
 	sy.tab = pb.tab; sy.hval = pb.hval; sy.mask = pb.mask();
 	sy.upper_keys = pb.list;
@@ -328,9 +382,15 @@ void build_schur_pattern(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy)
 			// (until round 5 every Mono level that analyses hashed every pose pair of every feature again: 66 GB and 28 ms of a
 			// synth-16k tree, profiles/r04_pmc_traffic_summary_synth16k.json)
 			if (sd->prev_nnzb) hipLaunchKernelGGL(k_pat_insert_keys_remap, dim3((sd->prev_nnzb + 255) / 256), dim3(256), 0, s, sd->prev_nnzb, sd->prev_keys, sd->pnew, sd->dropped, pb.tab, pb.mask(), pb.d_flags);
-			if (sd->NFY) hipLaunchKernelGGL(k_pat_insert_cross_remap, dim3((sd->NFY + 255) / 256), dim3(256), 0, s, *sd, pb.tab, pb.mask(), pb.d_flags);
+			// ... and the pairs across the two sources of a matched joint feature
+			if (sd->NFY)
+			{
+				PatPairsIn in;
+				in.n = sd->NFY; in.srcE = sd->srcE; in.srcC = sd->srcC; in.fptr = sd->fptr_in; in.photo = sd->photo_in; in.pnew = sd->pnew; in.dropped = sd->dropped;
+				pat_insert_matched_pairs(ctx, in, sd->srcE, sd->srcC, nullptr, pb);
+			}
 		}
-		else if (NF) hipLaunchKernelGGL(k_pat_insert_w, dim3((NF + 255) / 256), dim3(256), 0, s, NF, io.fptr, io.photo, pb.tab, pb.mask(), pb.d_flags);
+		else pat_insert_w(s, NF, io.fptr, io.photo, pb);
 	});
 	if (!built) LSFM_FAIL(LSFM_ERR_INTERNAL, "Schur pattern hash table kept overflowing");
 	// debug / test: a pair the seeded pattern lacked would lose its share of S without a word
@@ -374,7 +434,9 @@ void schur_pattern_early_issue(lsfm_context* ctx, const EarlyPatternIn& in)
 		pattern_begin(ctx, pattern_capacity((size_t)in.NU + in.M, in.M), pb);
 		const int nu = std::max(in.NU, in.M);
 		if (nu) hipLaunchKernelGGL(k_pat_insert_u, dim3((nu + 255) / 256), dim3(256), 0, s, in.NU, in.M, in.Ui, in.Uj, in.pose_map, in.hub, pb.tab, pb.mask(), pb.d_flags);
-		if (in.NFY) hipLaunchKernelGGL(k_pat_insert_w_early, dim3((in.NFY + 255) / 256), dim3(256), 0, s, in.NFY, in.srcE, in.srcC, in.fptr, in.photo, in.feat_map, in.hub, pb.tab, pb.mask(), pb.d_flags);
+		PatPairsIn pi;
+		pi.n = in.NFY; pi.srcE = in.srcE; pi.srcC = in.srcC; pi.fptr = in.fptr; pi.photo = in.photo; pi.feat_map = in.feat_map; pi.hub = in.hub;
+		pat_insert_pairs<false>(s, pi, pb.tab, pb.mask(), pb.d_flags);
 		pattern_compact(ctx, pb);
 		LSFM_CHECK_HIP(hipGetLastError());
 	}
@@ -432,7 +494,7 @@ bool schur_pattern_prefetch(lsfm_context* ctx, const DevBatch& Y, const int* d_t
                             std::vector<int>* counts, bool want_pattern, LevelIndex* keep)
 {
 	// prev_keys == null: the level that produced Y left no pattern (its systems were small enough for the dense path, which needs
-	// none): the pairs inside every map of Y are then taken from Y's own W runs (k_pat_insert_w), as a level without a predecessor does
+	// none): the pairs inside every map of Y are then taken from Y's own W runs (pat_insert_w), as a level without a predecessor does
 	if (!Y.M) return false;
 	hipStream_t s = ctx->stream;
 	Arena& sc = ctx->scratch;
@@ -479,8 +541,14 @@ bool schur_pattern_prefetch(lsfm_context* ctx, const DevBatch& Y, const int* d_t
 		const int nu = std::max(Y.NU, Y.M);
 		hipLaunchKernelGGL(k_pat_insert_u, dim3((nu + 255) / 256), dim3(256), 0, s, Y.NU, Y.M, Y.Ui, Y.Uj, Y.pose_map, hub, pb.tab, pb.mask(), pb.d_flags);
 		if (prev_keys && prev_nnzb) hipLaunchKernelGGL(k_pat_insert_keys, dim3((prev_nnzb + 255) / 256), dim3(256), 0, s, prev_nnzb, prev_keys, pb.tab, pb.mask(), pb.d_flags);
-		if (!prev_keys && Y.NF) hipLaunchKernelGGL(k_pat_insert_w, dim3((Y.NF + 255) / 256), dim3(256), 0, s, Y.NF, Y.fptr, Y.photo, pb.tab, pb.mask(), pb.d_flags);
-		if (Y.NF) hipLaunchKernelGGL(k_pat_insert_w_cross_match, dim3((Y.NF + 255) / 256), dim3(256), 0, s, Y.NF, Y.feat_map, match, Y.fptr, Y.photo, hub, pb.tab, pb.mask(), pb.d_flags);
+		if (!prev_keys) pat_insert_w(s, Y.NF, Y.fptr, Y.photo, pb);
+		// pairs across the two maps of a pair: the features of the second map that have a match in the first
+		if (Y.NF)
+		{
+			PatPairsIn in;
+			in.n = Y.NF; in.match = match; in.fptr = Y.fptr; in.photo = Y.photo; in.feat_map = Y.feat_map; in.hub = hub;
+			pat_insert_matched_pairs(ctx, in, match, nullptr, Y.feat_map, pb);
+		}
 	});
 }
 

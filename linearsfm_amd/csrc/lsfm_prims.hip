@@ -113,16 +113,15 @@ void dev_exclusive_scan(lsfm_context* ctx, const int* in, int* out, size_t n)
 	ctx->scratch.release(mk);
 }
 
-void dev_sort_keys_u64(lsfm_context* ctx, unsigned long long* keys, size_t n, int begin_bit, int end_bit)
+// out of place: `keys` is read, `sorted` (n entries of the caller's) written
+void dev_sort_keys_u64(lsfm_context* ctx, const unsigned long long* keys, unsigned long long* sorted, size_t n, int begin_bit, int end_bit)
 {
 	if (n == 0 || end_bit <= begin_bit) return;
 	size_t mk = ctx->scratch.mark();
-	unsigned long long* k2 = ctx->scratch.alloc<unsigned long long>(n);
 	size_t tb = 0;
-	LSFM_CHECK_HIP(rocprim::radix_sort_keys(nullptr, tb, keys, k2, n, begin_bit, end_bit, ctx->stream));
+	LSFM_CHECK_HIP(rocprim::radix_sort_keys(nullptr, tb, keys, sorted, n, begin_bit, end_bit, ctx->stream));
 	void* tmp = ctx->scratch.alloc_bytes(tb);
-	LSFM_CHECK_HIP(rocprim::radix_sort_keys(tmp, tb, keys, k2, n, begin_bit, end_bit, ctx->stream));
-	LSFM_CHECK_HIP(hipMemcpyAsync(keys, k2, n * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream));
+	LSFM_CHECK_HIP(rocprim::radix_sort_keys(tmp, tb, keys, sorted, n, begin_bit, end_bit, ctx->stream));
 	ctx->scratch.release(mk);
 }
 

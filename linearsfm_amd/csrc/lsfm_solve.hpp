@@ -134,9 +134,10 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long x)
 	x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
 	return x;
 }
-__device__ __forceinline__ void hash_insert(unsigned long long* tab, unsigned long long mask, unsigned long long key, int* overflow)
+// (hm: mix64(key), for a caller that has it already)
+__device__ __forceinline__ void hash_insert_mixed(unsigned long long* tab, unsigned long long mask, unsigned long long key, unsigned long long hm, int* overflow)
 {
-	unsigned long long h = mix64(key) & mask;
+	unsigned long long h = hm & mask;
 	for (int probe = 0; probe < 4096; probe++)
 	{
 		unsigned long long cur = tab[h];
@@ -150,16 +151,34 @@ __device__ __forceinline__ void hash_insert(unsigned long long* tab, unsigned lo
 	}
 	*overflow = 1;
 }
-// the wave in step (every lane of it calls): when all the lanes that have a key ask for the same one -- hub poses shared by
-// neighbouring features --, one lane inserts it
-__device__ __forceinline__ void hash_insert_wave(unsigned long long* tab, unsigned long long mask, bool valid, unsigned long long key, int* overflow)
+__device__ __forceinline__ void hash_insert(unsigned long long* tab, unsigned long long mask, unsigned long long key, int* overflow)
 {
-	const unsigned long long m = __ballot(valid);
-	if (m == 0ull) return;
-	const int leader = __ffsll((long long)m) - 1;
-	const unsigned long long first = (unsigned long long)__shfl((long long)key, leader, LSFM_WAVE);
-	const bool uniform = __ballot(valid && key != first) == 0ull;
-	if (uniform ? (int)(threadIdx.x & (LSFM_WAVE - 1)) == leader : valid) hash_insert(tab, mask, key, overflow);
+	hash_insert_mixed(tab, mask, key, mix64(key), overflow);
+}
+// A work-group's own set (LDS, open addressing) of the keys it has already sent to the table.  Neighbouring features are seen by the
+// same poses, so nearly every pair a work-group forms it has formed before: only a key NEW to the work-group goes to the global table.
+// A key that finds neither itself nor a free slot within PAIRSET_PROBES steps -- the set is full around it -- goes to the global table
+// directly: the result is a set union, so that is always correct.  (The lane that put a key into the set is the one that inserts it:
+// every key of the set is in the table when the kernel ends.)
+constexpr int PAIRSET_SLOTS = 2048; // 16 KB of LDS
+constexpr int PAIRSET_PROBES = 8;
+__device__ __forceinline__ void pairset_clear(unsigned long long* set) // (the caller synchronises the work-group)
+{
+	for (int i = threadIdx.x; i < PAIRSET_SLOTS; i += blockDim.x) set[i] = HEMPTY;
+}
+__device__ __forceinline__ void pairset_insert(unsigned long long* set, unsigned long long* tab, unsigned long long mask, unsigned long long key, int* overflow)
+{
+	const unsigned long long hm = mix64(key);
+	unsigned s = (unsigned)(hm >> 40) & (PAIRSET_SLOTS - 1);
+	for (int probe = 0; probe < PAIRSET_PROBES; probe++)
+	{
+		unsigned long long cur = set[s];
+		if (cur == HEMPTY) cur = atomicCAS(&set[s], HEMPTY, key); // HEMPTY: this lane has put it there
+		if (cur == key) return;
+		if (cur == HEMPTY) break;
+		s = (s + 1) & (PAIRSET_SLOTS - 1);
+	}
+	hash_insert_mixed(tab, mask, key, hm, overflow);
 }
 __device__ __forceinline__ int hash_find(const unsigned long long* __restrict__ tab, const int* __restrict__ val, unsigned long long mask,
                                          unsigned long long key)
