@@ -322,6 +322,54 @@ int lsfm_map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned 
  * of the emission of U' with the download */
 int lsfm_map_marginalise_timed(lsfm_context* ctx, const lsfm_map* map, const unsigned char* drop, lsfm_map* out, double* times);
 
+/* ---- marginalising poses out of a map: key-frame maps (NO reference counterpart) ----
+ * out = `map` with every pose p that has keep_pose[p] == 0 (keep_pose[m], one flag per pose in the map's order) marginalised out,
+ * together with the features that go with them.  Rules:
+ *   gauge     the Ref pose, where it is in the state, must be kept; for a Mono map (mono = 1) the ScaP pose too
+ *   features  a feature seen by a dropped pose must be dropped, or the marginal would not be a map (its fill would join a feature
+ *             to poses that never saw it).  drop_feat == NULL: exactly those features are dropped.  drop_feat[n] given: the flags
+ *             of lsfm_map_marginalise; a kept feature that a dropped pose sees is refused (lsfm_last_error names it), features
+ *             beyond those may be dropped as well.
+ * Stage A is lsfm_map_marginalise over the dropped features (U1; this version goes through the host between the stages).  Stage B,
+ * with D the dropped and K the kept poses:
+ *     U'_KK = U1_KK - U1_KD U1_DD^-1 U1_DK
+ * exact for a Gaussian.  U1_DD is factored by lsfm_map_covariance's own front end, in the order its symbolic analysis likes; the
+ * correction is formed as Y^T Y, Y = L^-1 D^-1/2 P U1_DK from a forward sweep alone (side by side, 32 boundary poses per chunk), on
+ * v_mfma_f64_16x16x4_f64 in a fixed order: it inherits the Cauchy-Schwarz bound element by element, which a solve followed by a product
+ * does not, and the diagonal blocks come out EXACTLY symmetric.  (The sweeps add with atomics: two calls agree to rounding.)
+ * The result is lsfm_map_marginalise's canonical form with the kept poses renumbered in their order, its structure from labels and
+ * flags alone: stno / stVal / pose_origin of the kept variables and Ref .. FFix are the input's; the kept features are bit for bit as
+ * stage A leaves them, photo[] renumbered; U' has exactly one block per pair (Ui <= Uj), sorted by (Ui, Uj), the diagonal first and
+ * full -- the pairs of U1_KK's pattern, every pair of kept poses that border the same connected component of the graph on D, every
+ * diagonal; a block that happens to be zero stays.  A Mono map's gauge rows and columns stay exactly zero.  Keeping every pose is
+ * lsfm_map_marginalise.
+ * Returns LSFM_OK; LSFM_ERR_NOT_SPD (a dropped V, or U1_DD) and > 0 = the number of floored pivots of U1_DD's factor, exactly as
+ * lsfm_map_covariance: nothing is written, out is untouched; LSFM_ERR_OOM when the swept columns (36 |D| |Bd| doubles, Bd the kept
+ * poses with a block into D) do not fit the device, the message has the size; LSFM_ERR_ARG for keep_pose == NULL, a rule above, and
+ * what lsfm_map_marginalise refuses.  out: library-allocated (lsfm_map_release).
+ * Lifetime: works in the context's arenas like lsfm_map_covariance -- a tree's result must be downloaded first. */
+int lsfm_map_marginalise_poses(lsfm_context* ctx, const lsfm_map* map, int mono, const unsigned char* keep_pose, const unsigned char* drop_feat,
+                               lsfm_map* out);
+/* measurement entry: the same, and times[5] (may be NULL) = HIP-event ms of stage A with its way through the host, of the structure +
+ * the uploads of stage B, of the factorisation (reduction, analysis, numbers), of the right-hand sides + forward sweeps, of the SYRK +
+ * the emission of U' with its download; info[8] (may be NULL) = { |D|, |Bd|, connected components of D, blocks of U', chunks, leaf
+ * tasks, supernode groups, group levels } (the last three: the factor of U1_DD; 0 when nothing is dropped) */
+int lsfm_map_marginalise_poses_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const unsigned char* keep_pose, const unsigned char* drop_feat,
+                                     lsfm_map* out, double* times, int* info);
+/* Test entry, NO device needed: the structure of lsfm_map_marginalise_poses from the map's labels and the flags alone (the values of
+ * `map` are not read; the pattern of U1 is formed on the host: the pairs of U, the pairs of poses that see a common dropped feature,
+ * every diagonal).  Outputs, each optional; pose indices are the INPUT map's except in Ui / Uj:
+ *   drop[n]     the feature flags stage A runs with
+ *   comp[m]     connected component of a dropped pose in the graph of U1_DD, numbered by their smallest pose; -1: kept
+ *   nptr[components + 1 <= m + 1], nidx[cap_n]   N(c) as a CSR: the kept poses with a block of U1 into component c, ascending
+ *   bd[<= m]    Bd, the union of all N(c), ascending
+ *   Ui, Uj[cap_u]   the pattern of U' in the OUTPUT's numbering, sorted
+ *   info[8]     { |D|, |Bd|, components, blocks of U', entries of nidx, dropped features, blocks of U1, fill pairs }
+ *   why[why_cap]    what is wrong, when LSFM_ERR_ARG is returned
+ * Call it once without nidx / Ui / Uj for the sizes.  LSFM_ERR_ARG as lsfm_map_marginalise_poses, and when a cap is too small. */
+int lsfm_marg_pose_structure(const lsfm_map* map, int mono, const unsigned char* keep_pose, const unsigned char* drop_feat, unsigned char* drop,
+                             int* comp, int* nptr, int* nidx, int cap_n, int* bd, int* Ui, int* Uj, int cap_u, int* info, char* why, int why_cap);
+
 /* replaces pba_inverseV (Imp.h:213, Imp.cpp:3022-3042): V^-1 of the n 3x3 feature blocks, IN PLACE like the reference's (which
  * inverts V in place and restores it afterwards, Imp.cpp:2210-2212, 2365): the upper triangle of the computed inverse, mirrored.
  * m is unused, as in the reference. */

@@ -133,6 +133,10 @@ def lib():
         L.lsfm_read_cov_columns.argtypes = [C.c_char_p, ip, ip, dp, C.c_int, ip]
         L.lsfm_map_marginalise.argtypes = [vp, P(LsfmMap), P(C.c_ubyte), P(LsfmMap)]
         L.lsfm_map_marginalise_timed.argtypes = [vp, P(LsfmMap), P(C.c_ubyte), P(LsfmMap), dp]
+        ub = P(C.c_ubyte)
+        L.lsfm_map_marginalise_poses.argtypes = [vp, P(LsfmMap), C.c_int, ub, ub, P(LsfmMap)]
+        L.lsfm_map_marginalise_poses_timed.argtypes = [vp, P(LsfmMap), C.c_int, ub, ub, P(LsfmMap), dp, ip]
+        L.lsfm_marg_pose_structure.argtypes = [P(LsfmMap), C.c_int, ub, ub, ub, ip, ip, ip, C.c_int, ip, ip, ip, C.c_int, ip, C.c_char_p, C.c_int]
         L.lsfm_tree_export_reduced_size.argtypes = [vp, vp, ip, C.c_int, P(C.c_size_t)]
         L.lsfm_tree_export_reduced_dev.argtypes = [vp, vp, ip, C.c_int, vp, C.c_size_t]
         L.lsfm_tree_export_reduced_dev_timed.argtypes = [vp, vp, ip, C.c_int, vp, C.c_size_t, dp]
@@ -157,7 +161,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_save_covariances", "lsfm_read_covariances",
            "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns",
            "lsfm_map_marginalise", "lsfm_map_marginalise_timed", "lsfm_tree_export_reduced_size", "lsfm_tree_export_reduced_dev",
-           "lsfm_tree_export_reduced_dev_timed"]
+           "lsfm_tree_export_reduced_dev_timed", "lsfm_map_marginalise_poses", "lsfm_map_marginalise_poses_timed", "lsfm_marg_pose_structure"]
 
 
 def _c(a, dtype):
@@ -624,6 +628,36 @@ class Context:
             return g, dict(zip(("structure_ms", "values_ms", "emit_ms"), t.tolist()))
         return g
 
+    def marginalise_poses(self, d, mono, keep_pose, drop_feat=None, times=False, info=False):
+        """lsfm_map_marginalise_poses: the map dict d with every pose p that has keep_pose[p] == 0 marginalised out (U'_KK = U1_KK - U1_KD
+        U1_DD^-1 U1_DK), after the features that go with them (drop_feat None: exactly the features a dropped pose sees; flags: those and
+        more), in canonical form with the kept poses renumbered in their order.  The Ref pose (Mono: and the ScaP pose) must be kept.  No
+        reference counterpart.  Returns a map dict of the form tree_download returns; times: also {"stage_a_ms", "structure_ms",
+        "factor_ms", "sweeps_ms", "syrk_emit_ms"} by HIP events; info: also a dict by MARG_POSES_INFO.  Raises LsfmError on an error or
+        floored pivots."""
+        h = HostMap(d)
+        kp = np.ascontiguousarray(np.asarray(keep_pose).astype(bool), dtype=np.uint8).reshape(-1)
+        if len(kp) != h.c.m:
+            raise LsfmError(f"marginalise_poses: {len(kp)} flags for {h.c.m} poses")
+        fl = None
+        if drop_feat is not None:
+            fl = np.ascontiguousarray(np.asarray(drop_feat).astype(bool), dtype=np.uint8).reshape(-1)
+            if len(fl) != h.c.n:
+                raise LsfmError(f"marginalise_poses: {len(fl)} flags for {h.c.n} features")
+        out = LsfmMap()
+        t = np.zeros(5)
+        inf = np.zeros(8, np.int32)
+        rc = self._check(lib().lsfm_map_marginalise_poses_timed(self._h, C.byref(h.c), int(mono), _ptr(kp, C.c_ubyte), _ptr(fl, C.c_ubyte) if fl is not None else None,
+                                                                C.byref(out), _ptr(t, C.c_double), _ptr(inf, C.c_int)), "lsfm_map_marginalise_poses")
+        if rc != 0:
+            raise LsfmError(f"lsfm_map_marginalise_poses: {rc} pivot(s) floored -- the dropped poses' own system is too close to singular")
+        res = [map_to_dict(out)]
+        if times:
+            res.append(dict(zip(("stage_a_ms", "structure_ms", "factor_ms", "sweeps_ms", "syrk_emit_ms"), t.tolist())))
+        if info:
+            res.append(dict(zip(MARG_POSES_INFO, (int(v) for v in inf))))
+        return res[0] if len(res) == 1 else tuple(res)
+
     def spmv_bench(self, rowptr, colidx, val, x, reps=20):
         rowptr = _c(rowptr, np.int32); colidx = _c(colidx, np.int32); val = _c(val, np.float64); x = _c(x, np.float64)
         m = len(rowptr) - 1
@@ -708,6 +742,37 @@ def symbolic_analyse(rowptr, colidx, origin=None, reps=1):
     if rc:
         raise LsfmError(f"lsfm_symbolic_analyse failed (rc={rc}): malformed pattern")
     return dict(perm=perm, colptr=colptr, rowidx=rowidx[:int(info[0])], info=info, ms=ms.value)
+
+
+MARG_POSES_INFO = ("dropped", "boundary", "components", "blocks", "chunks", "leaf_tasks", "groups", "group_levels")
+
+
+def marg_pose_structure(d, mono, keep_pose, drop_feat=None):
+    """Host-only (lsfm_marg_pose_structure): what lsfm_map_marginalise_poses makes of the labels of map dict d and the flags, without
+    a device.  Returns dict(drop [n] bool, comp [m] (component of a dropped pose, -1: kept), nptr / nidx (N(c) as a CSR, the input's pose
+    indices), bd, Ui / Uj (the pattern of U' in the output's numbering), info [8]).  Raises LsfmError with the library's reason."""
+    h = HostMap(d)
+    m, n = h.c.m, h.c.n
+    kp = None if keep_pose is None else np.ascontiguousarray(np.asarray(keep_pose).astype(bool), dtype=np.uint8).reshape(-1)
+    fl = None if drop_feat is None else np.ascontiguousarray(np.asarray(drop_feat).astype(bool), dtype=np.uint8).reshape(-1)
+    if (kp is not None and len(kp) != m) or (fl is not None and len(fl) != n):
+        raise LsfmError("marg_pose_structure: the flags do not fit the map")
+    info = np.zeros(8, np.int32)
+    why = C.create_string_buffer(512)
+    ub = C.c_ubyte
+    args = (C.byref(h.c), int(mono), _ptr(kp, ub) if kp is not None else None, _ptr(fl, ub) if fl is not None else None)
+    rc = lib().lsfm_marg_pose_structure(*args, None, None, None, None, 0, None, None, None, 0, _ptr(info, C.c_int), why, len(why))
+    if rc:
+        raise LsfmError(f"lsfm_marg_pose_structure failed (rc={rc}): {why.value.decode()}")
+    drop = np.zeros(max(n, 1), np.uint8); comp = np.zeros(m, np.int32); nptr = np.zeros(m + 1, np.int32); bd = np.zeros(m, np.int32)
+    nidx = np.zeros(max(int(info[4]), 1), np.int32); Ui = np.zeros(max(int(info[3]), 1), np.int32); Uj = np.zeros_like(Ui)
+    rc = lib().lsfm_marg_pose_structure(*args, _ptr(drop, ub), _ptr(comp, C.c_int), _ptr(nptr, C.c_int), _ptr(nidx, C.c_int), len(nidx), _ptr(bd, C.c_int),
+                                        _ptr(Ui, C.c_int), _ptr(Uj, C.c_int), len(Ui), _ptr(info, C.c_int), why, len(why))
+    if rc:
+        raise LsfmError(f"lsfm_marg_pose_structure failed (rc={rc}): {why.value.decode()}")
+    nc = int(info[2])
+    return dict(drop=drop[:n].astype(bool), comp=comp, nptr=nptr[:nc + 1].copy(), nidx=nidx[:int(info[4])].copy(), bd=bd[:int(info[1])].copy(),
+                Ui=Ui[:int(info[3])].copy(), Uj=Uj[:int(info[3])].copy(), info=info)
 
 
 LSFM_NODE_MAGIC = 1279870541  # first token of the tree-node trailer of a local-map file (lsfm_io.cpp)

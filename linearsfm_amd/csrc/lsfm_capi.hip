@@ -537,6 +537,19 @@ int lsfm_map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned 
 	return lsfm_map_marginalise_timed(ctx, map, drop, out, nullptr);
 }
 
+int lsfm_map_marginalise_poses_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const unsigned char* keep_pose, const unsigned char* drop_feat, lsfm_map* out,
+                                     double* times, int* info)
+{
+	if (!map || !keep_pose || !out || (mono != 0 && mono != 1) || map->m <= 0 || map->n < 0 || map->nU < 0 || map->nW < 0 || !map->stno || !map->stVal) return LSFM_ERR_ARG;
+	if ((map->nU && (!map->U || !map->Ui || !map->Uj)) || (map->nW && (!map->W || !map->photo || !map->feature)) || (map->n && !map->V)) return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() { return map_marginalise_poses(ctx, map, mono == 1, keep_pose, drop_feat, out, times, info); });
+}
+
+int lsfm_map_marginalise_poses(lsfm_context* ctx, const lsfm_map* map, int mono, const unsigned char* keep_pose, const unsigned char* drop_feat, lsfm_map* out)
+{
+	return lsfm_map_marginalise_poses_timed(ctx, map, mono, keep_pose, drop_feat, out, nullptr, nullptr);
+}
+
 int lsfm_map_covariance_columns_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* poses, int k, double* pose_cols, double* feat_cols,
                                       double* joint, int* steps, double* last_corr, double* times)
 {

@@ -19,7 +19,12 @@
 // the estimate the other files hold; no reference counterpart),
 // -keepf <file> (whitespace-separated feature ids, unknown ones ignored: after -gn / -relin and before any file is written the final map is
 // replaced by its reduction to these features -- every other feature marginalised out, lsfm_map_marginalise; -st, -p, -f, -full, -fullbin,
-// -info, -cov, -covf and -covcols describe the reduced map, -chi2 is evaluated on the full state first; no reference counterpart).
+// -info, -cov, -covf and -covcols describe the reduced map, -chi2 is evaluated on the full state first; no reference counterpart),
+// -keepp <file> (whitespace-separated pose ids, unknown ones ignored: at the same place the final map is replaced by its reduction to these
+// poses -- every other pose marginalised out together with the features it sees, lsfm_map_marginalise_poses: a key-frame map.  With -keepf
+// the dropped features are those -keepf drops plus those a dropped pose sees.  The files describe the reduced map as under -keepf; -covposes
+// naming a dropped pose, an unreadable file or a list without the gauge poses (Ref; Monocular: ScaP too) end the run non-zero with no file
+// written; no reference counterpart).
 #include <cmath>
 #include <chrono>
 #include <sys/stat.h>
@@ -49,15 +54,16 @@ static void print_help()
 	printf("-chi2 <file>		Save chi2 Of Every Local Map: index dof chi2 weight\n");
 	printf("-relin 1		Information Matrix (-info, -cov, -covf, -covcols) Of The Local Maps Linearised At The Final State\n");
 	printf("-keepf <file>		Keep Only The Features Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
+	printf("-keepp <file>		Keep Only The Poses Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
 	printf("\n");
 }
 
 int main(int argc, char** argv)
 {
-	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf;
+	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf, keepp;
 	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0, relin = 0;
 	double robust_c = 0.0;
-	bool has_path = false, has_num = false, has_keepf = false;
+	bool has_path = false, has_num = false, has_keepf = false, has_keepp = false;
 	double tol = 0;
 	for (int i = 1; i < argc; i++)
 	{
@@ -97,6 +103,7 @@ int main(int argc, char** argv)
 		else if (name == "covcols") covcols = next();
 		else if (name == "covposes") covposes = next();
 		else if (name == "keepf") { keepf = next(); has_keepf = true; }
+		else if (name == "keepp") { keepp = next(); has_keepp = true; }
 		else if (name == "robust")
 		{
 			const std::string k = next(), v = next();
@@ -123,19 +130,21 @@ int main(int argc, char** argv)
 		covids.push_back((int)v);
 		p = (size_t)(end - covposes.c_str()) + (*end ? 1 : 0);
 	}
-	// -keepf: the ids to keep, sorted; an unreadable file ends the run before anything is computed or written
-	std::vector<int> keepids;
-	if (has_keepf)
-	{
-		FILE* f = fopen(keepf.c_str(), "r");
-		if (!f) { fprintf(stderr, "LinearSFM: -keepf: cannot read %s\n", keepf.c_str()); return 1; }
+	// -keepf / -keepp: the ids to keep, sorted; an unreadable file ends the run before anything is computed or written
+	std::vector<int> keepids, keeppids;
+	auto read_ids = [](const char* flag, const char* what, const std::string& fn, std::vector<int>& ids) {
+		FILE* f = fopen(fn.c_str(), "r");
+		if (!f) { fprintf(stderr, "LinearSFM: %s: cannot read %s\n", flag, fn.c_str()); return false; }
 		int v = 0, got = 0;
-		while ((got = fscanf(f, "%d", &v)) == 1) keepids.push_back(v);
+		while ((got = fscanf(f, "%d", &v)) == 1) ids.push_back(v);
 		const bool junk = got != EOF;
 		fclose(f);
-		if (junk) { fprintf(stderr, "LinearSFM: -keepf: %s is not a list of feature ids\n", keepf.c_str()); return 1; }
-		std::sort(keepids.begin(), keepids.end());
-	}
+		if (junk) { fprintf(stderr, "LinearSFM: %s: %s is not a list of %s ids\n", flag, fn.c_str(), what); return false; }
+		std::sort(ids.begin(), ids.end());
+		return true;
+	};
+	if (has_keepf && !read_ids("-keepf", "feature", keepf, keepids)) return 1;
+	if (has_keepp && !read_ids("-keepp", "pose", keepp, keeppids)) return 1;
 	if (robust && gn <= 0) { fprintf(stderr, "LinearSFM: -robust applies to -gn <steps>: give -gn too\n"); return 1; }
 
 	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -297,7 +306,7 @@ int main(int argc, char** argv)
 		out = H;
 	}
 	std::vector<int> chi2dof; // -keepf with -chi2: filled before the reduction
-	if (has_keepf)
+	if (has_keepf || has_keepp)
 	{
 		// -chi2 needs the full state: evaluated now, its file is still written last
 		if (!chi2f.empty() && chi2v.empty())
@@ -305,11 +314,25 @@ int main(int argc, char** argv)
 			chi2v.resize(num); weightv.assign(num, 1.0); chi2dof.resize(num);
 			if (lsfm_map_chi2(ctx, maps.data(), num, type, &out, chi2v.data(), chi2dof.data()) < 0) { fprintf(stderr, "LinearSFM: chi2: %s\n", lsfm_last_error(ctx)); return 3; }
 		}
-		// the final map reduced to the features of -keepf: every other one marginalised out (lsfm_map_marginalise)
-		std::vector<unsigned char> drop(out.n > 0 ? out.n : 1);
-		for (int f = 0; f < out.n; f++) drop[f] = std::binary_search(keepids.begin(), keepids.end(), out.stno[6 * out.m + 3 * f]) ? 0 : 1;
+		// the final map reduced to the features of -keepf: every other one marginalised out (lsfm_map_marginalise); to the poses of -keepp:
+		// every other one marginalised out, with the features it sees (lsfm_map_marginalise_poses)
+		std::vector<unsigned char> drop(out.n > 0 ? out.n : 1, 0), keepflag(out.m, 1);
+		if (has_keepf)
+			for (int f = 0; f < out.n; f++) drop[f] = std::binary_search(keepids.begin(), keepids.end(), out.stno[6 * out.m + 3 * f]) ? 0 : 1;
 		lsfm_map R;
-		if (lsfm_map_marginalise(ctx, &out, drop.data(), &R) != LSFM_OK)
+		if (has_keepp)
+		{
+			for (int p = 0; p < out.m; p++) keepflag[p] = std::binary_search(keeppids.begin(), keeppids.end(), -out.stno[6 * p]) ? 1 : 0;
+			for (int w = 0; w < out.nW; w++)
+				if (!keepflag[out.photo[w]]) drop[out.feature[w]] = 1;
+			const int prc = lsfm_map_marginalise_poses(ctx, &out, type, keepflag.data(), drop.data(), &R);
+			if (prc != LSFM_OK)
+			{
+				fprintf(stderr, "LinearSFM: keepp: %s\n", prc < 0 ? lsfm_last_error(ctx) : "pivots had to be floored (the dropped poses' own system is too close to singular)");
+				return 3;
+			}
+		}
+		else if (lsfm_map_marginalise(ctx, &out, drop.data(), &R) != LSFM_OK)
 		{
 			fprintf(stderr, "LinearSFM: keepf: %s\n", lsfm_last_error(ctx));
 			return 3;

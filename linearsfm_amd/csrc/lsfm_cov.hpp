@@ -44,4 +44,11 @@ void cov_front(lsfm_context* ctx, const lsfm_map* map, bool mono, CovFront& fr);
 // the numerical status of the factorisation, read once: throws LSFM_ERR_NOT_SPD, returns the number of floored pivots
 int cov_front_status(lsfm_context* ctx, const CovFront& fr);
 
+// The side-by-side triangular sweeps of lsfm_covcols.hip against the factor `ch` (whole in ch.L / ch.Dinv), in place on a slab
+// V[6 ch.M][R] in elimination order, R <= 6 CC_KC = 192: V <- L^-1 V, and V <- L^-T V.  lsfm_map_covariance_columns runs one after the
+// other; lsfm_map_marginalise_poses the forward one alone.
+#define CC_KC 32 /* poses per chunk of columns (lsfm_covcols.hip) */
+void cc_sweep_forward(lsfm_context* ctx, const CholDev& ch, int R, double* V);
+void cc_sweep_backward(lsfm_context* ctx, const CholDev& ch, int R, double* V);
+
 } // namespace lsfm

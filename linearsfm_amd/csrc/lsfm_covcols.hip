@@ -42,7 +42,7 @@ namespace lsfm {
 
 namespace {
 
-#define CC_KC 32     /* poses per chunk (see above) */
+/* CC_KC = 32 poses per chunk (see above): lsfm_cov.hpp */
 #define CC_MAXT 768  /* lanes of a supernode-group work-group: columns x row slices */
 #define CC_GK (6 * CHOL_GS) /* most scalar columns of a group's run */
 #define CC_PANEL_DEFAULT 2 /* a group's panel product when the context does not say (lsfm_set_covcols_panel): 1 plain, 2 MFMA */
@@ -510,6 +510,59 @@ inline unsigned blocks_of(size_t n, unsigned per) { return (unsigned)((n + per -
 
 } // namespace
 
+// The two halves of (L L^T)^-1 on a slab V[6 M][R], in place, on CholDev's own schedule (shared with lsfm_marg_poses.hip, which needs
+// the forward half alone): the leaf tasks in one launch, then the supernode-group levels one after the other -- backward the other
+// way round.
+namespace {
+struct SweepShape {
+	unsigned rp, nsl, pt;
+	bool plain;
+	SweepShape(const lsfm_context* ctx, int R)
+	{
+		plain = (ctx->covcols_panel ? ctx->covcols_panel : CC_PANEL_DEFAULT) == 1;
+		rp = (unsigned)((R + LSFM_WAVE - 1) / LSFM_WAVE * LSFM_WAVE);
+		nsl = plain ? std::min(8u, CC_MAXT / rp) : 1u;
+		pt = (unsigned)((R + 15) / 16) * LSFM_WAVE; // a wave per 16 columns (<= CC_MAXT: R <= 6 CC_KC)
+	}
+};
+} // namespace
+
+void cc_sweep_forward(lsfm_context* ctx, const CholDev& ch, int R, double* V)
+{
+	hipStream_t s = ctx->stream;
+	const SweepShape sh(ctx, R);
+	const unsigned rp = sh.rp, nsl = sh.nsl, pt = sh.pt;
+	const bool plain = sh.plain;
+	const int ngl = (int)ch.glevel_ptr.size() - 1;
+	if (ch.ntask0) hipLaunchKernelGGL(k_cc_fwd<false>, dim3(ch.ntask0), dim3(rp, 1), 0, s, ch.task_ptr, ch.task_cols, ch.col_task, false, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
+	for (int l = 0; l < ngl; l++)
+	{
+		const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0, mnr = ch.glevel_maxnr[l];
+		if (!ng) continue;
+		hipLaunchKernelGGL(k_cc_fwd<true>, dim3(ng), dim3(rp, nsl), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, plain, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
+		if (!plain && mnr > 0)
+			hipLaunchKernelGGL(k_cc_fwd_panel, dim3(ng, std::min(CC_GY, (6 * mnr + 15) / 16)), dim3(pt), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, R, ch.colptr, ch.rowidx, ch.L, V);
+	}
+}
+
+void cc_sweep_backward(lsfm_context* ctx, const CholDev& ch, int R, double* V)
+{
+	hipStream_t s = ctx->stream;
+	const SweepShape sh(ctx, R);
+	const unsigned rp = sh.rp, nsl = sh.nsl, pt = sh.pt;
+	const bool plain = sh.plain;
+	const int ngl = (int)ch.glevel_ptr.size() - 1;
+	for (int l = ngl - 1; l >= 0; l--)
+	{
+		const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0, mnr = ch.glevel_maxnr[l];
+		if (!ng) continue;
+		if (!plain && mnr > 0)
+			hipLaunchKernelGGL(k_cc_bwd_panel, dim3(ng, std::min(CC_GY, (6 * mnr + CC_GK - 1) / CC_GK)), dim3(pt), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, R, ch.colptr, ch.rowidx, ch.L, V);
+		hipLaunchKernelGGL(k_cc_bwd<true>, dim3(ng), dim3(rp, nsl), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, plain, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
+	}
+	if (ch.ntask0) hipLaunchKernelGGL(k_cc_bwd<false>, dim3(ch.ntask0), dim3(rp, 1), 0, s, ch.task_ptr, ch.task_cols, (const int*)nullptr, false, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
+}
+
 int map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* poses, int k, double* pose_cols, double* feat_cols, double* joint,
                            int* steps_out, double* last_corr, double* times)
 {
@@ -560,31 +613,10 @@ int map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, co
 	int* dq = bQ.get<int>(k);
 	h2d(ctx, dq, poses, (size_t)k * sizeof(int));
 	hipEvent_t ev[3] = { ctx->pool_event(), ctx->pool_event(), ctx->pool_event() };
-	const int ngl = (int)ch.glevel_ptr.size() - 1;
-	const bool plain = (ctx->covcols_panel ? ctx->covcols_panel : CC_PANEL_DEFAULT) == 1;
 	// (L L^T)^-1 applied to V in place
 	auto sweep = [&](int R) {
-		const unsigned rp = (unsigned)((R + LSFM_WAVE - 1) / LSFM_WAVE * LSFM_WAVE);
-		const unsigned nsl = plain ? std::min(8u, CC_MAXT / rp) : 1u;
-		const unsigned pt = (unsigned)((R + 15) / 16) * LSFM_WAVE; // a wave per 16 columns (<= CC_MAXT: R <= 6 CC_KC)
-		if (ch.ntask0) hipLaunchKernelGGL(k_cc_fwd<false>, dim3(ch.ntask0), dim3(rp, 1), 0, s, ch.task_ptr, ch.task_cols, ch.col_task, false, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
-		for (int l = 0; l < ngl; l++)
-		{
-			const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0, mnr = ch.glevel_maxnr[l];
-			if (!ng) continue;
-			hipLaunchKernelGGL(k_cc_fwd<true>, dim3(ng), dim3(rp, nsl), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, plain, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
-			if (!plain && mnr > 0)
-				hipLaunchKernelGGL(k_cc_fwd_panel, dim3(ng, std::min(CC_GY, (6 * mnr + 15) / 16)), dim3(pt), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, R, ch.colptr, ch.rowidx, ch.L, V);
-		}
-		for (int l = ngl - 1; l >= 0; l--)
-		{
-			const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0, mnr = ch.glevel_maxnr[l];
-			if (!ng) continue;
-			if (!plain && mnr > 0)
-				hipLaunchKernelGGL(k_cc_bwd_panel, dim3(ng, std::min(CC_GY, (6 * mnr + CC_GK - 1) / CC_GK)), dim3(pt), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, R, ch.colptr, ch.rowidx, ch.L, V);
-			hipLaunchKernelGGL(k_cc_bwd<true>, dim3(ng), dim3(rp, nsl), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, plain, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
-		}
-		if (ch.ntask0) hipLaunchKernelGGL(k_cc_bwd<false>, dim3(ch.ntask0), dim3(rp, 1), 0, s, ch.task_ptr, ch.task_cols, (const int*)nullptr, false, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
+		cc_sweep_forward(ctx, ch, R, V);
+		cc_sweep_backward(ctx, ch, R, V);
 	};
 	const double tol = ctx->pcg.rel_tol;
 	const int max_steps = std::max(1, ctx->pcg.max_steps);

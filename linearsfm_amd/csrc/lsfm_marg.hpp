@@ -2,6 +2,7 @@
 // a resident result (lsfm_tree_export_reduced_*) share.
 #pragma once
 #include "lsfm_internal.hpp"
+#include "lsfm_marg_poses.hpp"
 #include "lsfm_solve.hpp"
 
 namespace lsfm {
@@ -46,5 +47,11 @@ void marg_export_reduced(lsfm_context* ctx, const DevBatch& b, bool mono, Arena&
                          double* times);
 // lsfm_map_marginalise
 int map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned char* drop, lsfm_map* out, double* times);
+// lsfm_map_marginalise_poses (lsfm_marg_poses.hip; the structure: lsfm_marg_poses.hpp): stage A = map_marginalise over the features that
+// go with the dropped poses, then U'_KK = U1_KK - Y^T Y from a forward sweep against the factor of U1_DD.  times (may be null): [5] ms of
+// stage A | structure + upload | factor | right-hand sides + sweeps | SYRK + emit + download; info (may be null): [8] = |D|, |Bd|,
+// components, output blocks, chunks, leaf tasks, supernode groups, group levels.  > 0: floored pivots, nothing written.
+int map_marginalise_poses(lsfm_context* ctx, const lsfm_map* map, bool mono, const unsigned char* keep_pose, const unsigned char* drop_feat, lsfm_map* out,
+                          double* times, int* info);
 
 } // namespace lsfm

@@ -6,7 +6,14 @@ usage: python tools/marg_bench.py <config> --blocks B [--maps N] [--reps R]  -> 
 Reported: HIP-event ms of the three parts of lsfm_map_marginalise on every downloaded root and of the five parts of the resident reduction;
 GB/s of the partition pass over W against NW * 2 * 144 bytes, beside lsfm_wstream_bench modes 0 (lane per block) and 2 (stream copy) at
 the same block count in the same process; features and W blocks before and after; t_total_ms of the top tree over full against reduced
-packs (first run: analysing; then the median of R planned runs)."""
+packs (first run: analysing; then the median of R planned runs).
+
+usage: python tools/marg_bench.py <config> --keep-poses every:K [--maps N] [--reps R]  -> profiles/marginalise_poses_<config>.json
+The whole set is joined, then the result is cut to every K-th pose (and the gauge poses) by lsfm_map_marginalise_poses.  Reported: the
+median HIP-event ms of its five parts and info[8]; GFLOP/s of k_pm_syrk against 2 * 36 * 6 |D| flops per output block over the last
+part's time (which also holds k_pm_emit and the download of U': a lower bound); the wall time of the call beside the only route the
+parent commit has to the information matrix of these poses at the same K: covariance_columns(joint=True) + numpy.linalg.inv (which
+loses every kept feature)."""
 import argparse
 import json
 import os
@@ -23,13 +30,59 @@ from linearsfm_amd import api, synth  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("config")
-ap.add_argument("--blocks", type=int, required=True)
+ap.add_argument("--blocks", type=int, default=0)
+ap.add_argument("--keep-poses", default="")
 ap.add_argument("--maps", type=int, default=0)
 ap.add_argument("--reps", type=int, default=3)
 a = ap.parse_args()
 typ, maps = synth.make_config(a.config, a.maps or None)
 mono = typ == "Monocular"
 dicts = [dict(m.__dict__) for m in maps]
+if a.keep_poses:
+    import time
+
+    if not a.keep_poses.startswith("every:") or int(a.keep_poses[6:]) < 1:
+        sys.exit("--keep-poses every:K, K >= 1")
+    K = int(a.keep_poses[6:])
+    ctx = api.Context(0)
+    G, stats, rc = ctx.divide_conquer(dicts, mono)
+    if rc < 0:
+        sys.exit(f"tree: rc {rc}")
+    m = int(G["m"])
+    ids = -np.asarray(G["stno"])[:6 * m:6]
+    keep = np.zeros(m, bool)
+    keep[::K] = True
+    keep[np.isin(ids, [int(G["Ref"])] + ([int(G["ScaP"])] if mono else []))] = True
+    ctx.marginalise_poses(G, mono, keep)  # (warm-up)
+    runs, wall = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        red, t, info = ctx.marginalise_poses(G, mono, keep, times=True, info=True)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        runs.append(t)
+    med = {k: float(np.median([x[k] for x in runs])) for k in runs[0]}
+    flops = 2.0 * 36 * 6 * info["dropped"] * info["blocks"]
+    kept = np.nonzero(keep)[0]
+    ctx.covariance_columns(G, mono, kept[:1], joint=True)  # (warm-up)
+    parent = []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        J = ctx.covariance_columns(G, mono, kept, joint=True)["joint"]
+        free = np.diag(J) != 0  # (a Mono map's gauge scalars: rows and columns of zeros)
+        np.linalg.inv(J[np.ix_(free, free)])
+        parent.append((time.perf_counter() - t0) * 1e3)
+    print(json.dumps({"config": a.config, "type": typ, "maps": len(dicts), "poses": m, "features": int(G["n"]), "keep_poses": a.keep_poses, "poses_kept": int(red["m"]),
+                      "features_kept": int(red["n"]), "nU": int(G["nU"]), "nU_reduced": int(red["nU"]), "info": info, "times_ms_median": med,
+                      "wall_ms_median": float(np.median(wall)), "syrk_flops": flops,
+                      "syrk_GFLOPs_lower_bound": flops / (med["syrk_emit_ms"] * 1e-3) / 1e9 if med["syrk_emit_ms"] > 0 else None,
+                      "parent_route_wall_ms_median": float(np.median(parent)),
+                      "note": "HIP events on the context's stream: stage A through the host | structure + uploads | factor of U1_DD | right-hand sides + forward "
+                              "sweeps | k_pm_syrk + k_pm_emit + download of U'; the parent route is covariance_columns(joint=True) of the kept poses + "
+                              "numpy.linalg.inv on the host, which gives the poses' information matrix alone"}, indent=1))
+    ctx.close()
+    sys.exit(0)
+if a.blocks < 1:
+    sys.exit("give --blocks B or --keep-poses every:K")
 N, B = len(dicts), a.blocks
 size = -(-N // B)
 bounds = [(lo, min(N, lo + size)) for lo in range(0, N, size)]
