@@ -616,6 +616,18 @@ int lsfm_selftest_chol(lsfm_context* ctx, int m, const int* rowptr, const int* c
                        const int* pose_seg, int nseg, const double* r, int nrhs, int mode, double* z, double* dot, int* perm, int* colptr, int* rowidx,
                        double* L, double* Dinv, double* dscale, int cap_blocks, int* info);
 
+/* Test entry: the batched coordinate transform (lsfm_transform.hip) on a batch of the caller's, as a tree level calls it -- several
+ * maps in one set of launches, each with a target of its own -- where lsfm_transform_stereo / lsfm_transform_mono hand it one map.  The
+ * N maps are uploaded as one batch, transformed once, and every map of the result is downloaded; no plans, no hook, no communicator.
+ *   tref[N]         id of each map's new reference pose; < 0: the map is passed through (so is one that is in that frame already)
+ *   tscap[N], tfix[N]   Mono: id of the new scale pose and the fixed component (ignored for Stereo; may be NULL then)
+ *   alias_passthrough   != 0: the transform leaves the W blocks of passed-through maps in its input and records where (as for a
+ *                   join that reads them from there); out[b].W of such a map is then filled from the input batch at the recorded
+ *                   offset, its photo / feature / FBlock are the transform's
+ *   out[N]          library-allocated, each released with lsfm_map_release */
+int lsfm_selftest_transform(lsfm_context* ctx, const lsfm_map* maps, int N, int mono, const int* tref, const int* tscap, const int* tfix,
+                            int alias_passthrough, lsfm_map* out);
+
 #ifdef __cplusplus
 }
 #endif

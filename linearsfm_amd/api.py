@@ -145,6 +145,7 @@ def lib():
         L.lsfm_selftest_prims.argtypes = [vp, C.c_int, C.c_uint]
         L.lsfm_selftest_chol.argtypes = [vp, C.c_int, ip, ip, dp, ip, P(C.c_ubyte), ip, C.c_int, dp, C.c_int, C.c_int, dp, dp, ip, ip, ip, dp, dp, dp,
                                          C.c_int, ip]
+        L.lsfm_selftest_transform.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, ip, ip, ip, C.c_int, P(LsfmMap)]
         _LIB = L
     return _LIB
 
@@ -156,7 +157,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_tree_upload_dev", "lsfm_tree_reload_dev", "lsfm_tree_set_comm", "lsfm_tree_set_comm_blocks", "lsfm_tree_export_slice_sizes", "lsfm_tree_export_slice_dev",
            "lsfm_tree_free", "lsfm_divide_conquer", "lsfm_read_localmap", "lsfm_read_localmaps", "lsfm_write_localmap", "lsfm_write_mapset", "lsfm_mapset_info", "lsfm_mapset_stamp", "lsfm_read_mapset", "lsfm_save_state_bin", "lsfm_save_state", "lsfm_save_poses", "lsfm_gn_polish",
            "lsfm_gn_polish_robust", "lsfm_map_chi2", "lsfm_gn_linearise", "lsfm_gn_linearise_timed",
-           "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_selftest_chol", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
+           "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_selftest_chol", "lsfm_selftest_transform", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
            "lsfm_map_covariance", "lsfm_map_covariance_timed",
            "lsfm_save_covariances", "lsfm_read_covariances",
            "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns",
@@ -723,6 +724,28 @@ def _selftest_chol(self, rowptr, colidx, val, r, origin=None, fixed=None, pose_s
 
 
 Context.selftest_chol = _selftest_chol
+
+
+def _selftest_transform(self, dicts, mono, targets, alias=False):
+    """lsfm_selftest_transform: the maps as ONE batch through the batched transform, as a tree level calls it.  targets: per map None
+    or a negative number (passed through), the new reference pose's id (Stereo), or (Ref, ScaP, Fix) (Mono).  alias: the W blocks of
+    passed-through maps stay in the transform's input (alias_passthrough) and are read from there.  Returns the list of result dicts."""
+    hms = [HostMap(d) for d in dicts]
+    N = len(hms)
+    if N < 1 or len(targets) != N:
+        raise LsfmError("selftest_transform: one target per map")
+    t = np.zeros((3, N), np.int32)
+    for b, tg in enumerate(targets):
+        t[:, b] = (-1, 0, 0) if tg is None else (tuple(tg) + (0, 0))[:3] if isinstance(tg, (tuple, list)) else (int(tg), 0, 0)
+    arr = (LsfmMap * N)(*[h.c for h in hms])
+    out = (LsfmMap * N)()
+    rc = lib().lsfm_selftest_transform(self._h, arr, N, int(bool(mono)), _ptr(t[0], C.c_int), _ptr(t[1], C.c_int), _ptr(t[2], C.c_int),
+                                       int(bool(alias)), out)
+    self._check(rc, "lsfm_selftest_transform")
+    return [map_to_dict(out[b]) for b in range(N)]
+
+
+Context.selftest_transform = _selftest_transform
 
 
 def symbolic_analyse(rowptr, colidx, origin=None, reps=1):

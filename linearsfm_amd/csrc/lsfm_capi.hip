@@ -1,5 +1,6 @@
 // C ABI (include/lsfm.h): argument checks and the error boundary of every entry point.  The work is elsewhere -- the tree scheduler in
 // lsfm_tree.hip, a system from host arrays in lsfm_system.hip, each stage in its own file.
+#include <climits>
 #include <cmath>
 #include <cstring>
 
@@ -630,6 +631,35 @@ int lsfm_selftest_chol(lsfm_context* ctx, int m, const int* rowptr, const int* c
 	return guarded(ctx, [&]() {
 		return chol_selftest(ctx, m, rowptr, colidx, val, origin, fixed, pose_seg, nseg, r, nrhs, mode, z, dot, perm, colptr, rowidx, L, Dinv, dscale, cap_blocks, info);
 	});
+}
+
+int lsfm_selftest_transform(lsfm_context* ctx, const lsfm_map* maps, int N, int mono, const int* tref, const int* tscap, const int* tfix,
+                            int alias_passthrough, lsfm_map* out)
+{
+	if (!maps || N <= 0 || !tref || !out || (mono && (!tscap || !tfix))) return LSFM_ERR_ARG;
+	for (int b = 0; b < N; b++) memset(&out[b], 0, sizeof out[b]);
+	int rc = guarded(ctx, [&]() {
+		ctx->ensure_arenas(estimate_arena(maps, N, 1));
+		ctx->arena[0].reset(); ctx->arena[1].reset(); ctx->scratch.reset();
+		DevBatch X, Y;
+		batch_upload(ctx, ctx->arena[0], maps, N, mono != 0, X);
+		std::vector<int> r(tref, tref + N), s(N, 0), f(N, 0);
+		if (mono) { s.assign(tscap, tscap + N); f.assign(tfix, tfix + N); }
+		transform_batch(ctx, ctx->arena[1], X, r, s, f, mono != 0, Y, alias_passthrough != 0);
+		// the download reads W of the result; the blocks a passed-through map left behind come from the input, at the offset the
+		// alias records (what a join's kernels do with W_alias / d_alias)
+		std::vector<int> delta(N, INT_MIN);
+		if (Y.W_alias) d2h(ctx, delta.data(), Y.d_alias, (size_t)N * sizeof(int));
+		for (int b = 0; b < N; b++)
+		{
+			batch_download_map(ctx, Y, b, mono != 0, &out[b]);
+			if (delta[b] == INT_MIN || !out[b].nW) continue;
+			d2h(ctx, out[b].W, Y.W_alias + ((ptrdiff_t)Y.w_off[b] + delta[b]) * 18, (size_t)out[b].nW * 18 * sizeof(double));
+		}
+		return LSFM_OK;
+	});
+	if (rc < 0) for (int b = 0; b < N; b++) lsfm_map_release(&out[b]);
+	return rc;
 }
 
 int lsfm_wstream_bench(lsfm_context* ctx, long long nblocks, int mode, int reps, double* avg_ms)
