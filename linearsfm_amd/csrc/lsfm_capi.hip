@@ -411,10 +411,10 @@ static int join_one(lsfm_context* ctx, const lsfm_map* End, const lsfm_map* Cur,
 		batch_upload(ctx, ctx->arena[0], two, 2, mono, X);
 		lsfm_stats st;
 		memset(&st, 0, sizeof st);
-		ctx->stats = &st;
-		try { (mono ? join_batch_mono : join_batch_stereo)(ctx, ctx->arena[1], X, Y, eP_out, eF_out); }
-		catch (...) { ctx->stats = nullptr; throw; }
-		ctx->stats = nullptr;
+		{
+			struct Sink { lsfm_context* c; Sink(lsfm_context* x, lsfm_stats* s) : c(x) { c->stats = s; } ~Sink() { c->stats = nullptr; } } sink(ctx, &st);
+			(mono ? join_batch_mono : join_batch_stereo)(ctx, ctx->arena[1], X, Y, eP_out, eF_out, 0);
+		}
 		batch_download_map(ctx, Y, 0, mono, joint);
 		return st.not_converged ? LSFM_NOT_CONVERGED : LSFM_OK;
 	});
@@ -446,7 +446,7 @@ static int solve_raw(lsfm_context* ctx, double* stVal, const double* eb, const d
 		SolveIO io;
 		// (the one-launch dense path walks a level by the ranges of its systems)
 		system_upload(ctx, h, SYS_VALUES | SYS_RHS | SYS_X | (small_level_strips(ctx, m) ? SYS_OFFSETS : 0u), fptr, gauge ? &fx : nullptr, io);
-		int rc = solve_batch(ctx, io);
+		const int rc = solve_batch(ctx, io).not_converged;
 		d2h(ctx, stVal, io.x_pose, (size_t)m * 6 * sizeof(double));
 		d2h(ctx, stVal + 6 * m, io.x_feat, (size_t)n * 3 * sizeof(double));
 		return rc ? LSFM_NOT_CONVERGED : LSFM_OK;

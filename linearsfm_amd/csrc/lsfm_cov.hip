@@ -300,7 +300,6 @@ void cov_front(lsfm_context* ctx, const lsfm_map* map, bool mono, CovFront& fr)
 	SchurSystem& sy = fr.sy;
 	CholDev& ch = fr.ch;
 	CholHostIn hin;
-	ctx->pattern_dep = false;
 	schur_vinv(ctx, io, sy);
 	build_schur_pattern(ctx, io, sy);
 	chol_fetch(ctx, sy, io.d_pose_origin, hin);

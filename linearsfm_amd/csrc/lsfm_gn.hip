@@ -969,7 +969,7 @@ int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_ma
 		if (!(F == F)) LSFM_FAIL(LSFM_ERR_INTERNAL, "gn polish: the objective is not a number");
 		const size_t smark = ctx->scratch.mark();
 		const double ts = wall();
-		const int rc = solve_batch(ctx, io);
+		const int rc = solve_batch(ctx, io).not_converged;
 		LSFM_CHECK_HIP(hipStreamSynchronize(s));
 		t_solve += wall() - ts; n_solve++;
 		ctx->scratch.release(smark);

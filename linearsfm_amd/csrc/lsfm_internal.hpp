@@ -282,16 +282,14 @@ struct lsfm_context {
 	unsigned long long generation = 0;
 	// side stream: the pattern of S is built there while the caller's right-hand-side kernels run on the main stream.
 	// evA = point of the main stream after which the index arrays of the joint map are complete (recorded by the caller,
-	// pattern_dep set), evB = pattern ready
+	// which says so in SolveIO::index_arrays_at_evA), evB = pattern ready
 	hipStream_t stream2 = nullptr;
 	hipEvent_t evA = nullptr, evB = nullptr;
-	bool pattern_dep = false;
 	// Early pattern of S (Stereo tree levels that analyse): the pose pairs of the JOINT map follow from the level's input index
 	// arrays, the feature matches and the hub pose of every transformed map, all known before the transform's heavy kernels
 	// run -- the pattern is put together on the side stream while those run, and the host's symbolic analysis no longer
-	// waits for them (lsfm_pattern.hip: schur_pattern_early_*).  tr_in / tr_hub: set by transform_batch around its hook.
-	const lsfm::DevBatch* tr_in = nullptr;
-	const int* tr_hub = nullptr;        // [B] global pose index of the hub column of every transformed map, -1: passed through
+	// waits for them (lsfm_pattern.hip: schur_pattern_early_*).  The level's input and the hub list reach the join through the
+	// transform's hook (join_stereo_prepare).
 	std::shared_ptr<lsfm::EarlyPattern> early; // the build in flight (null: none)
 	hipEvent_t ev_k9[2] = { nullptr, nullptr }; // K9: the 32-slot panel variant of a level runs on the side stream, beside the others (lsfm_schur_panel.hip)
 	hipStream_t stream3 = nullptr;      // its own stream: the side stream carries the transform's U stage, which waits for the block kernel
@@ -311,24 +309,15 @@ struct lsfm_context {
 	int pre_plan_level = -1;
 	std::unique_ptr<lsfm::HostWorker> worker;
 	void drop_prepared() { pre.reset(); pre_plan = lsfm::LevelPlan(); pre_plan_level = -1; }
-	hipEvent_t ev_solve_end = nullptr; // (LSFM_LEVEL_GAPS=1: the event behind the last solve, against the next level's first)
-	double dbg_gap_ms = 0.0;
+	double dbg_gap_ms = 0.0; // (LSFM_LEVEL_GAPS=1: from the event behind a level's solve to the next level's first, summed over a run)
 	hipEvent_t evY = nullptr, evP = nullptr; // joint index arrays of the level final (main stream) / prefetch complete (stream3)
 	hipEvent_t evU = nullptr;                // the transform's U stage may start: everything it reads is final, the block kernel of the features has not begun
 	hipEvent_t evK = nullptr;                // the level's Schur assembly (K9) has left the main stream: the chain of the factorisation starts
-	const unsigned long long* solved_keys = nullptr; // left by solve_batch: sorted upper pattern of the system it just solved (scratch arena)
-	int solved_nnzb = 0;
 	// LSFM_TIMELINE=1: host wall-clock marks of a tree run (where the enqueuing thread is when), printed at the end of the run
 	std::vector<std::pair<const char*, double>> timeline;
 	bool timeline_on = false;
 	void mark(const char* what);
 	bool in_tree_run = false;
-	int inject_level = -1; // tests: the level in which this rank's pass fails (LSFM_TEST_FAIL_RANK, lsfm_tree.hip), -1: none
-	// refinement steps of the level being run: step_hint > 0 = what an earlier run of this tree needed here (the steps are then
-	// enqueued without asking the device after each one; whether they sufficed is read at the end of the run), steps_used = what
-	// a level that did ask needed
-	bool level_syncs = false;                    // the level under way waits for the device at its end anyway (a Mono level that analyses): a hinted refinement may ask once
-	int step_hint = 0, steps_used = 0;           // lsfm_tree_run: errors of a level may be left in d_run and read at the end of the run
 	hipEvent_t evC = nullptr;
 	lsfm_stats* stats = nullptr; // optional sink during a tree run
 	lsfm::LevelPlan* plan = nullptr; // plan of the tree level being run (null: stage-level calls, nothing is recorded or reused)
@@ -440,20 +429,16 @@ struct TrRedirect {
 	int *photo = nullptr, *feature = nullptr, *srcf = nullptr;
 };
 // hook: called once everything of `out` except the information blocks exists (poses, feature values, V', run pointers,
-// offsets); its answer redirects the W blocks.  keep_scratch: the caller releases the scratch arena (allocations made in
-// the hook outlive the call).
+// offsets); its answer redirects the W blocks.  hub: [B] global pose index of the hub column of every transformed map, -1: passed
+// through (Stereo; null: Mono, or a batch without poses) -- with the transform's input, what the early pattern of S is made from.
+// keep_scratch: the caller releases the scratch arena (allocations made in the hook outlive the call).
+using TrHook = std::function<TrRedirect(DevBatch& mid, const int* hub)>;
 void transform_batch(lsfm_context* ctx, Arena& ar, const DevBatch& in, const std::vector<int>& target_ref,
                      const std::vector<int>& target_scap, const std::vector<int>& target_fix, bool mono, DevBatch& out,
-                     bool alias_passthrough = false, const std::function<TrRedirect(DevBatch&)>* hook = nullptr);
+                     bool alias_passthrough = false, const TrHook* hook = nullptr);
 
 // ---- join + solve (lsfm_join.hip, lsfm_pattern.hip, lsfm_solve.hip): K5-K11 ---------------------------------------------------
 struct JoinWork; // device work arrays shared between assembly and solve
-// groups: consecutive maps (2g, 2g+1) of `in` are joined, a trailing unpaired map is carried over unchanged.
-// Produces `out` (ceil(B/2) maps) with the solved state.  eP_out / eF_out (host, optional) receive the right-hand
-// sides of group 0 when B <= 2 (stage-level C ABI).
-void join_batch_stereo(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, double* eP_out, double* eF_out);
-void join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, double* eP_out, double* eF_out);
-
 struct SolveIO {
 	// system of `nseg` independent camera systems laid out back to back (block rows = poses of the batch)
 	int M = 0, NF = 0, NU = 0, NW = 0, nseg = 0;
@@ -480,6 +465,22 @@ struct SolveIO {
 	// optional (Mono tree levels that analyse): the pattern of S follows from the pattern of the level below instead of being built
 	// from every pose pair of every feature again (lsfm_solve.hpp PatternSeed; null: from scratch)
 	const struct PatternSeed* seed = nullptr;
+	// the caller recorded ctx->evA where the joint map's index arrays were complete and went on to enqueue its right-hand-side kernels:
+	// a level that analyses may build the pattern of S on the side stream from there (level_structure, case 5)
+	bool index_arrays_at_evA = false;
+	// refinement steps: > 0 = what an earlier run of this tree needed at this level (the steps are then enqueued without asking the
+	// device after each one; whether they sufficed is read at the end of the run -- lsfm_tree_run: errors of a level may be left in
+	// d_run and read there)
+	int step_hint = 0;
+	// the caller waits for the device behind the solve anyway (a Mono level that analyses): a hinted refinement may ask once
+	bool caller_syncs = false;
+};
+struct SolveOutcome {
+	int not_converged = 0;                    // systems left above their bound (0 where the outcome stays in the run's device record)
+	int steps_used = 0;                       // refinement steps a solve that asked after each one needed; 0: the steps were planned
+	const unsigned long long* keys = nullptr; // sorted upper pattern of the system just solved (scratch arena: valid until the caller releases it); null: the dense path leaves none
+	int nnzb = 0;
+	hipEvent_t end = nullptr;                 // recorded behind the back-substitution
 };
 // Does a level whose largest system has most_rows poses take the one-launch dense path?  16-row strips of its panel; 0: no (the
 // systems are too large -- lsfm_context::small_max --, or the run is feature-sharded or in mixed precision).  The ONE place that
@@ -490,7 +491,13 @@ inline int small_level_strips(const lsfm_context* ctx, const std::vector<int>& s
 // the join of such a level (io.seg_rows set): the ranges of its joins in the joint maps `out`, by which the dense path walks them, to io
 void small_level_offsets(lsfm_context* ctx, const DevBatch& out, SolveIO& io);
 void small_solve_launch(lsfm_context* ctx, const SolveIO& io, int strips, int* status, double* max_rel);
-int solve_batch(lsfm_context* ctx, const SolveIO& io);
+SolveOutcome solve_batch(lsfm_context* ctx, const SolveIO& io);
+// groups: consecutive maps (2g, 2g+1) of `in` are joined, a trailing unpaired map is carried over unchanged.
+// Produces `out` (ceil(B/2) maps) with the solved state.  eP_out / eF_out (host, optional) receive the right-hand
+// sides of group 0 when B <= 2 (stage-level C ABI).  step_hint: SolveIO::step_hint of the join's solve, whose outcome is returned
+// (systems left above their bound are counted into ctx->stats here).
+SolveOutcome join_batch_stereo(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, double* eP_out, double* eF_out, int step_hint = 0);
+SolveOutcome join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, double* eP_out, double* eF_out, int step_hint = 0);
 // Gauss-Newton polish of the map-joining objective over all local maps at once (lsfm_gn.hip; C ABI: lsfm_gn_polish)
 int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_map* x, int iters, int kind, double c, double* obj, double* gnorm,
               int* halvings, double* chi2, double* weight);
@@ -517,7 +524,9 @@ bool no_timing_events(); // (LSFM_NO_TIMING_EVENTS=1: the phase brackets are not
 #define LSFM_REC_T(e, s) do { if (!lsfm::no_timing_events()) LSFM_CHECK_HIP(hipEventRecord(e, s)); } while (0)
 unsigned timing_event_flags(); // (lsfm_prims.hip: events without the system-scope fence)
 unsigned order_event_flags();
-void prefetch_next_level(lsfm_context* ctx, const DevBatch& Y, const std::vector<int>& target_ref, int next_level, int step_hint);
+// level_keys / level_nnzb: SolveOutcome::keys / nnzb of the level whose joint maps Y are (the one being solved)
+void prefetch_next_level(lsfm_context* ctx, const DevBatch& Y, const std::vector<int>& target_ref, int next_level, int step_hint,
+                         const unsigned long long* level_keys, int level_nnzb);
 int spmv_external(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const double* x, double* y, int reps,
                   double* avg_ms, double* bytes);
 // the device Cholesky on a caller's matrix, without refinement (lsfm_chol.hip; C ABI: lsfm_selftest_chol); arguments checked by the caller

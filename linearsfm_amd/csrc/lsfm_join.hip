@@ -272,7 +272,7 @@ __global__ void k_shift_segments(int n, const int* __restrict__ map_of, int* __r
 // and lays the joint map out; st.wbase[f] is where the run of input feature f starts in the joint W arrays.  Whoever
 // fills out.W / photo / feature / st.srcf from there (k_join_wcopy here, or the transform's block kernel) is followed by
 // join_stereo_finish(): right-hand sides and the solve.  Scratch taken in prepare is released by finish.
-void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, JoinState& st)
+void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, JoinState& st, const DevBatch* level_in, const int* hub)
 {
 	hipStream_t s = ctx->stream;
 	const int B = in.B, G = (B + 1) / 2;
@@ -385,7 +385,7 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 	// (a level of small systems takes the dense path: no pattern at all; a level prepared one level ahead brings its pattern -- or,
 	// prepared with a plan, is warm)
 	const bool small_level = small_level_strips(ctx, seg_rows) > 0;
-	const bool early = !small_level && !ctx->comm && !(ctx->pre && !ctx->pre_plan.valid) && ctx->tr_in && ctx->tr_hub && !ctx->warm() && ctx->tr_in->NF == in.NF && ctx->tr_in->M == in.M;
+	const bool early = !small_level && !ctx->comm && !(ctx->pre && !ctx->pre_plan.valid) && level_in && hub && !ctx->warm() && level_in->NF == in.NF && level_in->M == in.M;
 	// the W part of the right-hand sides left to the Schur assembly (lsfm_solve.hpp RhsFused): a level on the sparse pipeline, one GPU
 	st.fuse_rhs = !small_level && !ctx->comm && !ctx->pcg.mixed;
 	int *srcE = nullptr, *srcC = nullptr;
@@ -400,10 +400,10 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 			                   newf, lenE, lenC, out.V, eF, out.feat_id, out.feat, srcE, srcC, side);
 	if (early)
 	{
-		const DevBatch& X = *ctx->tr_in; // the level's input: its W runs and U blocks with the poses they had before the transform
+		const DevBatch& X = *level_in; // the level's input: its W runs and U blocks with the poses they had before the transform
 		EarlyPatternIn ei;
 		ei.M = in.M; ei.NFY = NFY; ei.NU = X.NU;
-		ei.Ui = X.Ui; ei.Uj = X.Uj; ei.pose_map = X.pose_map; ei.hub = ctx->tr_hub;
+		ei.Ui = X.Ui; ei.Uj = X.Uj; ei.pose_map = X.pose_map; ei.hub = hub;
 		ei.fptr = X.fptr; ei.photo = X.photo; ei.feat_map = X.feat_map; ei.srcE = srcE; ei.srcC = srcC;
 		LSFM_CHECK_HIP(hipEventRecord(ctx->evC, s));
 		schur_pattern_early_issue(ctx, ei);
@@ -419,7 +419,7 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 	ctx->mark("jn_prep");
 }
 
-void join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch& out, JoinState& st, double* eP_out, double* eF_out)
+SolveOutcome join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch& out, JoinState& st, double* eP_out, double* eF_out, int step_hint)
 {
 	hipStream_t s = ctx->stream;
 	const int G = out.B, NFY = out.NF;
@@ -440,11 +440,8 @@ void join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch& out, Jo
 	LSFM_CHECK_HIP(hipEventRecord(ctx->evY, s)); // the joint maps' index arrays are final (prefetch_next_level reads them)
 	// everything the pattern of S needs is enqueued: the solve may build it beside the right-hand sides (unless it is under
 	// way already: schur_pattern_early_issue)
-	if (!eP_out && !eF_out && !ctx->early && !ctx->comm)
-	{
-		LSFM_CHECK_HIP(hipEventRecord(ctx->evA, s));
-		ctx->pattern_dep = true;
-	}
+	const bool at_evA = !eP_out && !eF_out && !ctx->early && !ctx->comm;
+	if (at_evA) LSFM_CHECK_HIP(hipEventRecord(ctx->evA, s));
 	// ---- right-hand sides ----
 	// (the W part: a pass over W of its own -- unless the Schur assembly takes it along, K9Out; a caller that wants eP / eF gets them whole)
 	const bool fuse_rhs = st.fuse_rhs && !eP_out && !eF_out;
@@ -465,6 +462,7 @@ void join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch& out, Jo
 	io.ea = eP; io.eb = eF; io.x0 = in.pose; io.d_fixed = nullptr; io.d_pose_origin = out.pose_origin;
 	io.x_pose = out.pose; io.x_feat = out.feat;
 	io.seg_rows = seg_rows;
+	io.index_arrays_at_evA = at_evA; io.step_hint = step_hint;
 	RhsFused rhs;
 	if (fuse_rhs)
 	{
@@ -473,24 +471,24 @@ void join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch& out, Jo
 	}
 	small_level_offsets(ctx, out, io); // a level of small systems goes to the one-launch dense path, which walks the joins by their ranges (lsfm_small.hip)
 	const bool warm = ctx->warm();
-	ctx->solved_keys = nullptr; ctx->solved_nnzb = 0;
-	int rc = solve_batch(ctx, io);
+	const SolveOutcome oc = solve_batch(ctx, io);
 	// a level of a tree run is only enqueued (its scratch is reused in stream order, errors are read at the end of the run); a
 	// stage-level call stops here so that a failure surfaces at its stage
 	if (!warm && !ctx->in_tree_run) LSFM_CHECK_HIP(hipStreamSynchronize(s));
 	ctx->scratch.release(st.smark);
-	if (rc > 0 && ctx->stats) ctx->stats->not_converged += rc;
+	if (oc.not_converged > 0 && ctx->stats) ctx->stats->not_converged += oc.not_converged;
 	if (ctx->plan && !eP_out && !eF_out) ctx->plan->valid = true; // every stage of the level has left its structure behind
+	return oc;
 }
 
-void join_batch_stereo(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, double* eP_out, double* eF_out)
+SolveOutcome join_batch_stereo(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, double* eP_out, double* eF_out, int step_hint)
 {
 	JoinState st;
-	join_stereo_prepare(ctx, ar, in, out, st);
+	join_stereo_prepare(ctx, ar, in, out, st, nullptr, nullptr);
 	if (in.NW)
 		hipLaunchKernelGGL(k_join_wcopy, dim3((in.NW + 255) / 256), dim3(256), 0, ctx->stream, in.NW, in.W, in.photo, in.feature, in.fptr, st.wbase,
 		                   st.newf, out.W, out.photo, out.feature, st.srcf, in.W_alias, in.d_alias, in.feat_map);
-	join_stereo_finish(ctx, in, out, st, eP_out, eF_out);
+	return join_stereo_finish(ctx, in, out, st, eP_out, eF_out, step_hint);
 }
 
 } // namespace lsfm

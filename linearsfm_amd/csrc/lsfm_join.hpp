@@ -22,8 +22,11 @@ struct JoinState {
 	bool fuse_rhs = false;                    // the W part of the right-hand sides goes with the Schur assembly (RhsFused)
 	int *srcE = nullptr, *srcC = nullptr;     // per joint feature its sources in the input batch (-1: none)
 };
-void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, JoinState& st);
-void join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch& out, JoinState& st, double* eP_out, double* eF_out);
+// level_in, hub: a tree level reached through the transform's hook -- the level's input (before the transform) and the hub pose of
+// every transformed map (TrHook), from which a level that analyses starts the early pattern of S; null: no early pattern
+void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, JoinState& st, const DevBatch* level_in, const int* hub);
+// step_hint: SolveIO::step_hint of the solve, whose outcome is returned
+SolveOutcome join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch& out, JoinState& st, double* eP_out, double* eF_out, int step_hint = 0);
 
 // match[f] = feature of the pair's first map with the same label (-1 none), unm[f] = 1 for unmatched features of the
 // second map (unm[NF] = 0)

@@ -326,7 +326,7 @@ __global__ void k_fill_int(int n, int* p, int v)
 	if (i < n) p[i] = v;
 }
 
-void join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, double* eP_out, double* eF_out)
+SolveOutcome join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, double* eP_out, double* eF_out, int step_hint)
 {
 	hipStream_t s = ctx->stream;
 	const int B = in.B, G = (B + 1) / 2, M = in.M;
@@ -485,6 +485,7 @@ void join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch&
 	}
 	out.NW = out.w_off[G];
 	out.W = ar.alloc<double>((size_t)out.NW * 18); out.photo = ar.alloc<int>(out.NW); out.feature = ar.alloc<int>(out.NW);
+	bool at_evA = false;
 	if (NFY)
 	{
 		int* dst = sc.alloc<int>((size_t)in.NW + 1);
@@ -495,11 +496,8 @@ void join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch&
 		                   out.photo, out.feature, dst, jf);
 		// the joint maps' index arrays are final here (U's were written by k_mono_u_fill): a level that analyses builds the pattern of S
 		// on the side stream from this point, beside the kernel that moves the W blocks and the right-hand sides (solve_batch)
-		if (!warm && !eP_out && !eF_out && !ctx->comm)
-		{
-			LSFM_CHECK_HIP(hipEventRecord(ctx->evA, s));
-			ctx->pattern_dep = true;
-		}
+		at_evA = !warm && !eP_out && !eF_out && !ctx->comm;
+		if (at_evA) LSFM_CHECK_HIP(hipEventRecord(ctx->evA, s));
 		if (in.NF)
 			hipLaunchKernelGGL(k_mono_w_copy, dim3((in.NF + MWC_TILE - 1) / MWC_TILE), dim3(256), 0, s, in.NF, in.fptr, in.photo, in.W, in.feat_map,
 			                   in.W_alias, in.d_alias, dst, jf, srcC, out.feat_map, d_mg, pnew, prior, in.feat, out.W, eP, eF);
@@ -523,6 +521,8 @@ void join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch&
 	io.ea = eP; io.eb = eF; io.x0 = x0; io.d_fixed = fixed; io.d_pose_origin = out.pose_origin;
 	io.x_pose = out.pose; io.x_feat = out.feat;
 	io.seg_rows = seg_rows;
+	io.index_arrays_at_evA = at_evA; io.step_hint = step_hint;
+	io.caller_syncs = !warm; // (this level waits for the device below: its refinement may ask once instead of guessing a margin)
 	small_level_offsets(ctx, out, io);
 	// the pattern of this level's system from the one below (a level that analyses; the level below left its pattern with its maps)
 	PatternSeed seed;
@@ -532,24 +532,20 @@ void join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch&
 		seed.NFY = NFY; seed.srcE = srcE; seed.srcC = srcC; seed.fptr_in = in.fptr; seed.photo_in = in.photo;
 		io.seed = &seed;
 	}
-	ctx->solved_keys = nullptr; ctx->solved_nnzb = 0;
-	ctx->level_syncs = !warm; // (this level waits for the device below: its refinement may ask once instead of guessing a margin)
-	int rc;
-	try { rc = solve_batch(ctx, io); }
-	catch (...) { ctx->level_syncs = false; throw; }
-	ctx->level_syncs = false;
-	if (!warm && ctx->in_tree_run && ctx->solved_keys && ctx->solved_nnzb > 0 && !ctx->comm)
+	const SolveOutcome oc = solve_batch(ctx, io);
+	if (!warm && ctx->in_tree_run && oc.keys && oc.nnzb > 0 && !ctx->comm)
 	{
 		// ... and this level's pattern stays with its output for the level above
-		unsigned long long* k = ar.alloc<unsigned long long>((size_t)ctx->solved_nnzb + 1);
-		LSFM_CHECK_HIP(hipMemcpyAsync(k, ctx->solved_keys, (size_t)ctx->solved_nnzb * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
-		out.s_keys = k; out.s_nnzb = ctx->solved_nnzb;
+		unsigned long long* k = ar.alloc<unsigned long long>((size_t)oc.nnzb + 1);
+		LSFM_CHECK_HIP(hipMemcpyAsync(k, oc.keys, (size_t)oc.nnzb * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+		out.s_keys = k; out.s_nnzb = oc.nnzb;
 	}
 	hipLaunchKernelGGL(k_mono_finish, dim3((G + 127) / 128), dim3(128), 0, s, G, d_mg, pnew, out.pose);
 	if (!warm) LSFM_CHECK_HIP(hipStreamSynchronize(s)); // a warm level is only enqueued: its scratch is reused in stream order
 	sc.release(smark);
-	if (rc > 0 && ctx->stats) ctx->stats->not_converged += rc;
+	if (oc.not_converged > 0 && ctx->stats) ctx->stats->not_converged += oc.not_converged;
 	if (plan && !eP_out && !eF_out) plan->valid = true; // every stage of the level has left its structure behind
+	return oc;
 }
 
 } // namespace lsfm

@@ -103,7 +103,8 @@ struct PreLevel {
 	// nothing the helper thread reads goes before the thread is done with it -- whichever path drops the object, exceptions included
 	~PreLevel() { try { wait(); } catch (...) {} }
 };
-void prefetch_next_level(lsfm_context* ctx, const DevBatch& Y, const std::vector<int>& target_ref, int next_level, int step_hint)
+void prefetch_next_level(lsfm_context* ctx, const DevBatch& Y, const std::vector<int>& target_ref, int next_level, int step_hint,
+                         const unsigned long long* level_keys, int level_nnzb)
 {
 	ctx->drop_prepared();
 	if (!Y.M || Y.B < 2) return;
@@ -134,7 +135,7 @@ void prefetch_next_level(lsfm_context* ctx, const DevBatch& Y, const std::vector
 		OnStream on(ctx, ctx->stream3, &sa); // (the small arena of the level's parity)
 		int* d_tref = ctx->scratch.alloc<int>(Y.B);
 		h2d(ctx, d_tref, target_ref.data(), sizeof(int) * (size_t)Y.B);
-		ok = schur_pattern_prefetch(ctx, Y, d_tref, ctx->solved_keys, ctx->solved_nnzb, pl->sy, whole ? &counts : nullptr, !next_small, whole ? &kept : nullptr);
+		ok = schur_pattern_prefetch(ctx, Y, d_tref, level_keys, level_nnzb, pl->sy, whole ? &counts : nullptr, !next_small, whole ? &kept : nullptr);
 		if (ok)
 		{
 			if (!next_small) chol_fetch(ctx, pl->sy, Y.pose_origin, pl->hin); // (synchronises stream3: the counts have arrived too)
@@ -251,9 +252,6 @@ static LevelStructure level_structure(lsfm_context* ctx, const SolveIO& io, Solv
 	LevelStructure ls;
 	SchurSystem& sy = ls.sy;
 	CholDev& ch = ls.ch;
-	// the caller's mark (evA) of the point where the joint map's index arrays were complete: consumed by whichever case runs
-	const bool pattern_dep = ctx->pattern_dep;
-	ctx->pattern_dep = false;
 	// K9 behind the pattern; the chain of the factorisation starts at evK
 	auto assemble = [&]() {
 		build_schur_values(ctx, io, sy);
@@ -317,7 +315,7 @@ static LevelStructure level_structure(lsfm_context* ctx, const SolveIO& io, Solv
 		}
 		if (have) LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->evB, 0));
 	}
-	else if (pattern_dep && !ctx->comm)
+	else if (io.index_arrays_at_evA && !ctx->comm)
 	{
 		// 5. the pattern depends on index arrays only: the caller marked the point of the main stream where those were complete
 		// (evA) and went on to enqueue its right-hand-side kernels -- the pattern is built on the side stream next to them
@@ -350,11 +348,10 @@ static LevelStructure level_structure(lsfm_context* ctx, const SolveIO& io, Solv
 // A level of small systems (at most 16 poses each): assembled, factored and solved by one launch (lsfm_small.hip) -- no pattern of S,
 // no symbolic factorisation; the level above builds its pattern from its own joint maps when this one leaves none
 // (schur_pattern_prefetch / schur_pattern_early_issue).  warm: the level has a recorded plan (SolvePlan::small)
-static int solve_level_dense(lsfm_context* ctx, const SolveIO& io, int strips, bool warm, hipEvent_t eb, hipEvent_t ec, hipEvent_t ed)
+static SolveOutcome solve_level_dense(lsfm_context* ctx, const SolveIO& io, int strips, bool warm, hipEvent_t eb, hipEvent_t ec, hipEvent_t ed)
 {
 	hipStream_t s = ctx->stream;
 	LevelPlan* lp = ctx->plan;
-	ctx->pattern_dep = false;
 	if (!warm) schur_pattern_early_drop(ctx);
 	int* d_small = nullptr; // [2] status of the small path + (as a double behind them) the level's largest relative residual
 	auto enqueue = [&]() {
@@ -372,13 +369,13 @@ static int solve_level_dense(lsfm_context* ctx, const SolveIO& io, int strips, b
 	if (warm) enqueue();
 	LSFM_REC_T(ec, s);
 	LSFM_REC_T(ed, s); if (roctx().mark) roctx().mark("lsfm solve: end");
-	ctx->ev_solve_end = ed;
-	ctx->solved_keys = nullptr; ctx->solved_nnzb = 0; // (no pattern left for the level above)
+	SolveOutcome oc; // (keys: no pattern left for the level above)
+	oc.end = ed;
+	oc.steps_used = 1;
 	if (ctx->stats) ctx->stats->pcg_iterations += 1;
-	ctx->steps_used = 1;
 	// (a plan made one level ahead is the run's own: nothing to record, nothing to stop for)
 	const bool deferred = ctx->in_tree_run && ctx->d_run && (warm || !lp || lp == &ctx->pre_plan);
-	if (deferred) return 0; // the kernel left its verdict in the run's device record (read at the end of the run)
+	if (deferred) return oc; // the kernel left its verdict in the run's device record (read at the end of the run)
 	int hs[4];
 	d2h_ints(ctx, d_small, hs, 4); // synchronises
 	if (hs[1]) LSFM_FAIL(LSFM_ERR_NOT_SPD, "Schur system is not positive definite (system " + std::to_string(hs[1] - 1) + " of the level)");
@@ -392,7 +389,8 @@ static int solve_level_dense(lsfm_context* ctx, const SolveIO& io, int strips, b
 		small_plan->its = 1; small_plan->mixed = false; small_plan->rel_tol = ctx->pcg.rel_tol; small_plan->small = true;
 		lp->solve = small_plan;
 	}
-	return hs[0];
+	oc.not_converged = hs[0];
+	return oc;
 }
 
 // LSFM_FACTOR_DIGEST=1 (tests): digests of S and of the factor into the run's device record, and -- one GPU -- the same system
@@ -467,7 +465,7 @@ static void debug_conv(lsfm_context* ctx, const SolveIO& io, const SchurSystem& 
 // One level's camera systems: the dense path for a level of small systems; otherwise the level's structure, the refinement's set-up,
 // the factorisation with the first forward substitution riding on it, the refinement, the back-substitution, and the outcome --
 // left in the run's device record, or read here and, for a level that converged, kept with its structure as the level's plan
-int solve_batch(lsfm_context* ctx, const SolveIO& io)
+SolveOutcome solve_batch(lsfm_context* ctx, const SolveIO& io)
 {
 	hipStream_t s = ctx->stream;
 	const int M = io.M;
@@ -504,7 +502,6 @@ int solve_batch(lsfm_context* ctx, const SolveIO& io)
 	// left in the run's device record and read once at the end of the run; a stage-level call, and a level whose structure is
 	// being recorded as a plan, reads it here
 	const bool deferred = warm || (ctx->in_tree_run && ctx->d_run && !lp);
-	ctx->solved_keys = sy.upper_keys; ctx->solved_nnzb = sy.nnzb;
 	const PcgSteps steps{ warm, deferred, sp ? sp->its : 0, sp ? sp->mixed : false, sp ? sp->rel_tol : 0.0 };
 	const PcgResult res = pcg_run(ctx, io, sy, ch, w, steps);
 	if (dbg)
@@ -531,7 +528,9 @@ int solve_batch(lsfm_context* ctx, const SolveIO& io)
 	launch_backsub(ctx, io, sy, io.x_pose);
 	LSFM_CHECK_HIP(hipGetLastError());
 	LSFM_REC_T(ed, s); if (roctx().mark) roctx().mark("lsfm solve: end");
-	ctx->ev_solve_end = ed;
+	SolveOutcome oc;
+	oc.keys = sy.upper_keys; oc.nnzb = sy.nnzb;
+	oc.end = ed;
 	if (ctx->stats)
 	{
 		lsfm_stats* st = ctx->stats;
@@ -544,14 +543,14 @@ int solve_batch(lsfm_context* ctx, const SolveIO& io)
 		st->spmv_bytes += spmv_bytes(sy);
 		st->spmv_nnzb_upper_last = sy.nnzb; st->spmv_rows_last = M;
 	}
-	ctx->steps_used = res.planned ? 0 : std::max(res.its, 1);
+	oc.steps_used = res.planned ? 0 : std::max(res.its, 1);
 	if (deferred)
 	{
 		if (warm && !res.planned) { sp->its = std::max(res.its, 1); sp->mixed = ctx->pcg.mixed; sp->rel_tol = ctx->pcg.rel_tol; } // precision / tolerance changed: the count was re-learnt
 		static const bool dbg_conv = getenv("LSFM_DEBUG_CONV") != nullptr;
 		if (dbg_conv) debug_conv(ctx, io, sy, ch, w.seg);
 		hipLaunchKernelGGL(k_pcg_run_stats, dim3((io.nseg + 127) / 128), dim3(128), 0, s, io.nseg, w.seg, ctx->d_run);
-		return 0; // the outcome is read at the end of the run (lsfm_tree_run)
+		return oc; // the outcome is read at the end of the run (lsfm_tree_run)
 	}
 	double maxrel = 0;
 	int notconv = pcg_read_verdict(ctx, io, w, &maxrel); // synchronises
@@ -568,7 +567,8 @@ int solve_batch(lsfm_context* ctx, const SolveIO& io)
 	}
 	// what depends on the structure only stays with the tree level for its next runs
 	if (lp && !lp->solve && notconv == 0) lp->solve = solve_plan_store(ctx, sy, ch, std::max(res.its, 1));
-	return notconv;
+	oc.not_converged = notconv;
+	return oc;
 }
 
 } // namespace lsfm

@@ -179,7 +179,6 @@ void marg_structure(lsfm_context* ctx, Arena& ar, const MargView& in, const int*
 	io.U = in.U; io.Ui = in.Ui; io.Uj = in.Uj; io.photo = w.dph; io.fptr = w.dfp; io.ea = ea; io.eb = eb;
 	io.seg_rows.assign(1, M);
 	w.sy = SchurSystem();
-	ctx->pattern_dep = false;
 	build_schur_pattern(ctx, io, w.sy);
 	LSFM_CHECK_HIP(hipGetLastError());
 }

@@ -250,7 +250,7 @@ PcgResult pcg_run(lsfm_context* ctx, const SolveIO& io, const SchurSystem& sy, c
 	// the step count was recorded with the preconditioner in this precision, for this tolerance, under this cap
 	// ... or, in a run that analyses, what an earlier run of the same tree needed at this level (a guess about values, checked at
 	// the end of the run like a plan's count)
-	const bool hinted = !steps.warm && steps.deferred && ctx->step_hint > 0 && ctx->step_hint <= maxit;
+	const bool hinted = !steps.warm && steps.deferred && io.step_hint > 0 && io.step_hint <= maxit;
 	const bool planned_run = hinted || (steps.warm && steps.mixed == mixed && steps.rel_tol == ctx->pcg.rel_tol && steps.its <= maxit);
 	// (a run that counts its steps does not stop to ask before the first one either: systems that start below their bound
 	// are frozen on the device, the step costs them nothing)
@@ -260,11 +260,11 @@ PcgResult pcg_run(lsfm_context* ctx, const SolveIO& io, const SchurSystem& sy, c
 	// for its count to vary from run to run -- one synth-16k run in
 	// eight asked for one more than the run before and had to be repeated as a whole: such levels get one step of margin; systems
 	// that are done are frozen on the device, the extra step costs them the launches only)
-	// A hinted level whose caller waits for the device at its end anyway (ctx->level_syncs: a Mono level that analyses) needs neither the
+	// A hinted level whose caller waits for the device at its end anyway (io.caller_syncs: a Mono level that analyses) needs neither the
 	// margin nor the repeat: it enqueues the steps the run before needed, asks ONCE whether every system is done, and goes on asking
 	// step by step if not -- one synth-16k analysing run in eight to twenty was repeated as a whole (twice its time) until round 6.
-	const bool ask_after = hinted && ctx->level_syncs && !ctx->comm;
-	const int base_steps = hinted ? ctx->step_hint : (planned_run ? steps.its : maxit);
+	const bool ask_after = hinted && io.caller_syncs && !ctx->comm;
+	const int base_steps = hinted ? io.step_hint : (planned_run ? steps.its : maxit);
 	const int planned = (planned_run && !ask_after && base_steps >= (mixed ? 3 : 2)) ? std::min(base_steps + 1, maxit) : base_steps;
 	bool counting = planned_run; // (the steps are enqueued without asking)
 	// (an extension is for the run that needs ONE step more than the run before -- the counts scatter by one or two; a system that is

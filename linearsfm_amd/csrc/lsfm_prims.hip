@@ -405,7 +405,7 @@ static void alloc_arenas(lsfm_context* c, size_t bytes_each)
 	// ctx->pre keeps alive, and its index arrays live in sarena[]): wait for it and forget what was prepared BEFORE
 	// anything is freed -- grow_arenas() is called from the handler of an LSFM_ERR_OOM thrown mid-level
 	c->drop_prepared();
-	c->early.reset(); c->solved_keys = nullptr; c->solved_nnzb = 0; // (pointers into the arenas about to go)
+	c->early.reset(); // (pointers into the arenas about to go)
 	c->arena[0].destroy(); c->arena[1].destroy(); c->arena[2].destroy(); c->scratch.destroy(); c->sarena[0].destroy(); c->sarena[1].destroy();
 	c->pre.reset();
 	c->arena[0].init(bytes_each);

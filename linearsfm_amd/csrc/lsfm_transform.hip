@@ -993,12 +993,12 @@ __global__ void k_tr_diag(int B, const TMap* __restrict__ tm, const double* __re
 template <int NH>
 static void launch_stage(lsfm_context* ctx, const DevBatch& in, DevBatch& out, const TMap* d_tm, const int* KU, const int* KW,
                          double* Dp, double* Cp, double* Gpose, double* PP, double nw_act_in, double nw_act_out, double nf_act,
-                         const std::function<TrRedirect(DevBatch&)>* hook)
+                         const TrHook* hook, const int* hub)
 {
 	hipStream_t s = ctx->stream;
 	const int M = in.M;
 	bool ev_entries = false, u_early = false;
-	if (!in.NF && hook) (void)(*hook)(out); // nothing to redirect, but the consumer still lays out its container
+	if (!in.NF && hook) (void)(*hook)(out, hub); // nothing to redirect, but the consumer still lays out its container
 	if (in.NF)
 	{
 		// per feature: D_f and C_s,f (written by the prologue, read per W block), sums of W^T C_s,k (entries -> epilogue)
@@ -1010,7 +1010,7 @@ static void launch_stage(lsfm_context* ctx, const DevBatch& in, DevBatch& out, c
 		                   out.fptr, out.V, FD, finfo, hubJ);
 		// the W blocks go to this container -- or straight into the next one when the consumer has laid it out already
 		TrRedirect rd;
-		if (hook) rd = (*hook)(out);
+		if (hook) rd = (*hook)(out, hub);
 		if (!rd.W) { rd = TrRedirect(); rd.wbase = out.fptr; rd.W = out.W; rd.photo = out.photo; rd.feature = out.feature; }
 		// The U blocks' kernel reads nothing the feature kernels write (U, the poses' Jacobians, the kept-block ranks) and ADDS to the pose
 		// rows of G like they do: it goes to the side stream HERE, beside the block kernel of the features, not behind it -- one lane per
@@ -1113,7 +1113,7 @@ int level_targets(const DevBatch& X, bool mono, std::vector<int>& tref, std::vec
 
 void transform_batch(lsfm_context* ctx, Arena& ar, const DevBatch& in, const std::vector<int>& target_ref,
                      const std::vector<int>& target_scap, const std::vector<int>& target_fix, bool mono, DevBatch& out,
-                     bool alias_passthrough, const std::function<TrRedirect(DevBatch&)>* hook)
+                     bool alias_passthrough, const TrHook* hook)
 {
 	hipStream_t s = ctx->stream;
 	const int B = in.B, nh = mono ? 2 : 1;
@@ -1184,18 +1184,16 @@ void transform_batch(lsfm_context* ctx, Arena& ar, const DevBatch& in, const std
 	batch_fill_maps(ctx, out);
 
 	const int M = in.M;
+	int* d_hub = nullptr; // [B] hub pose of every transformed map, for the hook
 	if (M)
 	{
 		hipLaunchKernelGGL(k_tr_find, dim3((M + 255) / 256), dim3(256), 0, s, in.pose_id, in.pose_map, M, d_tm);
 		hipLaunchKernelGGL(k_tr_params1, dim3((B + 127) / 128), dim3(128), 0, s, in.pose, d_tm, B, d_err);
 		hipLaunchKernelGGL(k_tr_new_poses, dim3((M + 255) / 256), dim3(256), 0, s, in.pose, in.pose_id, in.pose_map, M, d_tm, out.pose, out.pose_id);
 		// (for the consumer laid out inside the hook -- a Stereo join that analyses --: what the early pattern of S is made from)
-		int* d_hub = (hook && !mono && B) ? ctx->scratch.alloc<int>(B) : nullptr;
+		d_hub = (hook && !mono && B) ? ctx->scratch.alloc<int>(B) : nullptr;
 		hipLaunchKernelGGL(k_tr_params2, dim3((B + 127) / 128), dim3(128), 0, s, out.pose, d_tm, B, d_hub);
-		ctx->tr_in = nullptr; ctx->tr_hub = nullptr;
-		if (d_hub) { ctx->tr_in = &in; ctx->tr_hub = d_hub; }
 	}
-	else { ctx->tr_in = nullptr; ctx->tr_hub = nullptr; }
 	double* Dp = ctx->scratch.alloc<double>((size_t)M * 36);
 	// Stereo: + the 27 pose-dependent entries of (D_k, C_k) packed per pose, for k_tr_entries (after the one C section)
 	double* Cp = ctx->scratch.alloc<double>((size_t)M * 36 * nh + (nh == 1 ? (size_t)M * 27 : (size_t)M * 63));
@@ -1309,11 +1307,10 @@ void transform_batch(lsfm_context* ctx, Arena& ar, const DevBatch& in, const std
 			nw_act_in += in.w_off[b + 1] - in.w_off[b]; nw_act_out += out.w_off[b + 1] - out.w_off[b];
 			nf_act += in.feat_off[b + 1] - in.feat_off[b];
 		}
-	if (mono) launch_stage<2>(ctx, in, out, d_tm, KU, KW, Dp, Cp, Gpose, PP, nw_act_in, nw_act_out, nf_act, hook);
-	else launch_stage<1>(ctx, in, out, d_tm, KU, KW, Dp, Cp, Gpose, PP, nw_act_in, nw_act_out, nf_act, hook);
+	if (mono) launch_stage<2>(ctx, in, out, d_tm, KU, KW, Dp, Cp, Gpose, PP, nw_act_in, nw_act_out, nf_act, hook, d_hub);
+	else launch_stage<1>(ctx, in, out, d_tm, KU, KW, Dp, Cp, Gpose, PP, nw_act_in, nw_act_out, nf_act, hook, d_hub);
 	ctx->mark("tr_done");
 	LSFM_CHECK_HIP(hipGetLastError());
-	ctx->tr_in = nullptr; ctx->tr_hub = nullptr;
 	// Scratch is released for the caller's next stage: everything that touches it is ordered on the main stream (the side
 	// stream's part rejoins it through evB above).  A first run also stops here so that a failure surfaces at its stage --
 	// unless its consumer was laid out inside the hook: that one goes on enqueuing (its solve stops for the device soon

@@ -27,15 +27,16 @@ bool level_plan(lsfm_context* ctx, lsfm_tree* t, int level)
 
 // LSFM_LEVEL_GAPS=1: what the device waited for the host between the levels of a run (the event behind a level's solve was
 // handed over long before the host got here; this one is stamped when the stream reaches it, or when it arrives)
-void level_gap(lsfm_context* ctx, hipEvent_t level_begin)
+void level_gap(lsfm_context* ctx, hipEvent_t prev_solve_end, hipEvent_t level_begin)
 {
 	static const bool gaps = getenv("LSFM_LEVEL_GAPS") != nullptr;
-	if (gaps && ctx->ev_solve_end && ctx->in_tree_run) ctx->defer_time(ctx->ev_solve_end, level_begin, &ctx->dbg_gap_ms);
-	ctx->ev_solve_end = nullptr;
+	if (gaps && prev_solve_end) ctx->defer_time(prev_solve_end, level_begin, &ctx->dbg_gap_ms);
 }
 
-// one level: transform the maps that need it, then join the pairs
-void run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level)
+// one level: transform the maps that need it, then join the pairs.  prev_solve_end: the event behind the solve of the level below
+// (null: none); inject_level: tests -- the level in which this rank's pass fails (LSFM_TEST_FAIL_RANK), -1: none.  Returns the event
+// behind this level's solve
+hipEvent_t run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level, hipEvent_t prev_solve_end, int inject_level)
 {
 	const bool analysing = level_plan(ctx, t, level);
 	char rname[48];
@@ -43,8 +44,8 @@ void run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level)
 	Range rlevel(rname);
 	ctx->mark("level");
 	if ((int)t->step_hint.size() <= level) t->step_hint.resize(level + 1, 0);
-	ctx->step_hint = t->step_hint[level];
-	ctx->steps_used = 0;
+	// what an earlier run of this tree needed here (0: nothing known; SolveIO::step_hint)
+	const int step_hint = t->step_hint[level];
 	DevBatch& X = t->level;
 	const int npairs = X.B / 2;
 	std::vector<int> tref, tscap, tfix;
@@ -52,7 +53,7 @@ void run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level)
 	// stage times from events on the stream (a warm level is only enqueued: host clocks say nothing about it)
 	hipEvent_t e_t0 = ctx->pool_event(), e_t1 = ctx->pool_event(), e_t2 = ctx->pool_event();
 	LSFM_REC_T(e_t0, ctx->stream);
-	level_gap(ctx, e_t0);
+	level_gap(ctx, prev_solve_end, e_t0);
 	// three arenas in rotation: X (this level; slot -1 = the resident inputs, never written) stays alive until the join
 	// is done, because the W blocks of the maps the transform passes through are read from X, not copied (W_alias)
 	const int so = t->slot < 0 ? 0 : (t->slot + 1) % 3, sm = t->slot < 0 ? 1 : (t->slot + 2) % 3;
@@ -61,15 +62,16 @@ void run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level)
 	other.reset();
 	mine.reset();
 	DevBatch Xt, Y;
+	SolveOutcome oc;
 	// tests (tests/test_gpu_sharded.py): ONE rank of a feature-sharded run fails in the middle of a level, between two sums
-	const bool inject = ctx->inject_level == level;
+	const bool inject = inject_level == level;
 	if (t->mono)
 	{
 		{ Range r("lsfm transform"); transform_batch(ctx, other, X, tref, tscap, tfix, true, Xt, true); }
 		if (inject) LSFM_FAIL(LSFM_ERR_INTERNAL, "injected failure of this rank (LSFM_TEST_FAIL_RANK)");
 		LSFM_REC_T(e_t1, ctx->stream);
 		Range r("lsfm join + solve");
-		join_batch_mono(ctx, mine, Xt, Y, nullptr, nullptr);
+		oc = join_batch_mono(ctx, mine, Xt, Y, nullptr, nullptr, step_hint);
 	}
 	else
 	{
@@ -77,8 +79,8 @@ void run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level)
 		// W stage), and the transform's block kernel writes every W' block straight to its place in the joint map
 		JoinState js;
 		const size_t smark = ctx->scratch.mark();
-		std::function<TrRedirect(DevBatch&)> hook = [&](DevBatch& mid) {
-			join_stereo_prepare(ctx, mine, mid, Y, js);
+		TrHook hook = [&](DevBatch& mid, const int* hub) {
+			join_stereo_prepare(ctx, mine, mid, Y, js, &X, hub);
 			TrRedirect rd;
 			rd.wbase = js.wbase; rd.newf = js.newf; rd.W = Y.W; rd.photo = Y.photo; rd.feature = Y.feature; rd.srcf = js.srcf;
 			return rd;
@@ -88,7 +90,7 @@ void run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level)
 		LSFM_REC_T(e_t1, ctx->stream);
 		Range r("lsfm join + solve");
 		js.smark = smark; // everything of this level goes at once
-		join_stereo_finish(ctx, Xt, Y, js, nullptr, nullptr);
+		oc = join_stereo_finish(ctx, Xt, Y, js, nullptr, nullptr, step_hint);
 		ctx->pre_plan = LevelPlan(); // (consumed, if it was this level's)
 		ctx->pre_plan_level = -1;
 		if (analysing && Y.B > 1 && !ctx->comm)
@@ -96,13 +98,12 @@ void run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level)
 			// while the device solves this level: the next level's pattern and symbolic factorisation (lsfm_level.hip)
 			std::vector<int> nref, nscap, nfix;
 			level_targets(Y, false, nref, nscap, nfix);
-			prefetch_next_level(ctx, Y, nref, level + 1, level + 1 < (int)t->step_hint.size() ? t->step_hint[level + 1] : 0);
+			prefetch_next_level(ctx, Y, nref, level + 1, level + 1 < (int)t->step_hint.size() ? t->step_hint[level + 1] : 0, oc.keys, oc.nnzb);
 		}
 		else ctx->drop_prepared();
 	}
 	LSFM_REC_T(e_t2, ctx->stream);
-	if (ctx->steps_used > 0) t->step_hint[level] = ctx->steps_used;
-	ctx->step_hint = 0;
+	if (oc.steps_used > 0) t->step_hint[level] = oc.steps_used;
 	ctx->plan = nullptr;
 	t->level = Y;
 	t->slot = sm;
@@ -112,10 +113,11 @@ void run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level)
 		ctx->defer_time(e_t1, e_t2, &st->t_join_ms);
 		st->levels++; st->joins += npairs; st->transforms += ntr;
 	}
+	return oc.end;
 }
 
 // one pass over the tree; with valid plans nothing in here waits for the device before the final synchronisation
-void tree_pass(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st)
+void tree_pass(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int inject_level)
 {
 	Range rrun("lsfm tree run");
 	// level 0 reads the resident inputs where they are (no level writes its input), so a tree can be run repeatedly
@@ -124,8 +126,7 @@ void tree_pass(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st)
 	ctx->generation++;
 	ctx->arena[0].reset(); ctx->arena[1].reset(); ctx->arena[2].reset(); ctx->scratch.reset();
 	ctx->stage_off = 0; // the stream is idle: the staging ring starts over
-	ctx->drop_prepared(); ctx->early.reset(); ctx->solved_keys = nullptr; ctx->solved_nnzb = 0; // nothing prepared by an earlier run
-	ctx->ev_solve_end = nullptr;
+	ctx->drop_prepared(); ctx->early.reset(); // nothing prepared by an earlier run
 	LSFM_CHECK_HIP(hipMemsetAsync(ctx->d_run, 0, sizeof(RunStatsDev), ctx->stream));
 	static const bool poison = getenv("LSFM_POISON") != nullptr; // debug: every byte a run has not written itself reads as NaN / -1
 	if (poison)
@@ -138,7 +139,8 @@ void tree_pass(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st)
 	const int nlev = tree_levels(t->N);
 	if ((int)t->plans.size() != nlev + 1) t->plans.assign(nlev + 1, LevelPlan());
 	int level = 0;
-	while (t->level.B > 1 && (t->stop_level <= 0 || level < t->stop_level)) run_level(ctx, t, st, level++);
+	hipEvent_t solve_end = nullptr; // behind the solve of the level just run (LSFM_LEVEL_GAPS)
+	for (; t->level.B > 1 && (t->stop_level <= 0 || level < t->stop_level); level++) solve_end = run_level(ctx, t, st, level, solve_end, inject_level);
 	// final map back to its first frame (Imp.cpp:2039-2063 / 6613-6630)
 	DevBatch& X = t->level;
 	if (t->final_reanchor && X.B == 1 && X.Ref[0] > X.FRef[0])
@@ -186,11 +188,9 @@ Inject test_switches(const lsfm_context* ctx, int attempt)
 enum class Pass { DONE, AGAIN, AGAIN_GROWN };
 Pass run_pass(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int attempt, int inject_level, std::unique_ptr<Error>& pass_error)
 {
-	ctx->inject_level = inject_level;
-	try { tree_pass(ctx, t, st); }
+	try { tree_pass(ctx, t, st, inject_level); }
 	catch (const Error& e)
 	{
-		ctx->inject_level = -1;
 		if (ctx->comm)
 		{
 			// feature-sharded run: an error of this rank alone (LSFM_FAIL inside the pass) must still reach the exchange of the flags, or
@@ -215,7 +215,6 @@ Pass run_pass(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int attempt, int 
 		if (getenv("LSFM_DEBUG")) fprintf(stderr, "[lsfm] arenas grown to %zu MiB each after: %s\n", ctx->arena_bytes >> 20, e.msg.c_str());
 		return Pass::AGAIN_GROWN; // (not a numerical repeat)
 	}
-	ctx->inject_level = -1;
 	return Pass::DONE;
 }
 
@@ -352,18 +351,15 @@ int tree_run(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* stats)
 	lsfm_stats local;
 	memset(&local, 0, sizeof local);
 	lsfm_stats* st = stats ? stats : &local;
-	ctx->stats = st;
-	struct InRun { lsfm_context* c; InRun(lsfm_context* x, Comm* cm) : c(x) { c->in_tree_run = true; c->comm = cm; } ~InRun() { c->in_tree_run = false; c->comm = nullptr; } }
-		in_run(ctx, t->comm.fn ? &t->comm : nullptr);
+	struct InRun {
+		lsfm_context* c;
+		InRun(lsfm_context* x, Comm* cm, lsfm_stats* s) : c(x) { c->in_tree_run = true; c->comm = cm; c->stats = s; }
+		~InRun() { c->in_tree_run = false; c->comm = nullptr; c->stats = nullptr; }
+	} in_run(ctx, t->comm.fn ? &t->comm : nullptr, st);
 	LSFM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-	try
-	{
-		run_attempts(ctx, t, st);
-		ctx->flush_times();
-		if (getenv("LSFM_LEVEL_GAPS")) { fprintf(stderr, "[lsfm] device idle between the levels of this run: %.3f ms\n", ctx->dbg_gap_ms); ctx->dbg_gap_ms = 0.0; }
-	}
-	catch (...) { ctx->stats = nullptr; throw; }
-	ctx->stats = nullptr;
+	run_attempts(ctx, t, st);
+	ctx->flush_times();
+	if (getenv("LSFM_LEVEL_GAPS")) { fprintf(stderr, "[lsfm] device idle between the levels of this run: %.3f ms\n", ctx->dbg_gap_ms); ctx->dbg_gap_ms = 0.0; }
 	t->done = true;
 	t->generation = ctx->generation;
 	return st->not_converged ? LSFM_NOT_CONVERGED : LSFM_OK;

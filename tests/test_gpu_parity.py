@@ -426,21 +426,43 @@ def test_subtree_sharding_on_device_equals_single_tree(ctx, mono):
     assert feat_param_err(merged["stVal"], single["stVal"], single["stno"]) < 1e-8
 
 
-@pytest.mark.parametrize("mono", [False, True])
-def test_repeated_runs_of_a_resident_tree(ctx, mono):
+# (the ids of the cases without in-between calls are the ones they had before `between` existed)
+@pytest.mark.parametrize("mono,between", [(False, None), (True, None), (False, "other calls"), (True, "other calls")],
+                         ids=["False", "True", "False-other calls", "True-other calls"])
+def test_repeated_runs_of_a_resident_tree(ctx, mono, between):
     """lsfm_tree_run on the same upload: the first run analyses every level (container sizes, pattern of S, symbolic
     factorisation) and leaves that with the tree; the next runs reuse it and are enqueued without host round trips; with
-    plans switched off every run analyses again.  All three give the same map (summation order of atomics aside)."""
+    plans switched off every run analyses again.  All three give the same map (summation order of atomics aside).
+    between="other calls": other work on the same context between every two runs -- a tree of an unrelated set, a
+    marginalisation and a covariance, each of which solves systems of its own -- leaves nothing behind that a level of the
+    resident tree picks up; the first run is the map a plain divide_conquer of the set gives.  (Smaller sets: seven levels with
+    unpaired carries at 11 and 3 maps, the low ones on the dense path, the upper ones on the sparse pipeline.)"""
     from linearsfm_amd import api
-    maps = synth.make_mono_set(90, 20, 4, seed=21, **synth.SPIRAL) if mono else synth.make_stereo_set(300, 20, 5, seed=21, lap=50)
+    if between:
+        maps = synth.make_mono_set(88, new_per_frame=40, vis=4, seed=6, **synth.SPIRAL) if mono else synth.make_stereo_set(88, new_per_frame=20, vis=5, seed=5)
+        unrelated = [m.__dict__ for m in (synth.make_mono_set(8, 6, 5, seed=4) if mono else synth.make_stereo_set(8, 4, 5, seed=3))]
+    else:
+        maps = synth.make_mono_set(90, 20, 4, seed=21, **synth.SPIRAL) if mono else synth.make_stereo_set(300, 20, 5, seed=21, lap=50)
+
+    def other_calls(first):
+        if not between:
+            return
+        _, _, rc = ctx.divide_conquer(unrelated, mono)
+        assert rc == 0
+        reduced = ctx.marginalise(first, np.arange(int(first["n"])) % 2 == 1)
+        ctx.covariance(reduced, mono)
+
     t = ctx.tree_upload(maps, mono)
     try:
         s1, rc1 = ctx.tree_run(t)
         a = ctx.tree_download(t)
+        other_calls(a)
         s2, rc2 = ctx.tree_run(t)
         b = ctx.tree_download(t)
+        other_calls(a)
         s3, rc3 = ctx.tree_run(t)
         c = ctx.tree_download(t)
+        other_calls(a)
         ctx.tree_set_plans(t, False)
         s4, rc4 = ctx.tree_run(t)
         d = ctx.tree_download(t)
@@ -449,7 +471,12 @@ def test_repeated_runs_of_a_resident_tree(ctx, mono):
     assert rc1 == rc2 == rc3 == rc4 == 0
     for s in (s1, s2, s3, s4):
         assert s["not_converged"] == 0 and s["max_rel_residual"] < 1e-9, s
-    for other in (b, c, d):
+    others = [b, c, d]
+    if between:
+        plain, sp, rcp = ctx.divide_conquer(maps, mono)
+        assert rcp == 0 and sp["not_converged"] == 0 and sp["max_rel_residual"] < 1e-9, sp
+        others.append(plain)
+    for other in others:
         assert np.array_equal(other["stno"], a["stno"])
         for k in ("Ui", "Uj", "photo", "feature"):
             assert np.array_equal(other[k], a[k]), k
