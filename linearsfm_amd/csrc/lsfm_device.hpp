@@ -103,6 +103,21 @@ __device__ __forceinline__ void mv3(const double* R, const double* v, double* o)
 	o[1] = R[3] * v[0] + R[4] * v[1] + R[5] * v[2];
 	o[2] = R[6] * v[0] + R[7] * v[1] + R[8] * v[2];
 }
+// What one information block adds to the right-hand sides of a join, with the estimates of the map it came from:
+// a 6x3 W block (pose, feature): yp = W x_f for the pose, yf = W^T x_p for the feature (the three-term sums as plain expressions:
+// the compiler's contraction decides how they are rounded, as it did where they were written out)
+__device__ __forceinline__ void w_block_rhs(const double* W, const double* xf, const double* xp, double* yp, double* yf)
+{
+#pragma unroll
+	for (int r = 0; r < 6; r++) yp[r] = W[3 * r] * xf[0] + W[3 * r + 1] * xf[1] + W[3 * r + 2] * xf[2];
+	mtm<6, 3, 1, false>(W, xp, yf);
+}
+// a 6x6 U block (a, b): ya = U x_b for pose a and, off the diagonal, yb = U^T x_a for pose b (a diagonal block leaves yb alone)
+__device__ __forceinline__ void u_block_rhs(const double* U, const double* xa, const double* xb, bool offdiag, double* ya, double* yb)
+{
+	mm<6, 6, 1, false>(U, xb, ya);
+	if (offdiag) mtm<6, 6, 1, false>(U, xa, yb);
+}
 
 // 3x3 symmetric inverse written back symmetrised from the upper triangle (pba_inverseV, Imp.cpp:3022-3042)
 __device__ __forceinline__ void inv3_sym(const double* a, double* o)
@@ -364,6 +379,13 @@ __device__ __forceinline__ void tile_scatter_add_rot(int* keys, double* vals, in
 		const double v = stage[i];
 		if (sl >= 0) lds_add_f64(vals + sl * N + i, v); else atomic_add_f64(gdst + i, v);
 	}
+}
+// the empty table; a __syncthreads() before its first use
+template <int N>
+__device__ __forceinline__ void tile_clear(int* keys, double* vals, int cap)
+{
+	for (int i = threadIdx.x; i < cap; i += blockDim.x) keys[i] = -1;
+	for (int i = threadIdx.x; i < cap * N; i += blockDim.x) vals[i] = 0.0;
 }
 // after a __syncthreads(): every touched accumulator leaves the work-group once, N contiguous adds at gbase + key*N
 template <int N>

@@ -76,6 +76,18 @@ void join_match_features(lsfm_context* ctx, const DevBatch& in, int* match, int*
 	hipLaunchKernelGGL(k_join_hash_insert, dim3(nb), dim3(256), 0, s, in.NF, in.feat_id, in.feat_map, tab, tval, (unsigned long long)(cap - 1));
 	hipLaunchKernelGGL(k_join_hash_probe, dim3(nb), dim3(256), 0, s, in.NF, in.feat_id, in.feat_map, tab, tval, (unsigned long long)(cap - 1), match, unm);
 }
+JoinRanks join_rank_features(lsfm_context* ctx, const DevBatch& in)
+{
+	// (the three arrays first, the hash table of the matching after them: the high-water mark of the scratch arena depends on it)
+	JoinRanks jr;
+	jr.match = ctx->scratch.alloc<int>(in.NF + 1);
+	int* unm = ctx->scratch.alloc<int>(in.NF + 2);
+	jr.R = ctx->scratch.alloc<int>(in.NF + 2);
+	if (in.NF) join_match_features(ctx, in, jr.match, unm);
+	else dev_zero(ctx, unm, 2 * sizeof(int));
+	dev_exclusive_scan(ctx, unm, jr.R, in.NF);
+	return jr;
+}
 
 __global__ void k_gather_at(const int* __restrict__ src, const int* __restrict__ idx, int n, int* __restrict__ out)
 {
@@ -184,32 +196,20 @@ k_join_rhs_w(int NFY, const int* __restrict__ fptr_y, const double* __restrict__
 	__shared__ int sFp[RHS_TILE + 1];
 	__shared__ double sT[256 * 3];
 	const int f0 = blockIdx.x * RHS_TILE, nft = min(RHS_TILE, NFY - f0);
-	for (int i = threadIdx.x; i < ECAP; i += blockDim.x) ekeys[i] = -1;
-	for (int i = threadIdx.x; i < ECAP * 6; i += blockDim.x) evals[i] = 0.0;
+	tile_clear<6>(ekeys, evals, ECAP);
 	for (int i = threadIdx.x; i <= nft; i += blockDim.x) sFp[i] = fptr_y[f0 + i];
 	__syncthreads();
 	tile_runs<3>(nft, sFp, sT,
 		[&](int j, int, double* out) {
 			const int k = photo_y[j];
-			double W[18], xp[6], xf[3];
+			double W[18], xp[6], xf[3], y[6];
 			ld<18>(W, Wy + (size_t)j * 18);
 			ld<6>(xp, pose + (size_t)k * 6);
 			ld<3>(xf, feat + (size_t)srcf[j] * 3);
 			const int sl = lds_slot(ekeys, ECAP, k);
+			w_block_rhs(W, xf, xp, y, out);
 #pragma unroll
-			for (int r = 0; r < 6; r++)
-			{
-				const double y = W[3 * r] * xf[0] + W[3 * r + 1] * xf[1] + W[3 * r + 2] * xf[2];
-				if (sl >= 0) lds_add_f64(&evals[sl * 6 + r], y); else atomic_add_f64(eP + (size_t)k * 6 + r, y);
-			}
-#pragma unroll
-			for (int c = 0; c < 3; c++)
-			{
-				double sacc = 0.0;
-#pragma unroll
-				for (int r = 0; r < 6; r++) sacc = fma(W[3 * r + c], xp[r], sacc);
-				out[c] = sacc;
-			}
+			for (int r = 0; r < 6; r++) { if (sl >= 0) lds_add_f64(&evals[sl * 6 + r], y[r]); else atomic_add_f64(eP + (size_t)k * 6 + r, y[r]); }
 		},
 		[&](int fl, int q, double sum, bool) { eF[(size_t)(f0 + fl) * 3 + q] += sum; });
 	tile_flush<6>(ekeys, evals, ECAP, eP); // tile_runs ends with a barrier
@@ -225,8 +225,7 @@ __global__ void __launch_bounds__(128) k_join_rhs_u(int NU, const double* __rest
 {
 	__shared__ int ekeys[RHSU_CAP];
 	__shared__ double evals[RHSU_CAP * 6];
-	for (int q = threadIdx.x; q < RHSU_CAP; q += blockDim.x) ekeys[q] = -1;
-	for (int q = threadIdx.x; q < RHSU_CAP * 6; q += blockDim.x) evals[q] = 0.0;
+	tile_clear<6>(ekeys, evals, RHSU_CAP);
 	__syncthreads();
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	const bool have = i < NU;
@@ -237,23 +236,7 @@ __global__ void __launch_bounds__(128) k_join_rhs_u(int NU, const double* __rest
 		a = Ui[i]; b = Uj[i];
 		double u[36];
 		ld<36>(u, U + (size_t)i * 36);
-		const double* xb = pose + (size_t)b * 6;
-		for (int r = 0; r < 6; r++)
-		{
-			double s = 0;
-			for (int c = 0; c < 6; c++) s = fma(u[6 * r + c], xb[c], s);
-			sa[r] = s;
-		}
-		if (a != b)
-		{
-			const double* xa = pose + (size_t)a * 6;
-			for (int c = 0; c < 6; c++)
-			{
-				double s = 0;
-				for (int r = 0; r < 6; r++) s = fma(u[6 * r + c], xa[r], s);
-				sb[c] = s;
-			}
-		}
+		u_block_rhs(u, pose + (size_t)a * 6, pose + (size_t)b * 6, a != b, sa, sb);
 	}
 	tile_scatter_add<6>(ekeys, evals, RHSU_CAP, a, eP + (size_t)a * 6, sa, have);
 	tile_scatter_add<6>(ekeys, evals, RHSU_CAP, b, eP + (size_t)b * 6, sb, have && a != b);
@@ -261,10 +244,48 @@ __global__ void __launch_bounds__(128) k_join_rhs_u(int NU, const double* __rest
 	tile_flush<6>(ekeys, evals, RHSU_CAP, eP);
 }
 
-__global__ void k_shift_segments(int n, const int* __restrict__ map_of, int* __restrict__ seg)
+void join_layout(int B, const std::vector<int>& feat_off, const std::vector<int>& pose_off, const std::vector<int>& rb, int shared, DevBatch& out,
+                 std::vector<JGroup>& grp, std::vector<int>& seg_rows, std::vector<unsigned char>& seg_active)
 {
-	int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) seg[i] = map_of[i] >> 1;
+	const int G = (B + 1) / 2;
+	out.feat_off.assign(G + 1, 0); out.pose_off.assign(G + 1, 0);
+	grp.resize(G); seg_rows.assign(G, 0); seg_active.assign(G, 0);
+	for (int g = 0; g < G; g++)
+	{
+		const int a = 2 * g, b = 2 * g + 1;
+		const bool pair = b < B;
+		JGroup& jg = grp[g];
+		jg.F0E = feat_off[a]; jg.nE = feat_off[a + 1] - jg.F0E;
+		jg.F0C = pair ? feat_off[b] : feat_off[a + 1]; jg.nC = pair ? feat_off[b + 1] - jg.F0C : 0;
+		jg.FY0 = out.feat_off[g];
+		jg.rC0 = pair ? rb[b] : 0;
+		out.feat_off[g + 1] = jg.FY0 + jg.nE + (pair ? rb[b + 1] - rb[b] : 0);
+		seg_active[g] = pair ? 1 : 0;
+		seg_rows[g] = pair ? pose_off[b + 1] - pose_off[a] - shared : pose_off[a + 1] - pose_off[a];
+		out.pose_off[g + 1] = out.pose_off[g] + seg_rows[g];
+	}
+}
+
+SolveIO join_solve_io(lsfm_context* ctx, const DevBatch& out, const unsigned char* d_act, const double* eP, const double* eF,
+                      const std::vector<int>& seg_rows, bool at_evA, int step_hint)
+{
+	SolveIO io;
+	io.M = out.M; io.NF = out.NF; io.NU = out.NU; io.NW = out.NW; io.nseg = out.B;
+	io.d_pose_seg = out.pose_map; io.d_feat_seg = out.feat_map; io.d_seg_active = d_act;
+	io.U = out.U; io.Ui = out.Ui; io.Uj = out.Uj; io.W = out.W; io.photo = out.photo; io.fptr = out.fptr; io.V = out.V;
+	io.ea = eP; io.eb = eF; io.d_pose_origin = out.pose_origin;
+	io.x_pose = out.pose; io.x_feat = out.feat;
+	io.seg_rows = seg_rows;
+	io.index_arrays_at_evA = at_evA; io.step_hint = step_hint;
+	small_level_offsets(ctx, out, io); // a level of small systems goes to the one-launch dense path, which walks the joins by their ranges (lsfm_small.hip)
+	return io;
+}
+
+void join_close(lsfm_context* ctx, size_t smark, const SolveOutcome& oc, bool whole_level)
+{
+	ctx->scratch.release(smark);
+	if (oc.not_converged > 0 && ctx->stats) ctx->stats->not_converged += oc.not_converged;
+	if (ctx->plan && whole_level) ctx->plan->valid = true; // every stage of the level has left its structure behind
 }
 
 // A Stereo join in two steps, so that a caller (the tree scheduler) can let the transform write its W blocks straight into
@@ -277,7 +298,6 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 	hipStream_t s = ctx->stream;
 	const int B = in.B, G = (B + 1) / 2;
 	st.smark = ctx->scratch.mark();
-	st.ar = &ar;
 
 	// ---- common features (K5) ---- (from the level's plan when it holds them: LevelIndex, lsfm_internal.hpp)
 	LevelPlan* plan = ctx->plan;
@@ -291,13 +311,8 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 	}
 	else
 	{
-		int* mt = ctx->scratch.alloc<int>(in.NF + 1);
-		int* unm = ctx->scratch.alloc<int>(in.NF + 2);
-		int* Rw = ctx->scratch.alloc<int>(in.NF + 2);
-		if (in.NF) join_match_features(ctx, in, mt, unm);
-		else dev_zero(ctx, unm, 2 * sizeof(int));
-		dev_exclusive_scan(ctx, unm, Rw, in.NF);
-		match = mt; R = Rw;
+		const JoinRanks jr = join_rank_features(ctx, in);
+		match = jr.match; R = jr.R;
 		if (ctx->warm()) rb = plan->join_rb; // known from an earlier run of the same tree
 		else
 		{
@@ -311,8 +326,8 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 			if (plan && plan != &ctx->pre_plan && ctx->in_tree_run)
 			{
 				// a resident tree records the level: its later runs skip the matching and its scan
-				plan->idx.match = level_index_keep(ctx, plan->idx, mt, (size_t)in.NF + 1);
-				plan->idx.R = level_index_keep(ctx, plan->idx, Rw, (size_t)in.NF + 2);
+				plan->idx.match = level_index_keep(ctx, plan->idx, jr.match, (size_t)in.NF + 1);
+				plan->idx.R = level_index_keep(ctx, plan->idx, jr.R, (size_t)in.NF + 2);
 				plan->idx.NF = in.NF;
 			}
 		}
@@ -320,30 +335,21 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 
 	out = DevBatch();
 	out.B = G; out.M = in.M; out.NU = in.NU; out.NW = in.NW;
-	out.pose_off.assign(G + 1, 0); out.feat_off.assign(G + 1, 0); out.u_off.assign(G + 1, 0); out.w_off.assign(G + 1, 0);
+	out.u_off.assign(G + 1, 0); out.w_off.assign(G + 1, 0);
 	out.Ref.resize(G); out.FRef.resize(G); out.ScaP.assign(G, 0); out.Fix.assign(G, 0); out.Sign.assign(G, 1); out.FScaP.assign(G, 0); out.FFix.assign(G, 0);
-	std::vector<JGroup> grp(G);
+	std::vector<JGroup> grp;
 	std::vector<unsigned char>& seg_active = st.seg_active;
 	std::vector<int>& seg_rows = st.seg_rows;
-	seg_active.assign(G, 0); seg_rows.assign(G, 0);
+	join_layout(B, in.feat_off, in.pose_off, rb, 0, out, grp, seg_rows, seg_active);
 	for (int g = 0; g < G; g++)
 	{
+		// U and W are reused as they are: a joint map's blocks are its two sources' back to back
 		const int a = 2 * g, b = 2 * g + 1;
-		const bool pair = b < B;
-		JGroup& jg = grp[g];
-		jg.F0E = in.feat_off[a]; jg.nE = in.feat_off[a + 1] - jg.F0E;
-		jg.F0C = pair ? in.feat_off[b] : in.feat_off[a + 1]; jg.nC = pair ? in.feat_off[b + 1] - jg.F0C : 0;
-		jg.FY0 = out.feat_off[g];
-		jg.rC0 = pair ? rb[b] : 0;
-		const int nun = pair ? rb[b + 1] - rb[b] : 0;
-		out.feat_off[g + 1] = jg.FY0 + jg.nE + nun;
-		out.pose_off[g] = in.pose_off[a]; out.u_off[g] = in.u_off[a]; out.w_off[g] = in.w_off[a];
-		out.Ref[g] = pair ? in.Ref[b] : in.Ref[a];     // Imp.cpp:2974
+		out.u_off[g] = in.u_off[a]; out.w_off[g] = in.w_off[a];
+		out.Ref[g] = b < B ? in.Ref[b] : in.Ref[a];    // Imp.cpp:2974
 		out.FRef[g] = in.FRef[a];                      // Imp.cpp:2624
-		seg_active[g] = pair ? 1 : 0;
-		seg_rows[g] = (pair ? in.pose_off[b + 1] : in.pose_off[a + 1]) - in.pose_off[a];
 	}
-	out.pose_off[G] = in.M; out.u_off[G] = in.NU; out.w_off[G] = in.NW;
+	out.u_off[G] = in.NU; out.w_off[G] = in.NW;
 	out.NF = out.feat_off[G];
 	const int NFY = out.NF;
 
@@ -422,11 +428,9 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 SolveOutcome join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch& out, JoinState& st, double* eP_out, double* eF_out, int step_hint)
 {
 	hipStream_t s = ctx->stream;
-	const int G = out.B, NFY = out.NF;
+	const int NFY = out.NF;
 	double *eP = st.eP, *eF = st.eF;
 	int* srcf = st.srcf;
-	const std::vector<unsigned char>& seg_active = st.seg_active;
-	const std::vector<int>& seg_rows = st.seg_rows;
 	// U is reused unchanged (global pose indices); copied here because the caller may still have been producing it
 	// (the transform's U stage) while the joint map was laid out
 	if (in.NU)
@@ -454,30 +458,20 @@ SolveOutcome join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch&
 	if (eF_out) d2h(ctx, eF_out, eF, (size_t)NFY * 3 * sizeof(double));
 
 	// ---- solve (K7-K11) ----
-	unsigned char* d_act = st.d_act;
-	SolveIO io;
-	io.M = in.M; io.NF = NFY; io.NU = in.NU; io.NW = in.NW; io.nseg = G;
-	io.d_pose_seg = out.pose_map; io.d_feat_seg = out.feat_map; io.d_seg_active = d_act;
-	io.U = out.U; io.Ui = out.Ui; io.Uj = out.Uj; io.W = out.W; io.photo = out.photo; io.fptr = out.fptr; io.V = out.V;
-	io.ea = eP; io.eb = eF; io.x0 = in.pose; io.d_fixed = nullptr; io.d_pose_origin = out.pose_origin;
-	io.x_pose = out.pose; io.x_feat = out.feat;
-	io.seg_rows = seg_rows;
-	io.index_arrays_at_evA = at_evA; io.step_hint = step_hint;
+	SolveIO io = join_solve_io(ctx, out, st.d_act, eP, eF, st.seg_rows, at_evA, step_hint);
+	io.x0 = in.pose;
 	RhsFused rhs;
 	if (fuse_rhs)
 	{
 		rhs.srcE = st.srcE; rhs.srcC = st.srcC; rhs.feat_src = in.feat; rhs.pose_src = in.pose; rhs.pose_map_src = in.pose_map;
 		io.rhs = &rhs;
 	}
-	small_level_offsets(ctx, out, io); // a level of small systems goes to the one-launch dense path, which walks the joins by their ranges (lsfm_small.hip)
 	const bool warm = ctx->warm();
 	const SolveOutcome oc = solve_batch(ctx, io);
 	// a level of a tree run is only enqueued (its scratch is reused in stream order, errors are read at the end of the run); a
 	// stage-level call stops here so that a failure surfaces at its stage
 	if (!warm && !ctx->in_tree_run) LSFM_CHECK_HIP(hipStreamSynchronize(s));
-	ctx->scratch.release(st.smark);
-	if (oc.not_converged > 0 && ctx->stats) ctx->stats->not_converged += oc.not_converged;
-	if (ctx->plan && !eP_out && !eF_out) ctx->plan->valid = true; // every stage of the level has left its structure behind
+	join_close(ctx, st.smark, oc, !eP_out && !eF_out);
 	return oc;
 }
 

@@ -10,7 +10,6 @@
 //   * the solve removes 7 scalars: the reference pose and the gauge-fixed translation of the scale pose
 //     (lmj_solveLinearSFMMono, Imp.cpp:6981-7026), then sets stVal[Fix] = Sign.
 #include <climits>
-#include <cstdlib>
 
 #include "lsfm_device.hpp"
 #include "lsfm_internal.hpp"
@@ -142,6 +141,7 @@ __global__ void k_mono_u_fill(int NU, const double* __restrict__ U, const int* _
 		for (int q = 0; q < 36; q++) atomic_add_f64(d + q, u[q]);
 	}
 	if (!add_rhs) return; // feature-sharded run: U is replicated, its part of the right-hand side is rank 0's
+	// (written out, not u_block_rhs: every sum leaves as it is formed -- with both products held the kernel takes 112 registers for 98)
 	const double* xb = prior + (size_t)b * 6;
 	for (int r = 0; r < 6; r++)
 	{
@@ -242,8 +242,7 @@ k_mono_w_copy(int NF, const int* __restrict__ fptr, const int* __restrict__ phot
 	__shared__ int sFp[MWC_TILE + 1];
 	__shared__ double sT[256 * 3];
 	const int f0 = blockIdx.x * MWC_TILE, nft = min(MWC_TILE, NF - f0);
-	for (int i = threadIdx.x; i < ECAP; i += blockDim.x) ekeys[i] = -1;
-	for (int i = threadIdx.x; i < ECAP * 6; i += blockDim.x) evals[i] = 0.0;
+	tile_clear<6>(ekeys, evals, ECAP);
 	for (int i = threadIdx.x; i <= nft; i += blockDim.x) sFp[i] = fptr[f0 + i];
 	__syncthreads();
 	// blocks of a map the transform passed through are still in the transform's input
@@ -283,20 +282,10 @@ k_mono_w_copy(int NF, const int* __restrict__ fptr, const int* __restrict__ phot
 			const double* xf = feat + (size_t)f * 3;
 			const double* xp = prior + (size_t)k * 6;
 			const int es = lds_slot(ekeys, ECAP, kn);
+			double y[6];
+			w_block_rhs(w, xf, xp, y, out);
 #pragma unroll
-			for (int r = 0; r < 6; r++)
-			{
-				const double y = w[3 * r] * xf[0] + w[3 * r + 1] * xf[1] + w[3 * r + 2] * xf[2];
-				if (es >= 0) lds_add_f64(&evals[es * 6 + r], y); else atomic_add_f64(eP + (size_t)kn * 6 + r, y);
-			}
-#pragma unroll
-			for (int c = 0; c < 3; c++)
-			{
-				double sacc = 0.0;
-#pragma unroll
-				for (int r = 0; r < 6; r++) sacc = fma(w[3 * r + c], xp[r], sacc);
-				out[c] = sacc;
-			}
+			for (int r = 0; r < 6; r++) { if (es >= 0) lds_add_f64(&evals[es * 6 + r], y[r]); else atomic_add_f64(eP + (size_t)kn * 6 + r, y[r]); }
 		},
 		[&](int fl, int q, double sum, bool) {
 			const int nf = jf[f0 + fl];
@@ -319,11 +308,6 @@ __global__ void k_mono_finish(int G, const MGroup* __restrict__ grp, const int* 
 	int g = blockIdx.x * blockDim.x + threadIdx.x;
 	if (g >= G || grp[g].P2 < 0) return;
 	pose_y[(size_t)pnew[grp[g].P2] * 6 + grp[g].fix] = (double)grp[g].sign;
-}
-__global__ void k_fill_int(int n, int* p, int v)
-{
-	int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) p[i] = v;
 }
 
 SolveOutcome join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, double* eP_out, double* eF_out, int step_hint)
@@ -365,15 +349,10 @@ SolveOutcome join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, D
 	const int MY = M - 2 * npair;
 
 	// ---- common features (K5), same as Stereo ----
-	int* match = sc.alloc<int>(in.NF + 1);
-	int* unm = sc.alloc<int>(in.NF + 2);
-	int* RF = sc.alloc<int>(in.NF + 2);
+	const JoinRanks jr = join_rank_features(ctx, in);
 	const int nb = (in.NF + 255) / 256;
-	if (in.NF) join_match_features(ctx, in, match, unm);
-	else dev_zero(ctx, unm, 2 * sizeof(int));
-	dev_exclusive_scan(ctx, unm, RF, in.NF);
 	int* d_rb = sc.alloc<int>(B + 1);
-	hipLaunchKernelGGL(k_gather_at, dim3((B + 1 + 127) / 128), dim3(128), 0, s, RF, in.d_feat_off, B + 1, d_rb);
+	hipLaunchKernelGGL(k_gather_at, dim3((B + 1 + 127) / 128), dim3(128), 0, s, jr.R, in.d_feat_off, B + 1, d_rb);
 	// ---- U: which blocks survive (index work, needed on the host for the container sizes like the unmatched ranks) ----
 	int* keepU = sc.alloc<int>(in.NU + 1);
 	int* KU = sc.alloc<int>(in.NU + 2);
@@ -410,25 +389,15 @@ SolveOutcome join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, D
 
 	out = DevBatch();
 	out.B = G; out.M = MY;
-	out.pose_off.assign(G + 1, 0); out.feat_off.assign(G + 1, 0); out.u_off.assign(G + 1, 0); out.w_off.assign(G + 1, 0);
+	out.u_off.assign(G + 1, 0); out.w_off.assign(G + 1, 0);
 	out.Ref.resize(G); out.FRef.resize(G); out.ScaP.resize(G); out.Fix.resize(G); out.Sign.resize(G); out.FScaP.resize(G); out.FFix.resize(G);
-	std::vector<JGroup> grp(G);
-	std::vector<unsigned char> seg_active(G);
-	std::vector<int> seg_rows(G);
+	std::vector<JGroup> grp;
+	std::vector<unsigned char> seg_active;
+	std::vector<int> seg_rows;
+	join_layout(B, in.feat_off, in.pose_off, rb, 2, out, grp, seg_rows, seg_active);
 	for (int g = 0; g < G; g++)
 	{
-		const int a = 2 * g, b = 2 * g + 1;
-		const bool pair = b < B;
-		JGroup& jg = grp[g];
-		jg.F0E = in.feat_off[a]; jg.nE = in.feat_off[a + 1] - jg.F0E;
-		jg.F0C = pair ? in.feat_off[b] : in.feat_off[a + 1]; jg.nC = pair ? in.feat_off[b + 1] - jg.F0C : 0;
-		jg.FY0 = out.feat_off[g];
-		jg.rC0 = pair ? rb[b] : 0;
-		out.feat_off[g + 1] = jg.FY0 + jg.nE + (pair ? rb[b + 1] - rb[b] : 0);
-		const int rows = (pair ? in.pose_off[b + 1] : in.pose_off[a + 1]) - in.pose_off[a] - (pair ? 2 : 0);
-		out.pose_off[g + 1] = out.pose_off[g] + rows;
-		seg_rows[g] = rows; seg_active[g] = pair ? 1 : 0;
-		const int c = pair ? b : a; // Imp.cpp:7365-7373
+		const int a = 2 * g, c = a + 1 < B ? a + 1 : a; // Cur's, where there is one: Imp.cpp:7365-7373
 		out.Ref[g] = in.Ref[c]; out.ScaP[g] = in.ScaP[c]; out.Fix[g] = in.Fix[c]; out.Sign[g] = in.Sign[c];
 		out.FRef[g] = in.FRef[a]; out.FScaP[g] = in.FScaP[a]; out.FFix[g] = in.FFix[a];
 	}
@@ -466,7 +435,7 @@ SolveOutcome join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, D
 	int* srcC = sc.alloc<int>(NFY + 1);
 	if (in.NF)
 		for (int side = 0; side < 2; side++)
-			hipLaunchKernelGGL(k_join_features, dim3(nb), dim3(256), 0, s, in.NF, in.feat_map, in.feat_id, in.feat, in.V, in.fptr, match, RF, d_grp,
+			hipLaunchKernelGGL(k_join_features, dim3(nb), dim3(256), 0, s, in.NF, in.feat_map, in.feat_id, in.feat, in.V, in.fptr, jr.match, jr.R, d_grp,
 			                   newf, lenE, lenC, out.V, eF, out.feat_id, out.feat, srcE, srcC, side);
 	hipLaunchKernelGGL(k_mono_w_count, dim3((NFY + 256) / 256), dim3(256), 0, s, NFY, srcE, srcC, in.fptr, in.photo, out.feat_map, d_mg, lens);
 	dev_exclusive_scan(ctx, lens, out.fptr, NFY);
@@ -514,16 +483,9 @@ SolveOutcome join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, D
 	h2d(ctx, d_act, seg_active.data(), G);
 	double* x0 = sc.alloc<double>((size_t)MY * 6);
 	LSFM_CHECK_HIP(hipMemcpyAsync(x0, out.pose, (size_t)MY * 6 * sizeof(double), hipMemcpyDeviceToDevice, s));
-	SolveIO io;
-	io.M = MY; io.NF = NFY; io.NU = out.NU; io.NW = out.NW; io.nseg = G;
-	io.d_pose_seg = out.pose_map; io.d_feat_seg = out.feat_map; io.d_seg_active = d_act;
-	io.U = out.U; io.Ui = out.Ui; io.Uj = out.Uj; io.W = out.W; io.photo = out.photo; io.fptr = out.fptr; io.V = out.V;
-	io.ea = eP; io.eb = eF; io.x0 = x0; io.d_fixed = fixed; io.d_pose_origin = out.pose_origin;
-	io.x_pose = out.pose; io.x_feat = out.feat;
-	io.seg_rows = seg_rows;
-	io.index_arrays_at_evA = at_evA; io.step_hint = step_hint;
+	SolveIO io = join_solve_io(ctx, out, d_act, eP, eF, seg_rows, at_evA, step_hint);
+	io.x0 = x0; io.d_fixed = fixed;
 	io.caller_syncs = !warm; // (this level waits for the device below: its refinement may ask once instead of guessing a margin)
-	small_level_offsets(ctx, out, io);
 	// the pattern of this level's system from the one below (a level that analyses; the level below left its pattern with its maps)
 	PatternSeed seed;
 	if (!warm && in.s_keys && in.s_nnzb > 0 && !ctx->comm)
@@ -542,9 +504,7 @@ SolveOutcome join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, D
 	}
 	hipLaunchKernelGGL(k_mono_finish, dim3((G + 127) / 128), dim3(128), 0, s, G, d_mg, pnew, out.pose);
 	if (!warm) LSFM_CHECK_HIP(hipStreamSynchronize(s)); // a warm level is only enqueued: its scratch is reused in stream order
-	sc.release(smark);
-	if (oc.not_converged > 0 && ctx->stats) ctx->stats->not_converged += oc.not_converged;
-	if (plan && !eP_out && !eF_out) plan->valid = true; // every stage of the level has left its structure behind
+	join_close(ctx, smark, oc, !eP_out && !eF_out);
 	return oc;
 }
 
