@@ -432,16 +432,17 @@ int wstream_bench(lsfm_context* ctx, long long nblocks, int mode, int reps, doub
 	double* b = ctx->scratch.alloc<double>((size_t)nblocks * 18);
 	fill_async(s, a, 0, (size_t)nblocks * 144);
 	float total = 0;
+	hipEvent_t e0 = ctx->pool_event(), e1 = ctx->pool_event();
 	for (int k = 0; k < reps + 2; k++)
 	{
-		LSFM_CHECK_HIP(hipEventRecord(ctx->ev0, s));
+		LSFM_CHECK_HIP(hipEventRecord(e0, s));
 		if (mode == 0) hipLaunchKernelGGL(k_wstream_block18, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, s, nblocks, a, b);
 		else if (mode == 1) hipLaunchKernelGGL(k_wstream_block9x16, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, s, nblocks, (const double2*)a, (double2*)b);
 		else hipLaunchKernelGGL(k_wstream_linear, dim3((unsigned)((nblocks * 9 + 1023) / 1024)), dim3(256), 0, s, nblocks * 9, (const double2*)a, (double2*)b);
-		LSFM_CHECK_HIP(hipEventRecord(ctx->ev1, s));
-		LSFM_CHECK_HIP(hipEventSynchronize(ctx->ev1));
+		LSFM_CHECK_HIP(hipEventRecord(e1, s));
+		LSFM_CHECK_HIP(hipEventSynchronize(e1));
 		float t = 0;
-		LSFM_CHECK_HIP(hipEventElapsedTime(&t, ctx->ev0, ctx->ev1));
+		LSFM_CHECK_HIP(hipEventElapsedTime(&t, e0, e1));
 		if (k >= 2) total += t;
 	}
 	*avg_ms = total / reps;

@@ -31,11 +31,13 @@ template <class F> int guarded(lsfm_context* ctx, F&& f)
 		ctx->last_error = e.msg;
 		fprintf(stderr, "liblsfm_hip: %s\n", e.msg.c_str());
 		(void)hipGetLastError();
+		ctx->quiesce_side_streams(); // (the next call resets arenas that work left on stream2 or stream3 may still be reading)
 		return e.code;
 	}
 	catch (const std::exception& e)
 	{
 		ctx->last_error = e.what();
+		ctx->quiesce_side_streams();
 		return LSFM_ERR_INTERNAL;
 	}
 }

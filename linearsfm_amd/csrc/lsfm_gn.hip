@@ -874,8 +874,8 @@ void gn_chi2(lsfm_context* ctx, const GnCall& c)
 	                   c.d_x + (size_t)c.M * 6, c.X.feat, c.X.fptr, c.X.photo, c.X.W, c.X.V, c.d_chi2);
 }
 // the launches of one assembly at the state in d_x: F into Fsum (kind != 0: the robust weights first, G into d_G), the joint system
-// UJ / WJ / VJ and the right-hand sides ea / eb.  bracket_chi2: ev0 / ev1 of the context around the chi2 + weights kernels.
-void gn_assemble(lsfm_context* ctx, const GnCall& c, int kind, double cth, bool bracket_chi2)
+// UJ / WJ / VJ and the right-hand sides ea / eb.  bracket_chi2 (may be null): [2] events recorded around the chi2 + weights kernels.
+void gn_assemble(lsfm_context* ctx, const GnCall& c, int kind, double cth, const hipEvent_t* bracket_chi2)
 {
 	hipStream_t s = ctx->stream;
 	const DevBatch& X = c.X;
@@ -885,10 +885,10 @@ void gn_assemble(lsfm_context* ctx, const GnCall& c, int kind, double cth, bool 
 	gn_frames(ctx, c);
 	if (kind != 0)
 	{
-		if (bracket_chi2) LSFM_CHECK_HIP(hipEventRecord(ctx->ev0, s));
+		if (bracket_chi2) LSFM_CHECK_HIP(hipEventRecord(bracket_chi2[0], s));
 		gn_chi2(ctx, c);
 		hipLaunchKernelGGL(k_gn_robust_weights, dim3(1), dim3(GN_WEIGHT_LANES), 0, s, N, kind, cth, c.d_dof, c.d_chi2, c.d_gm, c.d_w, c.d_G);
-		if (bracket_chi2) LSFM_CHECK_HIP(hipEventRecord(ctx->ev1, s));
+		if (bracket_chi2) LSFM_CHECK_HIP(hipEventRecord(bracket_chi2[1], s));
 	}
 	if (X.NU) hipLaunchKernelGGL(k_gn_ublocks, grid_for(X.NU, 128), dim3(128), 0, s, X.NU, P, X.Ui, X.Uj, X.U, X.pose_map, c.d_gm, c.d_gp, c.Dp, c.Cp, c.rp, c.Gacc, c.UJ);
 	if (FI)
@@ -925,15 +925,17 @@ int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_ma
 	const bool robust = kind != 0;
 
 	// F (robust: G) and the step's system at the state in d_x
+	hipEvent_t e_chi2[2] = { nullptr, nullptr };
+	if (robust && timing) { e_chi2[0] = ctx->pool_event(); e_chi2[1] = ctx->pool_event(); }
 	auto assemble = [&]() -> double {
 		const double ta = wall();
-		gn_assemble(ctx, c, kind, cth, robust && timing);
+		gn_assemble(ctx, c, kind, cth, robust && timing ? e_chi2 : nullptr);
 		double F = 0.0;
 		d2h(ctx, &F, robust ? c.d_G : c.Fsum, sizeof(double));
 		if (robust && timing)
 		{
 			float ms = 0.0f;
-			LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+			LSFM_CHECK_HIP(hipEventElapsedTime(&ms, e_chi2[0], e_chi2[1]));
 			t_chi2 += ms;
 		}
 		t_asm += wall() - ta; n_asm++;
@@ -1043,13 +1045,15 @@ int gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, cons
 	const int M = c.M, NFG = c.NFG;
 	if (timing) LSFM_CHECK_HIP(hipStreamSynchronize(s));
 	const double tw1 = wall();
-	if (times) LSFM_CHECK_HIP(hipEventRecord(ctx->ev0, s));
-	gn_assemble(ctx, c, 0, 1.0, false);
-	if (times) LSFM_CHECK_HIP(hipEventRecord(ctx->ev1, s));
+	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr }; // around the assembly and the two coalescing launches
+	if (times) for (hipEvent_t& e : ev) e = ctx->pool_event();
+	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[0], s));
+	gn_assemble(ctx, c, 0, 1.0, nullptr);
+	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
 	if (co.nWo) hipLaunchKernelGGL(k_gn_coalesce_w, grid_for(co.nWo, 256), dim3(256), 0, s, co.nWo, co.d_wsp, co.d_wsi, c.WJ, co.Wo);
-	if (times) LSFM_CHECK_HIP(hipEventRecord(ctx->ev2, s));
+	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[2], s));
 	if (co.nUo) hipLaunchKernelGGL(k_gn_coalesce_u, grid_for(co.nUo, 256), dim3(256), 0, s, co.nUo, co.d_usp, co.d_usi, c.UJ, co.Uo);
-	if (times) LSFM_CHECK_HIP(hipEventRecord(ctx->ev3, s));
+	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[3], s));
 	if (timing) LSFM_CHECK_HIP(hipStreamSynchronize(s));
 	const double tw2 = wall();
 	lsfm_map g;
@@ -1085,9 +1089,7 @@ int gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, cons
 		if (times)
 		{
 			float ms[3] = { 0.0f, 0.0f, 0.0f };
-			LSFM_CHECK_HIP(hipEventElapsedTime(&ms[0], ctx->ev0, ctx->ev1));
-			LSFM_CHECK_HIP(hipEventElapsedTime(&ms[1], ctx->ev1, ctx->ev2));
-			LSFM_CHECK_HIP(hipEventElapsedTime(&ms[2], ctx->ev2, ctx->ev3));
+			for (int i = 0; i < 3; i++) LSFM_CHECK_HIP(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
 			for (int i = 0; i < 3; i++) times[i] = ms[i];
 		}
 	}

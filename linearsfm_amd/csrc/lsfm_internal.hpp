@@ -257,6 +257,29 @@ struct Range {
 };
 } // namespace lsfm
 
+namespace lsfm {
+// The events that order the three streams of a context (stream = main, stream2, stream3), one meaning each.  They live in
+// lsfm_context::ord and are made with order_event_flags().  A stream waits for one through Fork or wait_for() below only; one is
+// recorded by Fork, or in place where its point of the main stream lies ahead of the fork ("Streams and events", is the
+// same list as a table).
+enum Ord {
+	evA,        // the joint maps' index arrays are complete: join_stereo_finish / join_batch_mono, main -> level_structure case 5 starts the pattern on stream2
+	evB,        // the pattern of S is ready: level_structure case 4 (stream3) or 5 (stream2) -> level_structure, main, before the Schur assembly
+	evC_pairs,  // feature matches and hub poses are known: join_stereo_prepare, main -> schur_pattern_early_issue starts the first half of the early pattern on stream3
+	evC_runs,   // the joint run pointers are enqueued: join_stereo_prepare, main -> level_structure case 4 starts the second half of the early pattern on stream3
+	evY,        // the joint maps' index arrays of the level are final: join_stereo_finish, main -> prefetch_next_level starts on stream3
+	evP,        // what was prepared one level ahead is on the device: prefetch_next_level / pre_plan_complete, stream3 -> level_plan, level_structure case 3, pre_plan_complete, main
+	evU,        // everything the transform's U kernel reads is final, the block kernel of the features has not begun: launch_stage, main -> k_tr_ublocks on stream2
+	evG,        // the pose rows of G are complete: launch_stage, main (behind k_tr_entries) -> the U stage on stream2
+	evT,        // the U stage has rejoined: launch_stage, stream2 -> launch_stage, main, before k_tr_diag
+	evK9_fork,  // K9's lists and cursors are ready: launch_schur_panel, main -> the 16-slot variant on stream2
+	evK9_done,  // the 16-slot variant is done: launch_schur_panel, stream2 -> launch_schur_panel, main
+	evR_fork,   // the level's run pointers are final: build_schur_values, main -> k_sum_run_squares on stream2
+	evR_done,   // k_sum_run_squares has read them: build_schur_values, stream2 -> run_level, main, before the next level resets arenas
+	ORD_COUNT
+};
+} // namespace lsfm
+
 struct lsfm_context {
 	int device = 0;
 	hipStream_t stream = nullptr;
@@ -275,23 +298,24 @@ struct lsfm_context {
 	char* d_stage = nullptr; // ... as the device sees it (null: not mapped -- copies then go through hipMemcpyAsync)
 	size_t stage_size = 0, stage_off = 0;
 	hipEvent_t ev_half[2] = { nullptr, nullptr }; // h2d_gather: a half of the ring may be refilled once its copy has left
-	hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-	hipEvent_t evs[4] = { nullptr, nullptr, nullptr, nullptr }; // stage brackets of a solve (owned here: nothing to leak on an error path)
 	// Every entry point that resets or reallocates the arenas bumps this; a finished tree remembers the value it ended with,
 	// and lsfm_tree_download refuses a result that a later call on the same context has overwritten
 	unsigned long long generation = 0;
-	// side stream: the pattern of S is built there while the caller's right-hand-side kernels run on the main stream.
-	// evA = point of the main stream after which the index arrays of the joint map are complete (recorded by the caller,
-	// which says so in SolveIO::index_arrays_at_evA), evB = pattern ready
+	// side stream: the pattern of S is built there while the caller's right-hand-side kernels run on the main stream (behind evA, which
+	// the caller recorded and says so in SolveIO::index_arrays_at_evA); also the transform's U stage, K9's 16-slot variant and the
+	// run statistics
 	hipStream_t stream2 = nullptr;
-	hipEvent_t evA = nullptr, evB = nullptr;
+	hipEvent_t ord[lsfm::ORD_COUNT] = {}; // what orders stream, stream2 and stream3: one meaning per event (lsfm::Ord)
+	// Every exit that does not end with the run's events joined and the main stream synchronised (an Error caught by the run's
+	// handlers or at the C ABI, the destruction of the context) calls this before arenas are reset or freed: waits for stream2 and
+	// stream3, swallows and clears what they report.  Host only; twice is as good as once; the helper thread and `pre` are not its business
+	void quiesce_side_streams();
 	// Early pattern of S (Stereo tree levels that analyse): the pose pairs of the JOINT map follow from the level's input index
 	// arrays, the feature matches and the hub pose of every transformed map, all known before the transform's heavy kernels
 	// run -- the pattern is put together on the side stream while those run, and the host's symbolic analysis no longer
 	// waits for them (lsfm_pattern.hip: schur_pattern_early_*).  The level's input and the hub list reach the join through the
 	// transform's hook (join_stereo_prepare).
 	std::shared_ptr<lsfm::EarlyPattern> early; // the build in flight (null: none)
-	hipEvent_t ev_k9[2] = { nullptr, nullptr }; // K9: the 32-slot panel variant of a level runs on the side stream, beside the others (lsfm_schur_panel.hip)
 	hipStream_t stream3 = nullptr;      // its own stream: the side stream carries the transform's U stage, which waits for the block kernel
 	// One level ahead (Stereo tree runs that analyse): while the device factors and refines level L, the pattern of level
 	// L + 1's system is put together on stream3 from level L's joint maps (their index arrays are final long before the
@@ -310,15 +334,11 @@ struct lsfm_context {
 	std::unique_ptr<lsfm::HostWorker> worker;
 	void drop_prepared() { pre.reset(); pre_plan = lsfm::LevelPlan(); pre_plan_level = -1; }
 	double dbg_gap_ms = 0.0; // (LSFM_LEVEL_GAPS=1: from the event behind a level's solve to the next level's first, summed over a run)
-	hipEvent_t evY = nullptr, evP = nullptr; // joint index arrays of the level final (main stream) / prefetch complete (stream3)
-	hipEvent_t evU = nullptr;                // the transform's U stage may start: everything it reads is final, the block kernel of the features has not begun
-	hipEvent_t evK = nullptr;                // the level's Schur assembly (K9) has left the main stream: the chain of the factorisation starts
 	// LSFM_TIMELINE=1: host wall-clock marks of a tree run (where the enqueuing thread is when), printed at the end of the run
 	std::vector<std::pair<const char*, double>> timeline;
 	bool timeline_on = false;
 	void mark(const char* what);
 	bool in_tree_run = false;
-	hipEvent_t evC = nullptr;
 	lsfm_stats* stats = nullptr; // optional sink during a tree run
 	lsfm::LevelPlan* plan = nullptr; // plan of the tree level being run (null: stage-level calls, nothing is recorded or reused)
 	bool warm() const { return plan && plan->valid; }
@@ -351,6 +371,25 @@ struct OnStream {
 	~OnStream() { if (a) std::swap(c->scratch, *a); std::swap(c->stream, s); }
 	OnStream(const OnStream&) = delete;
 	OnStream& operator=(const OnStream&) = delete;
+};
+// "The main stream waits / a side stream starts behind a point someone recorded": the one place besides Fork that makes a stream wait
+inline void wait_for(lsfm_context* ctx, hipStream_t s, Ord e) { LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->ord[e], 0)); }
+// "This stretch runs on a side stream, beside the main stream": an OnStream scope whose side stream starts behind `start` -- recorded
+// here on the main stream, or (record = false) by someone else before; without a start, nothing the stretch reads comes from the main
+// stream.  join(e) records e behind the stretch and makes the main stream wait for it; done(e) only records it, for a wait_for()
+// elsewhere (the prefetch rejoins the NEXT level).  A scope left without either enqueues nothing more: the stretch is followed on its
+// stream by one that joins -- or an exception is passing, and the handlers wait for the side streams (quiesce_side_streams).
+// Inside the scope ctx->stream names the side stream and `side` the main one, as with OnStream.
+struct Fork {
+	lsfm_context* c; hipStream_t main; OnStream on;
+	Fork(lsfm_context* ctx, hipStream_t& side, Arena* arena = nullptr) : c(ctx), main(ctx->stream), on(ctx, side, arena) {}
+	Fork(lsfm_context* ctx, hipStream_t& side, Ord start, bool record = true, Arena* arena = nullptr) : Fork(ctx, side, arena)
+	{
+		if (record) LSFM_CHECK_HIP(hipEventRecord(c->ord[start], main));
+		wait_for(c, c->stream, start);
+	}
+	void done(Ord e) { LSFM_CHECK_HIP(hipEventRecord(c->ord[e], c->stream)); }
+	void join(Ord e) { done(e); wait_for(c, main, e); }
 };
 
 // ---- primitives (lsfm_prims.hip; rocPRIM scan / radix sort on the context stream) ------------------------
@@ -465,7 +504,7 @@ struct SolveIO {
 	// optional (Mono tree levels that analyse): the pattern of S follows from the pattern of the level below instead of being built
 	// from every pose pair of every feature again (lsfm_solve.hpp PatternSeed; null: from scratch)
 	const struct PatternSeed* seed = nullptr;
-	// the caller recorded ctx->evA where the joint map's index arrays were complete and went on to enqueue its right-hand-side kernels:
+	// the caller recorded evA where the joint map's index arrays were complete and went on to enqueue its right-hand-side kernels:
 	// a level that analyses may build the pattern of S on the side stream from there (level_structure, case 5)
 	bool index_arrays_at_evA = false;
 	// refinement steps: > 0 = what an earlier run of this tree needed at this level (the steps are then enqueued without asking the

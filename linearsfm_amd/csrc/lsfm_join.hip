@@ -411,13 +411,13 @@ void join_stereo_prepare(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBa
 		ei.M = in.M; ei.NFY = NFY; ei.NU = X.NU;
 		ei.Ui = X.Ui; ei.Uj = X.Uj; ei.pose_map = X.pose_map; ei.hub = hub;
 		ei.fptr = X.fptr; ei.photo = X.photo; ei.feat_map = X.feat_map; ei.srcE = srcE; ei.srcC = srcC;
-		LSFM_CHECK_HIP(hipEventRecord(ctx->evC, s));
+		LSFM_CHECK_HIP(hipEventRecord(ctx->ord[evC_pairs], s)); // the matches and the hub poses: the first half of the early pattern reads them
 		schur_pattern_early_issue(ctx, ei);
 	}
 	else schur_pattern_early_drop(ctx);
 	hipLaunchKernelGGL(k_add_lens, dim3((NFY + 256) / 256), dim3(256), 0, s, NFY, lenE, lenC, lens);
 	dev_exclusive_scan(ctx, lens, out.fptr, NFY);
-	if (early) LSFM_CHECK_HIP(hipEventRecord(ctx->evC, s)); // the joint run pointers: the second half of the early pattern reads them
+	if (early) LSFM_CHECK_HIP(hipEventRecord(ctx->ord[evC_runs], s)); // the joint run pointers: the second half of the early pattern reads them
 	// where the run of every input feature starts in the joint map
 	st.wbase = ctx->scratch.alloc<int>(in.NF + 1);
 	if (in.NF) hipLaunchKernelGGL(k_join_wbase, dim3(nb), dim3(256), 0, s, in.NF, in.feat_map, newf, lenE, out.fptr, st.wbase);
@@ -441,11 +441,11 @@ SolveOutcome join_stereo_finish(lsfm_context* ctx, const DevBatch& in, DevBatch&
 		cu.d2d(out.Uj, in.Uj, (size_t)in.NU * sizeof(int));
 		cu.flush();
 	}
-	LSFM_CHECK_HIP(hipEventRecord(ctx->evY, s)); // the joint maps' index arrays are final (prefetch_next_level reads them)
+	LSFM_CHECK_HIP(hipEventRecord(ctx->ord[evY], s)); // the joint maps' index arrays are final (prefetch_next_level reads them)
 	// everything the pattern of S needs is enqueued: the solve may build it beside the right-hand sides (unless it is under
 	// way already: schur_pattern_early_issue)
 	const bool at_evA = !eP_out && !eF_out && !ctx->early && !ctx->comm;
-	if (at_evA) LSFM_CHECK_HIP(hipEventRecord(ctx->evA, s));
+	if (at_evA) LSFM_CHECK_HIP(hipEventRecord(ctx->ord[evA], s));
 	// ---- right-hand sides ----
 	// (the W part: a pass over W of its own -- unless the Schur assembly takes it along, K9Out; a caller that wants eP / eF gets them whole)
 	const bool fuse_rhs = st.fuse_rhs && !eP_out && !eF_out;

@@ -466,7 +466,7 @@ SolveOutcome join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, D
 		// the joint maps' index arrays are final here (U's were written by k_mono_u_fill): a level that analyses builds the pattern of S
 		// on the side stream from this point, beside the kernel that moves the W blocks and the right-hand sides (solve_batch)
 		at_evA = !warm && !eP_out && !eF_out && !ctx->comm;
-		if (at_evA) LSFM_CHECK_HIP(hipEventRecord(ctx->evA, s));
+		if (at_evA) LSFM_CHECK_HIP(hipEventRecord(ctx->ord[evA], s));
 		if (in.NF)
 			hipLaunchKernelGGL(k_mono_w_copy, dim3((in.NF + MWC_TILE - 1) / MWC_TILE), dim3(256), 0, s, in.NF, in.fptr, in.photo, in.W, in.feat_map,
 			                   in.W_alias, in.d_alias, dst, jf, srcC, out.feat_map, d_mg, pnew, prior, in.feat, out.W, eP, eF);

@@ -122,24 +122,23 @@ void prefetch_next_level(lsfm_context* ctx, const DevBatch& Y, const std::vector
 	pl->M = Y.M;
 	Arena& sa = ctx->sarena[next_level & 1];
 	sa.reset();
-	// The joint maps' index arrays are final at evY: the pattern kernels start there, beside the level's right-hand-side kernels and
-	// K9.  Measured alternative: start them once K9 has left the main stream (evK), beside the factorisation's chain of small
-	// launches -- K9 then runs undisturbed (0.66 -> 0.58 ms per level) but the host gets its pattern 0.6 ms later at every level and
-	// the next level is enqueued late: 54.5 instead of 50.4 ms per tree.
-	LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream3, ctx->evY, 0));
-	if (ctx->timeline_on) { (void)hipEventSynchronize(ctx->evY); ctx->mark("pre_evY"); }
 	std::vector<int> counts;
 	LevelIndex kept;
 	bool ok = false;
 	{
-		OnStream on(ctx, ctx->stream3, &sa); // (the small arena of the level's parity)
+		// The joint maps' index arrays are final at evY: the pattern kernels start there, beside the level's right-hand-side kernels and
+		// K9.  Measured alternative: start them once K9 has left the main stream, beside the factorisation's chain of small
+		// launches -- K9 then runs undisturbed (0.66 -> 0.58 ms per level) but the host gets its pattern 0.6 ms later at every level and
+		// the next level is enqueued late: 54.5 instead of 50.4 ms per tree.
+		Fork side(ctx, ctx->stream3, evY, false, &sa); // (the small arena of the level's parity)
+		if (ctx->timeline_on) { (void)hipEventSynchronize(ctx->ord[evY]); ctx->mark("pre_evY"); }
 		int* d_tref = ctx->scratch.alloc<int>(Y.B);
 		h2d(ctx, d_tref, target_ref.data(), sizeof(int) * (size_t)Y.B);
 		ok = schur_pattern_prefetch(ctx, Y, d_tref, level_keys, level_nnzb, pl->sy, whole ? &counts : nullptr, !next_small, whole ? &kept : nullptr);
 		if (ok)
 		{
 			if (!next_small) chol_fetch(ctx, pl->sy, Y.pose_origin, pl->hin); // (synchronises stream3: the counts have arrived too)
-			LSFM_CHECK_HIP(hipEventRecord(ctx->evP, ctx->stream));
+			side.done(evP); // (the next level waits for it: level_plan, level_structure case 3)
 		}
 	}
 	ctx->mark("pre_pat");
@@ -180,11 +179,10 @@ static std::shared_ptr<SolvePlan> pre_plan_complete(lsfm_context* ctx, PreLevel&
 	sp->sy = pl.sy;
 	sp->its = pl.its; sp->mixed = ctx->pcg.mixed; sp->rel_tol = ctx->pcg.rel_tol;
 	{
-		OnStream on(ctx, ctx->stream3, &ctx->sarena[pl.level & 1]);
+		Fork side(ctx, ctx->stream3, &ctx->sarena[pl.level & 1]); // (what it sends comes from the host)
 		chol_upload_index(ctx, pl.sym, sp->ch);
-		LSFM_CHECK_HIP(hipEventRecord(ctx->evP, ctx->stream));
+		side.join(evP);
 	}
-	LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->evP, 0));
 	return sp;
 }
 
@@ -236,7 +234,7 @@ __global__ void k_chol_err_to_run(const int* err, RunStatsDev* run)
 }
 
 // The structure of a level on the sparse pipeline, from wherever the level gets it: the camera system with its values assembled, the
-// factorisation ready to be scattered into (ch.d_err zeroed), evK recorded behind the Schur assembly.
+// factorisation ready to be scattered into (ch.d_err zeroed).
 struct LevelStructure {
 	SchurSystem sy;
 	CholDev ch;
@@ -252,11 +250,10 @@ static LevelStructure level_structure(lsfm_context* ctx, const SolveIO& io, Solv
 	LevelStructure ls;
 	SchurSystem& sy = ls.sy;
 	CholDev& ch = ls.ch;
-	// K9 behind the pattern; the chain of the factorisation starts at evK
+	// K9 behind the pattern; the chain of the factorisation starts behind it
 	auto assemble = [&]() {
 		build_schur_values(ctx, io, sy);
 		LSFM_REC_T(eb, s); if (roctx().mark) roctx().mark("lsfm factor + refine: begin");
-		LSFM_CHECK_HIP(hipEventRecord(ctx->evK, s));
 	};
 	if (sp || pending)
 	{
@@ -291,16 +288,15 @@ static LevelStructure level_structure(lsfm_context* ctx, const SolveIO& io, Solv
 		prepared.IV = sy.IV; prepared.LY = sy.LY; prepared.ymax = sy.ymax; prepared.uu = sy.uu;
 		sy = prepared;
 		have = true;
-		LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->evP, 0));
+		wait_for(ctx, s, evP);
 		if (getenv("LSFM_CHECK_EARLY_PATTERN")) schur_pattern_check(ctx, io, sy, "prefetched");
 	}
 	else if (ctx->early && !ctx->comm)
 	{
 		// 4. the pattern was put together on stream3 from the level's inputs while the transform ran (a Stereo level that
-		// analyses): its second half, and the copy of it for the host's analysis, stay there
-		LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream3, ctx->evC, 0)); // (recorded again once the joint run pointers were enqueued)
+		// analyses): its second half, and the copy of it for the host's analysis, stay there, behind the joint run pointers (evC_runs)
 		{
-			OnStream on(ctx, ctx->stream3);
+			Fork side(ctx, ctx->stream3, evC_runs, false);
 			ctx->mark("sv_start");
 			have = schur_pattern_early_finish(ctx, io, sy);
 			ctx->mark("pat_fin");
@@ -310,23 +306,18 @@ static LevelStructure level_structure(lsfm_context* ctx, const SolveIO& io, Solv
 				chol_fetch(ctx, sy, io.d_pose_origin, hin);
 				ctx->mark("fetch");
 				schur_pattern_early_extras(ctx, sy);
-				LSFM_CHECK_HIP(hipEventRecord(ctx->evB, ctx->stream));
+				side.join(evB);
 			}
 		}
-		if (have) LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->evB, 0));
 	}
 	else if (io.index_arrays_at_evA && !ctx->comm)
 	{
 		// 5. the pattern depends on index arrays only: the caller marked the point of the main stream where those were complete
 		// (evA) and went on to enqueue its right-hand-side kernels -- the pattern is built on the side stream next to them
-		LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream2, ctx->evA, 0));
-		{
-			OnStream on(ctx, ctx->stream2);
-			build_schur_pattern(ctx, io, sy);
-			chol_fetch(ctx, sy, io.d_pose_origin, hin);
-			LSFM_CHECK_HIP(hipEventRecord(ctx->evB, ctx->stream));
-		}
-		LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->evB, 0));
+		Fork side(ctx, ctx->stream2, evA, false);
+		build_schur_pattern(ctx, io, sy);
+		chol_fetch(ctx, sy, io.d_pose_origin, hin);
+		side.join(evB);
 		have = true;
 	}
 	if (!have)
@@ -365,7 +356,6 @@ static SolveOutcome solve_level_dense(lsfm_context* ctx, const SolveIO& io, int 
 	// (a planned level brackets its launch like a level on the sparse pipeline brackets its factorisation)
 	if (!warm) enqueue();
 	LSFM_REC_T(eb, s); if (warm && roctx().mark) roctx().mark("lsfm factor + refine: begin");
-	LSFM_CHECK_HIP(hipEventRecord(ctx->evK, s));
 	if (warm) enqueue();
 	LSFM_REC_T(ec, s);
 	LSFM_REC_T(ed, s); if (roctx().mark) roctx().mark("lsfm solve: end");

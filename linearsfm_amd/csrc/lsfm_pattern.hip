@@ -425,10 +425,10 @@ void schur_pattern_early_issue(lsfm_context* ctx, const EarlyPatternIn& in)
 	ctx->early.reset();
 	auto ep = std::make_shared<EarlyPattern>();
 	ep->M = in.M;
-	// on the side stream, behind the point of the main stream where the matches and the hub poses are known (evC)
-	LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream3, ctx->evC, 0));
+	// on the side stream, behind the point of the main stream where the matches and the hub poses are known (the caller recorded
+	// evC_pairs).  Rejoins with the second half, which follows it on that stream (level_structure, case 4)
 	{
-		OnStream on(ctx, ctx->stream3);
+		Fork side(ctx, ctx->stream3, evC_pairs, false);
 		hipStream_t s = ctx->stream;
 		PatternBuild& pb = ep->pb;
 		pattern_begin(ctx, pattern_capacity((size_t)in.NU + in.M, in.M), pb);

@@ -387,6 +387,12 @@ hipEvent_t lsfm_context::pool_event()
 	}
 	return ev_pool[ev_next++];
 }
+void lsfm_context::quiesce_side_streams()
+{
+	if (stream2) (void)hipStreamSynchronize(stream2);
+	if (stream3) (void)hipStreamSynchronize(stream3);
+	(void)hipGetLastError();
+}
 void lsfm_context::flush_times()
 {
 	for (const Timed& t : timed)
@@ -536,14 +542,7 @@ int lsfm_context_create(int device, size_t arena_bytes, lsfm_context** out)
 			(void)hipDeviceGetStreamPriorityRange(&least, &greatest);
 			LSFM_CHECK_HIP(hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, greatest));
 		}
-		for (auto& e : c->ev_k9) LSFM_CHECK_HIP(hipEventCreateWithFlags(&e, lsfm::order_event_flags()));
-		LSFM_CHECK_HIP(hipEventCreateWithFlags(&c->evA, lsfm::order_event_flags()));
-		LSFM_CHECK_HIP(hipEventCreateWithFlags(&c->evB, lsfm::order_event_flags()));
-		LSFM_CHECK_HIP(hipEventCreateWithFlags(&c->evC, lsfm::order_event_flags()));
-		LSFM_CHECK_HIP(hipEventCreateWithFlags(&c->evY, lsfm::order_event_flags()));
-		LSFM_CHECK_HIP(hipEventCreateWithFlags(&c->evP, lsfm::order_event_flags()));
-		LSFM_CHECK_HIP(hipEventCreateWithFlags(&c->evK, lsfm::order_event_flags()));
-		LSFM_CHECK_HIP(hipEventCreateWithFlags(&c->evU, lsfm::order_event_flags()));
+		for (auto& e : c->ord) LSFM_CHECK_HIP(hipEventCreateWithFlags(&e, lsfm::order_event_flags()));
 		LSFM_CHECK_HIP(hipHostMalloc((void**)&c->h_pinned, 4096));
 		c->stage_size = (size_t)64 << 20;
 		LSFM_CHECK_HIP(hipHostMalloc((void**)&c->h_stage, c->stage_size));
@@ -552,11 +551,6 @@ int lsfm_context_create(int device, size_t arena_bytes, lsfm_context** out)
 			if (hipHostGetDevicePointer(&dp, c->h_stage, 0) == hipSuccess) c->d_stage = static_cast<char*>(dp);
 			else (void)hipGetLastError();
 		}
-		LSFM_CHECK_HIP(hipEventCreateWithFlags(&c->ev0, lsfm::timing_event_flags()));
-		LSFM_CHECK_HIP(hipEventCreateWithFlags(&c->ev1, lsfm::timing_event_flags()));
-		LSFM_CHECK_HIP(hipEventCreateWithFlags(&c->ev2, lsfm::timing_event_flags()));
-		LSFM_CHECK_HIP(hipEventCreateWithFlags(&c->ev3, lsfm::timing_event_flags()));
-		for (auto& e : c->evs) LSFM_CHECK_HIP(hipEventCreateWithFlags(&e, lsfm::timing_event_flags()));
 		LSFM_CHECK_HIP(hipMalloc((void**)&c->d_run, sizeof(lsfm::RunStatsDev)));
 		LSFM_CHECK_HIP(hipMemset(c->d_run, 0, sizeof(lsfm::RunStatsDev)));
 		if (arena_bytes) c->ensure_arenas(arena_bytes);
@@ -579,28 +573,17 @@ void lsfm_context_destroy(lsfm_context* c)
 	c->worker.reset(); // (joins the helper thread)
 	(void)hipSetDevice(c->device);
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
+	c->quiesce_side_streams();
 	c->arena[0].destroy(); c->arena[1].destroy(); c->arena[2].destroy(); c->scratch.destroy();
 	if (c->h_pinned) (void)hipHostFree(c->h_pinned);
 	if (c->h_stage) (void)hipHostFree(c->h_stage);
 	for (auto& e : c->ev_half) if (e) (void)hipEventDestroy(e);
-	if (c->ev0) (void)hipEventDestroy(c->ev0);
-	if (c->ev1) (void)hipEventDestroy(c->ev1);
-	if (c->ev2) (void)hipEventDestroy(c->ev2);
-	if (c->ev3) (void)hipEventDestroy(c->ev3);
-	for (auto& e : c->evs) if (e) (void)hipEventDestroy(e);
 	for (auto& e : c->ev_pool) if (e) (void)hipEventDestroy(e);
 	if (c->d_run) (void)hipFree(c->d_run);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
 	if (c->stream2) (void)hipStreamDestroy(c->stream2);
 	if (c->stream3) (void)hipStreamDestroy(c->stream3);
-	for (auto& e : c->ev_k9) if (e) (void)hipEventDestroy(e);
-	if (c->evA) (void)hipEventDestroy(c->evA);
-	if (c->evB) (void)hipEventDestroy(c->evB);
-	if (c->evC) (void)hipEventDestroy(c->evC);
-	if (c->evY) (void)hipEventDestroy(c->evY);
-	if (c->evP) (void)hipEventDestroy(c->evP);
-	if (c->evK) (void)hipEventDestroy(c->evK);
-	if (c->evU) (void)hipEventDestroy(c->evU);
+	for (auto& e : c->ord) if (e) (void)hipEventDestroy(e);
 	c->pre.reset();
 	c->sarena[0].destroy(); c->sarena[1].destroy();
 	c->early.reset();

@@ -854,10 +854,9 @@ void launch_schur_panel(lsfm_context* ctx, int NF, const int* fptr, const int* p
 	// 40 -> 55 ms per tree); the next-level stream (it has the pattern of the next level queued at this point); a head start for
 	// part of the 32-slot list (7.9 -> 8.4); everything in one stream (8.5-9.1); half / twice as many work-groups on the lists.
 	static const int ncu = []() { int d = 0, n = 0; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
-	hipStream_t s1 = ctx->stream2;
 	if (!fresh_lists) fill_async(s, kc.wcnt + 4, 0, 4 * sizeof(int)); // the variants' cursors into their lists (k_schur_lists zeroes them when it has just run)
-	LSFM_CHECK_HIP(hipEventRecord(ctx->ev_k9[0], s));
-	LSFM_CHECK_HIP(hipStreamWaitEvent(s1, ctx->ev_k9[0], 0));
+	Fork side(ctx, ctx->stream2, evK9_fork);
+	hipStream_t s1 = ctx->stream;
 	const dim3 wgrid(std::min(ntiles, ncu));
 	// (widest first: a work-group of the 64-slot variant needs a CU's whole LDS to start -- behind the others it would wait for the
 	// 16-slot variant to drain even when its list is empty)
@@ -865,8 +864,7 @@ void launch_schur_panel(lsfm_context* ctx, int NF, const int* fptr, const int* p
 	hipLaunchKernelGGL((k_schur_panel<PM_SMAX_BIG, PM_WIDE, true>), wgrid, dim3(PM_WIDE), 0, s, NF, fptr, photo, W, LY, tab, val, mask, out, fallback, 0, kc.wlist + ntiles, kc.wcnt + 1, kc.wcnt + 5, 0, kc);
 	hipLaunchKernelGGL((k_schur_panel<PM_SMAX, LSFM_K9_T32, true>), wgrid, dim3(LSFM_K9_T32), 0, s, NF, fptr, photo, W, LY, tab, val, mask, out, fallback, 0, kc.wlist, kc.wcnt, kc.wcnt + 4, 0, kc);
 	hipLaunchKernelGGL((k_schur_panel<16, LSFM_K9_T16, false>), grid, dim3(LSFM_K9_T16), 0, s1, NF, fptr, photo, W, LY, tab, val, mask, out, fallback, 0, none, none, (int*)nullptr, 0, kc);
-	LSFM_CHECK_HIP(hipEventRecord(ctx->ev_k9[1], s1));
-	LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->ev_k9[1], 0));
+	side.join(evK9_done);
 }
 
 } // namespace lsfm

@@ -703,7 +703,7 @@ void schur_vinv(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy)
 }
 
 // Values of S and E: enqueued without a host synchronisation (the caller overlaps host work with K9); the K9 launch is
-// bracketed by the events ev2/ev3 of the context, read back by schur_values_stats() after the caller's next sync
+// bracketed by two events of the context's pool, whose time flush_times() adds to the run's statistics
 void build_schur_values(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy)
 {
 	hipStream_t s = ctx->stream;
@@ -785,12 +785,13 @@ void build_schur_values(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy)
 			// and the estimates they read -- until round 5 a pass of its own, k_join_rhs_w)
 			if (io.rhs) { ctx->stats->schur_flops += (double)io.NW * 72.0; ctx->stats->schur_bytes += (double)io.NF * (48 + 24) + (double)io.M * 48; }
 			// (on the side stream, behind the 16-slot variant and its event: a number for the run's statistics has no place in the
-			// chain of the main stream -- 9 us per level; lsfm_tree_run waits for that stream before it reads the record)
+			// chain of the main stream -- 9 us per level; lsfm_tree_run waits for that stream before it reads the record, and the next
+			// level for evR_done before it resets an arena: io.fptr lives in one)
 			if (ctx->in_tree_run && ctx->d_run)
 			{
-				LSFM_CHECK_HIP(hipEventRecord(ctx->ev_k9[0], s)); // (the run pointers are final at this point of the main stream)
-				LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream2, ctx->ev_k9[0], 0));
-				hipLaunchKernelGGL(k_sum_run_squares, dim3(std::min((NF + 255) / 256, 512)), dim3(256), 0, ctx->stream2, NF, io.fptr, &ctx->d_run->k2);
+				Fork side(ctx, ctx->stream2, evR_fork); // (the run pointers are final at this point of the main stream)
+				hipLaunchKernelGGL(k_sum_run_squares, dim3(std::min((NF + 255) / 256, 512)), dim3(256), 0, ctx->stream, NF, io.fptr, &ctx->d_run->k2);
+				side.done(evR_done);
 			}
 		}
 	}
@@ -897,15 +898,16 @@ int spmv_external(lsfm_context* ctx, int m, const int* rowptr, const int* colidx
 	h2d(ctx, dx, x, (size_t)m * 6 * sizeof(double));
 	build_spmv_index(ctx, sy, dk);
 	float total = 0;
+	hipEvent_t e0 = ctx->pool_event(), e1 = ctx->pool_event();
 	for (int k = 0; k < reps + 2; k++)
 	{
 		dev_zero(ctx, dy, (size_t)m * 6 * sizeof(double));
-		LSFM_CHECK_HIP(hipEventRecord(ctx->ev0, s));
+		LSFM_CHECK_HIP(hipEventRecord(e0, s));
 		launch_spmv(ctx, sy, dx, dy, nullptr, nullptr, nullptr, nullptr, 1);
-		LSFM_CHECK_HIP(hipEventRecord(ctx->ev1, s));
-		LSFM_CHECK_HIP(hipEventSynchronize(ctx->ev1));
+		LSFM_CHECK_HIP(hipEventRecord(e1, s));
+		LSFM_CHECK_HIP(hipEventSynchronize(e1));
 		float t = 0;
-		LSFM_CHECK_HIP(hipEventElapsedTime(&t, ctx->ev0, ctx->ev1));
+		LSFM_CHECK_HIP(hipEventElapsedTime(&t, e0, e1));
 		if (k >= 2) total += t;
 	}
 	d2h(ctx, y, dy, (size_t)m * 6 * sizeof(double));

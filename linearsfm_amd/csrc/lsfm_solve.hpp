@@ -77,7 +77,7 @@ struct EarlyPatternIn {
 void build_schur_pattern(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy);
 // the block pattern of S alone (K8), from the index members of io: upper block CSR left in the scratch arena
 void schur_pattern_only(lsfm_context* ctx, const SolveIO& io, int* nnzb, const int** rowptr, const int** colidx);
-void schur_pattern_early_issue(lsfm_context* ctx, const EarlyPatternIn& in); // enqueues on the side stream; the caller has recorded evC
+void schur_pattern_early_issue(lsfm_context* ctx, const EarlyPatternIn& in); // enqueues on the side stream; the caller has recorded evC_pairs
 void schur_pattern_early_drop(lsfm_context* ctx);
 bool schur_pattern_early_finish(lsfm_context* ctx, const SolveIO& io, SchurSystem& sy);
 void schur_pattern_early_extras(lsfm_context* ctx, SchurSystem& sy);

@@ -1019,9 +1019,8 @@ static void launch_stage(lsfm_context* ctx, const DevBatch& in, DevBatch& out, c
 		// reads the finished rows, still waits for the block kernel.
 		if (!ctx->comm && in.NU)
 		{
-			LSFM_CHECK_HIP(hipEventRecord(ctx->evU, s));
-			LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream2, ctx->evU, 0));
-			hipLaunchKernelGGL(k_tr_ublocks<NH>, dim3((in.NU + 127) / 128), dim3(128), 0, ctx->stream2, in.NU, M, d_tm, in.pose_map, in.U, in.Ui, in.Uj, KU,
+			Fork early(ctx, ctx->stream2, evU); // (rejoins with the U stage below, which follows it on that stream)
+			hipLaunchKernelGGL(k_tr_ublocks<NH>, dim3((in.NU + 127) / 128), dim3(128), 0, ctx->stream, in.NU, M, d_tm, in.pose_map, in.U, in.Ui, in.Uj, KU,
 			                   Dp, Cp, out.U, out.Ui, out.Uj, Gpose);
 			u_early = true;
 		}
@@ -1030,7 +1029,7 @@ static void launch_stage(lsfm_context* ctx, const DevBatch& in, DevBatch& out, c
 		hipLaunchKernelGGL(k_tr_entries<NH>, dim3((in.NF + TRE_TILE - 1) / TRE_TILE), dim3(TRE_ROUND), 0, s, in.NF, M, finfo, in.fptr, in.W,
 		                   in.photo, KW, Dp, Cp, FD, rd.W, rd.photo, rd.feature, Gsum, Gpose, hubJ, out.W_alias ? 1 : 0, rd.wbase, rd.newf, rd.srcf);
 		if (ctx->stats) LSFM_REC_T(e1, s);
-		LSFM_CHECK_HIP(hipEventRecord(ctx->evA, s)); // pose rows of G complete: the U stage may start on the side stream
+		LSFM_CHECK_HIP(hipEventRecord(ctx->ord[evG], s)); // pose rows of G complete: the U stage may start on the side stream
 		ev_entries = true;
 		hipLaunchKernelGGL(k_tr_feat_post<NH>, dim3((in.NF + 255) / 256), dim3(256), 0, s, in.NF, M, d_tm, in.feat_map, in.fptr, in.V, in.W, in.photo,
 		                   Dp, FD, Gsum, hubJ, rd.wbase, rd.newf, rd.srcf, rd.W, rd.photo, rd.feature, PP);
@@ -1052,19 +1051,21 @@ static void launch_stage(lsfm_context* ctx, const DevBatch& in, DevBatch& out, c
 	// feature-sharded run: what the features of this rank's slice added to the pose rows of G (k_tr_entries) and to the hub-hub
 	// blocks (k_tr_feat_post) becomes the sum over all slices before the pose kernels read and extend it
 	if (ctx->comm) ctx->comm->allreduce(s, Gpose, (size_t)M * 36 * NH + (size_t)in.B * 3 * 36, LSFM_DTYPE_F64);
-	hipStream_t su = (ev_entries && !ctx->comm) ? ctx->stream2 : s;
-	if (su != s) LSFM_CHECK_HIP(hipStreamWaitEvent(su, ctx->evA, 0));
-	if (in.NU && !u_early)
-		hipLaunchKernelGGL(k_tr_ublocks<NH>, dim3((in.NU + 127) / 128), dim3(128), 0, su, in.NU, M, d_tm, in.pose_map, in.U, in.Ui, in.Uj, KU,
-		                   Dp, Cp, out.U, out.Ui, out.Uj, Gpose);
-	if (M)
-		hipLaunchKernelGGL(k_tr_poseslots<NH>, dim3((M + 127) / 128), dim3(128), 0, su, M, d_tm, in.pose_map, Dp, Cp, Gpose, out.U, out.Ui,
-		                   out.Uj, PP);
-	if (su != s)
+	auto u_stage = [&](hipStream_t su) {
+		if (in.NU && !u_early)
+			hipLaunchKernelGGL(k_tr_ublocks<NH>, dim3((in.NU + 127) / 128), dim3(128), 0, su, in.NU, M, d_tm, in.pose_map, in.U, in.Ui, in.Uj, KU,
+			                   Dp, Cp, out.U, out.Ui, out.Uj, Gpose);
+		if (M)
+			hipLaunchKernelGGL(k_tr_poseslots<NH>, dim3((M + 127) / 128), dim3(128), 0, su, M, d_tm, in.pose_map, Dp, Cp, Gpose, out.U, out.Ui,
+			                   out.Uj, PP);
+	};
+	if (ev_entries && !ctx->comm)
 	{
-		LSFM_CHECK_HIP(hipEventRecord(ctx->evB, su));
-		LSFM_CHECK_HIP(hipStreamWaitEvent(s, ctx->evB, 0));
+		Fork side(ctx, ctx->stream2, evG, false);
+		u_stage(ctx->stream);
+		side.join(evT);
 	}
+	else u_stage(s);
 	hipLaunchKernelGGL(k_tr_diag<NH>, dim3((in.B + 127) / 128), dim3(128), 0, s, in.B, d_tm, PP, out.U);
 }
 
@@ -1312,7 +1313,7 @@ void transform_batch(lsfm_context* ctx, Arena& ar, const DevBatch& in, const std
 	ctx->mark("tr_done");
 	LSFM_CHECK_HIP(hipGetLastError());
 	// Scratch is released for the caller's next stage: everything that touches it is ordered on the main stream (the side
-	// stream's part rejoins it through evB above).  A first run also stops here so that a failure surfaces at its stage --
+	// stream's part rejoins it through evT above).  A first run also stops here so that a failure surfaces at its stage --
 	// unless its consumer was laid out inside the hook: that one goes on enqueuing (its solve stops for the device soon
 	// enough), so that the host's part of the solve's analysis runs beside these kernels, not after them.
 	if (!warm && !hook && !ctx->in_tree_run) LSFM_CHECK_HIP(hipStreamSynchronize(s)); // (a level of a tree run is only enqueued: errors are read at the end of the run)

@@ -20,7 +20,7 @@ bool level_plan(lsfm_context* ctx, lsfm_tree* t, int level)
 	{
 		// ... all of it: the plan of this level was made while the level below was being solved (prefetch_next_level)
 		ctx->plan = &ctx->pre_plan;
-		LSFM_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->evP, 0));
+		wait_for(ctx, ctx->stream, evP);
 	}
 	return analysing;
 }
@@ -59,6 +59,8 @@ hipEvent_t run_level(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int level,
 	const int so = t->slot < 0 ? 0 : (t->slot + 1) % 3, sm = t->slot < 0 ? 1 : (t->slot + 2) % 3;
 	Arena& other = ctx->arena[so];
 	Arena& mine = ctx->arena[sm];
+	// (the run statistics of the level below read its run pointers on stream2: long done, but nothing else says so)
+	wait_for(ctx, ctx->stream, evR_done);
 	other.reset();
 	mine.reset();
 	DevBatch Xt, Y;
@@ -197,6 +199,7 @@ Pass run_pass(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int attempt, int 
 			// its peers would wait there for a sum this rank never joins; it is rethrown after the exchange
 			pass_error.reset(new Error(e));
 			(void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError();
+			ctx->quiesce_side_streams();
 			ctx->drop_prepared();
 			return Pass::DONE;
 		}
@@ -205,11 +208,13 @@ Pass run_pass(lsfm_context* ctx, lsfm_tree* t, lsfm_stats* st, int attempt, int 
 		if (e.code == LSFM_ERR_NOT_SPD && attempt < 3)
 		{
 			(void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError();
+			ctx->quiesce_side_streams();
 			ctx->stats = st; ctx->plan = nullptr; // (tree_pass was left mid-level)
 			t->step_hint.clear(); t->plans.clear();
 			if (getenv("LSFM_DEBUG_CONV")) fprintf(stderr, "[lsfm conv] attempt %d: %s -- joining the tree again\n", attempt, e.msg.c_str());
 			return Pass::AGAIN;
 		}
+		ctx->quiesce_side_streams(); // (the pass was left mid-level: nothing of it may still be running when arenas grow or the caller resets them)
 		// (the arenas start at an eighth of the upper bound the upload asked for: a run that exhausts one doubles them and starts over)
 		if (e.code != LSFM_ERR_OOM || !ctx->grow_arenas()) throw;
 		if (getenv("LSFM_DEBUG")) fprintf(stderr, "[lsfm] arenas grown to %zu MiB each after: %s\n", ctx->arena_bytes >> 20, e.msg.c_str());

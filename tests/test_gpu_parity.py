@@ -680,6 +680,49 @@ def test_error_paths_of_the_c_abi(ctx):
     assert rc == 0 and int(out["m"]) == 2 and stats["attempts"] == 1
 
 
+def test_error_in_an_upper_level_leaves_the_context_usable(ctx):
+    """An error thrown at a level of the sparse pipeline -- with the next level being prepared on the side stream and the helper
+    thread, and this level's side work enqueued -- comes back as an error, and the same context then gives the sound result.
+    Sixteen Stereo maps of one pose each: levels 0 and 1 take the dense path, levels 2 and 3 the sparse pipeline.  Input map 8 gets
+    FRef = 5, an id below every id of the set that no pose carries: an even map's FRef is not consulted at levels 0-2; at level 3 it
+    is the FRef of joint map 1, whose Ref is larger, so the transform is sent to pose 5 and reports it.  (A regression guard: the
+    exits it walks wait for the side streams before arenas are reset, which no test can show without racing a kernel against one.)"""
+    from linearsfm_amd import api
+    good = [oracle_free_dict(m) for m in synth.make_stereo_set(16, 6, 4, seed=3, first_id=10)]
+    A, sa, rca = ctx.divide_conquer(good, False)
+    assert rca == 0 and sa["not_converged"] == 0, sa
+    bad = [dict(m) for m in good]
+    bad[8]["FRef"] = 5
+    t = ctx.tree_upload(bad, False)
+    try:
+        ctx.tree_set_stop_level(t, 3)
+        _, rc = ctx.tree_run(t)
+        assert rc == 0  # levels 0-2 are sound: the failure is level 3's
+        ctx.tree_set_stop_level(t, 0)
+        for plans in (True, False):
+            ctx.tree_set_plans(t, plans)
+            with pytest.raises(api.LsfmError, match="target pose id not found"):
+                ctx.tree_run(t)
+    finally:
+        ctx.tree_free(t)
+    for plans in (True, False):
+        t = ctx.tree_upload(good, False)
+        try:
+            ctx.tree_set_plans(t, plans)
+            s, rc = ctx.tree_run(t)
+            out = ctx.tree_download(t)
+        finally:
+            ctx.tree_free(t)
+        assert rc == 0 and s["attempts"] == 1 and s["not_converged"] == 0, s
+        assert np.array_equal(out["stno"], A["stno"])
+        for k in ("Ui", "Uj", "photo", "feature"):
+            assert np.array_equal(out[k], A[k]), k
+        assert pose_param_err(out["stVal"], A["stVal"], A["stno"]) < 1e-9
+        assert feat_param_err(out["stVal"], A["stVal"], A["stno"]) < 1e-9
+        for k in ("U", "W", "V"):
+            assert rel_err(out[k], A[k]) < 1e-7, k
+
+
 def oracle_free_dict(m):
     """LocalMap -> the dict the ctypes view takes (same fields as pyoracle.localmap_to_dict, without importing the oracle)."""
     return dict(Ref=m.Ref, FRef=m.Ref, m=m.m, n=m.n, stno=m.stno, stVal=m.stVal, U=m.U, Ui=m.Ui, Uj=m.Uj, W=m.W, photo=m.photo,
