@@ -628,6 +628,31 @@ int lsfm_selftest_chol(lsfm_context* ctx, int m, const int* rowptr, const int* c
 int lsfm_selftest_transform(lsfm_context* ctx, const lsfm_map* maps, int N, int mono, const int* tref, const int* tscap, const int* tfix,
                             int alias_passthrough, lsfm_map* out);
 
+/* Test entry: the one-launch dense path for camera systems of at most 16 poses (lsfm_small.hip, lsfm_set_small_solve) on a batch of
+ * the caller's, as a tree level hands it one -- G independent systems back to back in ONE launch, where lsfm_solve_stereo /
+ * lsfm_solve_mono hand it a single system.  Host plumbing only: the arrays are uploaded, x_pose / x_feat are filled with the
+ * caller's values, the kernel is launched once, the outputs are downloaded; no plans, no run record, no refusal of a bad system
+ * (what the kernel reports is returned in status).
+ *   pose_off[G + 1], feat_off[G + 1], u_off[G + 1]   first pose / feature / U block of every system; from 0 to M / NF / NU.  Every
+ *                   system has at least one pose; one without features or without U blocks is allowed
+ *   active[G]       0: a carried system -- its x_pose becomes x0 (0 where x0 is NULL), its x_feat is not touched (NULL: all active)
+ *   U, Ui, Uj       [36 NU], [NU]: blocks in the batch's pose numbering, Ui <= Uj, both inside the system the block is listed under
+ *   W, photo, feature, nW   [18 nW], [nW]: sorted by feature (the batch's numbering), every feature with at least one block, every
+ *                   block's pose inside its feature's system
+ *   V [9 NF], ea [6 M], eb [3 NF], x0 [6 M] (may be NULL), fixed [6 M] (may be NULL; != 0: a scalar held at zero, the Mono gauge)
+ *   strips          16-row strips of the kernel instance to launch: 1, 2, 3 or 6 (systems of at most 2, 5, 8, 16 poses); 0: the
+ *                   instance of the largest system, as a level chooses it
+ *   x_pose [6 M], x_feat [3 NF]   in: the prefill; out: the solution where the kernel wrote one
+ *   status[2]       systems left above the residual bound or with a V that has no factor; 1 + a system with a non-positive pivot
+ *                   (0: none) -- that system's x_pose and x_feat are not written
+ *   max_rel         the largest relative residual of the launch
+ * LSFM_ERR_ARG, before anything is enqueued, for strips outside { 0, 1, 2, 3, 6 }, a system with more poses than the instance's panel
+ * has rows for (6 m > 16 strips), more than 16 poses, offsets that do not tile the batch, or a block of another system's pose. */
+int lsfm_selftest_small(lsfm_context* ctx, int G, const int* pose_off, const int* feat_off, const int* u_off, const unsigned char* active,
+                        const double* U, const int* Ui, const int* Uj, const double* W, const int* photo, const int* feature, int nW, const double* V,
+                        const double* ea, const double* eb, const double* x0, const unsigned char* fixed, int strips, double* x_pose, double* x_feat,
+                        int* status, double* max_rel);
+
 #ifdef __cplusplus
 }
 #endif

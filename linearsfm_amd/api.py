@@ -146,6 +146,7 @@ def lib():
         L.lsfm_selftest_chol.argtypes = [vp, C.c_int, ip, ip, dp, ip, P(C.c_ubyte), ip, C.c_int, dp, C.c_int, C.c_int, dp, dp, ip, ip, ip, dp, dp, dp,
                                          C.c_int, ip]
         L.lsfm_selftest_transform.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, ip, ip, ip, C.c_int, P(LsfmMap)]
+        L.lsfm_selftest_small.argtypes = [vp, C.c_int, ip, ip, ip, ub, dp, ip, ip, dp, ip, ip, C.c_int, dp, dp, dp, dp, ub, C.c_int, dp, dp, ip, dp]
         _LIB = L
     return _LIB
 
@@ -157,7 +158,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_tree_upload_dev", "lsfm_tree_reload_dev", "lsfm_tree_set_comm", "lsfm_tree_set_comm_blocks", "lsfm_tree_export_slice_sizes", "lsfm_tree_export_slice_dev",
            "lsfm_tree_free", "lsfm_divide_conquer", "lsfm_read_localmap", "lsfm_read_localmaps", "lsfm_write_localmap", "lsfm_write_mapset", "lsfm_mapset_info", "lsfm_mapset_stamp", "lsfm_read_mapset", "lsfm_save_state_bin", "lsfm_save_state", "lsfm_save_poses", "lsfm_gn_polish",
            "lsfm_gn_polish_robust", "lsfm_map_chi2", "lsfm_gn_linearise", "lsfm_gn_linearise_timed",
-           "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_selftest_chol", "lsfm_selftest_transform", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
+           "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_selftest_chol", "lsfm_selftest_transform", "lsfm_selftest_small", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
            "lsfm_map_covariance", "lsfm_map_covariance_timed",
            "lsfm_save_covariances", "lsfm_read_covariances",
            "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns",
@@ -746,6 +747,48 @@ def _selftest_transform(self, dicts, mono, targets, alias=False):
 
 
 Context.selftest_transform = _selftest_transform
+
+
+def _selftest_small(self, B, strips=0, active=None, fixed=None, x0=None, prefill=None):
+    """lsfm_selftest_small: the systems of B -- dict(pose_off, feat_off, u_off [G + 1]; U, Ui, Uj, W, photo, feature, V, ea, eb in the
+    batch's numbering) -- through ONE launch of the dense small-system kernel, at the instance of `strips` 16-row strips (0: that of
+    the largest system).  active [G], fixed [6 M], x0 [6 M]: optional.  prefill: (x_pose, x_feat) as they are before the launch
+    (default: NaN, so that what the kernel did not write shows).  Returns (x_pose, x_feat, status [2], max_rel)."""
+    po, fo, uo = (_c(B[k], np.int32) for k in ("pose_off", "feat_off", "u_off"))
+    G = len(po) - 1
+    if G < 1 or len(fo) != G + 1 or len(uo) != G + 1:
+        raise LsfmError("selftest_small: pose_off / feat_off / u_off must have one entry per system and one more")
+    M, NF, NU = int(po[-1]), int(fo[-1]), int(uo[-1])
+    U = _c(B["U"], np.float64); Ui = _c(B["Ui"], np.int32); Uj = _c(B["Uj"], np.int32)
+    W = _c(B["W"], np.float64); ph = _c(B["photo"], np.int32); fe = _c(B["feature"], np.int32); V = _c(B["V"], np.float64)
+    ea = _c(B["ea"], np.float64); eb = _c(B["eb"], np.float64)
+    nW = len(ph)
+    if (len(U), len(Ui), len(Uj)) != (36 * NU, NU, NU) or (len(W), len(fe)) != (18 * nW, nW) or (len(V), len(ea), len(eb)) != (9 * NF, 6 * M, 3 * NF):
+        raise LsfmError("selftest_small: the arrays do not fit the offsets")
+    flags = lambda a, n, what: None if a is None else _fit(np.ascontiguousarray(np.asarray(a).astype(bool), dtype=np.uint8).reshape(-1), n, what)
+    act, fx = flags(active, G, "active"), flags(fixed, 6 * M, "fixed")
+    x0 = None if x0 is None else _fit(_c(x0, np.float64), 6 * M, "x0")
+    if prefill is None:
+        xp, xf = np.full(6 * M, np.nan), np.full(3 * NF, np.nan)
+    else:
+        xp, xf = _fit(np.array(_c(prefill[0], np.float64)), 6 * M, "prefill"), _fit(np.array(_c(prefill[1], np.float64)), 3 * NF, "prefill")
+    st = np.zeros(2, np.int32)
+    mr = C.c_double()
+    d, i, opt = C.c_double, C.c_int, lambda a, t: None if a is None else _ptr(a, t)
+    rc = lib().lsfm_selftest_small(self._h, G, _ptr(po, i), _ptr(fo, i), _ptr(uo, i), opt(act, C.c_ubyte), _ptr(U, d), _ptr(Ui, i), _ptr(Uj, i),
+                                   _ptr(W, d), _ptr(ph, i), _ptr(fe, i), nW, _ptr(V, d), _ptr(ea, d), _ptr(eb, d), opt(x0, d), opt(fx, C.c_ubyte),
+                                   int(strips), _ptr(xp, d), _ptr(xf, d), _ptr(st, i), C.byref(mr))
+    self._check(rc, "lsfm_selftest_small")
+    return xp, xf, st, mr.value
+
+
+def _fit(a, n, what):
+    if len(a) != n:
+        raise LsfmError(f"selftest_small: {what} has {len(a)} entries, not {n}")
+    return a
+
+
+Context.selftest_small = _selftest_small
 
 
 def symbolic_analyse(rowptr, colidx, origin=None, reps=1):

@@ -664,6 +664,24 @@ int lsfm_selftest_transform(lsfm_context* ctx, const lsfm_map* maps, int N, int 
 	return rc;
 }
 
+int lsfm_selftest_small(lsfm_context* ctx, int G, const int* pose_off, const int* feat_off, const int* u_off, const unsigned char* active,
+                        const double* U, const int* Ui, const int* Uj, const double* W, const int* photo, const int* feature, int nW, const double* V,
+                        const double* ea, const double* eb, const double* x0, const unsigned char* fixed, int strips, double* x_pose, double* x_feat,
+                        int* status, double* max_rel)
+{
+	if (G <= 0 || !pose_off || !feat_off || !u_off || !ea || !x_pose || !status || !max_rel || strips < 0 || nW < 0) return LSFM_ERR_ARG;
+	const int M = pose_off[G], NF = feat_off[G], NU = u_off[G];
+	if (M <= 0 || NF < 0 || NU < 0 || (NU && (!U || !Ui || !Uj)) || (nW && (!W || !photo || !feature)) || (NF && (!V || !eb || !x_feat))) return LSFM_ERR_ARG;
+	status[0] = status[1] = 0; *max_rel = 0.0;
+	return guarded(ctx, [&]() {
+		HostSystem h;
+		h.m = M; h.n = NF; h.nU = NU; h.nW = nW;
+		h.Ui = Ui; h.Uj = Uj; h.photo = photo; h.feature = feature;
+		h.U = U; h.W = W; h.V = V; h.ea = ea; h.eb = eb; h.x0 = x0;
+		return small_selftest(ctx, G, pose_off, feat_off, u_off, active, h, fixed, strips, x_pose, x_feat, status, max_rel);
+	});
+}
+
 int lsfm_wstream_bench(lsfm_context* ctx, long long nblocks, int mode, int reps, double* avg_ms)
 {
 	if (nblocks <= 0 || mode < 0 || mode > 2 || reps <= 0 || !avg_ms) return LSFM_ERR_ARG;

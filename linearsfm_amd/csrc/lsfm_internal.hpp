@@ -530,6 +530,10 @@ inline int small_level_strips(const lsfm_context* ctx, const std::vector<int>& s
 // the join of such a level (io.seg_rows set): the ranges of its joins in the joint maps `out`, by which the dense path walks them, to io
 void small_level_offsets(lsfm_context* ctx, const DevBatch& out, SolveIO& io);
 void small_solve_launch(lsfm_context* ctx, const SolveIO& io, int strips, int* status, double* max_rel);
+// lsfm_selftest_small: G systems back to back in h (the batch's numbering), one small_solve_launch; x_pose / x_feat go in as the prefill
+struct HostSystem;
+int small_selftest(lsfm_context* ctx, int G, const int* pose_off, const int* feat_off, const int* u_off, const unsigned char* active, const HostSystem& h,
+                   const unsigned char* fixed, int strips, double* x_pose, double* x_feat, int* status, double* max_rel);
 SolveOutcome solve_batch(lsfm_context* ctx, const SolveIO& io);
 // groups: consecutive maps (2g, 2g+1) of `in` are joined, a trailing unpaired map is carried over unchanged.
 // Produces `out` (ceil(B/2) maps) with the solved state.  eP_out / eF_out (host, optional) receive the right-hand

@@ -16,9 +16,15 @@
 //   4. streams the W blocks a second time (they are in L2 / Infinity Cache) for the features: x_f = V^-1 (eb - sum W^T x_p)
 //      (pba_solveFeatures, Imp.cpp:2980-3020).
 // No sum of it crosses work-groups: the result is the same bits in every run.  Levels with larger systems keep the sparse path.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <type_traits>
+
 #include "lsfm_device.hpp"
 #include "lsfm_internal.hpp"
 #include "lsfm_solve.hpp"
+#include "lsfm_system.hpp"
 
 namespace lsfm {
 
@@ -518,6 +524,57 @@ void small_solve_launch(lsfm_context* ctx, const SolveIO& io, int strips, int* s
 	default: launch_small<6>(ctx->stream, a); break;
 	}
 	LSFM_CHECK_HIP(hipGetLastError());
+}
+
+// lsfm_selftest_small (include/lsfm.h): host plumbing only -- G systems back to back in a batch's numbering, uploaded, ONE
+// small_solve_launch, the outputs back.  Whatever would let the kernel leave its LDS -- a panel with fewer rows than a system has
+// scalars, a block whose pose lies outside its system's range -- is refused before anything is enqueued.
+int small_selftest(lsfm_context* ctx, int G, const int* pose_off, const int* feat_off, const int* u_off, const unsigned char* active, const HostSystem& h,
+                   const unsigned char* fixed, int strips, double* x_pose, double* x_feat, int* status, double* max_rel)
+{
+	if (pose_off[0] || feat_off[0] || u_off[0] || pose_off[G] != h.m || feat_off[G] != h.n || u_off[G] != h.nU)
+		LSFM_FAIL(LSFM_ERR_ARG, "the offsets must run from 0 to the batch's poses / features / U blocks");
+	const std::vector<int> fptr = system_fptr(h); // (W sorted by feature, every feature with a block, 0 <= Ui <= Uj < M, 0 <= photo < M)
+	int most = 0;
+	for (int g = 0; g < G; g++)
+	{
+		const int p0 = pose_off[g], p1 = pose_off[g + 1];
+		if (p1 <= p0 || feat_off[g + 1] < feat_off[g] || u_off[g + 1] < u_off[g]) LSFM_FAIL(LSFM_ERR_ARG, "system " + std::to_string(g) + ": empty or negative range");
+		most = std::max(most, p1 - p0);
+		for (int i = u_off[g]; i < u_off[g + 1]; i++)
+			if (h.Ui[i] < p0 || h.Uj[i] >= p1) LSFM_FAIL(LSFM_ERR_ARG, "system " + std::to_string(g) + ": a U block of another system's pose");
+		for (int j = fptr[feat_off[g]]; j < fptr[feat_off[g + 1]]; j++)
+			if (h.photo[j] < p0 || h.photo[j] >= p1) LSFM_FAIL(LSFM_ERR_ARG, "system " + std::to_string(g) + ": a W block of another system's pose");
+	}
+	if (most > 16) LSFM_FAIL(LSFM_ERR_ARG, "a system of " + std::to_string(most) + " poses: the dense path holds 16");
+	if (!strips) strips = small_solve_strips(most, 16);
+	if (strips != 1 && strips != 2 && strips != 3 && strips != 6) LSFM_FAIL(LSFM_ERR_ARG, "strips must be 0, 1, 2, 3 or 6");
+	if (6 * most > 16 * strips) LSFM_FAIL(LSFM_ERR_ARG, "a system of " + std::to_string(most) + " poses does not fit a panel of " + std::to_string(strips) + " strips");
+	SolveIO io;
+	system_upload(ctx, h, SYS_VALUES | SYS_RHS | SYS_X, fptr, nullptr, io);
+	Arena& ar = ctx->arena[0];
+	auto up = [&](auto* src, size_t count) {
+		auto* d = ar.alloc<std::remove_cv_t<std::remove_pointer_t<decltype(src)>>>(count);
+		h2d(ctx, d, src, count * sizeof *src);
+		return d;
+	};
+	io.nseg = G;
+	io.d_pose_off = up(pose_off, (size_t)G + 1); io.d_feat_off = up(feat_off, (size_t)G + 1); io.d_u_off = up(u_off, (size_t)G + 1);
+	if (active) io.d_seg_active = up(active, (size_t)G);
+	if (fixed) io.d_fixed = up(fixed, (size_t)h.m * 6);
+	// (the caller's arrays go in first: what the launch does not write comes back as it went in)
+	h2d(ctx, io.x_pose, x_pose, (size_t)h.m * 6 * sizeof(double));
+	h2d(ctx, io.x_feat, x_feat, (size_t)h.n * 3 * sizeof(double));
+	int* d_small = ctx->scratch.alloc<int>(4); // status[2], and behind them the largest relative residual as a double
+	dev_zero(ctx, d_small, 4 * sizeof(int));
+	small_solve_launch(ctx, io, strips, d_small, reinterpret_cast<double*>(d_small + 2));
+	int hs[4];
+	d2h_ints(ctx, d_small, hs, 4);
+	status[0] = hs[0]; status[1] = hs[1];
+	memcpy(max_rel, hs + 2, sizeof *max_rel);
+	d2h(ctx, x_pose, io.x_pose, (size_t)h.m * 6 * sizeof(double));
+	d2h(ctx, x_feat, io.x_feat, (size_t)h.n * 3 * sizeof(double));
+	return LSFM_OK;
 }
 
 } // namespace lsfm

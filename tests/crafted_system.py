@@ -17,13 +17,14 @@ EPS_V = 0.25   # V_f = sum B^T B + EPS_V I
 PRIOR = 0.5    # U_pp += PRIOR diag(data term of U_pp)
 
 
-def craft(m, tiles, seed, decades=0.0, dup=0.1, offdiag=False, bad_v=None):
+def craft(m, tiles, seed, decades=0.0, dup=0.1, offdiag=False, bad_v=None, split_u=False):
     """tiles: one dict per tile of TILE consecutive features, in order: n (features, default TILE; only the last may have fewer),
     poses (the poses that see it: each of them sees at least one of its features, no other pose does), run (lo, hi: the number of
     poses that see a feature, uniform), dup_tail (optional (first feature of the tile, probability): repeats forced onto the blocks of
     the tile's last features).  dup: probability that an observation is stored as two W blocks that sum to A^T B (the second ones
     behind the feature's first blocks, as a join leaves them).  offdiag: U blocks (p, p + 1) of a chain.  bad_v (feature, rel): that
-    V_f gets one eigenvalue of -rel times its largest.  Returns the system in the layout of common.golden_system, and beside it
+    V_f gets one eigenvalue of -rel times its largest.  split_u: every U block is stored as two addends, cut element by element like
+    the repeats of W (those of a diagonal block stay symmetric).  Returns the system in the layout of common.golden_system, and beside it
     `scale` [m, 6] and `counts` (the poses of each tile as described)."""
     rng = np.random.default_rng(seed)
     scale = 10.0 ** rng.uniform(-decades, decades, (m, 6)) if decades else np.ones((m, 6))
@@ -94,6 +95,11 @@ def craft(m, tiles, seed, decades=0.0, dup=0.1, offdiag=False, bad_v=None):
     d = np.einsum("kii->ki", Ud)
     Ud[:, np.arange(6), np.arange(6)] += np.where(d > 0, PRIOR * d, scale ** 2)  # (a pose nothing sees: the prior alone)
     U = np.concatenate([Ud, Uo]) if len(Uo) else Ud
+    if split_u:
+        T = rng.uniform(-1.0, 2.0, U.shape)
+        T[:m] = 0.5 * (T[:m] + T[:m].transpose(0, 2, 1))
+        U = np.concatenate([U * T, U - U * T])
+        Ui, Uj = Ui + Ui, Uj + Uj
     return dict(m=int(m), n=int(n), U=U.reshape(-1, 36), Ui=np.concatenate(Ui).astype(np.int32), Uj=np.concatenate(Uj).astype(np.int32),
                 W=Wb.reshape(-1, 18), V=V.reshape(-1, 9), photo=pb.astype(np.int32), feature=fb.astype(np.int32),
                 scale=scale, counts=[len(t["poses"]) for t in tiles])

@@ -48,12 +48,14 @@ def test_small_path_and_pipeline_vs_dense_lapack(ctx, both, name):
             assert st_s[sa[2]] == sa[3] and np.all(st_s[6 * sa[0]:6 * sa[0] + 6] == 0.0)
 
 
-@pytest.mark.parametrize("mono,n_maps", [(False, 8), (False, 37), (True, 8), (True, 21)])
+@pytest.mark.parametrize("mono,n_maps", [(False, 8), (False, 37), (True, 8), (True, 21), (False, 9)])
 def test_trees_through_the_small_path(ctx, both, oracle, mono, n_maps):
     """Whole trees: the lowest levels (systems of 2-16 poses) by the dense path, the rest by the pipeline -- against the same tree
     with every level in the pipeline (1e-9: both are direct solves of the same systems) and against the ORACLE (1e-6, BASELINE.json);
-    lsfm_stats.small_levels says how many levels took the path."""
-    maps = synth.make_mono_set(n_maps, 8, 4, seed=5, **synth.SPIRAL) if mono else synth.make_stereo_set(n_maps, 8, 5, seed=5, lap=30, home=5)
+    lsfm_stats.small_levels says how many levels took the path.  The set of 9 maps has 130 new features a frame (the benchmark's
+    density): every join of level 0 has more than 256 features -- a second chunk of run pointers -- and one map is carried."""
+    npf = 130 if n_maps == 9 else 8
+    maps = synth.make_mono_set(n_maps, npf, 4, seed=5, **synth.SPIRAL) if mono else synth.make_stereo_set(n_maps, npf, 5, seed=5, lap=30, home=5)
     dicts = [dict(m.__dict__) for m in maps]
     (a, sa, rca), (b, sb, rcb) = both(lambda: ctx.divide_conquer(dicts, mono))
     assert rca == 0 and rcb == 0
