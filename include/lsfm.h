@@ -217,6 +217,30 @@ int lsfm_map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, int type, cons
 int lsfm_gn_polish_robust(lsfm_context* ctx, const lsfm_map* maps, int N, int type, lsfm_map* x, int iters, int kind, double c,
                           double* obj, double* gnorm, int* halvings, double* chi2, double* weight);
 
+/* ---- per-feature consistency and the polish that down-weights single features (NO reference counterpart: PARITY UNPINNED; the tests
+ * hold both against the CPU checker's F on re-weighted map dicts) ----
+ * For local map k with I_k = [U W; W^T V] and residual r = (r_p, r_f) at the global state x,
+ *     chi2_k = r_p^T (U - sum_f W_f V_f^-1 W_f^T) r_p + sum_f c_kf,   c_kf = g_f^T V_f^-1 g_f >= 0,   g_f = V_f r_f + sum_a W_af^T r_a:
+ * c_kf is the chi^2 (3 degrees of freedom) of feature f of map k given the map's poses.
+ * fchi2[sum_k n_k]: c_kf in map order, within a map in the map's feature order.  pose_chi2[N] (may be NULL): chi2_k - sum_f c_kf, the pose
+ * part under the map's own Schur complement.  Arguments and errors: lsfm_map_chi2's; x is read only.  LSFM_ERR_NOT_SPD: a V_f is not
+ * positive definite (lsfm_last_error names the map and the feature).  One work-group per map, V_f^-1 by a 3x3 Cholesky in registers,
+ * every sum in a fixed order and no atomics: the same input gives the same bits. */
+int lsfm_map_feature_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, double* fchi2, double* pose_chi2);
+/* Gauss-Newton polish with single features of single local maps as the M-estimator's residuals (IRLS).  kind: 0 none (exactly
+ * lsfm_gn_polish), 1 Huber, 2 Cauchy with rho and rho' as stated for lsfm_gn_polish_robust, on s_kf = c_kf / 3; c > 0 finite.  Minimises
+ *     G(x) = sum_k (chi2_k - sum_f c_kf) + 3 sum_kf rho(c_kf / 3).
+ * Scaling the conditional term of feature f by w_f is again an information matrix,
+ *     I_k(w) = [U - sum_f (1 - w_f) W_f V_f^-1 W_f^T,  w_f W_f;  w_f W_f^T,  w_f V_f]     (w = 1: I_k;  w_f = 0: f marginalised out),
+ * so a step solves the Gauss-Newton system of the maps I_k(w_k), w_kf = rho'(s_kf) at the current state, and takes x += a d, a halved
+ * while G does not fall, as the other polishes do (G summed in a fixed order).  No map-level weight is applied (w_k = 1): the two
+ * estimators are not combined.  A redescending weight (Cauchy) on Monocular sets can choose the wrong instance of a pulled feature
+ * (DESIGN.md 16): prefer Huber there.  obj / gnorm / halvings as lsfm_gn_polish_robust; fchi2[sum_k n_k], fweight[sum_k n_k] (each may be
+ * NULL): at the returned state, fchi2 bit for bit what lsfm_map_feature_chi2 gives there; kind 0: every weight 1.  Returns and argument
+ * errors: lsfm_gn_polish_robust's; LSFM_ERR_NOT_SPD as lsfm_map_feature_chi2. */
+int lsfm_gn_polish_robust_features(lsfm_context* ctx, const lsfm_map* maps, int N, int type, lsfm_map* x, int iters, int kind, double c,
+                                   double* obj, double* gnorm, int* halvings, double* fchi2, double* fweight);
+
 /* ---- the information matrix at a state: the joint map of the N local maps linearised at x ----
  * H = sum_k w_k J_k^T I_k J_k and the state x as an lsfm_map (library-allocated: lsfm_map_release), the matrix a step of
  * lsfm_gn_polish[_robust] solves with at x.  maps / N / type / x and every argument check: lsfm_gn_polish's; x is read only.

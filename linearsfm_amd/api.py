@@ -120,6 +120,8 @@ def lib():
         L.lsfm_gn_polish.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), C.c_int, dp, dp, ip]
         L.lsfm_gn_polish_robust.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), C.c_int, C.c_int, C.c_double, dp, dp, ip, dp, dp]
         L.lsfm_map_chi2.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, ip]
+        L.lsfm_map_feature_chi2.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, dp]
+        L.lsfm_gn_polish_robust_features.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), C.c_int, C.c_int, C.c_double, dp, dp, ip, dp, dp]
         L.lsfm_gn_linearise.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, P(LsfmMap), dp, dp]
         L.lsfm_gn_linearise_timed.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, P(LsfmMap), dp, dp, dp, ip]
         L.lsfm_solve_features.argtypes = [vp, dp, dp, dp, dp, dp, dp, C.c_int, C.c_int, ip, ip]
@@ -157,7 +159,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_tree_download", "lsfm_tree_set_stop_level", "lsfm_tree_node_count", "lsfm_tree_download_node", "lsfm_tree_download_state", "lsfm_tree_set_plans", "lsfm_tree_export_size", "lsfm_tree_export_dev", "lsfm_packed_size",
            "lsfm_tree_upload_dev", "lsfm_tree_reload_dev", "lsfm_tree_set_comm", "lsfm_tree_set_comm_blocks", "lsfm_tree_export_slice_sizes", "lsfm_tree_export_slice_dev",
            "lsfm_tree_free", "lsfm_divide_conquer", "lsfm_read_localmap", "lsfm_read_localmaps", "lsfm_write_localmap", "lsfm_write_mapset", "lsfm_mapset_info", "lsfm_mapset_stamp", "lsfm_read_mapset", "lsfm_save_state_bin", "lsfm_save_state", "lsfm_save_poses", "lsfm_gn_polish",
-           "lsfm_gn_polish_robust", "lsfm_map_chi2", "lsfm_gn_linearise", "lsfm_gn_linearise_timed",
+           "lsfm_gn_polish_robust", "lsfm_map_chi2", "lsfm_map_feature_chi2", "lsfm_gn_polish_robust_features", "lsfm_gn_linearise", "lsfm_gn_linearise_timed",
            "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_selftest_chol", "lsfm_selftest_transform", "lsfm_selftest_small", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
            "lsfm_map_covariance", "lsfm_map_covariance_timed",
            "lsfm_save_covariances", "lsfm_read_covariances",
@@ -489,6 +491,35 @@ class Context:
         if rc < 0:
             self._check(rc, "lsfm_gn_polish_robust")
         return st, obj, gn, hv[:iters], chi2, w, rc
+
+    def map_feature_chi2(self, maps, mono, G):
+        """lsfm_map_feature_chi2: c_kf = g_f^T V_f^-1 g_f, the chi^2 (3 dof) of feature f of local map k given the map's poses, at the
+        global state G, and pose_chi2_k = chi2_k - sum_f c_kf.  Deterministic.  No reference counterpart.  Returns (list of arrays, one
+        per map in the map's feature order, pose_chi2 [N])."""
+        hms, arr, x, keep = _gn_args(maps, G)
+        ns = [int(h.c.n) for h in hms]
+        fchi2, pose = np.zeros(max(sum(ns), 1)), np.zeros(len(hms))
+        self._check(lib().lsfm_map_feature_chi2(self._h, arr, len(hms), int(mono), C.byref(x), _ptr(fchi2, C.c_double), _ptr(pose, C.c_double)),
+                    "lsfm_map_feature_chi2")
+        return np.split(fchi2[:sum(ns)], np.cumsum(ns)[:-1]), pose
+
+    def gn_polish_robust_features(self, maps, mono, G, iters, kind, c):
+        """lsfm_gn_polish_robust_features: gn_polish with single features of single local maps down-weighted by an M-estimator on
+        s_kf = c_kf / 3 (IRLS on the maps I_k(w)); kind 0 none (= gn_polish), 1 / "huber", 2 / "cauchy"; c > 0.  On Monocular sets prefer
+        Huber.  No reference counterpart.  Returns (stVal, obj[iters + 1] (G per iterate), gnorm[iters + 1],
+        halvings[iters], fchi2, fweight (lists of arrays per map, at the returned state), rc)."""
+        kind = {"none": 0, "huber": 1, "cauchy": 2}.get(kind, kind)
+        hms, arr, x, keep = _gn_args(maps, G)
+        st = keep[1]
+        ns = [int(h.c.n) for h in hms]
+        obj, gn, hv = np.zeros(iters + 1), np.zeros(iters + 1), np.zeros(max(iters, 1), np.int32)
+        fchi2, fw = np.zeros(max(sum(ns), 1)), np.zeros(max(sum(ns), 1))
+        rc = lib().lsfm_gn_polish_robust_features(self._h, arr, len(hms), int(mono), C.byref(x), int(iters), int(kind), float(c), _ptr(obj, C.c_double),
+                                                  _ptr(gn, C.c_double), _ptr(hv, C.c_int), _ptr(fchi2, C.c_double), _ptr(fw, C.c_double))
+        if rc < 0:
+            self._check(rc, "lsfm_gn_polish_robust_features")
+        cut = np.cumsum(ns)[:-1]
+        return st, obj, gn, hv[:iters], np.split(fchi2[:sum(ns)], cut), np.split(fw[:sum(ns)], cut), rc
 
     def gn_linearise(self, maps, mono, G, weight=None, want_b=False, timed=False):
         """lsfm_gn_linearise: the joint map of the local maps linearised at the global state G (as gn_polish takes it; read only) --

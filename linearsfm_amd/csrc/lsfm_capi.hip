@@ -495,6 +495,20 @@ int lsfm_map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, int type, cons
 	return guarded(ctx, [&]() { return map_chi2(ctx, maps, N, type == 1, x, chi2, dof); });
 }
 
+int lsfm_map_feature_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, double* fchi2, double* pose_chi2)
+{
+	if (!maps || N <= 0 || !x || !fchi2 || (type != 0 && type != 1)) return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() { return map_feature_chi2(ctx, maps, N, type == 1, x, fchi2, pose_chi2); });
+}
+
+int lsfm_gn_polish_robust_features(lsfm_context* ctx, const lsfm_map* maps, int N, int type, lsfm_map* x, int iters, int kind, double c, double* obj,
+                                   double* gnorm, int* halvings, double* fchi2, double* fweight)
+{
+	if (!maps || N <= 0 || !x || iters < 0 || !obj || !gnorm || (type != 0 && type != 1) || kind < 0 || kind > 2 || !(c > 0.0) || !std::isfinite(c))
+		return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() { return gn_polish_features(ctx, maps, N, type == 1, x, iters, kind, c, obj, gnorm, halvings, fchi2, fweight); });
+}
+
 int lsfm_gn_linearise_timed(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, const double* weight, lsfm_map* out, double* obj,
                             double* b, double* times, int* counts)
 {

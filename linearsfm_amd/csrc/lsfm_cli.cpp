@@ -14,6 +14,11 @@
 // line per (requested pose, pose): "id_q id_p" and the 36 entries of Sigma_{p,q}; the two flags go together),
 // -robust huber|cauchy <c> (-gn uses lsfm_gn_polish_robust: whole local maps down-weighted by an M-estimator on chi2_k / dof_k),
 // -chi2 <file> (per local map, in input order, "index dof chi2 weight" at the final state: lsfm_map_chi2; no reference counterpart),
+// -robustf huber|cauchy <c> (-gn uses lsfm_gn_polish_robust_features: single features of single local maps down-weighted by an M-estimator on
+// their conditional chi2 c_kf / 3; not together with -robust or -relin: the two estimators are not combined, and linearising with feature
+// weights is not offered),
+// -chi2f <file> (per local map and feature, in input order, "map_index feature_id chi2 weight" at the final state: lsfm_map_feature_chi2, the
+// weight 1 without -robustf; written after -chi2 through a temporary file renamed into place; no reference counterpart),
 // -relin 1 (the final map's information matrix -- U / W / V and their index arrays -- is replaced by the local maps linearised at the final
 // state, after -gn if given and with the polish's weights under -robust: lsfm_gn_linearise; -info, -cov, -covf and -covcols then describe
 // the estimate the other files hold; no reference counterpart),
@@ -52,6 +57,8 @@ static void print_help()
 	printf("			II : Stereo\n");
 	printf("-robust huber|cauchy <c>	With -gn: Down-Weight Inconsistent Local Maps (Threshold c On chi2 / dof)\n");
 	printf("-chi2 <file>		Save chi2 Of Every Local Map: index dof chi2 weight\n");
+	printf("-robustf huber|cauchy <c>	With -gn: Down-Weight Inconsistent Single Features (Threshold c On Their chi2 / 3); Not With -robust Or -relin\n");
+	printf("-chi2f <file>		Save chi2 Of Every Feature Of Every Local Map: map_index feature_id chi2 weight\n");
 	printf("-relin 1		Information Matrix (-info, -cov, -covf, -covcols) Of The Local Maps Linearised At The Final State\n");
 	printf("-keepf <file>		Keep Only The Features Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
 	printf("-keepp <file>		Keep Only The Poses Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
@@ -60,9 +67,9 @@ static void print_help()
 
 int main(int argc, char** argv)
 {
-	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf, keepp;
-	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0, relin = 0;
-	double robust_c = 0.0;
+	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf, keepp, chi2ff;
+	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0, relin = 0, robustf = 0;
+	double robust_c = 0.0, robustf_c = 0.0;
 	bool has_path = false, has_num = false, has_keepf = false, has_keepp = false;
 	double tol = 0;
 	for (int i = 1; i < argc; i++)
@@ -104,14 +111,16 @@ int main(int argc, char** argv)
 		else if (name == "covposes") covposes = next();
 		else if (name == "keepf") { keepf = next(); has_keepf = true; }
 		else if (name == "keepp") { keepp = next(); has_keepp = true; }
-		else if (name == "robust")
+		else if (name == "chi2f") chi2ff = next();
+		else if (name == "robust" || name == "robustf")
 		{
 			const std::string k = next(), v = next();
 			char* end = nullptr;
-			robust_c = strtod(v.c_str(), &end);
-			robust = k == "huber" ? 1 : (k == "cauchy" ? 2 : 0);
-			if (!robust) robust_err = "-robust: the kind must be huber or cauchy (got '" + k + "')";
-			else if (v.empty() || *end || !std::isfinite(robust_c) || robust_c <= 0) robust_err = "-robust " + k + " <c>: c must be a positive number (got '" + v + "')";
+			const double c = strtod(v.c_str(), &end);
+			const int kind = k == "huber" ? 1 : (k == "cauchy" ? 2 : 0);
+			if (name == "robust") { robust = kind; robust_c = c; } else { robustf = kind; robustf_c = c; }
+			if (!kind) robust_err = "-" + name + ": the kind must be huber or cauchy (got '" + k + "')";
+			else if (v.empty() || *end || !std::isfinite(c) || c <= 0) robust_err = "-" + name + " " + k + " <c>: c must be a positive number (got '" + v + "')";
 		}
 	}
 	if (!has_path) { printf("LinerSFM Error: Please Input Right File Path:\n"); return 0; }
@@ -146,6 +155,9 @@ int main(int argc, char** argv)
 	if (has_keepf && !read_ids("-keepf", "feature", keepf, keepids)) return 1;
 	if (has_keepp && !read_ids("-keepp", "pose", keepp, keeppids)) return 1;
 	if (robust && gn <= 0) { fprintf(stderr, "LinearSFM: -robust applies to -gn <steps>: give -gn too\n"); return 1; }
+	if (robustf && gn <= 0) { fprintf(stderr, "LinearSFM: -robustf applies to -gn <steps>: give -gn too\n"); return 1; }
+	if (robustf && robust) { fprintf(stderr, "LinearSFM: -robustf and -robust do not go together: the map and the feature estimator are not combined\n"); return 1; }
+	if (robustf && relin) { fprintf(stderr, "LinearSFM: -robustf and -relin do not go together: linearising with feature weights is not offered\n"); return 1; }
 
 	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double w0 = now();
@@ -275,6 +287,9 @@ int main(int argc, char** argv)
 		        stats.not_converged, stats.max_rel_residual);
 	printf("Total Used Time:  %lf  sec\n\n", stats.t_total_ms * 1e-3); // Imp.cpp:2072
 	std::vector<double> chi2v, weightv; // -robust: per-map chi2 and weights at the polished state
+	std::vector<double> fchi2v, fweightv; // -robustf: per-feature chi2 and weights at the polished state (every feature of every map, input order)
+	size_t nfeat = 0;
+	for (const lsfm_map& g : maps) nfeat += (size_t)g.n;
 	if (gn > 0)
 	{
 		// -gn <steps>: Gauss-Newton polish of the map-joining objective over all local maps, from the tree's result (lsfm_gn_polish; the
@@ -283,7 +298,9 @@ int main(int argc, char** argv)
 		std::vector<int> halv(gn);
 		const double g0 = now();
 		if (robust) { chi2v.resize(num); weightv.resize(num); }
-		const int grc = robust ? lsfm_gn_polish_robust(ctx, maps.data(), num, type, &out, gn, robust, robust_c, obj.data(), gnorm.data(), halv.data(), chi2v.data(), weightv.data())
+		if (robustf) { fchi2v.resize(nfeat + 1); fweightv.resize(nfeat + 1); }
+		const int grc = robustf ? lsfm_gn_polish_robust_features(ctx, maps.data(), num, type, &out, gn, robustf, robustf_c, obj.data(), gnorm.data(), halv.data(), fchi2v.data(), fweightv.data())
+		              : robust ? lsfm_gn_polish_robust(ctx, maps.data(), num, type, &out, gn, robust, robust_c, obj.data(), gnorm.data(), halv.data(), chi2v.data(), weightv.data())
 		                       : lsfm_gn_polish(ctx, maps.data(), num, type, &out, gn, obj.data(), gnorm.data(), halv.data());
 		if (grc < 0) { fprintf(stderr, "LinearSFM: %s\n", lsfm_last_error(ctx)); return 3; }
 		if (!quiet)
@@ -313,6 +330,11 @@ int main(int argc, char** argv)
 		{
 			chi2v.resize(num); weightv.assign(num, 1.0); chi2dof.resize(num);
 			if (lsfm_map_chi2(ctx, maps.data(), num, type, &out, chi2v.data(), chi2dof.data()) < 0) { fprintf(stderr, "LinearSFM: chi2: %s\n", lsfm_last_error(ctx)); return 3; }
+		}
+		if (!chi2ff.empty() && fchi2v.empty())
+		{
+			fchi2v.resize(nfeat + 1); fweightv.assign(nfeat + 1, 1.0);
+			if (lsfm_map_feature_chi2(ctx, maps.data(), num, type, &out, fchi2v.data(), nullptr) < 0) { fprintf(stderr, "LinearSFM: chi2f: %s\n", lsfm_last_error(ctx)); return 3; }
 		}
 		// the final map reduced to the features of -keepf: every other one marginalised out (lsfm_map_marginalise); to the poses of -keepp:
 		// every other one marginalised out, with the features it sees (lsfm_map_marginalise_poses)
@@ -427,6 +449,27 @@ int main(int argc, char** argv)
 			fclose(f);
 		}
 		else fprintf(stderr, "LinearSFM: cannot write %s\n", chi2f.c_str());
+	}
+	if (!chi2ff.empty())
+	{
+		// per-feature chi2 of the same state (-robustf: the polish's own, with its weights; otherwise weight 1), through a temporary file
+		if (fchi2v.empty())
+		{
+			fchi2v.resize(nfeat + 1); fweightv.assign(nfeat + 1, 1.0);
+			if (lsfm_map_feature_chi2(ctx, maps.data(), num, type, &out, fchi2v.data(), nullptr) < 0) { fprintf(stderr, "LinearSFM: chi2f: %s\n", lsfm_last_error(ctx)); return 3; }
+		}
+		const std::string tmp = chi2ff + ".tmp";
+		FILE* f = fopen(tmp.c_str(), "w");
+		bool ok = f != nullptr;
+		if (f)
+		{
+			size_t q = 0;
+			for (int k = 0; k < num; k++)
+				for (int i = 0; i < maps[k].n; i++, q++)
+					ok = fprintf(f, "%d %d %.17g %.17g\n", k + 1, maps[k].stno[6 * maps[k].m + 3 * i], fchi2v[q], fweightv[q]) > 0 && ok;
+			ok = fclose(f) == 0 && ok;
+		}
+		if (!ok || rename(tmp.c_str(), chi2ff.c_str()) != 0) { fprintf(stderr, "LinearSFM: cannot write %s\n", chi2ff.c_str()); remove(tmp.c_str()); }
 	}
 	if (want_stats)
 		fprintf(stderr, "lsfm_e2e: read %.3f s, context %.3f s, upload %.3f s, join tree %.3f s, download %.3f s, write %.3f s\n", w1 - w0, w2 - w1, w3 - w2,

@@ -242,20 +242,22 @@ k_gn_ublocks(int NU, int P, const int* __restrict__ Ui, const int* __restrict__ 
 }
 
 // one lane per local feature (see the header).  NH: 1 Stereo, 2 Mono (a Stereo map in the global frame has t.nh = 0: its C are zero
-// and it owns no hub blocks)
-template <int NH>
+// and it owns no hub blocks).  FW (lsfm_gn_polish_robust_features only): the instance's W and V blocks are weighted
+// by t.w * fw[f], the weight of the feature's conditional term (k_gn_feature_chi2); FW = false is the kernel of the plain and the map-robust polish, fw unused
+template <int NH, bool FW>
 __global__ void __launch_bounds__(256)
 k_gn_features(int NF, int P, const int* __restrict__ feat_map, const GnMap* __restrict__ gm, const int* __restrict__ gf, const double* __restrict__ xf,
               const double* __restrict__ fhat, const int* __restrict__ fptr, const int* __restrict__ photo, const double* __restrict__ W,
               const double* __restrict__ V, const double* __restrict__ Dp, const double* __restrict__ Cp, const double* __restrict__ rp,
               const int* __restrict__ wdst, double* __restrict__ WJ, double* __restrict__ Vinst, double* __restrict__ eFinst,
-              double* __restrict__ Gacc, double* __restrict__ Hacc)
+              double* __restrict__ Gacc, double* __restrict__ Hacc, const double* __restrict__ fw)
 {
 	const int f = blockIdx.x * blockDim.x + threadIdx.x;
 	const bool live = f < NF;
 	const int fc = live ? f : 0;
 	const int k = feat_map[fc];
 	const GnMap& t = gm[k];
+	const double fwv = FW ? fw[fc] : 1.0;
 	const bool hubs = t.nh > 0;
 	double fv[3], Df[9], adt[9], tmpc[9], adtt[9], Cf[NH][18], rf[3], Vb[9];
 	gn_trans(t, xf + (size_t)gf[fc] * 3, fv, Df, adt, tmpc, adtt);
@@ -273,7 +275,7 @@ k_gn_features(int NF, int P, const int* __restrict__ feat_map, const GnMap* __re
 	}
 	ld<9>(Vb, V + (size_t)fc * 9);
 #pragma unroll
-	for (int q = 0; q < 9; q++) Vb[q] *= t.w;
+	for (int q = 0; q < 9; q++) Vb[q] *= FW ? t.w * fwv : t.w;
 	double gfv[3], Gf[NH][18];
 	mm<3, 3, 1, false>(Vb, rf, gfv);
 #pragma unroll
@@ -291,7 +293,7 @@ k_gn_features(int NF, int P, const int* __restrict__ feat_map, const GnMap* __re
 		double Wb[18], pc[GN_GW];
 		ld<18>(Wb, W + (size_t)j * 18);
 #pragma unroll
-		for (int q = 0; q < 18; q++) Wb[q] *= t.w;
+		for (int q = 0; q < 18; q++) Wb[q] *= FW ? t.w * fwv : t.w;
 		{
 			double ra[6], T[18], Da[36];
 			ld<6>(ra, rp + (size_t)a * 6);
@@ -601,6 +603,232 @@ k_gn_robust_weights(int N, int kind, double c, const int* __restrict__ dof, cons
 	}
 }
 
+// ---- per-feature chi^2 and the feature-robust polish (lsfm_map_feature_chi2, lsfm_gn_polish_robust_features) ----
+// With g_f = V_f r_f + sum_a W_af^T r_a the map's chi^2 splits into a pose part under the map's own Schur complement and one conditional
+// term per feature:  chi2_k = r_p^T (U - sum_f W_f V_f^-1 W_f^T) r_p + sum_f c_kf,  c_kf = g_f^T V_f^-1 g_f >= 0.  Scaling the conditional
+// term of f by w_f is the information matrix  I_k(w) = [U - sum_f (1 - w_f) W_f V_f^-1 W_f^T, w_f W_f; w_f W_f^T, w_f V_f]  (w = 1: I_k,
+// w_f = 0: f marginalised out), so IRLS on c_kf is the plain step on re-weighted maps: k_gn_features<NH, true> scales W and V, the
+// correction of U goes into slots of its own behind the map's U blocks (k_gn_feature_ufill) and k_gn_ublocks places them like any other.
+
+// V = L L^T of a 3x3 block in registers (lower triangle read): L = l00 l10 l11 l20 l21 l22; false when V is not positive definite
+__device__ __forceinline__ bool gn_chol3(const double* V, double* L)
+{
+	bool ok = V[0] > 0.0;
+	L[0] = sqrt(V[0]);
+	L[1] = V[3] / L[0]; L[3] = V[6] / L[0];
+	const double d1 = V[4] - L[1] * L[1];
+	ok = ok && d1 > 0.0;
+	L[2] = sqrt(d1);
+	L[4] = (V[7] - L[3] * L[1]) / L[2];
+	const double d2 = V[8] - L[3] * L[3] - L[4] * L[4];
+	ok = ok && d2 > 0.0;
+	L[5] = sqrt(d2);
+	return ok;
+}
+// y = L^-1 g
+__device__ __forceinline__ void gn_lsolve3(const double* L, const double* g, double* y)
+{
+	y[0] = g[0] / L[0];
+	y[1] = (g[1] - L[1] * y[0]) / L[2];
+	y[2] = (g[2] - L[3] * y[0] - L[4] * y[1]) / L[5];
+}
+
+// One work-group per map, as k_gn_map_chi2 and reading what it reads (every U, W and V block of the map once): the lanes stride over the
+// map's OWN U blocks (nu_own: the correction slots behind them are not part of I_k) and over its features; per feature c_kf, its weight
+// w_kf = rho'(c_kf / 3) (kind 0: 1, 1 Huber, 2 Cauchy, as k_gn_robust_weights) and the feature's share of chi2_k; per map chi2_k,
+// sum_f c_kf and sum_f rho(c_kf / 3) (msum[3 k ..]) by lane sums, wave sums and a fixed-order sum over the waves -- no atomics on any
+// sum.  bad: the smallest feature instance whose V is not positive definite (an integer minimum: the same for every order).
+#define GN_FCHI2_LANES 256
+__global__ void __launch_bounds__(GN_FCHI2_LANES)
+k_gn_feature_chi2(int kind, double c, const GnMap* __restrict__ gm, const int* __restrict__ nu_own, const double* __restrict__ U,
+                  const int* __restrict__ Ui, const int* __restrict__ Uj, const double* __restrict__ rp, const int* __restrict__ gf,
+                  const double* __restrict__ xf, const double* __restrict__ fhat, const int* __restrict__ fptr, const int* __restrict__ photo,
+                  const double* __restrict__ W, const double* __restrict__ V, double* __restrict__ fchi2, double* __restrict__ fweight,
+                  double* __restrict__ msum, int* __restrict__ bad)
+{
+	__shared__ double part[3][GN_FCHI2_LANES / LSFM_WAVE];
+	const int k = blockIdx.x;
+	const GnMap& t = gm[k];
+	const double c2 = c * c;
+	double acc = 0.0, accc = 0.0, accr = 0.0;
+	for (int i = t.u0 + (int)threadIdx.x; i < t.u0 + nu_own[k]; i += GN_FCHI2_LANES)
+	{
+		const int a = Ui[i], b = Uj[i];
+		double Ub[36], ra[6], rb[6], y[6];
+		ld<36>(Ub, U + (size_t)i * 36);
+		ld<6>(ra, rp + (size_t)a * 6);
+		ld<6>(rb, rp + (size_t)b * 6);
+		mm<6, 6, 1, false>(Ub, rb, y);
+		double d = 0.0;
+#pragma unroll
+		for (int q = 0; q < 6; q++) d += ra[q] * y[q];
+		acc += a == b ? d : 2.0 * d;
+	}
+	for (int f = t.f0 + (int)threadIdx.x; f < t.f0 + t.n; f += GN_FCHI2_LANES)
+	{
+		const double* xn = xf + (size_t)gf[f] * 3;
+		double t222[3] = { xn[0] - t.t[0], xn[1] - t.t[1], xn[2] - t.t[2] }, t22[3], rf[3], Vb[9], g[3], L[6], y[3];
+		mv3(t.R, t222, t22);
+#pragma unroll
+		for (int r = 0; r < 3; r++) rf[r] = fhat[(size_t)f * 3 + r] - t22[r] / t.Scale;
+		ld<9>(Vb, V + (size_t)f * 9);
+		mm<3, 3, 1, false>(Vb, rf, g);
+		double d = rf[0] * g[0] + rf[1] * g[1] + rf[2] * g[2];
+		for (int j = fptr[f]; j < fptr[f + 1]; j++)
+		{
+			double Wb[18], ra[6], z[6];
+			ld<18>(Wb, W + (size_t)j * 18);
+			ld<6>(ra, rp + (size_t)photo[j] * 6);
+			mm<6, 3, 1, false>(Wb, rf, z);
+			double e = 0.0;
+#pragma unroll
+			for (int q = 0; q < 6; q++) e += ra[q] * z[q];
+			d += 2.0 * e;
+			mtm<6, 3, 1, true>(Wb, ra, g);
+		}
+		if (!gn_chol3(Vb, L)) atomicMin(bad, f);
+		gn_lsolve3(L, g, y);
+		const double cf = y[0] * y[0] + y[1] * y[1] + y[2] * y[2], s = cf / 3.0;
+		double w = 1.0, rho = s;
+		if (kind == 1)
+		{
+			const bool in = s <= c2;
+			w = in ? 1.0 : c / sqrt(s);
+			rho = in ? s : 2.0 * c * sqrt(s) - c2;
+		}
+		else if (kind == 2)
+		{
+			w = 1.0 / (1.0 + s / c2);
+			rho = c2 * log1p(s / c2);
+		}
+		fchi2[f] = cf;
+		fweight[f] = w;
+		acc += d; accc += cf; accr += rho;
+	}
+	acc = wave_sum(acc); accc = wave_sum(accc); accr = wave_sum(accr);
+	if ((threadIdx.x & (LSFM_WAVE - 1)) == 0)
+	{
+		part[0][threadIdx.x / LSFM_WAVE] = acc; part[1][threadIdx.x / LSFM_WAVE] = accc; part[2][threadIdx.x / LSFM_WAVE] = accr;
+	}
+	__syncthreads();
+	if (threadIdx.x < 3)
+	{
+		double sum = 0.0;
+#pragma unroll
+		for (int w = 0; w < GN_FCHI2_LANES / LSFM_WAVE; w++) sum += part[threadIdx.x][w];
+		msum[(size_t)3 * k + threadIdx.x] = sum;
+	}
+}
+
+// one work-group: pose_chi2[k] = chi2_k - sum_f c_kf and G = sum_k (pose_chi2[k] + 3 sum_f rho(c_kf / 3)) in a fixed order
+__global__ void __launch_bounds__(GN_WEIGHT_LANES)
+k_gn_feature_objective(int N, const double* __restrict__ msum, double* __restrict__ pose_chi2, double* __restrict__ Gsum)
+{
+	__shared__ double part[GN_WEIGHT_LANES / LSFM_WAVE];
+	double acc = 0.0;
+	for (int k = threadIdx.x; k < N; k += GN_WEIGHT_LANES)
+	{
+		const double p = msum[(size_t)3 * k] - msum[(size_t)3 * k + 1];
+		pose_chi2[k] = p;
+		acc += p + 3.0 * msum[(size_t)3 * k + 2];
+	}
+	acc = wave_sum(acc);
+	if ((threadIdx.x & (LSFM_WAVE - 1)) == 0) part[threadIdx.x / LSFM_WAVE] = acc;
+	__syncthreads();
+	if (threadIdx.x == 0)
+	{
+		double sum = 0.0;
+#pragma unroll
+		for (int w = 0; w < GN_WEIGHT_LANES / LSFM_WAVE; w++) sum += part[w];
+		*Gsum = sum;
+	}
+}
+
+// the maps' own U blocks into the extended list (every map's blocks followed by its correction slots): block i moves by its map's shift
+__global__ void __launch_bounds__(256)
+k_gn_extend_u(int NU, const int* __restrict__ Ui, const int* __restrict__ pose_map, const int* __restrict__ ushift, const double* __restrict__ U,
+              double* __restrict__ Ux)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= NU) return;
+	double Ub[36];
+	ld<36>(Ub, U + (size_t)i * 36);
+	st<36>(Ux + (size_t)(i + ushift[pose_map[Ui[i]]]) * 36, Ub);
+}
+
+// The correction of U: slot (a, b), a <= b, of map k holds  - sum_f (1 - w_f) Wbar_af V_f^-1 Wbar_bf^T  over the features f of k that both
+// poses see, Wbar_af = the sum of f's W blocks of pose a (entry e: blocks eidx[eptr[e] .. eptr[e + 1]); a (pose, feature) pair may repeat
+// in a map, and summing per pose first makes a diagonal slot full and symmetric).  One wave per slot: its lanes stride the slot's
+// contributors (feature cf, entries ca / cb) in their order, every lane sums in registers, one butterfly per entry of the block, lane 0
+// stores -- no atomics, the same weights give the same bits.  With V = L L^T the product is Y_a^T Y_b, Y = L^-1 Wbar^T.  A contributor of
+// weight 1 adds exactly 0 and is skipped.  Every slot is written by every launch.
+#define GN_UFILL_LANES 256
+__global__ void __launch_bounds__(GN_UFILL_LANES)
+k_gn_feature_ufill(int NS, const int* __restrict__ sptr, const int* __restrict__ cf, const int* __restrict__ ca, const int* __restrict__ cb,
+                   const int* __restrict__ eptr, const int* __restrict__ eidx, const int* __restrict__ sdst, const double* __restrict__ W,
+                   const double* __restrict__ V, const double* __restrict__ fw, double* __restrict__ Ux)
+{
+	const int s = blockIdx.x * (GN_UFILL_LANES / LSFM_WAVE) + (int)threadIdx.x / LSFM_WAVE, lane = threadIdx.x & (LSFM_WAVE - 1);
+	if (s >= NS) return; // (the whole wave)
+	double acc[36];
+	zero<36>(acc);
+	for (int q = sptr[s] + lane; q < sptr[s + 1]; q += LSFM_WAVE)
+	{
+		const int f = cf[q];
+		const double w = fw[f];
+		if (w == 1.0) continue;
+		double Vb[9], L[6], Wa[18], Wv[18], Ya[18], Yb[18];
+		ld<9>(Vb, V + (size_t)f * 9);
+		gn_chol3(Vb, L); // (k_gn_feature_chi2 has reported a V that is not positive definite)
+		const int ea = ca[q], eb = cb[q];
+		zero<18>(Wa);
+		for (int e = eptr[ea]; e < eptr[ea + 1]; e++)
+		{
+			ld<18>(Wv, W + (size_t)eidx[e] * 18);
+#pragma unroll
+			for (int i = 0; i < 18; i++) Wa[i] += Wv[i];
+		}
+#pragma unroll
+		for (int i = 0; i < 6; i++)
+		{
+			double y[3];
+			gn_lsolve3(L, Wa + 3 * i, y);
+			Ya[i] = y[0]; Ya[6 + i] = y[1]; Ya[12 + i] = y[2];
+		}
+		if (eb == ea)
+		{
+#pragma unroll
+			for (int i = 0; i < 18; i++) Yb[i] = Ya[i];
+		}
+		else
+		{
+			zero<18>(Wa);
+			for (int e = eptr[eb]; e < eptr[eb + 1]; e++)
+			{
+				ld<18>(Wv, W + (size_t)eidx[e] * 18);
+#pragma unroll
+				for (int i = 0; i < 18; i++) Wa[i] += Wv[i];
+			}
+#pragma unroll
+			for (int i = 0; i < 6; i++)
+			{
+				double y[3];
+				gn_lsolve3(L, Wa + 3 * i, y);
+				Yb[i] = y[0]; Yb[6 + i] = y[1]; Yb[12 + i] = y[2];
+			}
+		}
+		const double m = 1.0 - w;
+#pragma unroll
+		for (int i = 0; i < 6; i++)
+#pragma unroll
+			for (int j = 0; j < 6; j++)
+				acc[6 * i + j] -= m * (Ya[i] * Yb[j] + Ya[6 + i] * Yb[6 + j] + Ya[12 + i] * Yb[12 + j]);
+	}
+#pragma unroll
+	for (int i = 0; i < 36; i++) acc[i] = wave_sum(acc[i]);
+	if (lane == 0) st<36>(Ux + (size_t)sdst[s] * 36, acc);
+}
+
 // largest |v| over the scalars that are not fixed, as the bits of a non-negative double (they order like the numbers)
 __global__ void k_gn_maxabs(size_t n, const double* __restrict__ v, const unsigned char* __restrict__ fixed, unsigned long long* out)
 {
@@ -644,6 +872,73 @@ struct GnCall {
 	unsigned long long* d_max = nullptr;
 };
 
+// lsfm_map_feature_chi2 / lsfm_gn_polish_robust_features only: the per-feature arrays and, for the polish (slots), the correction slots
+// of U.  Everything here follows from the labels and index arrays alone, never from values.
+struct GnFeat {
+	bool slots = true; // false: no system is assembled (lsfm_map_feature_chi2)
+	int NS = 0;        // correction slots over all maps
+	size_t NC = 0;     // contributors over all slots
+	int *d_nu_own = nullptr, *d_sptr = nullptr, *d_cf = nullptr, *d_ca = nullptr, *d_cb = nullptr, *d_eptr = nullptr, *d_eidx = nullptr, *d_sdst = nullptr,
+	    *d_bad = nullptr;
+	double *fchi2 = nullptr, *fw = nullptr, *msum = nullptr, *pose_chi2 = nullptr;
+};
+// the correction slots on the host: per map one slot per distinct pair (a <= b, local poses) of poses that see a common feature, sorted by
+// (a, b); per slot its contributors in feature order
+struct GnSlots {
+	std::vector<int> before;           // [N + 1] slots ahead of map k
+	std::vector<int> a, b;             // [NS] the slot's local poses
+	std::vector<int> sptr, cf, ca, cb; // contributors of slot s: sptr[s] .. sptr[s + 1]; feature instance, entries of a and of b
+	std::vector<int> eptr, eidx;       // entry e = one (feature instance, pose): its W blocks eidx[eptr[e] .. eptr[e + 1]) (batch indices)
+};
+void gn_feature_slots(const lsfm_map* maps, int N, const DevBatch& X, GnSlots& sl)
+{
+	struct Tup { long long key; int f, ea, eb; };
+	std::vector<Tup> tup;
+	std::vector<std::pair<int, int>> run; // (local pose, W block)
+	std::vector<int> ent, entpose;
+	sl.before.assign(N + 1, 0); sl.sptr.clear(); sl.eptr.assign(1, 0);
+	for (int k = 0; k < N; k++)
+	{
+		const lsfm_map& L = maps[k];
+		tup.clear();
+		int j = 0;
+		for (int f = 0; f < L.n; f++)
+		{
+			run.clear();
+			for (; j < L.nW && L.feature[j] == f; j++) run.push_back({ L.photo[j], X.w_off[k] + j });
+			const auto by_pose = [](const std::pair<int, int>& p, const std::pair<int, int>& q) { return p.first < q.first; };
+			if (!std::is_sorted(run.begin(), run.end(), by_pose)) std::stable_sort(run.begin(), run.end(), by_pose);
+			ent.clear(); entpose.clear();
+			for (size_t r = 0; r < run.size(); r++)
+			{
+				if (r == 0 || run[r].first != run[r - 1].first)
+				{
+					ent.push_back((int)sl.eptr.size() - 1); entpose.push_back(run[r].first);
+					sl.eptr.push_back((int)sl.eidx.size());
+				}
+				sl.eidx.push_back(run[r].second);
+				sl.eptr.back() = (int)sl.eidx.size();
+			}
+			for (size_t i = 0; i < ent.size(); i++)
+				for (size_t q = i; q < ent.size(); q++) tup.push_back(Tup{ (long long)entpose[i] * L.m + entpose[q], X.feat_off[k] + f, ent[i], ent[q] });
+		}
+		const auto by_key = [](const Tup& p, const Tup& q) { return p.key < q.key; };
+		if (!std::is_sorted(tup.begin(), tup.end(), by_key)) std::stable_sort(tup.begin(), tup.end(), by_key);
+		if (sl.cf.size() + tup.size() > (size_t)INT32_MAX) LSFM_FAIL(LSFM_ERR_ARG, "gn polish: too many co-observations for the feature weights' correction of U");
+		for (size_t i = 0; i < tup.size(); i++)
+		{
+			if (i == 0 || tup[i].key != tup[i - 1].key)
+			{
+				sl.a.push_back((int)(tup[i].key / L.m)); sl.b.push_back((int)(tup[i].key % L.m));
+				sl.sptr.push_back((int)sl.cf.size());
+			}
+			sl.cf.push_back(tup[i].f); sl.ca.push_back(tup[i].ea); sl.cb.push_back(tup[i].eb);
+		}
+		sl.before[k + 1] = (int)sl.a.size();
+	}
+	sl.sptr.push_back((int)sl.cf.size());
+}
+
 // lsfm_gn_linearise only: the joint system with every block once.  Output W sorted by feature, within a feature by pose; output U sorted
 // by (i, j); per output block its sources in WJ / UJ as a CSR (wsp / wsi, usp / usi), in source (= map) order.  Index arrays on the host
 // (they go straight into the map handed out), the CSR and the output blocks on the device.
@@ -657,7 +952,10 @@ struct GnCoalesce {
 // the structure of a call, on the host from the labels, and the upload: which global variable every local one is, where every local
 // block lands in the joint system, the gauge (Mono); the state x goes to d_x.  Throws Error (LSFM_ERR_ARG) for what it cannot place.
 // weight (may be null: all 1): the maps' weights w_k.  co (may be null): the coalescing structure of lsfm_gn_linearise is built as well.
-void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, GnCall& c, const double* weight = nullptr, GnCoalesce* co = nullptr)
+// fr (may be null): the per-feature arrays of the feature chi^2 pass; with fr->slots every map's U range is extended by its correction
+// slots (c.X.U / Ui / Uj / NU then are the extended list, the maps' own blocks first).
+void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, GnCall& c, const double* weight = nullptr, GnCoalesce* co = nullptr,
+              GnFeat* fr = nullptr)
 {
 	const int M = c.M = x->m, NFG = c.NFG = x->n;
 	c.N = N; c.mono = mono;
@@ -675,6 +973,19 @@ void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const l
 		need += ((nW + 2 * FI) * 400 + (nU + 3 * P + 3 * (size_t)N) * 800 + (FI + NFG) * 500 + (P + M) * 6000) * 2 + (size_t)N * 64;
 		// (the coalesced blocks and their source lists: at most one output block and one source per joint block)
 		if (co) need += (nW + 2 * FI) * (144 + 16) + (nU + 2 * P + 3 * (size_t)N) * (288 + 16) + 1024;
+		if (fr)
+		{
+			// per feature 2 doubles; slots: at most one per contributor, a contributor per pair of blocks of a feature's run
+			size_t nc = 0;
+			for (int k = 0; k < N; k++)
+				for (int j = 0, len = 0; j < maps[k].nW; j++)
+				{
+					len++;
+					if (j + 1 == maps[k].nW || maps[k].feature[j + 1] != maps[k].feature[j]) { nc += (size_t)len * (len + 1) / 2; len = 0; }
+				}
+			need += FI * 16 + (size_t)N * 64 + 4096;
+			if (fr->slots) need += (nU + nc) * (288 + 800 + 8 + 288) + nc * (16 + 36) + nW * 8;
+		}
 	}
 	ctx->ensure_arenas(need);
 	ctx->arena[0].reset(); ctx->arena[1].reset(); ctx->scratch.reset();
@@ -682,6 +993,9 @@ void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const l
 	DevBatch& X = c.X;
 	batch_upload(ctx, ar, maps, N, mono, X);
 	const int P = c.P = X.M, FI = c.FI = X.NF;
+	GnSlots sl;
+	if (fr && fr->slots) gn_feature_slots(maps, N, X, sl);
+	else sl.before.assign(N + 1, 0);
 	std::vector<GnMap> gm(N);
 	c.dof.resize(N);
 	std::vector<int> gp(P), gfi(FI), wdst(FI), origin(M, INT32_MAX);
@@ -692,7 +1006,7 @@ void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const l
 		const lsfm_map& L = maps[k];
 		GnMap& t = gm[k];
 		memset(&t, 0, sizeof t);
-		t.p0 = X.pose_off[k]; t.m = L.m; t.f0 = X.feat_off[k]; t.n = L.n; t.u0 = X.u_off[k]; t.nu = L.nU;
+		t.p0 = X.pose_off[k]; t.m = L.m; t.f0 = X.feat_off[k]; t.n = L.n; t.u0 = X.u_off[k] + sl.before[k]; t.nu = L.nU + (sl.before[k + 1] - sl.before[k]);
 		t.hub[0] = t.hub[1] = -1;
 		t.w = weight ? weight[k] : 1.0;
 		if ((c.dof[k] = 6 * L.m + 3 * L.n) <= 0) LSFM_FAIL(LSFM_ERR_ARG, "gn polish: local map " + std::to_string(k + 1) + " is empty");
@@ -709,7 +1023,7 @@ void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const l
 			}
 		}
 		t.ubase = NUJ;
-		NUJ += t.nh * L.m + t.nh * (t.nh + 1) / 2 + L.nU;
+		NUJ += t.nh * L.m + t.nh * (t.nh + 1) / 2 + t.nu;
 		for (int i = 0; i < L.m; i++)
 		{
 			const int g = lab_find(pt, -L.stno[6 * i]);
@@ -777,7 +1091,9 @@ void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const l
 		if (t.nh == 2) { UiJ[q] = std::min(t.hub[0], t.hub[1]); UjJ[q] = std::max(t.hub[0], t.hub[1]); q++; UiJ[q] = UjJ[q] = t.hub[1]; q++; }
 		for (int i = 0; i < t.nu; i++, q++)
 		{
-			const int ga = gp[t.p0 + maps[k].Ui[i]], gb = gp[t.p0 + maps[k].Uj[i]];
+			// (the map's own blocks, then its correction slots)
+			const int own = maps[k].nU, sq = sl.before[k] + i - own;
+			const int ga = gp[t.p0 + (i < own ? maps[k].Ui[i] : sl.a[sq])], gb = gp[t.p0 + (i < own ? maps[k].Uj[i] : sl.b[sq])];
 			UiJ[q] = std::min(ga, gb); UjJ[q] = std::max(ga, gb);
 		}
 	}
@@ -819,6 +1135,48 @@ void gn_setup(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const l
 	h2d(ctx, c.d_dof, c.dof.data(), c.dof.size() * sizeof(int));
 	h2d(ctx, c.d_x, x->stVal, RS * sizeof(double));
 	dev_zero(ctx, d_seg, (size_t)(M + NFG + 1) * sizeof(int));
+	if (fr)
+	{
+		std::vector<int> nu_own(N);
+		for (int k = 0; k < N; k++) nu_own[k] = maps[k].nU;
+		fr->d_nu_own = ar.alloc<int>(N); fr->d_bad = ar.alloc<int>(1);
+		fr->fchi2 = ar.alloc<double>(FI); fr->fw = ar.alloc<double>(FI); fr->msum = ar.alloc<double>((size_t)3 * N); fr->pose_chi2 = ar.alloc<double>(N);
+		h2d(ctx, fr->d_nu_own, nu_own.data(), nu_own.size() * sizeof(int));
+		const int none = INT32_MAX;
+		h2d(ctx, fr->d_bad, &none, sizeof(int));
+	}
+	if (fr && fr->slots)
+	{
+		// the extended U list: every map's own blocks (copied once: k_gn_extend_u), then its slots (k_gn_feature_ufill, every assembly)
+		const int NS = fr->NS = (int)sl.a.size(), NUX = X.NU + NS;
+		fr->NC = sl.cf.size();
+		std::vector<int> Uix(NUX), Ujx(NUX), sdst(NS), ushift(N);
+		for (int k = 0; k < N; k++)
+		{
+			const GnMap& t = gm[k];
+			ushift[k] = sl.before[k];
+			for (int i = 0; i < maps[k].nU; i++) { Uix[t.u0 + i] = t.p0 + maps[k].Ui[i]; Ujx[t.u0 + i] = t.p0 + maps[k].Uj[i]; }
+			for (int q = sl.before[k]; q < sl.before[k + 1]; q++)
+			{
+				const int d = t.u0 + maps[k].nU + (q - sl.before[k]);
+				sdst[q] = d; Uix[d] = t.p0 + sl.a[q]; Ujx[d] = t.p0 + sl.b[q];
+			}
+		}
+		double* Ux = ar.alloc<double>((size_t)NUX * 36);
+		int *d_Uix = ar.alloc<int>(NUX), *d_Ujx = ar.alloc<int>(NUX), *d_ushift = ar.alloc<int>(N);
+		fr->d_sptr = ar.alloc<int>(NS + 1); fr->d_cf = ar.alloc<int>(fr->NC); fr->d_ca = ar.alloc<int>(fr->NC); fr->d_cb = ar.alloc<int>(fr->NC);
+		fr->d_eptr = ar.alloc<int>(sl.eptr.size()); fr->d_eidx = ar.alloc<int>(sl.eidx.size()); fr->d_sdst = ar.alloc<int>(NS);
+		h2d(ctx, d_Uix, Uix.data(), Uix.size() * sizeof(int)); h2d(ctx, d_Ujx, Ujx.data(), Ujx.size() * sizeof(int));
+		h2d(ctx, d_ushift, ushift.data(), ushift.size() * sizeof(int));
+		h2d(ctx, fr->d_sptr, sl.sptr.data(), sl.sptr.size() * sizeof(int));
+		h2d(ctx, fr->d_cf, sl.cf.data(), sl.cf.size() * sizeof(int)); h2d(ctx, fr->d_ca, sl.ca.data(), sl.ca.size() * sizeof(int));
+		h2d(ctx, fr->d_cb, sl.cb.data(), sl.cb.size() * sizeof(int));
+		h2d(ctx, fr->d_eptr, sl.eptr.data(), sl.eptr.size() * sizeof(int)); h2d(ctx, fr->d_eidx, sl.eidx.data(), sl.eidx.size() * sizeof(int));
+		h2d(ctx, fr->d_sdst, sdst.data(), sdst.size() * sizeof(int));
+		dev_zero(ctx, Ux, (size_t)NUX * 36 * sizeof(double));
+		if (X.NU) hipLaunchKernelGGL(k_gn_extend_u, grid_for(X.NU, 256), dim3(256), 0, ctx->stream, X.NU, X.Ui, X.pose_map, d_ushift, X.U, Ux);
+		X.U = Ux; X.Ui = d_Uix; X.Uj = d_Ujx; X.NU = NUX;
+	}
 	if (co)
 	{
 		// W: every feature's joint run sorted stably by pose, equal poses merged
@@ -873,9 +1231,28 @@ void gn_chi2(lsfm_context* ctx, const GnCall& c)
 	hipLaunchKernelGGL(k_gn_map_chi2, dim3(c.N), dim3(GN_CHI2_LANES), 0, ctx->stream, c.d_gm, c.X.U, c.X.Ui, c.X.Uj, c.rp, c.d_gf,
 	                   c.d_x + (size_t)c.M * 6, c.X.feat, c.X.fptr, c.X.photo, c.X.W, c.X.V, c.d_chi2);
 }
+// c_kf, w_kf and the per-map sums at the state in d_x (after gn_frames), then pose_chi2 and G into d_G
+void gn_feature_chi2(lsfm_context* ctx, const GnCall& c, const GnFeat& fr, int kind, double cth)
+{
+	hipLaunchKernelGGL(k_gn_feature_chi2, dim3(c.N), dim3(GN_FCHI2_LANES), 0, ctx->stream, kind, cth, c.d_gm, fr.d_nu_own, c.X.U, c.X.Ui, c.X.Uj, c.rp,
+	                   c.d_gf, c.d_x + (size_t)c.M * 6, c.X.feat, c.X.fptr, c.X.photo, c.X.W, c.X.V, fr.fchi2, fr.fw, fr.msum, fr.d_bad);
+	hipLaunchKernelGGL(k_gn_feature_objective, dim3(1), dim3(GN_WEIGHT_LANES), 0, ctx->stream, c.N, fr.msum, fr.pose_chi2, c.d_G);
+}
+// what k_gn_feature_chi2 found: throws LSFM_ERR_NOT_SPD naming the first feature whose V is not positive definite
+void gn_feature_check(lsfm_context* ctx, const lsfm_map* maps, const GnCall& c, const GnFeat& fr)
+{
+	int bad = INT32_MAX;
+	d2h(ctx, &bad, fr.d_bad, sizeof(int));
+	if (bad == INT32_MAX) return;
+	const int k = (int)(std::upper_bound(c.X.feat_off.begin(), c.X.feat_off.end(), bad) - c.X.feat_off.begin()) - 1, f = bad - c.X.feat_off[k];
+	LSFM_FAIL(LSFM_ERR_NOT_SPD, "feature chi2: V of feature " + std::to_string(f + 1) + " (label " + std::to_string(maps[k].stno[6 * maps[k].m + 3 * f]) +
+	                                ") of local map " + std::to_string(k + 1) + " is not positive definite");
+}
 // the launches of one assembly at the state in d_x: F into Fsum (kind != 0: the robust weights first, G into d_G), the joint system
 // UJ / WJ / VJ and the right-hand sides ea / eb.  bracket_chi2 (may be null): [2] events recorded around the chi2 + weights kernels.
-void gn_assemble(lsfm_context* ctx, const GnCall& c, int kind, double cth, const hipEvent_t* bracket_chi2)
+// fr (may be null; then kind != 0): the estimator is on the features -- the feature chi2 pass (G into d_G), the correction slots of U,
+// W and V weighted per feature; the maps' own weights stay as gn_setup left them.  bracket_chi2 then is [4]: [2], [3] around the slots' fill.
+void gn_assemble(lsfm_context* ctx, const GnCall& c, int kind, double cth, const hipEvent_t* bracket_chi2, const GnFeat* fr = nullptr)
 {
 	hipStream_t s = ctx->stream;
 	const DevBatch& X = c.X;
@@ -883,7 +1260,17 @@ void gn_assemble(lsfm_context* ctx, const GnCall& c, int kind, double cth, const
 	const bool mono = c.mono;
 	dev_zero(ctx, c.Gacc, ((size_t)P * GN_GW + (size_t)N * GN_HW + 2) * sizeof(double));
 	gn_frames(ctx, c);
-	if (kind != 0)
+	if (fr)
+	{
+		if (bracket_chi2) LSFM_CHECK_HIP(hipEventRecord(bracket_chi2[0], s));
+		gn_feature_chi2(ctx, c, *fr, kind, cth);
+		if (bracket_chi2) { LSFM_CHECK_HIP(hipEventRecord(bracket_chi2[1], s)); LSFM_CHECK_HIP(hipEventRecord(bracket_chi2[2], s)); }
+		if (fr->NS)
+			hipLaunchKernelGGL(k_gn_feature_ufill, grid_for(fr->NS, GN_UFILL_LANES / LSFM_WAVE), dim3(GN_UFILL_LANES), 0, s, fr->NS, fr->d_sptr, fr->d_cf, fr->d_ca,
+			                   fr->d_cb, fr->d_eptr, fr->d_eidx, fr->d_sdst, X.W, X.V, fr->fw, X.U);
+		if (bracket_chi2) LSFM_CHECK_HIP(hipEventRecord(bracket_chi2[3], s));
+	}
+	else if (kind != 0)
 	{
 		if (bracket_chi2) LSFM_CHECK_HIP(hipEventRecord(bracket_chi2[0], s));
 		gn_chi2(ctx, c);
@@ -893,8 +1280,16 @@ void gn_assemble(lsfm_context* ctx, const GnCall& c, int kind, double cth, const
 	if (X.NU) hipLaunchKernelGGL(k_gn_ublocks, grid_for(X.NU, 128), dim3(128), 0, s, X.NU, P, X.Ui, X.Uj, X.U, X.pose_map, c.d_gm, c.d_gp, c.Dp, c.Cp, c.rp, c.Gacc, c.UJ);
 	if (FI)
 	{
-		if (mono) hipLaunchKernelGGL((k_gn_features<2>), grid_for(FI, 256), dim3(256), 0, s, FI, P, X.feat_map, c.d_gm, c.d_gf, c.d_x + (size_t)M * 6, X.feat, X.fptr, X.photo, X.W, X.V, c.Dp, c.Cp, c.rp, c.d_wdst, c.WJ, c.Vinst, c.eFinst, c.Gacc, c.Hacc);
-		else hipLaunchKernelGGL((k_gn_features<1>), grid_for(FI, 256), dim3(256), 0, s, FI, P, X.feat_map, c.d_gm, c.d_gf, c.d_x + (size_t)M * 6, X.feat, X.fptr, X.photo, X.W, X.V, c.Dp, c.Cp, c.rp, c.d_wdst, c.WJ, c.Vinst, c.eFinst, c.Gacc, c.Hacc);
+#define GN_FEATURES_CALL X.feat_map, c.d_gm, c.d_gf, c.d_x + (size_t)M * 6, X.feat, X.fptr, X.photo, X.W, X.V, c.Dp, c.Cp, c.rp, c.d_wdst, c.WJ, c.Vinst, c.eFinst, c.Gacc, c.Hacc
+		const double* none = nullptr;
+		if (fr)
+		{
+			if (mono) hipLaunchKernelGGL((k_gn_features<2, true>), grid_for(FI, 256), dim3(256), 0, s, FI, P, GN_FEATURES_CALL, fr->fw);
+			else hipLaunchKernelGGL((k_gn_features<1, true>), grid_for(FI, 256), dim3(256), 0, s, FI, P, GN_FEATURES_CALL, fr->fw);
+		}
+		else if (mono) hipLaunchKernelGGL((k_gn_features<2, false>), grid_for(FI, 256), dim3(256), 0, s, FI, P, GN_FEATURES_CALL, none);
+		else hipLaunchKernelGGL((k_gn_features<1, false>), grid_for(FI, 256), dim3(256), 0, s, FI, P, GN_FEATURES_CALL, none);
+#undef GN_FEATURES_CALL
 	}
 	hipLaunchKernelGGL(k_gn_pose_post, grid_for(P, 128), dim3(128), 0, s, P, X.pose_map, c.d_gm, c.d_gp, c.Dp, c.Cp, c.rp, c.Gacc, c.UJ, c.ePinst, c.Hacc);
 	hipLaunchKernelGGL(k_gn_hubhub, grid_for(N, 128), dim3(128), 0, s, N, c.d_gm, c.Hacc, c.UJ, c.Fsum);
@@ -908,35 +1303,40 @@ void gn_assemble(lsfm_context* ctx, const GnCall& c, int kind, double cth, const
 // threshold c (IRLS: every assembly forms chi2, the weights w_k = rho'(s_k) and G first, then the system with w_k I_k).
 // obj / gnorm: [iters + 1]; halvings: [iters] or null; chi2 / weight: [N] or null, at the returned state.  Returns LSFM_OK or
 // LSFM_NOT_CONVERGED (a step's camera system was left above its residual bound); throws Error for invalid input.
+// feat: the estimator is on the features (kind 1 or 2): G of lsfm_gn_polish_robust_features; chi2 / weight then are per local feature
+// instance [sum n_k] and the maps keep weight 1.
 int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_map* x, int iters, int kind, double cth, double* obj, double* gnorm,
-              int* halvings, double* chi2, double* weight)
+              int* halvings, double* chi2, double* weight, bool feat)
 {
 	hipStream_t s = ctx->stream;
 	// LSFM_GN_TIMING=1: wall clock of the call's parts on stderr (every part ends with a synchronisation of its own)
 	static const bool timing = getenv("LSFM_GN_TIMING") != nullptr;
 	auto wall = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double tw0 = wall();
-	double t_asm = 0.0, t_solve = 0.0, t_chi2 = 0.0;
+	double t_asm = 0.0, t_solve = 0.0, t_chi2 = 0.0, t_fill = 0.0;
 	int n_asm = 0, n_solve = 0;
 	GnCall c;
-	gn_setup(ctx, maps, N, mono, x, c);
+	GnFeat fr;
+	gn_setup(ctx, maps, N, mono, x, c, nullptr, nullptr, feat ? &fr : nullptr);
 	const int M = c.M, NFG = c.NFG;
 	const size_t RS = c.RS;
 	const bool robust = kind != 0;
 
 	// F (robust: G) and the step's system at the state in d_x
-	hipEvent_t e_chi2[2] = { nullptr, nullptr };
-	if (robust && timing) { e_chi2[0] = ctx->pool_event(); e_chi2[1] = ctx->pool_event(); }
+	hipEvent_t e_chi2[4] = { nullptr, nullptr, nullptr, nullptr };
+	if (robust && timing) for (int i = 0; i < (feat ? 4 : 2); i++) e_chi2[i] = ctx->pool_event();
 	auto assemble = [&]() -> double {
 		const double ta = wall();
-		gn_assemble(ctx, c, kind, cth, robust && timing ? e_chi2 : nullptr);
+		gn_assemble(ctx, c, kind, cth, robust && timing ? e_chi2 : nullptr, feat ? &fr : nullptr);
 		double F = 0.0;
 		d2h(ctx, &F, robust ? c.d_G : c.Fsum, sizeof(double));
+		if (feat && n_asm == 0) gn_feature_check(ctx, maps, c, fr); // (V does not change during the call)
 		if (robust && timing)
 		{
 			float ms = 0.0f;
 			LSFM_CHECK_HIP(hipEventElapsedTime(&ms, e_chi2[0], e_chi2[1]));
 			t_chi2 += ms;
+			if (feat) { LSFM_CHECK_HIP(hipEventElapsedTime(&ms, e_chi2[2], e_chi2[3])); t_fill += ms; }
 		}
 		t_asm += wall() - ta; n_asm++;
 		return F;
@@ -997,17 +1397,30 @@ int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_ma
 	}
 	d2h(ctx, x->stVal, c.d_x, RS * sizeof(double));
 	// chi2 / weights at the returned state: the last assembly's (robust), or formed once now from its frames and residuals (plain)
-	if (chi2)
+	if (feat)
 	{
-		if (!robust) gn_chi2(ctx, c);
-		d2h(ctx, chi2, c.d_chi2, (size_t)N * sizeof(double));
+		if (chi2 && c.FI) d2h(ctx, chi2, fr.fchi2, (size_t)c.FI * sizeof(double));
+		if (weight && c.FI) d2h(ctx, weight, fr.fw, (size_t)c.FI * sizeof(double));
 	}
-	if (weight)
+	else
 	{
-		if (robust) d2h(ctx, weight, c.d_w, (size_t)N * sizeof(double));
-		else std::fill(weight, weight + N, 1.0);
+		if (chi2)
+		{
+			if (!robust) gn_chi2(ctx, c);
+			d2h(ctx, chi2, c.d_chi2, (size_t)N * sizeof(double));
+		}
+		if (weight)
+		{
+			if (robust) d2h(ctx, weight, c.d_w, (size_t)N * sizeof(double));
+			else std::fill(weight, weight + N, 1.0);
+		}
 	}
-	if (timing)
+	if (timing && feat)
+		fprintf(stderr, "lsfm_gn: %d maps, %d poses, %d features, joint system %d U / %d W blocks; structure + upload %.2f ms, %d assemblies %.2f ms each "
+		                "(chi2 + weights %.3f ms each, U correction %.3f ms each: %d slots, %zu contributors), %d solves %.2f ms each, call %.2f ms\n", N, M, NFG,
+		        c.NUJ, c.NWJ, tw1 - tw0, n_asm, n_asm ? t_asm / n_asm : 0.0, n_asm ? t_chi2 / n_asm : 0.0, n_asm ? t_fill / n_asm : 0.0, fr.NS, fr.NC, n_solve,
+		        n_solve ? t_solve / n_solve : 0.0, wall() - tw0);
+	else if (timing)
 		fprintf(stderr, "lsfm_gn: %d maps, %d poses, %d features, joint system %d U / %d W blocks; structure + upload %.2f ms, %d assemblies %.2f ms each "
 		                "(chi2 + weights %.3f ms each), %d solves %.2f ms each, call %.2f ms\n", N, M, NFG, c.NUJ, c.NWJ, tw1 - tw0, n_asm,
 		        n_asm ? t_asm / n_asm : 0.0, n_asm ? t_chi2 / n_asm : 0.0, n_solve, n_solve ? t_solve / n_solve : 0.0, wall() - tw0);
@@ -1024,6 +1437,38 @@ int map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const ls
 	d2h(ctx, chi2, c.d_chi2, (size_t)N * sizeof(double));
 	if (dof) std::copy(c.dof.begin(), c.dof.end(), dof);
 	return LSFM_OK;
+}
+
+// c_kf of every local feature instance at the global state x (x is read only), in map order and within a map in its feature order;
+// pose_chi2 (may be null) [N] = chi2_k - sum_f c_kf
+int map_feature_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, double* fchi2, double* pose_chi2)
+{
+	GnCall c;
+	GnFeat fr;
+	fr.slots = false;
+	gn_setup(ctx, maps, N, mono, x, c, nullptr, nullptr, &fr);
+	gn_frames(ctx, c);
+	gn_feature_chi2(ctx, c, fr, 0, 1.0);
+	gn_feature_check(ctx, maps, c, fr);
+	if (c.FI) d2h(ctx, fchi2, fr.fchi2, (size_t)c.FI * sizeof(double));
+	if (pose_chi2) d2h(ctx, pose_chi2, fr.pose_chi2, (size_t)N * sizeof(double));
+	return LSFM_OK;
+}
+
+// lsfm_gn_polish_robust_features: kind 0 is the plain polish with the feature chi2 of its result; fchi2 / fweight [sum n_k], may be null
+int gn_polish_features(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_map* x, int iters, int kind, double cth, double* obj, double* gnorm,
+                       int* halvings, double* fchi2, double* fweight)
+{
+	if (kind != 0) return gn_polish(ctx, maps, N, mono, x, iters, kind, cth, obj, gnorm, halvings, fchi2, fweight, true);
+	const int rc = gn_polish(ctx, maps, N, mono, x, iters, 0, 1.0, obj, gnorm, halvings, nullptr, nullptr, false);
+	size_t FI = 0;
+	for (int k = 0; k < N; k++) FI += maps[k].n;
+	if (fchi2)
+	{
+		map_feature_chi2(ctx, maps, N, mono, x, fchi2, nullptr);
+	}
+	if (fweight) std::fill(fweight, fweight + FI, 1.0);
+	return rc;
 }
 
 // The joint system of the N local maps linearised at x, as a map like any other (C ABI: lsfm_gn_linearise).  One assembly at x with the

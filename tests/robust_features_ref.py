@@ -1,0 +1,181 @@
+"""numpy statements of what lsfm_map_feature_chi2 / lsfm_gn_polish_robust_features compute, for the tests (test_robust_features_cpu.py
+holds them to the oracle, the GPU tests use them on the device's results).
+
+For a local map with information I = [U W; W^T V] (V block diagonal) the conditional term of feature f scaled by w_f is
+
+    I(w) = I - sum_f (1 - w_f) C_f V_f^-1 C_f^T,   C_f = the columns of I that belong to f,
+
+i.e. U - sum_f (1 - w_f) W_f V_f^-1 W_f^T, w_f W_f, w_f V_f.  `reweight` writes it as a map dict: the map's own U blocks plus appended
+blocks (entries with equal coordinates add up), W and V scaled."""
+import numpy as np
+
+from linearsfm_amd import synth
+
+
+def dense_info(d):
+    """The dense information matrix (6m + 3n) of a map dict: diagonal U blocks full, an off-diagonal block with its transpose, blocks
+    with equal coordinates summed."""
+    m, n = int(d["m"]), int(d["n"])
+    U = np.asarray(d["U"], np.float64).reshape(-1, 6, 6)
+    W = np.asarray(d["W"], np.float64).reshape(-1, 6, 3)
+    V = np.asarray(d["V"], np.float64).reshape(-1, 3, 3)
+    H = np.zeros((6 * m + 3 * n, 6 * m + 3 * n))
+    for B, a, b in zip(U, d["Ui"], d["Uj"]):
+        H[6 * a:6 * a + 6, 6 * b:6 * b + 6] += B
+        if a != b:
+            H[6 * b:6 * b + 6, 6 * a:6 * a + 6] += B.T
+    for B, a, f in zip(W, d["photo"], d["feature"]):
+        H[6 * a:6 * a + 6, 6 * m + 3 * f:6 * m + 3 * f + 3] += B
+        H[6 * m + 3 * f:6 * m + 3 * f + 3, 6 * a:6 * a + 6] += B.T
+    for f in range(n):
+        H[6 * m + 3 * f:6 * m + 3 * f + 3, 6 * m + 3 * f:6 * m + 3 * f + 3] += V[f]
+    return H
+
+
+def dense_reweight(H, m, n, w):
+    """I(w) from the dense I, by the column formula of the module's header."""
+    out = H.copy()
+    for f in range(n):
+        s = slice(6 * m + 3 * f, 6 * m + 3 * f + 3)
+        C = H[:, s]
+        out -= (1.0 - w[f]) * C @ np.linalg.solve(H[s, s], C.T)
+    return out
+
+
+def reweight(d, w):
+    """I(w) of map dict d as a map dict: U gets one appended block -(sum_f (1 - w_f) Wbar_af V_f^-1 Wbar_bf^T) per pair a <= b of poses
+    that see a common feature, Wbar_af = the sum of f's W blocks of pose a (a (pose, feature) pair may repeat; summing per pose first
+    makes the diagonal block full and symmetric); W and V are scaled by w_f.  w: [n]."""
+    n = int(d["n"])
+    w = np.asarray(w, np.float64)
+    assert w.shape == (n,)
+    W = np.asarray(d["W"], np.float64).reshape(-1, 6, 3)
+    V = np.asarray(d["V"], np.float64).reshape(-1, 3, 3)
+    photo, feature = np.asarray(d["photo"]), np.asarray(d["feature"])
+    corr = {}
+    for f in range(n):
+        idx = np.nonzero(feature == f)[0]
+        poses = sorted(set(int(a) for a in photo[idx]))
+        Wb = {a: W[idx[photo[idx] == a]].sum(0) for a in poses}
+        Vi = np.linalg.inv(V[f])
+        for i, a in enumerate(poses):
+            for b in poses[i:]:
+                corr[(a, b)] = corr.get((a, b), 0.0) - (1.0 - w[f]) * Wb[a] @ Vi @ Wb[b].T
+    keys = sorted(corr)
+    e = dict(d)
+    e["U"] = np.concatenate([np.asarray(d["U"], np.float64).reshape(-1, 36)] + [corr[k].reshape(1, 36) for k in keys])
+    e["Ui"] = np.concatenate([np.asarray(d["Ui"], np.int32), np.array([k[0] for k in keys], np.int32)])
+    e["Uj"] = np.concatenate([np.asarray(d["Uj"], np.int32), np.array([k[1] for k in keys], np.int32)])
+    e["W"] = (W * w[feature][:, None, None]).reshape(-1, 18)
+    e["V"] = (V * w[:, None, None]).reshape(-1, 9)
+    return e
+
+
+def rho(kind, s, c):
+    """rho(s) as include/lsfm.h states it (kind 0: s)."""
+    s = np.asarray(s, np.float64)
+    if kind == 0:
+        return s
+    if kind == 1:
+        return np.where(s <= c * c, s, 2 * c * np.sqrt(s) - c * c)
+    return c * c * np.log1p(s / (c * c))
+
+
+def weights(kind, s, c):
+    """rho'(s), in the same operations as the device."""
+    s = np.asarray(s, np.float64)
+    if kind == 0:
+        return np.ones_like(s)
+    if kind == 1:
+        return np.where(s <= c * c, 1.0, c / np.sqrt(np.where(s > 0, s, 1.0)))
+    return 1.0 / (1.0 + s / (c * c))
+
+
+def objective(kind, c, fchi2, pose_chi2):
+    """G = sum_k (chi2_k - sum_f c_kf) + 3 sum_kf rho(c_kf / 3) from per-map lists of c_kf and the pose parts."""
+    return float(sum(p + 3.0 * np.sum(rho(kind, np.asarray(f) / 3.0, c)) for f, p in zip(fchi2, pose_chi2)))
+
+
+def map_objective(oracle, dicts, mono, G, k, dk):
+    """The oracle's F with map k replaced by dk and every other map's information scaled by 0: r_k^T I(dk) r_k."""
+    ds = []
+    for j, d in enumerate(dicts):
+        if j == k:
+            ds.append(dk)
+        else:
+            e = dict(d)
+            e["U"], e["W"], e["V"] = np.asarray(d["U"]) * 0.0, np.asarray(d["W"]) * 0.0, np.asarray(d["V"]) * 0.0
+            ds.append(e)
+    return oracle.gn_objective(ds, mono, G, False)[0]
+
+
+def feature_chi2_by_oracle(oracle, dicts, mono, G, k):
+    """(c_kf for every f of map k, F(I_k(0)), chi2_k) with c_kf = F(I_k(e_f)) - F(I_k(0))."""
+    d = dicts[k]
+    n = int(d["n"])
+    F0 = map_objective(oracle, dicts, mono, G, k, reweight(d, np.zeros(n)))
+    c = np.zeros(n)
+    for f in range(n):
+        e = np.zeros(n)
+        e[f] = 1.0
+        c[f] = map_objective(oracle, dicts, mono, G, k, reweight(d, e)) - F0
+    return c, F0, map_objective(oracle, dicts, mono, G, k, d)
+
+
+def observation_map(m, runs, rng, prior=1.0, stereo=True):
+    """(U, Ui, Uj, W, photo, feature, V) of a map with information sum J^T J over random observation Jacobians J = [Jp (3x6) | Jx (3x3)],
+    one per entry of runs[f] = the poses of feature f's W run IN THE GIVEN ORDER (a pose may repeat: a block of its own each time), plus
+    prior * identity on every pose: positive definite, V block diagonal by construction.  U: the diagonal blocks only (pairs of poses
+    have no block of their own)."""
+    U = np.stack([prior * np.eye(6) for _ in range(m)])
+    W, photo, feature, V = [], [], [], np.zeros((len(runs), 3, 3))
+    for f, run in enumerate(runs):
+        for a in run:
+            Jp, Jx = rng.normal(0, 1, (3, 6)), rng.normal(0, 1, (3, 3)) + 2.0 * np.eye(3)
+            U[a] += Jp.T @ Jp
+            W.append(Jp.T @ Jx)
+            photo.append(a)
+            feature.append(f)
+            V[f] += Jx.T @ Jx
+    return (U.reshape(m, 36), np.arange(m, dtype=np.int32), np.arange(m, dtype=np.int32), np.array(W).reshape(-1, 18),
+            np.array(photo, np.int32), np.array(feature, np.int32), V.reshape(-1, 9))
+
+
+def crafted_stereo_map(G, ref_id, pose_ids, feat_ids, runs, rng, noise=1e-3, prior=1.0):
+    """A Stereo local map dict over poses / features of the global state G (labels), anchored at pose ref_id: information by
+    observation_map, estimate = the global state seen from ref_id plus noise."""
+    m, stno, st = int(G["m"]), np.asarray(G["stno"]), np.asarray(G["stVal"], np.float64)
+    pose_at = {-int(stno[6 * i]): i for i in range(m)}
+    feat_at = {int(stno[6 * m + 3 * i]): i for i in range(int(G["n"]))}
+
+    def gpose(i):
+        return np.zeros(6) if i == int(G["Ref"]) else st[6 * pose_at[i]:6 * pose_at[i] + 6]
+    pr = gpose(ref_id)
+    Rr, tr = synth.rot_ypr(*pr[3:]), pr[:3]
+    vals = []
+    for i in pose_ids:
+        p = gpose(i)
+        vals.append(np.concatenate([Rr @ (p[:3] - tr), synth.ypr_from_rot(synth.rot_ypr(*p[3:]) @ Rr.T)]))
+    for i in feat_ids:
+        vals.append(Rr @ (st[6 * m + 3 * feat_at[i]:6 * m + 3 * feat_at[i] + 3] - tr))
+    val = np.concatenate(vals)
+    val = val + rng.normal(0, noise, val.shape)
+    U, Ui, Uj, W, photo, feature, V = observation_map(len(pose_ids), runs, rng, prior)
+    lab = np.concatenate([np.repeat(-np.asarray(pose_ids), 6), np.repeat(np.asarray(feat_ids), 3)]).astype(np.int32)
+    # FBlock: the first W block of every feature
+    fb = np.array([int(np.nonzero(feature == f)[0][0]) for f in range(len(feat_ids))], np.int32)
+    return dict(Ref=int(ref_id), FRef=int(ref_id), m=len(pose_ids), n=len(feat_ids), ScaP=0, Fix=0, Sign=1, FScaP=0, FFix=0, stno=lab, stVal=val,
+                U=U, Ui=Ui, Uj=Uj, W=W, photo=photo, feature=feature, V=V, FBlock=fb)
+
+
+def corrupt_features(d, feats, sigmas=30.0):
+    """Map dict d with the estimates of the given features moved by sigmas * sigma * (1, -1, 1), sigma = sqrt(diag(V_f^-1))."""
+    e = dict(d)
+    st = np.array(d["stVal"], np.float64, copy=True)
+    V = np.asarray(d["V"], np.float64).reshape(-1, 3, 3)
+    m = int(d["m"])
+    for f in feats:
+        sig = np.sqrt(np.diag(np.linalg.inv(V[f])))
+        st[6 * m + 3 * f:6 * m + 3 * f + 3] += sigmas * sig * np.array([1.0, -1.0, 1.0])
+    e["stVal"] = st
+    return e

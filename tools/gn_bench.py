@@ -6,7 +6,11 @@ steps of the plain polish beside it (wall clock per step of each, the chi2 kerne
 polish, lsfm_gn_linearise at the polished state (profiles/gn_linearise_<config>.json), one warm-up and the medians of 3 calls: HIP-event ms
 of the assembly and of the two coalescing launches, the block counts of the working form and of the map, the GB/s of k_gn_coalesce_w
 against (NWJ + nW') * 144 bytes, the call's wall ms with the library's own split (structure + upload, device, download), and the wall ms
-of lsfm_map_covariance on the result beside the same call on the tree's own map."""
+of lsfm_map_covariance on the result beside the same call on the tree's own map.  --robust-features huber|cauchy --c <c>:
+lsfm_gn_polish_robust_features beside the plain and the map-robust polish (same kind and c), two calls of each and the warm one read
+(profiles/gn_robust_features_<config>.json): per assembly the HIP-event ms of the feature chi2 pass (k_gn_feature_chi2 + the objective
+kernel) with its GB/s on the bytes it must read (every U, W and V block and feature estimate of the local maps once), beside
+k_gn_map_chi2 (+ weights kernel) on the same arrays, the HIP-event ms of the U correction kernel, and the wall ms per assembly and step."""
 import json
 import os
 import re
@@ -34,6 +38,25 @@ if len(sys.argv) > 1 and sys.argv[1] != "--child":
         up, dev, down, call = (sorted(r[i] for r in rows)[len(rows) // 2] for i in range(4))
         d["linearise"]["library_wall_ms"] = {"structure_upload": up, "device": dev, "download": down, "call": call,
                                              "upload_download_share": (up + down) / call}
+    if "robust_features" in d and len(tim) >= 6:
+        def parse(t):
+            g = lambda pat: float(re.search(pat, t).group(1))
+            o = {"assembly_ms": g(r"assemblies ([0-9.]+) ms each"), "solve_ms": g(r"solves ([0-9.]+) ms each"), "n_asm": int(re.search(r"(\d+) assemblies", t).group(1)),
+                 "n_solve": int(re.search(r"(\d+) solves", t).group(1)), "call_ms": g(r"call ([0-9.]+) ms"), "structure_upload_ms": g(r"structure \+ upload ([0-9.]+) ms"),
+                 "chi2_weights_ms": g(r"chi2 \+ weights ([0-9.]+) ms each")}
+            m = re.search(r"U correction ([0-9.]+) ms each: (\d+) slots, (\d+) contributors", t)
+            if m:
+                o.update(u_correction_ms=float(m.group(1)), slots=int(m.group(2)), contributors=int(m.group(3)))
+            o["step_ms"] = (o["n_asm"] * o["assembly_ms"] + o["n_solve"] * o["solve_ms"]) / max(o["n_solve"], 1)
+            return o
+        p_, r_, f_ = parse(tim[1]), parse(tim[3]), parse(tim[5])
+        d["plain_warm"], d["map_robust_warm"], d["feature_robust_warm"] = p_, r_, f_
+        B = d["chi2_pass_bytes"]
+        d["feature_chi2_GBps"] = B / (f_["chi2_weights_ms"] * 1e6) if f_["chi2_weights_ms"] > 0 else None
+        d["map_chi2_GBps"] = B / (r_["chi2_weights_ms"] * 1e6) if r_["chi2_weights_ms"] > 0 else None
+        d["feature_chi2_over_map_chi2"] = f_["chi2_weights_ms"] / r_["chi2_weights_ms"] if r_["chi2_weights_ms"] > 0 else None
+        d["u_correction_share_of_assembly"] = f_["u_correction_ms"] / f_["assembly_ms"]
+        d["feature_robust_over_plain_step"] = f_["step_ms"] / p_["step_ms"]
     if "robust" in d and len(tim) >= 4:
         # per step = one solve + the assemblies of the line search; from the warm call of each kind
         def parse(t):
@@ -61,6 +84,7 @@ ap.add_argument("steps", nargs="?", type=int, default=3)
 ap.add_argument("maps", nargs="?", type=int, default=0)
 ap.add_argument("--robust", choices=["huber", "cauchy"])
 ap.add_argument("--c", type=float, default=1.0)
+ap.add_argument("--robust-features", choices=["huber", "cauchy"])
 ap.add_argument("--linearise", action="store_true")
 a = ap.parse_args(sys.argv[2:])
 cfg, steps, nmaps = a.config, a.steps, a.maps
@@ -74,6 +98,30 @@ for rep in range(2):
     t0 = time.perf_counter()
     st, obj, gn, hv, rc2 = ctx.gn_polish(d, mono, G, steps)
     calls.append(1e3 * (time.perf_counter() - t0))
+if a.robust_features:
+    runs = {}
+    for name, call in (("map_robust_run", lambda: ctx.gn_polish_robust(d, mono, G, steps, a.robust_features, a.c)),
+                       ("feature_robust_run", lambda: ctx.gn_polish_robust_features(d, mono, G, steps, a.robust_features, a.c))):
+        walls = []
+        for rep in range(2):
+            t0 = time.perf_counter()
+            rst, robj, rgn, rhv, _, w, rrc = call()
+            walls.append(1e3 * (time.perf_counter() - t0))
+        w = np.concatenate(w) if isinstance(w, list) else w
+        runs[name] = {"objective": robj.tolist(), "halvings": rhv.tolist(), "call_wall_ms": walls, "rc": rrc, "weight_min": float(np.min(w)),
+                      "weight_median": float(np.median(w)), "weights_below_1": float(np.mean(w < 1.0))}
+    nW, nF, nU = sum(m.nW for m in maps), sum(m.n for m in maps), sum(m.nU for m in maps)
+    sys.stdout.flush()
+    print(json.dumps({"config": cfg, "type": typ, "maps": len(maps), "poses": int(G["m"]), "features": int(G["n"]), "steps": steps,
+                      "robust_features": a.robust_features, "c": a.c, "local_W_blocks": nW, "local_features": nF, "local_U_blocks": nU,
+                      "chi2_pass_bytes": 144 * nW + (72 + 24) * nF + 288 * nU,
+                      "plain": {"objective": obj.tolist(), "halvings": hv.tolist(), "call_wall_ms": calls}, **runs,
+                      "note": "plain = lsfm_gn_polish, map_robust_run = lsfm_gn_polish_robust, feature_robust_run = lsfm_gn_polish_robust_features, same "
+                              "kind, c and steps from the device's tree result; library_timing: the library's own clocks, in call order plain, plain, "
+                              "map-robust x 2, feature-robust x 2 (the second of each warm); chi2_weights_ms: HIP events around k_gn_map_chi2 + "
+                              "k_gn_robust_weights resp. k_gn_feature_chi2 + k_gn_feature_objective; chi2_pass_bytes: every local U, W and V block "
+                              "and feature estimate once, the least either pass reads"}))
+    sys.exit(0)
 if a.robust:
     rcalls = []
     for rep in range(2):
