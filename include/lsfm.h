@@ -394,6 +394,25 @@ int lsfm_map_marginalise_poses_timed(lsfm_context* ctx, const lsfm_map* map, int
 int lsfm_marg_pose_structure(const lsfm_map* map, int mono, const unsigned char* keep_pose, const unsigned char* drop_feat, unsigned char* drop,
                              int* comp, int* nptr, int* nidx, int cap_n, int* bd, int* Ui, int* Uj, int cap_u, int* info, char* why, int why_cap);
 
+/* Test entry, NO device needed: the structure of the joint system that lsfm_gn_polish[_robust[_features]], lsfm_map[_feature]_chi2 and
+ * lsfm_gn_linearise build from the labels and index arrays of the N local maps and the global state x alone (no value is read).
+ * want_slots: every map's U range is extended by the correction slots of lsfm_gn_polish_robust_features; want_coalesce: the coalesced
+ * form of lsfm_gn_linearise as well.  Outputs, each optional; poses and features are indices into x unless said otherwise:
+ *   info[10]      { M, NFG, local poses P, local feature instances FI, NUJ, NWJ, nU', nW', slots, contributors } (NUJ / NWJ: blocks of the
+ *                 working form, every map writes its own; nU' / nW': coalesced, 0 without want_coalesce)
+ *   map_hubs[3 N] per map { hub columns nh (0: the map's frame is the global one), pose of Ref_k, pose of ScaP_k (-1: none) }
+ *   wdst[FI]      first block of a feature instance in the joint W: its nh hub blocks, then its own run
+ *   fptrJ[NFG + 1], photoJ[cap_wj]   the joint W: the run of every global feature and the pose of every block
+ *   UiJ, UjJ[cap_uj]   the joint U's coordinates
+ *   photo, feature[cap_w], FBlock[NFG], Ui, Uj[cap_u]   the coalesced W (sorted by feature, then pose) and U (sorted by (Ui, Uj))
+ *   slot_map, slot_a, slot_b, slot_count[cap_s]   per correction slot its map, its LOCAL poses a <= b and the number of its contributors
+ *   why[why_cap]  what is wrong, when LSFM_ERR_ARG is returned
+ * Call it once with info alone for the sizes.  LSFM_ERR_ARG for what the calls above cannot place, and when a cap is too small. */
+int lsfm_gn_structure(const lsfm_map* maps, int N, int type, const lsfm_map* x, int want_slots, int want_coalesce, int* info, int* map_hubs,
+                      int* wdst, int* fptrJ, int* photoJ, int cap_wj, int* UiJ, int* UjJ, int cap_uj, int* photo, int* feature, int* FBlock,
+                      int cap_w, int* Ui, int* Uj, int cap_u, int* slot_map, int* slot_a, int* slot_b, int* slot_count, int cap_s, char* why,
+                      int why_cap);
+
 /* replaces pba_inverseV (Imp.h:213, Imp.cpp:3022-3042): V^-1 of the n 3x3 feature blocks, IN PLACE like the reference's (which
  * inverts V in place and restores it afterwards, Imp.cpp:2210-2212, 2365): the upper triangle of the computed inverse, mirrored.
  * m is unused, as in the reference. */

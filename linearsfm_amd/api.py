@@ -139,6 +139,8 @@ def lib():
         L.lsfm_map_marginalise_poses.argtypes = [vp, P(LsfmMap), C.c_int, ub, ub, P(LsfmMap)]
         L.lsfm_map_marginalise_poses_timed.argtypes = [vp, P(LsfmMap), C.c_int, ub, ub, P(LsfmMap), dp, ip]
         L.lsfm_marg_pose_structure.argtypes = [P(LsfmMap), C.c_int, ub, ub, ub, ip, ip, ip, C.c_int, ip, ip, ip, C.c_int, ip, C.c_char_p, C.c_int]
+        L.lsfm_gn_structure.argtypes = [P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), C.c_int, C.c_int, ip, ip, ip, ip, ip, C.c_int, ip, ip, C.c_int, ip, ip, ip,
+                                        C.c_int, ip, ip, C.c_int, ip, ip, ip, ip, C.c_int, C.c_char_p, C.c_int]
         L.lsfm_tree_export_reduced_size.argtypes = [vp, vp, ip, C.c_int, P(C.c_size_t)]
         L.lsfm_tree_export_reduced_dev.argtypes = [vp, vp, ip, C.c_int, vp, C.c_size_t]
         L.lsfm_tree_export_reduced_dev_timed.argtypes = [vp, vp, ip, C.c_int, vp, C.c_size_t, dp]
@@ -165,7 +167,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_save_covariances", "lsfm_read_covariances",
            "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns",
            "lsfm_map_marginalise", "lsfm_map_marginalise_timed", "lsfm_tree_export_reduced_size", "lsfm_tree_export_reduced_dev",
-           "lsfm_tree_export_reduced_dev_timed", "lsfm_map_marginalise_poses", "lsfm_map_marginalise_poses_timed", "lsfm_marg_pose_structure"]
+           "lsfm_tree_export_reduced_dev_timed", "lsfm_map_marginalise_poses", "lsfm_map_marginalise_poses_timed", "lsfm_marg_pose_structure", "lsfm_gn_structure"]
 
 
 def _c(a, dtype):
@@ -870,6 +872,37 @@ def marg_pose_structure(d, mono, keep_pose, drop_feat=None):
     nc = int(info[2])
     return dict(drop=drop[:n].astype(bool), comp=comp, nptr=nptr[:nc + 1].copy(), nidx=nidx[:int(info[4])].copy(), bd=bd[:int(info[1])].copy(),
                 Ui=Ui[:int(info[3])].copy(), Uj=Uj[:int(info[3])].copy(), info=info)
+
+
+GN_STRUCTURE_INFO = ("M", "NFG", "P", "FI", "NUJ", "NWJ", "nU", "nW", "slots", "contributors")
+
+
+def gn_structure(maps, mono, G, slots=False, coalesce=False):
+    """Host-only (lsfm_gn_structure): the joint system that the Gauss-Newton calls build from the labels of the local map dicts `maps` and
+    the global state G, without a device.  Returns dict(info (by GN_STRUCTURE_INFO), map_hubs [N, 3] (nh, Ref pose, ScaP pose), wdst, fptrJ,
+    photoJ, UiJ / UjJ (the working form), photo / feature / FBlock / Ui / Uj (coalesced; empty without `coalesce`), slot_map / slot_a /
+    slot_b / slot_count (the correction slots; empty without `slots`)).  Raises LsfmError with the library's reason."""
+    hms, arr, x, keep = _gn_args(maps, G)
+    N = len(hms)
+    info = np.zeros(10, np.int32)
+    why = C.create_string_buffer(512)
+    head = (arr, N, 1 if mono else 0, C.byref(x), int(bool(slots)), int(bool(coalesce)), _ptr(info, C.c_int))
+    rc = lib().lsfm_gn_structure(*head, None, None, None, None, 0, None, None, 0, None, None, None, 0, None, None, 0, None, None, None, None, 0, why, len(why))
+    if rc:
+        raise LsfmError(f"lsfm_gn_structure failed (rc={rc}): {why.value.decode()}")
+    v = dict(zip(GN_STRUCTURE_INFO, (int(i) for i in info)))
+    z = lambda n: np.zeros(max(n, 1), np.int32)
+    hubs, wdst, fptrJ, photoJ, UiJ, UjJ = z(3 * N), z(v["FI"]), z(v["NFG"] + 1), z(v["NWJ"]), z(v["NUJ"]), z(v["NUJ"])
+    photo, feature, FBlock, Ui, Uj = z(v["nW"]), z(v["nW"]), z(v["NFG"]), z(v["nU"]), z(v["nU"])
+    sm, sa, sb, sc = z(v["slots"]), z(v["slots"]), z(v["slots"]), z(v["slots"])
+    p = lambda a: _ptr(a, C.c_int)
+    rc = lib().lsfm_gn_structure(*head, p(hubs), p(wdst), p(fptrJ), p(photoJ), len(photoJ), p(UiJ), p(UjJ), len(UiJ), p(photo), p(feature), p(FBlock),
+                                 len(photo), p(Ui), p(Uj), len(Ui), p(sm), p(sa), p(sb), p(sc), len(sm), why, len(why))
+    if rc:
+        raise LsfmError(f"lsfm_gn_structure failed (rc={rc}): {why.value.decode()}")
+    return dict(info=v, map_hubs=hubs.reshape(N, 3), wdst=wdst[:v["FI"]], fptrJ=fptrJ, photoJ=photoJ[:v["NWJ"]], UiJ=UiJ[:v["NUJ"]], UjJ=UjJ[:v["NUJ"]],
+                photo=photo[:v["nW"]], feature=feature[:v["nW"]], FBlock=FBlock[:v["NFG"] if coalesce else 0], Ui=Ui[:v["nU"]], Uj=Uj[:v["nU"]],
+                slot_map=sm[:v["slots"]], slot_a=sa[:v["slots"]], slot_b=sb[:v["slots"]], slot_count=sc[:v["slots"]])
 
 
 LSFM_NODE_MAGIC = 1279870541  # first token of the tree-node trailer of a local-map file (lsfm_io.cpp)

@@ -217,6 +217,20 @@ __device__ __forceinline__ double wave_sum(double v)
 	for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, LSFM_WAVE);
 	return v;
 }
+// v summed over a work-group of LANES lanes in a fixed order: the wave sums, then the waves in order from part[LANES / LSFM_WAVE] in
+// LDS -- no atomics, the same values give the same bits.  Every lane returns the sum; all lanes must call it (one barrier), and `part`
+// may be used again only after another barrier.
+template <int LANES>
+__device__ __forceinline__ double block_sum_fixed(double v, double* part)
+{
+	v = wave_sum(v);
+	if ((threadIdx.x & (LSFM_WAVE - 1)) == 0) part[threadIdx.x / LSFM_WAVE] = v;
+	__syncthreads();
+	double sum = 0.0;
+#pragma unroll
+	for (int w = 0; w < LANES / LSFM_WAVE; w++) sum += part[w];
+	return sum;
+}
 
 __device__ __forceinline__ void atomic_add_f64(double* p, double v)
 {

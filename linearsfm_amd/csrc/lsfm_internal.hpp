@@ -541,15 +541,16 @@ SolveOutcome solve_batch(lsfm_context* ctx, const SolveIO& io);
 // (systems left above their bound are counted into ctx->stats here).
 SolveOutcome join_batch_stereo(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, double* eP_out, double* eF_out, int step_hint = 0);
 SolveOutcome join_batch_mono(lsfm_context* ctx, Arena& ar, const DevBatch& in, DevBatch& out, double* eP_out, double* eF_out, int step_hint = 0);
-// Gauss-Newton polish of the map-joining objective over all local maps at once (lsfm_gn.hip; C ABI: lsfm_gn_polish)
+// Gauss-Newton polish of the map-joining objective over all local maps at once (lsfm_gn.hip, shared declarations
+// lsfm_gn.hpp: structure lsfm_gn_structure.cpp, one assembly lsfm_gn_assemble.hip, chi^2 and weights lsfm_gn_chi2.hip; C ABI: lsfm_gn_polish)
 int gn_polish(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_map* x, int iters, int kind, double c, double* obj, double* gnorm,
-              int* halvings, double* chi2, double* weight, bool feat = false);
+              int* halvings, double* chi2, double* weight);
 // per-feature chi^2 c_kf of every local feature instance at a global state and the Gauss-Newton polish that down-weights single
-// features by an M-estimator on c_kf / 3 (lsfm_gn.hip; C ABI: lsfm_map_feature_chi2, lsfm_gn_polish_robust_features)
+// features by an M-estimator on c_kf / 3 (lsfm_gn.hip, kernels lsfm_gn_chi2.hip; C ABI: lsfm_map_feature_chi2, lsfm_gn_polish_robust_features)
 int map_feature_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, double* fchi2, double* pose_chi2);
 int gn_polish_features(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_map* x, int iters, int kind, double c, double* obj, double* gnorm,
                        int* halvings, double* fchi2, double* fweight);
-// per-map chi^2 of the map-joining objective at a global state (lsfm_gn.hip; C ABI: lsfm_map_chi2)
+// per-map chi^2 of the map-joining objective at a global state (lsfm_gn.hip, kernel lsfm_gn_chi2.hip; C ABI: lsfm_map_chi2)
 int map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, double* chi2, int* dof);
 // the joint system of the local maps linearised at x as a map of its own, every block once (lsfm_gn.hip; C ABI: lsfm_gn_linearise).
 // times (may be null): [3] ms of the assembly, the W and the U coalescing launch; counts (may be null): [4] NWJ, nW', NUJ, nU'

@@ -13,7 +13,7 @@
 //   k_marg_index / _photo      run pointers and poses of the dropped features (what the pattern needs: index arrays alone)
 //   k_marg_w                   THE pass over W: every 144-byte block is read once and written to exactly one of two places -- a kept
 //                              block to the output (with its pose and renumbered feature), a dropped block to K9's input; order
-//                              inside a run is preserved.  One lane per block, as k_slice_w (lsfm_batch.hip) and k_gn_coalesce_w
+//                              inside a run is preserved.  One lane per block, as k_slice_w (lsfm_batch.hip) and k_gn_coalesce<18>
 //   k_marg_features            per feature: V, estimate, label and run pointer of a kept one to the output, V of a dropped one to
 //                              k_vinv's input
 //   k_marg_emit                U' / Ui / Uj from S and its keys, consecutive lanes on consecutive numbers

@@ -168,6 +168,31 @@ def crafted_stereo_map(G, ref_id, pose_ids, feat_ids, runs, rng, noise=1e-3, pri
                 U=U, Ui=Ui, Uj=Uj, W=W, photo=photo, feature=feature, V=V, FBlock=fb)
 
 
+def crafted_set(oracle):
+    """A 22-map Stereo set (its first map's Ref is the global Ref: nh = 0) plus three crafted maps over its poses and features:
+    A: 20 poses, 3 features; feature 0 is seen by every pose, its W run in DESCENDING pose order (210 pose pairs, each a slot without a
+       U block of its own; the 20 diagonal slots lie beside the map's own diagonal blocks), feature 1 by poses 3, 5, 3 (a repeated
+       (pose, feature) block), feature 2 by one pose;
+    B: anchored at the global Ref (nh = 0), 2 poses, 600 features (more than two passes of the chi^2 kernel's 256 lanes), seen by the
+       first, the second or both poses (the second first);
+    C: 2 poses and no feature (n = 0).
+    Information: sum J^T J of random observation Jacobians plus a pose prior; estimate: the tree's state seen from the map's Ref plus
+    noise of 0.02 (about a tenth of a standard deviation of such a map)."""
+    base = [oracle.localmap_to_dict(m) for m in synth.make_stereo_set(22, 30, 4, seed=3)]
+    G, _, rc = oracle.divide_conquer(base, False)
+    assert rc == 0 and int(G["n"]) >= 600
+    rng = np.random.default_rng(17)
+    ids = -np.asarray(G["stno"])[:6 * int(G["m"]):6]
+    feats = np.asarray(G["stno"])[6 * int(G["m"])::3]
+    pa = [int(i) for i in ids[1:21]]
+    A = crafted_stereo_map(G, int(ids[21]), pa, [int(feats[5]), int(feats[40]), int(feats[77])],
+                           [list(range(19, -1, -1)), [3, 5, 3], [7]], rng, noise=0.02)
+    runs = [[[0], [1], [1, 0]][f % 3] for f in range(600)]
+    B = crafted_stereo_map(G, int(G["Ref"]), [int(ids[3]), int(ids[8])], [int(f) for f in feats[:600]], runs, rng, noise=0.02)
+    Cm = crafted_stereo_map(G, int(ids[4]), [int(ids[9]), int(ids[10])], [], [], rng, noise=0.02)
+    return base + [A, B, Cm], G
+
+
 def corrupt_features(d, feats, sigmas=30.0):
     """Map dict d with the estimates of the given features moved by sigmas * sigma * (1, -1, 1), sigma = sqrt(diag(V_f^-1))."""
     e = dict(d)

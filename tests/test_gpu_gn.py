@@ -1,4 +1,4 @@
-"""-m gpu: lsfm_gn_polish (csrc/lsfm_gn.hip) -- the Gauss-Newton polish of the map-joining objective over all local maps -- against
+"""-m gpu: lsfm_gn_polish (csrc/lsfm_gn.hip, one assembly: csrc/lsfm_gn_assemble.hip) -- the Gauss-Newton polish of the map-joining objective over all local maps -- against
 the oracle's statement of the same steps (oracle/lsfm_gn.inc) and by its properties.  The reference has no iterative step: parity is
 UNPINNED for this entry point; tests/test_gn_cpu.py pins the oracle's step to the objective itself."""
 import os

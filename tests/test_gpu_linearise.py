@@ -1,4 +1,4 @@
-"""-m gpu: lsfm_gn_linearise (csrc/lsfm_gn.hip) -- the joint map of the N local maps linearised at a given state: H = sum_k w_k J_k^T I_k J_k
+"""-m gpu: lsfm_gn_linearise (csrc/lsfm_gn.hip, structure: csrc/lsfm_gn_structure.cpp) -- the joint map of the N local maps linearised at a given state: H = sum_k w_k J_k^T I_k J_k
 as U / W / V with every block once, the matrix a step of lsfm_gn_polish[_robust] solves with.  No reference counterpart (parity UNPINNED).
 The expected H is the oracle's (oracle/lsfm_gn.inc, orc_gn_hessian_times), made dense here; b and F are the oracle's gn_objective.
 

@@ -1,4 +1,4 @@
-"""-m gpu: lsfm_map_chi2 and lsfm_gn_polish_robust (csrc/lsfm_gn.hip) -- the per-map chi^2 of the map-joining objective and the
+"""-m gpu: lsfm_map_chi2 and lsfm_gn_polish_robust (csrc/lsfm_gn.hip, kernels: csrc/lsfm_gn_chi2.hip) -- the per-map chi^2 of the map-joining objective and the
 Gauss-Newton polish that re-weights whole local maps by an M-estimator on chi2_k / dof_k (IRLS).  No reference counterpart (parity
 UNPINNED).  The oracle checks both exactly without a change of its own: I_k enters F linearly, so scaling map k's U, W and V by w_k in
 the map dicts turns the oracle's F into sum_k w_k chi2_k."""

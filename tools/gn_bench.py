@@ -4,13 +4,13 @@ solve).  usage: python tools/gn_bench.py <config> [steps] [maps] [--robust huber
 -> one JSON object per call on stdout (profiles/r06_gn_polish_<config>.json).  --robust: lsfm_gn_polish_robust instead, and the same
 steps of the plain polish beside it (wall clock per step of each, the chi2 kernel's share of an assembly).  --linearise: after the
 polish, lsfm_gn_linearise at the polished state (profiles/gn_linearise_<config>.json), one warm-up and the medians of 3 calls: HIP-event ms
-of the assembly and of the two coalescing launches, the block counts of the working form and of the map, the GB/s of k_gn_coalesce_w
+of the assembly and of the two coalescing launches, the block counts of the working form and of the map, the GB/s of k_gn_coalesce<18>
 against (NWJ + nW') * 144 bytes, the call's wall ms with the library's own split (structure + upload, device, download), and the wall ms
 of lsfm_map_covariance on the result beside the same call on the tree's own map.  --robust-features huber|cauchy --c <c>:
 lsfm_gn_polish_robust_features beside the plain and the map-robust polish (same kind and c), two calls of each and the warm one read
-(profiles/gn_robust_features_<config>.json): per assembly the HIP-event ms of the feature chi2 pass (k_gn_feature_chi2 + the objective
+(profiles/gn_robust_features_<config>.json): per assembly the HIP-event ms of the feature chi2 pass (k_gn_chi2<true> + the objective
 kernel) with its GB/s on the bytes it must read (every U, W and V block and feature estimate of the local maps once), beside
-k_gn_map_chi2 (+ weights kernel) on the same arrays, the HIP-event ms of the U correction kernel, and the wall ms per assembly and step."""
+k_gn_chi2<false> (+ weights kernel) on the same arrays, the HIP-event ms of the U correction kernel, and the wall ms per assembly and step."""
 import json
 import os
 import re
@@ -118,8 +118,8 @@ if a.robust_features:
                       "plain": {"objective": obj.tolist(), "halvings": hv.tolist(), "call_wall_ms": calls}, **runs,
                       "note": "plain = lsfm_gn_polish, map_robust_run = lsfm_gn_polish_robust, feature_robust_run = lsfm_gn_polish_robust_features, same "
                               "kind, c and steps from the device's tree result; library_timing: the library's own clocks, in call order plain, plain, "
-                              "map-robust x 2, feature-robust x 2 (the second of each warm); chi2_weights_ms: HIP events around k_gn_map_chi2 + "
-                              "k_gn_robust_weights resp. k_gn_feature_chi2 + k_gn_feature_objective; chi2_pass_bytes: every local U, W and V block "
+                              "map-robust x 2, feature-robust x 2 (the second of each warm); chi2_weights_ms: HIP events around k_gn_chi2<false> + "
+                              "k_gn_robust_weights resp. k_gn_chi2<true> + k_gn_feature_objective; chi2_pass_bytes: every local U, W and V block "
                               "and feature estimate once, the least either pass reads"}))
     sys.exit(0)
 if a.robust:
