@@ -16,6 +16,7 @@
 // untouched blocks in their old order; per feature first its block(s) to h_1 [h_2], then its old blocks.
 #include <algorithm>
 #include <climits>
+#include <cstddef>
 
 #include "lsfm_device.hpp"
 #include "lsfm_internal.hpp"
@@ -330,16 +331,36 @@ __global__ void k_tr_gather_counts(const int* __restrict__ KU, const int* __rest
 
 // ---------------------------------------------------------------------------------------------------------
 // the feature stage (K3/K4 of SURVEY 2a): Imp.cpp:1300-1915 / 5017-6501, in three launches
-//   k_tr_feat_pre   one lane per feature : x', D_f, C_s,f, V' = D_f^T V D_f, new run pointer
+//   k_tr_feat_pre   one lane per feature : x', V' = D_f^T V D_f, new run pointer, the record of the feature for the block
+//                   kernel (finfo), "no hub block seen" (hubJ); Mono only: D_f, C_s,f as a record of 45 doubles (FD)
 //   k_tr_entries    one lane per W block : W' = D_k^T W D_f at its new place, the block's share of the feature rows
 //                   of G (W^T C_s,k, summed per feature through LDS) and of the pose rows of G (W C_s,f, LDS table)
 //   k_tr_feat_post  one lane per feature : G_s,f complete, the new block(s) to the hub pose(s), C_s^T G_t
 // The W blocks -- 90 % of the bytes -- are read and written by consecutive lanes (one 144-byte block per lane,
 // contiguous over the wave); a lane per feature walking its run strided the wave's accesses by the run length and
 // needed 340 registers (one wave per SIMD).
+// Stereo keeps no D_f / C_f per feature: D_f = R is the map's, C_f = [-R | T_f] with T_f = [dRA dd, dRB dd, dRG dd],
+// dd = x' - t, so the two consumers form them from the map's record (TR_REC doubles of TMap) and the 24 bytes of x' that
+// the prologue writes anyway (stereo_tf) -- 216 bytes per feature less to write once and to read twice.  Mono's record
+// comes out of mono_trans_jac per feature (every entry of C_1,f and C_2,f holds R (x' - t) over the scale and its
+// derivatives: a dozen divisions, then the gauge cases c2fix / c3zero): Mono keeps it, a later change may look at it.
 // ---------------------------------------------------------------------------------------------------------
 #define TRE_TILE 128 /* features per work-group: the LDS pose table is flushed once per tile */
 #define TRE_ROUND 256 /* W blocks per round = threads */
+#define TRE_MAPS 4 /* Stereo: records of the tile's first maps kept in LDS by k_tr_entries (a lane of a later map reads global memory) */
+#define TR_REC 39 /* R, dRA, dRB, dRG, t of a map: what the Stereo Jacobians of its features are made from */
+static_assert(offsetof(TMap, dRA) == offsetof(TMap, R) + 72 && offsetof(TMap, dRB) == offsetof(TMap, R) + 144 && offsetof(TMap, dRG) == offsetof(TMap, R) + 216 &&
+              offsetof(TMap, t) == offsetof(TMap, R) + 288, "R, dRA, dRB, dRG, t of TMap are read as one run of TR_REC doubles");
+
+// T_f [3x3, row major] of a Stereo feature: rec = the TR_REC doubles of its map, xn = its new value.  The same mv3 calls on the same
+// numbers wherever it is formed, so that every kernel holds the same C_f
+__device__ __forceinline__ void stereo_tf(const double* rec, const double* xn, double* Tf)
+{
+	double dd[3] = { xn[0] - rec[36], xn[1] - rec[37], xn[2] - rec[38] }, tmp1[3], tmp2[3], tmp3[3];
+	mv3(rec + 9, dd, tmp1); mv3(rec + 18, dd, tmp2); mv3(rec + 27, dd, tmp3);
+#pragma unroll
+	for (int r = 0; r < 3; r++) { Tf[3 * r] = tmp1[r]; Tf[3 * r + 1] = tmp2[r]; Tf[3 * r + 2] = tmp3[r]; }
+}
 
 template <int NH>
 __global__ void __launch_bounds__(256)
@@ -360,13 +381,13 @@ k_tr_feat_pre(int NF, const TMap* __restrict__ tm, const int* __restrict__ feat_
 		nfeat[3 * (size_t)f] = x[0]; nfeat[3 * (size_t)f + 1] = x[1]; nfeat[3 * (size_t)f + 2] = x[2];
 		for (int i = 0; i < 9; i++) Vn[(size_t)f * 9 + i] = Vold[(size_t)f * 9 + i];
 		nfptr[f] = t->W0n + (j0 - t->W0);
-		finfo[f] = make_int4(0, -1, -1, -j0); // new place of block j: (start of the feature's new run) + w + j
+		finfo[f] = make_int4(0, -1, NH == 2 ? -1 : feat_map[f], -j0); // new place of block j: (start of the feature's new run) + w + j
 		return;
 	}
 	nfptr[f] = t->W0n + NH * (f - t->F0) + (KW[j0] - t->kW0);
 	// per feature record for the block kernel: active, hub pose(s), new place of a kept block j = (start of the
-	// feature's new run) + w + KW[j]
-	finfo[f] = make_int4(1, t->hub[0], NH == 2 ? t->hub[1] : -1, NH - KW[j0]);
+	// feature's new run) + w + KW[j].  Stereo has no second hub: z is the feature's map, whose record its Jacobians are made from
+	finfo[f] = make_int4(1, t->hub[0], NH == 2 ? t->hub[1] : feat_map[f], NH - KW[j0]);
 	double Df[9], Cf[NH][18], xn[3];
 	// new feature value, Imp.cpp:449-451 / 3300-3302
 	double d[3] = { x[0] - t->t1[0], x[1] - t->t1[1], x[2] - t->t1[2] };
@@ -374,17 +395,10 @@ k_tr_feat_pre(int NF, const TMap* __restrict__ tm, const int* __restrict__ feat_
 	if (NH == 2) { xn[0] = xn[0] / t->scale1; xn[1] = xn[1] / t->scale1; xn[2] = xn[2] / t->scale1; }
 	nfeat[3 * (size_t)f] = xn[0]; nfeat[3 * (size_t)f + 1] = xn[1]; nfeat[3 * (size_t)f + 2] = xn[2];
 	// D_f, C_f: Imp.cpp:638-680 / 3587-3684
-	if (NH == 1)
+	if constexpr (NH == 1)
 	{
-		double dd[3] = { xn[0] - t->t[0], xn[1] - t->t[1], xn[2] - t->t[2] }, tmp1[3], tmp2[3], tmp3[3];
-		mv3(t->dRA, dd, tmp1); mv3(t->dRB, dd, tmp2); mv3(t->dRG, dd, tmp3);
-#pragma unroll
-		for (int r = 0; r < 3; r++)
-		{
-			Df[3 * r] = t->R[3 * r]; Df[3 * r + 1] = t->R[3 * r + 1]; Df[3 * r + 2] = t->R[3 * r + 2];
-			Cf[0][6 * r] = -t->R[3 * r]; Cf[0][6 * r + 1] = -t->R[3 * r + 1]; Cf[0][6 * r + 2] = -t->R[3 * r + 2];
-			Cf[0][6 * r + 3] = tmp1[r]; Cf[0][6 * r + 4] = tmp2[r]; Cf[0][6 * r + 5] = tmp3[r];
-		}
+		// D_f = R; C_f = [-R | T_f] is formed where it is used (stereo_tf), from R, dRA, dRB, dRG, t and the x' just written
+		ld<9>(Df, t->R);
 	}
 	else
 	{
@@ -411,10 +425,13 @@ k_tr_feat_pre(int NF, const TMap* __restrict__ tm, const int* __restrict__ feat_
 	mtm<3, 3, 3, false>(Df, V, T);
 	mm<3, 3, 3, false>(T, Df, Vnew);
 	st<9>(Vn + (size_t)f * 9, Vnew);
-	double* fd = FD + (size_t)f * (9 + 18 * NH);
-	st<9>(fd, Df);
+	if constexpr (NH == 2)
+	{
+		double* fd = FD + (size_t)f * (9 + 18 * NH);
+		st<9>(fd, Df);
 #pragma unroll
-	for (int s = 0; s < NH; s++) st<18>(fd + 9 + 18 * s, Cf[s]);
+		for (int s = 0; s < NH; s++) st<18>(fd + 9 + 18 * s, Cf[s]);
+	}
 }
 
 // Profiling aid (make K9_TIMING=1; tools/tr_phase_times.py): lane 0 of every work-group adds up the shader clocks it spends
@@ -440,10 +457,13 @@ template <int NH>
 __global__ void __launch_bounds__(TRE_ROUND, NH == 1 ? 3 : 2)
 k_tr_entries(int NF, int M, const int4* __restrict__ finfo, const int* __restrict__ fptr,
              const double* __restrict__ Wold, const int* __restrict__ photo, const int* __restrict__ KW, const double* __restrict__ Dp,
-             const double* __restrict__ Cp, const double* __restrict__ FD, double* __restrict__ Wn_, int* __restrict__ nphoto,
+             const double* __restrict__ Cp, const double* __restrict__ FD, const TMap* __restrict__ tm, const double* __restrict__ xnew,
+             double* __restrict__ Wn_, int* __restrict__ nphoto,
              int* __restrict__ nfeature, double* __restrict__ Gsum, double* __restrict__ Gpose, int* __restrict__ hubJ, int alias_passthrough,
              const int* __restrict__ wbase, const int* __restrict__ newf, int* __restrict__ srcf)
 {
+	// FD: Mono's D_f / C_s,f records (null for Stereo); tm, xnew: the maps' records and the new feature values x' that Stereo makes
+	// D_f and C_f from (not read by Mono)
 	// LDS: pose table + 36 KB block rows.  Stereo: 32 poses, 9 KB -> three work-groups per CU.  Mono: two hub columns, and far up
 	// a deep tree a tile of 128 features is seen by 33-64 poses (two hub blocks per feature and level) -- with a 32-entry table
 	// most of a top level's blocks fell through to 72 global atomics each on rows the neighbouring tiles also add to (a synth-16k
@@ -454,9 +474,24 @@ k_tr_entries(int NF, int M, const int4* __restrict__ finfo, const int* __restric
 	__shared__ double sT[TRE_ROUND * 18];
 	__shared__ int sFp[TRE_TILE + 1];
 	__shared__ unsigned char sAct[TRE_TILE]; // finfo.x of the tile's features (the feature sums asked memory for it every round)
+	// Stereo: the records (R, dRA, dRB, dRG, t) of the tile's first TRE_MAPS maps, 1.2 KB.  The features lie map by map, so a tile's maps
+	// are those from its first feature's to its last feature's; a tile of 128 features rarely holds more, and a lane of a later map
+	// reads the record from global memory
+	__shared__ double sMap[NH == 1 ? TRE_MAPS * TR_REC : 1];
 	const int tid = threadIdx.x;
 	TRT_DECL;
 	const int f0 = blockIdx.x * TRE_TILE, f1 = min(f0 + TRE_TILE, NF), nft = f1 - f0;
+	int mb = 0, mn = 0; // the maps mb .. mb + mn - 1 are in sMap
+	if constexpr (NH == 1)
+	{
+		mb = finfo[f0].z;
+		mn = max(min(finfo[f1 - 1].z - mb + 1, TRE_MAPS), 0);
+		for (int i = tid; i < mn * TR_REC; i += TRE_ROUND)
+		{
+			const double* rec = tm[mb + i / TR_REC].R;
+			sMap[i] = rec[i % TR_REC];
+		}
+	}
 	for (int i = tid; i < GCAP; i += TRE_ROUND) gkeys[i] = -1;
 	for (int i = tid; i < NH * GCAP * 36; i += TRE_ROUND) gvals[i] = 0.0;
 	for (int i = tid; i <= nft; i += TRE_ROUND) sFp[i] = fptr[f0 + i];
@@ -488,6 +523,7 @@ k_tr_entries(int NF, int M, const int4* __restrict__ finfo, const int* __restric
 #endif
 			bool act = false, is_hub = false;
 			int f = 0, k = 0, sl = -1;
+			int mc = 0; // Stereo: the feature's map, counted from the first of sMap (in sMap: 0 <= mc < mn)
 			double W[18];
 			const double* fd = nullptr;
 			if (have)
@@ -520,14 +556,16 @@ k_tr_entries(int NF, int M, const int4* __restrict__ finfo, const int* __restric
 				else
 				{
 					ld<18>(W, Wold + (size_t)j * 18);
-					fd = FD + (size_t)f * (9 + TW);
+					if constexpr (NH == 1) mc = fi.z - mb; else fd = FD + (size_t)f * (9 + TW);
 					const bool hub = (k == fi.y) || (NH == 2 && k == fi.z);
 					is_hub = hub;
 					if (!hub)
 					{
 						// W' = D_k^T W D_f at its new place: after the feature's hub block(s), old order kept
 						double T1[18], Df[9], Wn[18];
-						ld<9>(Df, fd);
+						if constexpr (NH == 2) ld<9>(Df, fd);
+						else if ((unsigned)mc < (unsigned)mn) ld<9>(Df, &sMap[mc * TR_REC]);
+						else ld<9>(Df, tm[mb + mc].R);
 						if constexpr (NH == 1)
 						{
 							// D_k = [R 0; 0 DD2_k], R = D_f (Stereo): the same sums as the 6x6 product, without its zero terms
@@ -599,14 +637,27 @@ k_tr_entries(int NF, int M, const int4* __restrict__ finfo, const int* __restric
 				if (act)
 				{
 					double Cf[18], R[9];
-					if constexpr (NH == 1) ld<9>(R, fd);
 					if constexpr (NH == 1)
 					{
-						// C_f = [-R | T_f] (k_tr_feat_pre): R is in registers already, only the feature's own 9 numbers are fetched
+						// C_f = [-R | T_f]: R and T_f from the map's record -- in LDS for the tile's first maps -- and the feature's x'
+						double xn[3], Tf[9];
+						ld<3>(xn, xnew + (size_t)f * 3);
+						if ((unsigned)mc < (unsigned)mn)
+						{
+							const double* rec = &sMap[mc * TR_REC];
+							ld<9>(R, rec);
+							stereo_tf(rec, xn, Tf);
+						}
+						else
+						{
+							const double* rec = tm[mb + mc].R;
+							ld<9>(R, rec);
+							stereo_tf(rec, xn, Tf);
+						}
 #pragma unroll
 						for (int m = 0; m < 3; m++)
 #pragma unroll
-							for (int c = 0; c < 3; c++) { Cf[6 * m + c] = -R[3 * m + c]; Cf[6 * m + 3 + c] = fd[9 + 6 * m + 3 + c]; }
+							for (int c = 0; c < 3; c++) { Cf[6 * m + c] = -R[3 * m + c]; Cf[6 * m + 3 + c] = Tf[3 * m + c]; }
 					}
 					else ld<18>(Cf, fd + 9 + 18 * s);
 					// pose row of G_s: W C_s,f  [6x6] into the tile's LDS table.  The lanes of a wave that share a pose (a tile's 128
@@ -725,10 +776,11 @@ template <int NH>
 __global__ void __launch_bounds__(256, NH == 1 ? 2 : 1)
 k_tr_feat_post(int NF, int M, const TMap* __restrict__ tm, const int* __restrict__ feat_map, const int* __restrict__ fptr,
                const double* __restrict__ Vold, const double* __restrict__ Wold, const int* __restrict__ photo, const double* __restrict__ Dp,
-               const double* __restrict__ FD, const double* __restrict__ Gsum, const int* __restrict__ hubJ, const int* __restrict__ wbase,
-               const int* __restrict__ newf, int* __restrict__ srcf, double* __restrict__ Wn_,
+               const double* __restrict__ FD, const double* __restrict__ xnew, const double* __restrict__ Gsum, const int* __restrict__ hubJ,
+               const int* __restrict__ wbase, const int* __restrict__ newf, int* __restrict__ srcf, double* __restrict__ Wn_,
                int* __restrict__ nphoto, int* __restrict__ nfeature, double* __restrict__ PP)
 {
+	// FD: Mono's records (null for Stereo, which makes D_f and C_f from the map's record t and the feature's new value in xnew)
 	constexpr int TW = 18 * NH;
 	const int f = blockIdx.x * blockDim.x + threadIdx.x;
 	const bool inb = f < NF;
@@ -737,8 +789,8 @@ k_tr_feat_post(int NF, int M, const TMap* __restrict__ tm, const int* __restrict
 	double Df[9], Cf[NH][18], G[NH][18];
 	if (act)
 	{
-		const double* fd = FD + (size_t)f * (9 + TW);
-		ld<9>(Df, fd);
+		const double* fd = NH == 2 ? FD + (size_t)f * (9 + TW) : nullptr;
+		if constexpr (NH == 1) ld<9>(Df, t->R); else ld<9>(Df, fd);
 		const int base = wbase[f];
 		const int hubs[2] = { t->hub[0], NH == 2 ? t->hub[1] : -1 };
 		double hubW[NH][18];
@@ -781,7 +833,18 @@ k_tr_feat_post(int NF, int M, const TMap* __restrict__ tm, const int* __restrict
 #pragma unroll
 			for (int s = 0; s < NH; s++)
 			{
-				ld<18>(Cf[s], fd + 9 + 18 * s);
+				if constexpr (NH == 1)
+				{
+					// C_f = [-R | T_f]: R = D_f is in registers
+					double xn[3], Tf[9];
+					ld<3>(xn, xnew + (size_t)f * 3);
+					stereo_tf(t->R, xn, Tf);
+#pragma unroll
+					for (int m = 0; m < 3; m++)
+#pragma unroll
+						for (int c = 0; c < 3; c++) { Cf[s][6 * m + c] = -Df[3 * m + c]; Cf[s][6 * m + 3 + c] = Tf[3 * m + c]; }
+				}
+				else ld<18>(Cf[s], fd + 9 + 18 * s);
 				double Gs[18];
 				ld<18>(Gs, Gsum + (size_t)f * TW + 18 * s);
 				mm<3, 3, 6, false>(V, Cf[s], G[s]);
@@ -1001,8 +1064,9 @@ static void launch_stage(lsfm_context* ctx, const DevBatch& in, DevBatch& out, c
 	if (!in.NF && hook) (void)(*hook)(out, hub); // nothing to redirect, but the consumer still lays out its container
 	if (in.NF)
 	{
-		// per feature: D_f and C_s,f (written by the prologue, read per W block), sums of W^T C_s,k (entries -> epilogue)
-		double* FD = ctx->scratch.alloc<double>((size_t)in.NF * (9 + 18 * NH));
+		// per feature: Mono's D_f and C_s,f (written by the prologue, read per W block; Stereo makes them from the map's record and
+		// out.feat), sums of W^T C_s,k (entries -> epilogue)
+		double* FD = NH == 2 ? ctx->scratch.alloc<double>((size_t)in.NF * (9 + 18 * NH)) : nullptr;
 		double* Gsum = ctx->scratch.alloc<double>((size_t)in.NF * 18 * NH);
 		int* hubJ = ctx->scratch.alloc<int>((size_t)in.NF * NH);
 		int4* finfo = ctx->scratch.alloc<int4>(in.NF);
@@ -1027,22 +1091,22 @@ static void launch_stage(lsfm_context* ctx, const DevBatch& in, DevBatch& out, c
 		hipEvent_t e0 = nullptr, e1 = nullptr; // the events bracket k_tr_entries alone; read at the end of the run
 		if (ctx->stats) { e0 = ctx->pool_event(); e1 = ctx->pool_event(); LSFM_REC_T(e0, s); }
 		hipLaunchKernelGGL(k_tr_entries<NH>, dim3((in.NF + TRE_TILE - 1) / TRE_TILE), dim3(TRE_ROUND), 0, s, in.NF, M, finfo, in.fptr, in.W,
-		                   in.photo, KW, Dp, Cp, FD, rd.W, rd.photo, rd.feature, Gsum, Gpose, hubJ, out.W_alias ? 1 : 0, rd.wbase, rd.newf, rd.srcf);
+		                   in.photo, KW, Dp, Cp, FD, d_tm, out.feat, rd.W, rd.photo, rd.feature, Gsum, Gpose, hubJ, out.W_alias ? 1 : 0, rd.wbase, rd.newf, rd.srcf);
 		if (ctx->stats) LSFM_REC_T(e1, s);
 		LSFM_CHECK_HIP(hipEventRecord(ctx->ord[evG], s)); // pose rows of G complete: the U stage may start on the side stream
 		ev_entries = true;
 		hipLaunchKernelGGL(k_tr_feat_post<NH>, dim3((in.NF + 255) / 256), dim3(256), 0, s, in.NF, M, d_tm, in.feat_map, in.fptr, in.V, in.W, in.photo,
-		                   Dp, FD, Gsum, hubJ, rd.wbase, rd.newf, rd.srcf, rd.W, rd.photo, rd.feature, PP);
+		                   Dp, FD, out.feat, Gsum, hubJ, rd.wbase, rd.newf, rd.srcf, rd.W, rd.photo, rd.feature, PP);
 		if (ctx->stats)
 		{
 			ctx->defer_time(e0, e1, &ctx->stats->trf_ms);
 			ctx->stats->trf_launches++;
 			// k_tr_entries, every input and output once.  Blocks of transformed maps: W block + photo + kept-rank in, W' block
 			// + photo' + feature' out (the blocks to the hub poses are not written here); per feature of a transformed map
-			// D_f/C_f + record + run pointer in, the W^T C sums out.  Blocks of pass-through maps: photo in, photo' + feature'
-			// out, plus the W block itself both ways when it is copied (not aliased)
+			// D_f/C_f (Stereo: x', 24 bytes; the maps' records are not counted) + record + run pointer in, the W^T C sums out.  Blocks of
+			// pass-through maps: photo in, photo' + feature' out, plus the W block itself both ways when it is copied (not aliased)
 			const double nw_pass = (double)in.NW - nw_act_in;
-			ctx->stats->trf_bytes += nw_act_in * (144 + 4 + 4) + nf_act * ((9 + 18 * NH) * 8 + 16 + 4) + (nw_act_out - NH * nf_act) * (144 + 8) +
+			ctx->stats->trf_bytes += nw_act_in * (144 + 4 + 4) + nf_act * ((NH == 1 ? 24 : (9 + 18 * NH) * 8) + 16 + 4) + (nw_act_out - NH * nf_act) * (144 + 8) +
 			                         nf_act * 18 * NH * 8 + nw_pass * (4 + 8 + (out.W_alias ? 0 : 288)) + (double)(in.NF - nf_act) * (16 + 4);
 		}
 	}
