@@ -323,6 +323,41 @@ int lsfm_map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, int mono
 int lsfm_map_covariance_columns_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* poses, int k, double* pose_cols, double* feat_cols,
                                       double* joint, int* steps, double* last_corr, double* times);
 
+/* ---- whole columns of Sigma for chosen features, and an exact gate for feature pairs (NO reference counterpart) ----
+ * The question "are feature f and feature g the same point?" needs Sigma_d = Var(x_f - x_g) = Sigma_ff + Sigma_gg - Sigma_fg - Sigma_gf
+ * and d^2 = (x_f - x_g)^T Sigma_d^-1 (x_f - x_g).  Sigma_fg is off every pattern the library keeps.  Both entries solve three
+ * right-hand sides per item against the factor of the camera system S, side by side in chunks of 64 items, by
+ * lsfm_map_covariance_columns' sweeps and refinement:
+ *     B_a = -sum_(h,s) s W_h V_h^-1 over the item's signed features (f, +1)[, (g, -1)];   X_a = S^-1 B_a
+ *     Sigma_{p,a} = X_a rows;   Sigma_{h,a} = s_h V_h^-1 [h in a] - V_h^-1 sum_b W_bh^T X_a[p_b]
+ *     a pair:  Sigma_d = V_f^-1 + V_g^-1 + B_a^T X_a -- a sum of positive semi-definite terms, no cancellation of marginals
+ * map, mono, the gauge, the argument checks, the lifetime in the context's arenas, the refinement rule and the statuses
+ * (LSFM_ERR_NOT_SPD, > 0 floored pivots with nothing written and *steps = 0, LSFM_NOT_CONVERGED with the results written,
+ * LSFM_ERR_OOM) are lsfm_map_covariance_columns'; always fp64, always the sparse factorisation.
+ *
+ * lsfm_map_covariance_feature_columns: Sigma_{.,F} for the k distinct features F = feats[0..k) (indices into the map's feature order).
+ *   pose_cols[18 k m]  block Sigma_{p, feats[a]} at pose_cols + 18 (a m + p), row-major 6x3 (Mono: zero rows for the fixed scalars)
+ *   feat_cols[9 k n]   block Sigma_{g, feats[a]} at feat_cols + 9 (a n + g), row-major 3x3, the feature's own diagonal block included
+ *   joint[3k * 3k]     Sigma_FF, row-major, exactly symmetric by the rule of lsfm_map_covariance_columns' joint
+ *   last_corr[k]       per requested feature the largest |delta_c|_inf / |x_c|_inf of the last correction over its three columns
+ * LSFM_ERR_ARG for all outputs NULL, k < 1, an index out of range or given twice.
+ *
+ * lsfm_map_feature_pair_gate: for the K pairs (f, g) = (pairs[2 a], pairs[2 a + 1]), f != g; a feature may occur in several pairs.
+ *   d2[K]              d^2 of the pair, x_f - x_g from map->stVal; NaN where Sigma_d has a non-positive Cholesky pivot (the call goes on)
+ *   cov_diff[9 K]      Sigma_d, row-major 3x3, exactly symmetric (may be NULL; at least one of d2, cov_diff is not)
+ *   last_corr[K]       as above, per pair
+ * LSFM_ERR_ARG for all outputs NULL, K < 1, an index out of range or f == g. */
+int lsfm_map_covariance_feature_columns(lsfm_context* ctx, const lsfm_map* map, int mono, const int* feats, int k, double* pose_cols, double* feat_cols,
+                                        double* joint, int* steps, double* last_corr);
+int lsfm_map_feature_pair_gate(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, double* d2, double* cov_diff, int* steps,
+                               double* last_corr);
+/* measurement entries: the same, and times[4] (may be NULL) = HIP-event ms of the Schur reduction + symbolic analysis, the numeric
+ * factorisation, all sweeps and products of the solve and its refinement, the feature part / the gate kernel */
+int lsfm_map_covariance_feature_columns_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* feats, int k, double* pose_cols,
+                                              double* feat_cols, double* joint, int* steps, double* last_corr, double* times);
+int lsfm_map_feature_pair_gate_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, double* d2, double* cov_diff, int* steps,
+                                     double* last_corr, double* times);
+
 /* ---- marginalising features out of a map (NO reference counterpart: the reference keeps every feature to the end) ----
  * out = `map` with every feature f that has drop[f] != 0 (drop[n], one flag per feature in the map's order) marginalised out:
  *     U' = U - sum_{f dropped} W_f V_f^-1 W_f^T
@@ -605,6 +640,13 @@ int lsfm_save_cov_columns(const char* path, const int* stno, int m, const int* p
 /* ... and back: ids_q[cap], ids_p[cap], blocks[36 cap]; *count = lines read.  LSFM_ERR_IO for a line cut short, LSFM_ERR_ARG when
  * cap is too small */
 int lsfm_read_cov_columns(const char* path, int* ids_q, int* ids_p, double* blocks, int cap, int* count);
+/* The -gateout file (lsfm_map_feature_pair_gate): one line per pair in the order given -- "id_f id_g d2" and the six upper entries
+ * of Sigma_d row by row at %.17g.  ids[2 K] the labels of the pairs' features, d2[K] and cov_diff[9 K] as the gate writes them.
+ * Written through a temporary file that is renamed into place. */
+int lsfm_save_pair_gate(const char* path, const int* ids, int K, const double* d2, const double* cov_diff);
+/* ... and back: ids_f[cap], ids_g[cap], d2[cap], the full symmetric blocks cov_diff[9 cap]; *count = lines read.  LSFM_ERR_IO for a
+ * line cut short, LSFM_ERR_ARG when cap is too small */
+int lsfm_read_pair_gate(const char* path, int* ids_f, int* ids_g, double* d2, double* cov_diff, int cap, int* count);
 int lsfm_save_state(const char* path, const double* st, const int* stno, int n);
 /* the same state vector as raw doubles (parity tooling): int32 n, int32 0, stno[n] (+ 4 bytes of padding when n is odd),
  * st[n] float64 */

@@ -131,8 +131,14 @@ def lib():
         L.lsfm_read_covariances.argtypes = [C.c_char_p, C.c_int, ip, dp, C.c_int, ip]
         L.lsfm_map_covariance_columns.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, dp, ip, dp]
         L.lsfm_map_covariance_columns_timed.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, dp, ip, dp, dp]
+        L.lsfm_map_covariance_feature_columns.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, dp, ip, dp]
+        L.lsfm_map_covariance_feature_columns_timed.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, dp, ip, dp, dp]
+        L.lsfm_map_feature_pair_gate.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, ip, dp]
+        L.lsfm_map_feature_pair_gate_timed.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, ip, dp, dp]
         L.lsfm_save_cov_columns.argtypes = [C.c_char_p, ip, C.c_int, ip, C.c_int, dp]
         L.lsfm_read_cov_columns.argtypes = [C.c_char_p, ip, ip, dp, C.c_int, ip]
+        L.lsfm_save_pair_gate.argtypes = [C.c_char_p, ip, C.c_int, dp, dp]
+        L.lsfm_read_pair_gate.argtypes = [C.c_char_p, ip, ip, dp, dp, C.c_int, ip]
         L.lsfm_map_marginalise.argtypes = [vp, P(LsfmMap), P(C.c_ubyte), P(LsfmMap)]
         L.lsfm_map_marginalise_timed.argtypes = [vp, P(LsfmMap), P(C.c_ubyte), P(LsfmMap), dp]
         ub = P(C.c_ubyte)
@@ -166,6 +172,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_map_covariance", "lsfm_map_covariance_timed",
            "lsfm_save_covariances", "lsfm_read_covariances",
            "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns",
+           "lsfm_map_covariance_feature_columns", "lsfm_map_covariance_feature_columns_timed", "lsfm_map_feature_pair_gate", "lsfm_map_feature_pair_gate_timed", "lsfm_save_pair_gate", "lsfm_read_pair_gate",
            "lsfm_map_marginalise", "lsfm_map_marginalise_timed", "lsfm_tree_export_reduced_size", "lsfm_tree_export_reduced_dev",
            "lsfm_tree_export_reduced_dev_timed", "lsfm_map_marginalise_poses", "lsfm_map_marginalise_poses_timed", "lsfm_marg_pose_structure", "lsfm_gn_structure"]
 
@@ -645,6 +652,65 @@ class Context:
             raise LsfmError(f"lsfm_map_covariance_columns: {rc} pivot(s) floored -- the information matrix is too close to singular")
         return {"pose": pose, "feature": feat, "joint": jt, "steps": steps, "last_corr": corr, "converged": rc == 0}
 
+    def covariance_feature_columns_raw(self, d, mono, feats, poses=True, features=False, joint=False, times=False):
+        """lsfm_map_covariance_feature_columns(_timed) as it is: (rc, pose [k,m,6,3] or None, feature [k,n,3,3] or None, joint [3k,3k] or
+        None, steps, last_corr [k], times[4] or None).  rc is returned, not raised (tests of the argument checks and statuses)."""
+        h = HostMap(d)
+        m, n = h.c.m, h.c.n
+        q = _c(feats, np.int32)
+        k = len(q)
+        pose = np.zeros((k, m, 6, 3)) if poses else None
+        feat = np.zeros((k, n, 3, 3)) if features else None
+        jt = np.zeros((3 * k, 3 * k)) if joint else None
+        steps = C.c_int(0)
+        corr = np.zeros(max(k, 1))
+        t = np.zeros(4) if times else None
+        rc = lib().lsfm_map_covariance_feature_columns_timed(self._h, C.byref(h.c), int(mono), _ptr(q, C.c_int) if k else None, k,
+                                                             _ptr(pose, C.c_double) if poses else None, _ptr(feat, C.c_double) if features else None,
+                                                             _ptr(jt, C.c_double) if joint else None, C.byref(steps), _ptr(corr, C.c_double),
+                                                             _ptr(t, C.c_double) if times else None)
+        return rc, pose, feat, jt, steps.value, corr[:k], t
+
+    def covariance_feature_columns(self, d, mono, feats, poses=True, features=False, joint=False):
+        """lsfm_map_covariance_feature_columns: the whole columns of Sigma = I^-1 of map dict d for the features `feats` (indices into
+        d's feature order, distinct), three columns per feature through covariance_columns' sweeps and refinement.  No reference
+        counterpart.  Returns {"pose": (k,m,6,3) with [a, p] = Sigma_{p, feats[a]} or None, "feature": (k,n,3,3) with [a, g] =
+        Sigma_{g, feats[a]} or None, "joint": (3k,3k) exactly symmetric or None, "steps", "last_corr": (k,), "converged"}.  Errors and
+        statuses as covariance_columns."""
+        rc, pose, feat, jt, steps, corr, _ = self.covariance_feature_columns_raw(d, mono, feats, poses=poses, features=features, joint=joint)
+        self._check(rc, "lsfm_map_covariance_feature_columns")
+        if rc > 0 and steps == 0:
+            raise LsfmError(f"lsfm_map_covariance_feature_columns: {rc} pivot(s) floored -- the information matrix is too close to singular")
+        return {"pose": pose, "feature": feat, "joint": jt, "steps": steps, "last_corr": corr, "converged": rc == 0}
+
+    def feature_pair_gate_raw(self, d, mono, pairs, d2=True, cov=True, times=False):
+        """lsfm_map_feature_pair_gate(_timed) as it is: (rc, d2 [K] or None, cov_diff [K,3,3] or None, steps, last_corr [K], times[4] or
+        None) for pairs [K, 2] of feature indices.  rc is returned, not raised."""
+        h = HostMap(d)
+        pr = _c(pairs, np.int32)
+        K = len(pr) // 2
+        dd = np.zeros(max(K, 1)) if d2 else None
+        cv = np.zeros((max(K, 1), 3, 3)) if cov else None
+        steps = C.c_int(0)
+        corr = np.zeros(max(K, 1))
+        t = np.zeros(4) if times else None
+        rc = lib().lsfm_map_feature_pair_gate_timed(self._h, C.byref(h.c), int(mono), _ptr(pr, C.c_int) if K else None, K,
+                                                    _ptr(dd, C.c_double) if d2 else None, _ptr(cv, C.c_double) if cov else None, C.byref(steps),
+                                                    _ptr(corr, C.c_double), _ptr(t, C.c_double) if times else None)
+        return rc, (dd[:K] if d2 else None), (cv[:K] if cov else None), steps.value, corr[:K], t
+
+    def feature_pair_gate(self, d, mono, pairs):
+        """lsfm_map_feature_pair_gate: for every pair (f, g) of pairs [K, 2] (indices into map dict d's feature order, f != g) the exact
+        Sigma_d = Var(x_f - x_g) of Sigma = I^-1, cross-covariance included, and d^2 = (x_f - x_g)^T Sigma_d^-1 (x_f - x_g) at d's
+        estimates -- the gate of "are f and g the same point".  Three columns per pair, no cancelling sum of marginals.  No reference
+        counterpart.  Returns {"d2": (K,) (NaN where Sigma_d is not positive definite), "cov_diff": (K,3,3), "steps", "last_corr": (K,),
+        "converged"}.  Errors and statuses as covariance_columns."""
+        rc, dd, cv, steps, corr, _ = self.feature_pair_gate_raw(d, mono, pairs)
+        self._check(rc, "lsfm_map_feature_pair_gate")
+        if rc > 0 and steps == 0:
+            raise LsfmError(f"lsfm_map_feature_pair_gate: {rc} pivot(s) floored -- the information matrix is too close to singular")
+        return {"d2": dd, "cov_diff": cv, "steps": steps, "last_corr": corr, "converged": rc == 0}
+
     def marginalise(self, d, drop, times=False):
         """lsfm_map_marginalise: the map dict d with every feature f that has drop[f] != 0 marginalised out (U' = U - sum W_f V_f^-1
         W_f^T over the dropped features), in canonical form: kept features in their order with V / W / photo unchanged, one U block
@@ -1012,3 +1078,33 @@ def read_cov_columns(path, cap=None):
     if rc != 0:
         raise LsfmError(f"lsfm_read_cov_columns({path}) failed (rc={rc})")
     return iq[:cnt.value].copy(), ip_[:cnt.value].copy(), blk[:cnt.value].copy()
+
+
+def save_pair_gate(path, ids, d2, cov_diff):
+    """lsfm_save_pair_gate: the -gateout file for the pairs' feature labels ids [K, 2], d2 [K] and cov_diff [K, 3, 3] as
+    feature_pair_gate gives them."""
+    i = _c(ids, np.int32)
+    dd = _c(d2, np.float64)
+    cv = _c(cov_diff, np.float64)
+    if len(i) != 2 * len(dd) or len(cv) != 9 * len(dd):
+        raise LsfmError(f"save_pair_gate: {len(i)} ids, {len(dd)} d2 and {len(cv)} covariance entries do not belong together")
+    rc = lib().lsfm_save_pair_gate(path.encode(), _ptr(i, C.c_int), len(dd), _ptr(dd, C.c_double), _ptr(cv, C.c_double))
+    if rc != 0:
+        raise LsfmError(f"lsfm_save_pair_gate failed (rc={rc})")
+
+
+def read_pair_gate(path, cap=None):
+    """lsfm_read_pair_gate: a -gateout file as (ids [count, 2], d2 [count], cov_diff [count, 3, 3])."""
+    if cap is None:
+        with open(path) as f:
+            cap = sum(1 for line in f if line.strip())
+    jf = np.zeros(max(cap, 1), np.int32)
+    jg = np.zeros(max(cap, 1), np.int32)
+    dd = np.zeros(max(cap, 1))
+    cv = np.zeros((max(cap, 1), 3, 3))
+    cnt = C.c_int(0)
+    rc = lib().lsfm_read_pair_gate(path.encode(), _ptr(jf, C.c_int), _ptr(jg, C.c_int), _ptr(dd, C.c_double), _ptr(cv, C.c_double), int(cap), C.byref(cnt))
+    if rc != 0:
+        raise LsfmError(f"lsfm_read_pair_gate({path}) failed (rc={rc})")
+    k = cnt.value
+    return np.stack([jf[:k], jg[:k]], axis=1), dd[:k].copy(), cv[:k].copy()

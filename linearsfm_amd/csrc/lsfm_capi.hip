@@ -582,6 +582,40 @@ int lsfm_map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, int mono
 {
 	return lsfm_map_covariance_columns_timed(ctx, map, mono, poses, k, pose_cols, feat_cols, joint, steps, last_corr, nullptr);
 }
+
+// what lsfm_map_covariance_columns asks of its map; need_state: and the estimates (the gate's x_f - x_g)
+static bool feature_map_ok(const lsfm_map* map, int mono, bool need_state)
+{
+	if (!map || (mono != 0 && mono != 1) || map->m <= 0 || map->n < 0 || map->nU < 0 || map->nW < 0 || (need_state && !map->stVal)) return false;
+	return !((map->nU && (!map->U || !map->Ui || !map->Uj)) || (map->nW && (!map->W || !map->photo || !map->feature)) || (map->n && !map->V) || (mono && !map->stno));
+}
+
+int lsfm_map_covariance_feature_columns_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* feats, int k, double* pose_cols, double* feat_cols,
+                                              double* joint, int* steps, double* last_corr, double* times)
+{
+	if (!feature_map_ok(map, mono, false) || !feats || k < 1 || (!pose_cols && !feat_cols && !joint)) return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() { return map_covariance_feature_columns(ctx, map, mono == 1, feats, k, pose_cols, feat_cols, joint, steps, last_corr, times); });
+}
+
+int lsfm_map_covariance_feature_columns(lsfm_context* ctx, const lsfm_map* map, int mono, const int* feats, int k, double* pose_cols, double* feat_cols,
+                                        double* joint, int* steps, double* last_corr)
+{
+	return lsfm_map_covariance_feature_columns_timed(ctx, map, mono, feats, k, pose_cols, feat_cols, joint, steps, last_corr, nullptr);
+}
+
+int lsfm_map_feature_pair_gate_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, double* d2, double* cov_diff, int* steps,
+                                     double* last_corr, double* times)
+{
+	if (!feature_map_ok(map, mono, true) || !pairs || K < 1 || (!d2 && !cov_diff)) return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() { return map_feature_pair_gate(ctx, map, mono == 1, pairs, K, d2, cov_diff, steps, last_corr, times); });
+}
+
+int lsfm_map_feature_pair_gate(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, double* d2, double* cov_diff, int* steps,
+                               double* last_corr)
+{
+	return lsfm_map_feature_pair_gate_timed(ctx, map, mono, pairs, K, d2, cov_diff, steps, last_corr, nullptr);
+}
+
 int lsfm_inverse_v(lsfm_context* ctx, double* V, int m, int n)
 {
 	(void)m;

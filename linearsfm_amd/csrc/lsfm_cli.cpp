@@ -12,6 +12,11 @@
 // -cov <file> / -covf <file> (marginal covariances of the final map's poses / features: lsfm_map_covariance; no reference counterpart),
 // -covcols <file> -covposes <id,id,...> (whole columns of the covariance for the poses with these labels: lsfm_map_covariance_columns; one
 // line per (requested pose, pose): "id_q id_p" and the 36 entries of Sigma_{p,q}; the two flags go together),
+// -gate <pairs file> -gateout <file> (the exact gate "are these two features one point": the pairs file holds whitespace-separated feature
+// ids, two per candidate; one line per pair in input order, "id_f id_g d2" and the six upper entries of Sigma_d = Var(x_f - x_g) at %.17g:
+// lsfm_map_feature_pair_gate; written after -covcols and before -chi2 through a temporary file renamed into place; the two flags go together;
+// an unreadable file, an odd count, a pair naming one id twice or an id the final map does not have end the run non-zero with no file
+// written; with -keepf / -keepp / -relin the ids are resolved in the map the other covariance files describe; no reference counterpart),
 // -robust huber|cauchy <c> (-gn uses lsfm_gn_polish_robust: whole local maps down-weighted by an M-estimator on chi2_k / dof_k),
 // -chi2 <file> (per local map, in input order, "index dof chi2 weight" at the final state: lsfm_map_chi2; no reference counterpart),
 // -robustf huber|cauchy <c> (-gn uses lsfm_gn_polish_robust_features: single features of single local maps down-weighted by an M-estimator on
@@ -61,16 +66,17 @@ static void print_help()
 	printf("-chi2f <file>		Save chi2 Of Every Feature Of Every Local Map: map_index feature_id chi2 weight\n");
 	printf("-relin 1		Information Matrix (-info, -cov, -covf, -covcols) Of The Local Maps Linearised At The Final State\n");
 	printf("-keepf <file>		Keep Only The Features Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
+	printf("-gate <file> -gateout <file>	Gate Candidate Feature Pairs (Two Ids Each): id_f id_g d2 And The Upper Triangle Of Var(x_f - x_g)\n");
 	printf("-keepp <file>		Keep Only The Poses Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
 	printf("\n");
 }
 
 int main(int argc, char** argv)
 {
-	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf, keepp, chi2ff;
+	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf, keepp, chi2ff, gate, gateout;
 	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0, relin = 0, robustf = 0;
 	double robust_c = 0.0, robustf_c = 0.0;
-	bool has_path = false, has_num = false, has_keepf = false, has_keepp = false;
+	bool has_path = false, has_num = false, has_keepf = false, has_keepp = false, has_gate = false, has_gateout = false;
 	double tol = 0;
 	for (int i = 1; i < argc; i++)
 	{
@@ -112,6 +118,8 @@ int main(int argc, char** argv)
 		else if (name == "keepf") { keepf = next(); has_keepf = true; }
 		else if (name == "keepp") { keepp = next(); has_keepp = true; }
 		else if (name == "chi2f") chi2ff = next();
+		else if (name == "gate") { gate = next(); has_gate = true; }
+		else if (name == "gateout") { gateout = next(); has_gateout = true; }
 		else if (name == "robust" || name == "robustf")
 		{
 			const std::string k = next(), v = next();
@@ -154,6 +162,20 @@ int main(int argc, char** argv)
 	};
 	if (has_keepf && !read_ids("-keepf", "feature", keepf, keepids)) return 1;
 	if (has_keepp && !read_ids("-keepp", "pose", keepp, keeppids)) return 1;
+	// -gate: the candidate pairs by label, in input order; a file that cannot be a list of pairs ends the run before anything is computed
+	std::vector<int> gateids;
+	if (has_gate != has_gateout || (has_gate && (gate.empty() || gateout.empty()))) { fprintf(stderr, "LinearSFM: -gate <pairs file> and -gateout <file> go together\n"); return 1; }
+	if (has_gate)
+	{
+		FILE* f = fopen(gate.c_str(), "r");
+		if (!f) { fprintf(stderr, "LinearSFM: -gate: cannot read %s\n", gate.c_str()); return 1; }
+		int v = 0, got = 0;
+		while ((got = fscanf(f, "%d", &v)) == 1) gateids.push_back(v);
+		fclose(f);
+		if (got != EOF || gateids.empty() || gateids.size() % 2) { fprintf(stderr, "LinearSFM: -gate: %s is not a list of feature id pairs\n", gate.c_str()); return 1; }
+		for (size_t a = 0; a < gateids.size(); a += 2)
+			if (gateids[a] == gateids[a + 1]) { fprintf(stderr, "LinearSFM: -gate: a pair names feature %d twice\n", gateids[a]); return 1; }
+	}
 	if (robust && gn <= 0) { fprintf(stderr, "LinearSFM: -robust applies to -gn <steps>: give -gn too\n"); return 1; }
 	if (robustf && gn <= 0) { fprintf(stderr, "LinearSFM: -robustf applies to -gn <steps>: give -gn too\n"); return 1; }
 	if (robustf && robust) { fprintf(stderr, "LinearSFM: -robustf and -robust do not go together: the map and the feature estimator are not combined\n"); return 1; }
@@ -376,6 +398,15 @@ int main(int argc, char** argv)
 		for (int e : q) if (e == at) { fprintf(stderr, "LinearSFM: -covposes: pose %d is named twice\n", id); return 3; }
 		q.push_back(at);
 	}
+	// -gate: labels to features of the final map, likewise
+	std::vector<int> gatepairs;
+	for (int id : gateids)
+	{
+		int at = -1;
+		for (int f = 0; f < out.n; f++) if (out.stno[6 * out.m + 3 * f] == id) at = f; // (the last state entry of an id, as the feature file)
+		if (at < 0) { fprintf(stderr, "LinearSFM: -gate: the final map has no feature %d\n", id); return 3; }
+		gatepairs.push_back(at);
+	}
 	const int r = 6 * out.m + 3 * out.n;
 	if (!st.empty()) lsfm_save_state(st.c_str(), out.stVal, out.stno, r);
 	if (!pose.empty() && !fea.empty()) lsfm_save_poses(pose.c_str(), fea.c_str(), out.stno, out.stVal, r); // only together (Imp.cpp:2078)
@@ -412,6 +443,21 @@ int main(int argc, char** argv)
 		}
 		if (crc > 0) fprintf(stderr, "LinearSFM: covariance columns: the refinement took all %d steps and its last correction is still above the tolerance\n", steps);
 		if (lsfm_save_cov_columns(covcols.c_str(), out.stno, out.m, q.data(), (int)q.size(), pc.data())) fprintf(stderr, "LinearSFM: cannot write %s\n", covcols.c_str());
+	}
+	if (has_gate)
+	{
+		// the gate of the candidate pairs in the same map's covariance
+		const int K = (int)gatepairs.size() / 2;
+		std::vector<double> d2(K), cd((size_t)K * 9);
+		int steps = 0;
+		const int grc = lsfm_map_feature_pair_gate(ctx, &out, type, gatepairs.data(), K, d2.data(), cd.data(), &steps, nullptr);
+		if (grc < 0 || (grc > 0 && steps == 0))
+		{
+			fprintf(stderr, "LinearSFM: gate: %s\n", grc < 0 ? lsfm_last_error(ctx) : "pivots had to be floored (the information matrix is too close to singular)");
+			return 3;
+		}
+		if (grc > 0) fprintf(stderr, "LinearSFM: gate: the refinement took all %d steps and its last correction is still above the tolerance\n", steps);
+		if (lsfm_save_pair_gate(gateout.c_str(), gateids.data(), K, d2.data(), cd.data())) fprintf(stderr, "LinearSFM: cannot write %s\n", gateout.c_str());
 	}
 	if (!json.empty())
 	{

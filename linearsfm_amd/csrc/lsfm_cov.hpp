@@ -2,6 +2,7 @@
 // front end that checks a map, uploads it, reduces it to the camera system and factors that, and the device memory of one call.
 #pragma once
 #include <algorithm>
+#include <functional>
 #include <vector>
 
 #include "lsfm_chol.hpp"
@@ -50,5 +51,30 @@ int cov_front_status(lsfm_context* ctx, const CovFront& fr);
 #define CC_KC 32 /* poses per chunk of columns (lsfm_covcols.hip) */
 void cc_sweep_forward(lsfm_context* ctx, const CholDev& ch, int R, double* V);
 void cc_sweep_backward(lsfm_context* ctx, const CholDev& ch, int R, double* V);
+
+// ---- what lsfm_covcols.hip shares with lsfm_featcols.hip: a chunk of R <= 192 columns X = S^-1 B, solved side by side and refined ----
+// the device memory of a columns call, whatever its right-hand sides are: three slabs [6 M][Rmax] and the norms of a refinement step
+struct CcWork {
+	DevBuf bV, bX, bY, bN;
+	double* V = nullptr;  // elimination order, scaled: right-hand side in, solution out
+	double* Xo = nullptr; // the solved columns of the chunk in the map's numbering, [6 m][R]
+	double* Y = nullptr;  // B, then the residual [6 m][R]; free for the caller's layouts once the chunk is solved
+	unsigned long long* norm = nullptr;
+	std::vector<double> hn;
+	std::vector<double> ratio; // [R] per column the |delta|_inf / |x|_inf of the last correction
+	void alloc(int M, int Rmax);
+};
+struct CcOutcome { int steps = 0; bool undone = false; }; // undone: max_steps steps were taken and the last correction was above rel_tol
+// enqueues B, unscaled and in the map's numbering (fixed scalars zero), into B[6 M][R] on the context's stream
+using CcRhs = std::function<void(double* B)>;
+// wk.Xo = S^-1 B by the sweeps against fr's factor and lsfm_map_covariance_columns' refinement rule (lsfm.h); wk.ratio is filled
+CcOutcome cc_solve_refine(lsfm_context* ctx, const CovFront& fr, int R, CcWork& wk, const CcRhs& rhs);
+// width = the columns of one requested item, 6 (a pose) or 3 (a feature, or a pair of features):
+// out[a][6 m][width] = Xo[row][width a + c], the pose rows of the chunk in the caller's layout
+void cc_pose_out(lsfm_context* ctx, int width, int M, int R, const double* Xo, double* out);
+// out[a][nrows][3][width]: the feature rows -V^-1 W^T Xo of the features rows[nrows] (rows null: all nrows = n features); grp (width 3,
+// may be null): [2 per column group] the features (f, +1), (g, -1 or none: g < 0) the group's columns belong to, whose own rows
+// receive +- V^-1 as well
+void cc_feat(lsfm_context* ctx, int width, const CovFront& fr, int R, const int* rows, int nrows, const int* grp, const double* Xo, double* out);
 
 } // namespace lsfm

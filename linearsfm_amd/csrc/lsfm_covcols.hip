@@ -54,19 +54,17 @@ namespace {
 // a value another wave of the work-group has just added to by atomics (they are performed in L2): read it there
 __device__ __forceinline__ double ld_l2(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// The unit columns of the requested poses, column 6 a + c = scalar c of pose qpose[a] (a fixed scalar's column is zero).
-// perm == null: E_Q in the map's numbering.  perm != null: B = D^-1/2 P E_Q, written directly (block row i is pose perm[i]).
-__global__ void k_cc_unit(int M, int R, const int* __restrict__ perm, const double* __restrict__ dscale, const unsigned char* __restrict__ fixed,
-                          const int* __restrict__ qpose, double* __restrict__ out)
+// The unit columns E_Q of the requested poses in the map's numbering, column 6 a + c = scalar c of pose qpose[a] (a fixed scalar's
+// column is zero).
+__global__ void k_cc_unit(int M, int R, const unsigned char* __restrict__ fixed, const int* __restrict__ qpose, double* __restrict__ out)
 {
 	const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (idx >= (size_t)M * 6 * R) return;
 	const int r = (int)(idx % R);
 	const size_t row = idx / R;
-	const int i = (int)(row / 6), q = (int)(row % 6);
-	const int p = perm ? perm[i] : i;
-	const bool one = p == qpose[r / 6] && q == r % 6 && !(fixed && fixed[(size_t)p * 6 + q]);
-	out[idx] = one ? (dscale ? dscale[row] : 1.0) : 0.0;
+	const int p = (int)(row / 6), q = (int)(row % 6);
+	const bool one = p == qpose[r / 6] && q == r % 6 && !(fixed && fixed[row]);
+	out[idx] = one ? 1.0 : 0.0;
 }
 
 // V = D^-1/2 P Y (a residual into elimination order, scaled like the factor; fixed scalars zero)
@@ -454,15 +452,17 @@ __global__ void __launch_bounds__(CC_KC * 6) k_cc_resid(int nent, const unsigned
 }
 
 // ---- back to the caller's layouts -----------------------------------------------------------------------------------------------
-// pose_cols of the chunk: out[a][6 m rows][6] = Xo[row][6 a + c]
+// CW = the columns of one requested item: 6 (a pose, lsfm_map_covariance_columns) or 3 (a feature or a pair of features,
+// lsfm_featcols.hip).  pose_cols of the chunk: out[a][6 m rows][CW] = Xo[row][CW a + c]
+template <int CW>
 __global__ void k_cc_pose_out(int M, int R, const double* __restrict__ Xo, double* __restrict__ out)
 {
 	const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	const size_t per = (size_t)M * 36;
-	if (idx >= per * (R / 6)) return;
+	const size_t per = (size_t)M * 6 * CW;
+	if (idx >= per * (R / CW)) return;
 	const int a = (int)(idx / per);
 	const size_t rem = idx - (size_t)a * per;
-	out[idx] = Xo[(rem / 6) * R + 6 * a + rem % 6];
+	out[idx] = Xo[(rem / CW) * R + CW * a + rem % CW];
 }
 // the rows of all k requested poses (for `joint`): out[6 b + q][R] = Xo[6 qall[b] + q][R]
 __global__ void k_cc_rows(int k, int R, const int* __restrict__ qall, const double* __restrict__ Xo, double* __restrict__ out)
@@ -474,17 +474,23 @@ __global__ void k_cc_rows(int k, int R, const int* __restrict__ qall, const doub
 }
 
 // Sigma_{f,Q} = -V_f^-1 sum_a W_af^T Sigma_{p_a,Q}: one pass over W for all columns.  A work-group takes CC_FB features in turn; the
-// feature's run of W blocks and its V^-1 are uniform (broadcast), a lane sums its column.  out[a][n][3][6] (feat_cols of the chunk):
-// the 18 values of one (feature, requested pose) are contiguous and consecutive features follow each other.
-__global__ void __launch_bounds__(CC_KC * 6) k_cc_feat(int NF, const int* __restrict__ fptr, const int* __restrict__ photo, const double* __restrict__ W,
-                                                       const double* __restrict__ IV, int R, const double* __restrict__ Xo, double* __restrict__ out)
+// feature's run of W blocks and its V^-1 are uniform (broadcast), a lane sums its column.  out[a][NR][3][CW] (feat_cols of the chunk):
+// the 3 CW values of one (feature, requested item) are contiguous and consecutive features follow each other.
+// rows (may be null: every feature, NR = the map's n): the NR features whose rows are wanted, row i of the output is feature rows[i].
+// grp (CW == 3 only, may be null): the signed features (f, +1), (g, -1; g < 0: none) of column group a at grp[2 a], grp[2 a + 1] --
+// the columns are then those of I^-1 (e_f - e_g), and the rows of f and g themselves receive the diagonal term +- V^-1.
+template <int CW>
+__global__ void __launch_bounds__(CC_KC * 6) k_cc_feat(int NR, const int* __restrict__ rows, const int* __restrict__ grp, const int* __restrict__ fptr,
+                                                       const int* __restrict__ photo, const double* __restrict__ W, const double* __restrict__ IV, int R,
+                                                       const double* __restrict__ Xo, double* __restrict__ out)
 {
 	const int r = threadIdx.x;
 	if (r >= R) return;
-	const int f0 = blockIdx.x * CC_FB, f1 = min(f0 + CC_FB, NF);
-	const int a = r / 6, c = r - 6 * a;
-	for (int f = f0; f < f1; f++)
+	const int i0 = blockIdx.x * CC_FB, i1 = min(i0 + CC_FB, NR);
+	const int a = r / CW, c = r - CW * a;
+	for (int fi = i0; fi < i1; fi++)
 	{
+		const int f = rows ? rows[fi] : fi;
 		const int w0 = fptr[f], w1 = fptr[f + 1];
 		double t[3] = { 0, 0, 0 };
 		for (int w = w0; w < w1; w++)
@@ -500,9 +506,15 @@ __global__ void __launch_bounds__(CC_KC * 6) k_cc_feat(int NF, const int* __rest
 			}
 		}
 		const double* iv = IV + (size_t)f * 9;
-		double* o = out + ((size_t)a * NF + f) * 18 + c;
+		double* o = out + ((size_t)a * NR + fi) * (3 * CW) + c;
+		double sgn = 0.0;
+		if (CW == 3 && grp) sgn = f == grp[2 * a] ? 1.0 : (f == grp[2 * a + 1] ? -1.0 : 0.0);
 #pragma unroll
-		for (int i = 0; i < 3; i++) o[i * 6] = -(iv[i * 3] * t[0] + iv[i * 3 + 1] * t[1] + iv[i * 3 + 2] * t[2]);
+		for (int i = 0; i < 3; i++)
+		{
+			const double v = -(iv[i * 3] * t[0] + iv[i * 3 + 1] * t[1] + iv[i * 3 + 2] * t[2]);
+			o[i * CW] = (CW == 3 && sgn != 0.0) ? sgn * iv[i * 3 + c] + v : v;
+		}
 	}
 }
 
@@ -563,6 +575,88 @@ void cc_sweep_backward(lsfm_context* ctx, const CholDev& ch, int R, double* V)
 	if (ch.ntask0) hipLaunchKernelGGL(k_cc_bwd<false>, dim3(ch.ntask0), dim3(rp, 1), 0, s, ch.task_ptr, ch.task_cols, (const int*)nullptr, false, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
 }
 
+void CcWork::alloc(int M, int Rmax)
+{
+	const size_t slab = (size_t)M * 6 * Rmax;
+	V = bV.get<double>(slab);
+	Xo = bX.get<double>(slab);
+	Y = bY.get<double>(slab);
+	norm = bN.get<unsigned long long>(2 * (size_t)Rmax);
+	hn.assign(2 * (size_t)Rmax, 0.0);
+}
+
+// Xo = S^-1 B for the R columns of a chunk: the unrefined solve against the factor, then refinement in fp64 against S itself --
+// always one step, then while the corrections are above the tolerance and still halving.  rhs(dst) enqueues B, unscaled and in the
+// map's numbering, into dst[6 M][R]: once for the first solve and once per step as the start of Y = B - S Xo.
+CcOutcome cc_solve_refine(lsfm_context* ctx, const CovFront& fr, int R, CcWork& wk, const CcRhs& rhs)
+{
+	const SolveIO& io = fr.io;
+	const SchurSystem& sy = fr.sy;
+	const CholDev& ch = fr.ch;
+	hipStream_t s = ctx->stream;
+	const int M = ch.M;
+	const unsigned rp = (unsigned)((R + LSFM_WAVE - 1) / LSFM_WAVE * LSFM_WAVE);
+	const size_t cells = (size_t)M * 6 * R;
+	double *V = wk.V, *Xo = wk.Xo, *Y = wk.Y;
+	// (L L^T)^-1 applied to V in place
+	auto sweep = [&]() {
+		cc_sweep_forward(ctx, ch, R, V);
+		cc_sweep_backward(ctx, ch, R, V);
+	};
+	const double tol = ctx->pcg.rel_tol;
+	const int max_steps = std::max(1, ctx->pcg.max_steps);
+	// ---- the unrefined solve ----
+	rhs(Y);
+	hipLaunchKernelGGL(k_cc_perm_in, dim3(blocks_of(cells, 256)), dim3(256), 0, s, M, R, ch.perm, ch.dscale, io.d_fixed, Y, V);
+	sweep();
+	hipLaunchKernelGGL(k_cc_perm_out, dim3(blocks_of((size_t)M * 6, CC_ROWS)), dim3(rp), 0, s, M, R, ch.pinv, ch.dscale, io.d_fixed, V, Xo);
+	// ---- refinement ----
+	CcOutcome oc;
+	double prev = 0.0;
+	std::vector<double>& hn = wk.hn;
+	std::vector<double>& ratio = wk.ratio;
+	ratio.assign(R, 0.0);
+	for (;;)
+	{
+		rhs(Y);
+		hipLaunchKernelGGL(k_cc_resid, dim3(blocks_of((size_t)2 * sy.nnzb, CC_EPW)), dim3(rp), 0, s, 2 * sy.nnzb, sy.gent, sy.goth, sy.S, io.d_fixed, R, Xo, Y);
+		hipLaunchKernelGGL(k_cc_perm_in, dim3(blocks_of(cells, 256)), dim3(256), 0, s, M, R, ch.perm, ch.dscale, io.d_fixed, Y, V);
+		sweep();
+		dev_zero(ctx, wk.norm, 2 * (size_t)R * sizeof(unsigned long long));
+		hipLaunchKernelGGL(k_cc_perm_add, dim3(blocks_of((size_t)M * 6, CC_ROWS)), dim3(rp), 0, s, M, R, ch.pinv, ch.dscale, io.d_fixed, V, Xo, wk.norm);
+		LSFM_CHECK_HIP(hipGetLastError());
+		d2h(ctx, hn.data(), wk.norm, 2 * (size_t)R * sizeof(double)); // (the bit patterns of non-negative doubles)
+		oc.steps++;
+		double worst = 0.0;
+		for (int r = 0; r < R; r++)
+		{
+			ratio[r] = hn[R + r] > 0.0 ? hn[r] / hn[R + r] : (hn[r] > 0.0 ? INFINITY : 0.0);
+			if (!(ratio[r] <= worst)) worst = ratio[r]; // (a NaN counts as the worst)
+		}
+		if (worst <= tol) break;
+		if (oc.steps >= max_steps) { oc.undone = true; break; }
+		if (oc.steps > 1 && !(worst <= 0.5 * prev)) break; // as far as fp64 refinement against this factor goes
+		prev = worst;
+	}
+	return oc;
+}
+
+void cc_pose_out(lsfm_context* ctx, int width, int M, int R, const double* Xo, double* out)
+{
+	const dim3 grid(blocks_of((size_t)M * 6 * R, 256)), block(256);
+	if (width == 6) hipLaunchKernelGGL(k_cc_pose_out<6>, grid, block, 0, ctx->stream, M, R, Xo, out);
+	else hipLaunchKernelGGL(k_cc_pose_out<3>, grid, block, 0, ctx->stream, M, R, Xo, out);
+}
+
+void cc_feat(lsfm_context* ctx, int width, const CovFront& fr, int R, const int* rows, int nrows, const int* grp, const double* Xo, double* out)
+{
+	if (nrows <= 0) return;
+	const SolveIO& io = fr.io;
+	const dim3 grid(blocks_of(nrows, CC_FB)), block((unsigned)((R + LSFM_WAVE - 1) / LSFM_WAVE * LSFM_WAVE));
+	if (width == 6) hipLaunchKernelGGL(k_cc_feat<6>, grid, block, 0, ctx->stream, nrows, rows, (const int*)nullptr, io.fptr, io.photo, io.W, fr.sy.IV, R, Xo, out);
+	else hipLaunchKernelGGL(k_cc_feat<3>, grid, block, 0, ctx->stream, nrows, rows, grp, io.fptr, io.photo, io.W, fr.sy.IV, R, Xo, out);
+}
+
 int map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* poses, int k, double* pose_cols, double* feat_cols, double* joint,
                            int* steps_out, double* last_corr, double* times)
 {
@@ -603,72 +697,38 @@ int map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, co
 		if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b)
 			throw Error{ LSFM_ERR_OOM, "out of device memory: the columns of " + std::to_string(kc) + " poses need " + std::to_string(need) + " bytes, " + std::to_string(free_b) + " are free" };
 	}
-	DevBuf bV, bX, bY, bF, bN, bJ, bQ;
-	double* V = bV.get<double>(slab);   // elimination order, scaled: right-hand side in, solution out
-	double* Xo = bX.get<double>(slab);  // Sigma_{.,Q} of the chunk, [6 m][R]
-	double* Y = bY.get<double>(slab);   // residual [6 m][R]; at the end the chunk of pose_cols
+	CcWork wk;
+	wk.alloc(M, Rmax);
+	double *Xo = wk.Xo, *Y = wk.Y; // Sigma_{.,Q} of the chunk, [6 m][R] | at the end the chunk of pose_cols
+	DevBuf bF, bJ, bQ;
 	double* F = want_feat ? bF.get<double>((size_t)n * 18 * kc) : nullptr;
-	unsigned long long* norm = bN.get<unsigned long long>(2 * (size_t)Rmax);
 	double* Jd = joint ? bJ.get<double>((size_t)k * 6 * Rmax) : nullptr;
 	int* dq = bQ.get<int>(k);
 	h2d(ctx, dq, poses, (size_t)k * sizeof(int));
 	hipEvent_t ev[3] = { ctx->pool_event(), ctx->pool_event(), ctx->pool_event() };
-	// (L L^T)^-1 applied to V in place
-	auto sweep = [&](int R) {
-		cc_sweep_forward(ctx, ch, R, V);
-		cc_sweep_backward(ctx, ch, R, V);
-	};
-	const double tol = ctx->pcg.rel_tol;
-	const int max_steps = std::max(1, ctx->pcg.max_steps);
-	std::vector<double> hn(2 * (size_t)Rmax), hj(joint ? (size_t)k * 6 * Rmax : 0);
+	std::vector<double> hj(joint ? (size_t)k * 6 * Rmax : 0);
 	int most_steps = 0;
 	bool undone = false;
 	double t_solve = 0.0, t_feat = 0.0;
 	for (int c0 = 0; c0 < k; c0 += kc)
 	{
 		const int kcur = std::min(kc, k - c0), R = 6 * kcur;
-		const unsigned rp = (unsigned)((R + LSFM_WAVE - 1) / LSFM_WAVE * LSFM_WAVE);
 		const size_t cells = (size_t)M * 6 * R;
 		const int* qpose = dq + c0;
 		LSFM_CHECK_HIP(hipEventRecord(ev[0], s));
-		// ---- the unrefined solve ----
-		hipLaunchKernelGGL(k_cc_unit, dim3(blocks_of(cells, 256)), dim3(256), 0, s, M, R, ch.perm, ch.dscale, io.d_fixed, qpose, V);
-		sweep(R);
-		hipLaunchKernelGGL(k_cc_perm_out, dim3(blocks_of((size_t)M * 6, CC_ROWS)), dim3(rp), 0, s, M, R, ch.pinv, ch.dscale, io.d_fixed, V, Xo);
-		// ---- refinement: always one step, then while the corrections are above the tolerance and still halving ----
-		int steps = 0;
-		double prev = 0.0;
-		std::vector<double> ratio(R, 0.0);
-		for (;;)
-		{
-			hipLaunchKernelGGL(k_cc_unit, dim3(blocks_of(cells, 256)), dim3(256), 0, s, M, R, (const int*)nullptr, (const double*)nullptr, io.d_fixed, qpose, Y);
-			hipLaunchKernelGGL(k_cc_resid, dim3(blocks_of((size_t)2 * sy.nnzb, CC_EPW)), dim3(rp), 0, s, 2 * sy.nnzb, sy.gent, sy.goth, sy.S, io.d_fixed, R, Xo, Y);
-			hipLaunchKernelGGL(k_cc_perm_in, dim3(blocks_of(cells, 256)), dim3(256), 0, s, M, R, ch.perm, ch.dscale, io.d_fixed, Y, V);
-			sweep(R);
-			dev_zero(ctx, norm, 2 * (size_t)R * sizeof(unsigned long long));
-			hipLaunchKernelGGL(k_cc_perm_add, dim3(blocks_of((size_t)M * 6, CC_ROWS)), dim3(rp), 0, s, M, R, ch.pinv, ch.dscale, io.d_fixed, V, Xo, norm);
-			LSFM_CHECK_HIP(hipGetLastError());
-			d2h(ctx, hn.data(), norm, 2 * (size_t)R * sizeof(double)); // (the bit patterns of non-negative doubles)
-			steps++;
-			double worst = 0.0;
-			for (int r = 0; r < R; r++)
-			{
-				ratio[r] = hn[R + r] > 0.0 ? hn[r] / hn[R + r] : (hn[r] > 0.0 ? INFINITY : 0.0);
-				if (!(ratio[r] <= worst)) worst = ratio[r]; // (a NaN counts as the worst)
-			}
-			if (worst <= tol) break;
-			if (steps >= max_steps) { undone = true; break; }
-			if (steps > 1 && !(worst <= 0.5 * prev)) break; // as far as fp64 refinement against this factor goes
-			prev = worst;
-		}
-		most_steps = std::max(most_steps, steps);
+		const CcOutcome oc = cc_solve_refine(ctx, fr, R, wk, [&](double* B) {
+			hipLaunchKernelGGL(k_cc_unit, dim3(blocks_of(cells, 256)), dim3(256), 0, s, M, R, io.d_fixed, qpose, B);
+		});
+		const std::vector<double>& ratio = wk.ratio;
+		most_steps = std::max(most_steps, oc.steps);
+		undone = undone || oc.undone;
 		if (last_corr)
 			for (int a = 0; a < kcur; a++) last_corr[c0 + a] = *std::max_element(ratio.begin() + 6 * a, ratio.begin() + 6 * a + 6);
 		// ---- the caller's layouts ----
-		if (pose_cols) hipLaunchKernelGGL(k_cc_pose_out, dim3(blocks_of(cells, 256)), dim3(256), 0, s, M, R, Xo, Y);
+		if (pose_cols) cc_pose_out(ctx, 6, M, R, Xo, Y);
 		if (joint) hipLaunchKernelGGL(k_cc_rows, dim3(blocks_of((size_t)k * 6 * R, 256)), dim3(256), 0, s, k, R, dq, Xo, Jd);
 		LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
-		if (want_feat) hipLaunchKernelGGL(k_cc_feat, dim3(blocks_of(n, CC_FB)), dim3(rp), 0, s, n, io.fptr, io.photo, io.W, sy.IV, R, Xo, F);
+		if (want_feat) cc_feat(ctx, 6, fr, R, nullptr, n, nullptr, Xo, F);
 		LSFM_CHECK_HIP(hipEventRecord(ev[2], s));
 		LSFM_CHECK_HIP(hipGetLastError());
 		if (pose_cols) d2h(ctx, pose_cols + (size_t)c0 * m * 36, Y, cells * sizeof(double));

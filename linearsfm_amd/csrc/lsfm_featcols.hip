@@ -1,0 +1,307 @@
+// Columns of Sigma = I^-1 for chosen FEATURES and an exact gate for feature pairs (C ABI: lsfm_map_covariance_feature_columns,
+// lsfm_map_feature_pair_gate).  No reference counterpart.
+//
+// One formulation serves both.  A column group a holds up to two signed features (f, +1)[, (g, -1)] and three columns, those of
+// I^-1 (e_f - e_g):
+//     B_a = - sum_(h,s) s W_h V_h^-1                 6 m x 3, non-zero on the rows of the poses that see f or g (fixed scalars zero)
+//     X_a = S^-1 B_a                                 the pose rows: lsfm_covcols.hip's sweeps and refinement (cc_solve_refine)
+//     Sigma_{h,a} = s_h V_h^-1 [h in a] - V_h^-1 sum_b W_bh^T X_a[p_b]          the feature rows (k_cc_feat<3>)
+//     a pair:  Sigma_d = Var(x_f - x_g) = V_f^-1 + V_g^-1 + B_a^T X_a           a sum of positive semi-definite terms
+// The pair's block Sigma_fg is off every pattern the library keeps; through the columns of the poses of f and g it would take
+// 6 |P(f) u P(g)| columns and end in a cancelling sum of large marginals.  Here a pair costs 3 columns, nothing cancels, and the
+// refinement's relative criterion acts on the scale of the difference.
+//
+// A chunk is 64 groups = 192 columns: the slabs and launch shapes of a full chunk of lsfm_map_covariance_columns.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "lsfm_chol.hpp"
+#include "lsfm_cov.hpp"
+#include "lsfm_device.hpp"
+#include "lsfm_internal.hpp"
+#include "lsfm_solve.hpp"
+
+namespace lsfm {
+
+namespace {
+
+#define FC_KC (2 * CC_KC) /* column groups per chunk: 3 FC_KC = 6 CC_KC columns */
+#define FC_SLOTS 7        /* W blocks a wave of k_fc_gate works on side by side: 9 lanes each */
+
+// B of the chunk into the ZEROED slab B[6 M][R], R = 3 groups: one work-group per column group, lane (q, c) of 18 owns the scalar
+// row q of every pose and column c of the group, walks the W blocks of f, then of g, and adds in that order.  A group owns its
+// columns, so the only entries met twice -- a pose that sees both features, a pose stored twice in one feature's run -- are met
+// by the same lane one after the other: no atomics.
+__global__ void __launch_bounds__(LSFM_WAVE) k_fc_rhs(int R, const int* __restrict__ grp, const int* __restrict__ fptr, const int* __restrict__ photo,
+                                                      const double* __restrict__ W, const double* __restrict__ IV, const unsigned char* __restrict__ fixed,
+                                                      double* __restrict__ B)
+{
+	const int a = blockIdx.x, lane = threadIdx.x;
+	if (lane >= 18) return;
+	const int q = lane / 3, c = lane - 3 * q;
+	for (int side = 0; side < 2; side++)
+	{
+		const int h = grp[2 * a + side];
+		if (h < 0) continue;
+		const double sgn = side ? 1.0 : -1.0; // B = -s W V^-1
+		const double* iv = IV + (size_t)h * 9;
+		for (int w = fptr[h]; w < fptr[h + 1]; w++)
+		{
+			const size_t row = (size_t)photo[w] * 6 + q;
+			if (fixed && fixed[row]) continue;
+			const double* wb = W + (size_t)w * 18 + q * 3;
+			const double v = wb[0] * iv[c] + wb[1] * iv[3 + c] + wb[2] * iv[6 + c];
+			B[row * R + 3 * a + c] += sgn * v;
+		}
+	}
+}
+
+// The gate of one pair per wave: T_h = sum_w W_w^T X_a[p_w] over the runs of f and g (lane (slot, l, j): every FC_SLOTS-th block,
+// the slots summed in a fixed order), Sigma_d = V_f^-1 + V_g^-1 - V_f^-T T_f + V_g^-T T_g, symmetrised, a 3 x 3 Cholesky, d^2 =
+// |L^-1 dx|^2.  A non-positive pivot: d^2 = NaN for this pair.
+__global__ void __launch_bounds__(LSFM_WAVE) k_fc_gate(int R, const int* __restrict__ grp, const int* __restrict__ fptr, const int* __restrict__ photo,
+                                                       const double* __restrict__ W, const double* __restrict__ IV, const double* __restrict__ Xo,
+                                                       const double* __restrict__ dx, double* __restrict__ d2, double* __restrict__ cov)
+{
+	__shared__ double part[2][FC_SLOTS * 9];
+	__shared__ double T[2][9];
+	const int a = blockIdx.x, lane = threadIdx.x;
+	const int slot = lane / 9, lj = lane - 9 * slot, l = lj / 3, j = lj - 3 * l;
+	const int f = grp[2 * a], g = grp[2 * a + 1];
+	if (slot < FC_SLOTS)
+		for (int side = 0; side < 2; side++)
+		{
+			const int h = side ? g : f;
+			double t = 0.0;
+			for (int w = fptr[h] + slot; w < fptr[h + 1]; w += FC_SLOTS)
+			{
+				const double* wb = W + (size_t)w * 18 + l;
+				const double* src = Xo + (size_t)photo[w] * 6 * R + 3 * a + j;
+#pragma unroll
+				for (int q = 0; q < 6; q++) t = fma(wb[q * 3], src[(size_t)q * R], t);
+			}
+			part[side][lane] = t;
+		}
+	__syncthreads();
+	if (lane < 18)
+	{
+		const int side = lane / 9, e = lane - 9 * side;
+		double t = 0.0;
+		for (int sl = 0; sl < FC_SLOTS; sl++) t += part[side][sl * 9 + e];
+		T[side][e] = t;
+	}
+	__syncthreads();
+	if (lane != 0) return;
+	const double *ivf = IV + (size_t)f * 9, *ivg = IV + (size_t)g * 9;
+	double C[9];
+	for (int i = 0; i < 3; i++)
+		for (int jj = 0; jj < 3; jj++)
+		{
+			double bx = 0.0; // (B^T X)_ij
+			for (int ll = 0; ll < 3; ll++) bx += ivg[ll * 3 + i] * T[1][ll * 3 + jj] - ivf[ll * 3 + i] * T[0][ll * 3 + jj];
+			C[i * 3 + jj] = ivf[i * 3 + jj] + ivg[i * 3 + jj] + bx;
+		}
+	for (int i = 0; i < 3; i++)
+		for (int jj = i + 1; jj < 3; jj++) C[i * 3 + jj] = C[jj * 3 + i] = 0.5 * (C[i * 3 + jj] + C[jj * 3 + i]);
+	if (cov)
+		for (int e = 0; e < 9; e++) cov[(size_t)a * 9 + e] = C[e];
+	if (!d2) return;
+	// C = L L^T;  y = L^-1 dx
+	const double* x = dx + (size_t)a * 3;
+	double res = NAN;
+	const double p0 = C[0];
+	if (p0 > 0.0)
+	{
+		const double l00 = sqrt(p0), l10 = C[3] / l00, l20 = C[6] / l00;
+		const double p1 = C[4] - l10 * l10;
+		if (p1 > 0.0)
+		{
+			const double l11 = sqrt(p1), l21 = (C[7] - l20 * l10) / l11;
+			const double p2 = C[8] - l20 * l20 - l21 * l21;
+			if (p2 > 0.0)
+			{
+				const double l22 = sqrt(p2);
+				const double y0 = x[0] / l00, y1 = (x[1] - l10 * y0) / l11, y2 = (x[2] - l20 * y0 - l21 * y1) / l22;
+				res = y0 * y0 + y1 * y1 + y2 * y2;
+			}
+		}
+	}
+	d2[a] = res;
+}
+
+// What the two entries share: the factor of the camera system, then per chunk of FC_KC groups the right-hand sides, the refined solve
+// and the caller's part -- prep() allocates the call's own outputs on the device once the factor stands, emit(c0, kcur, R, dgrp, fr, wk)
+// enqueues the caller's kernels behind the solve of a chunk, fetch(c0, kcur, R, wk) downloads what they wrote.
+template <class Prep, class Emit, class Fetch>
+int fc_run(lsfm_context* ctx, const lsfm_map* map, bool mono, const std::vector<int>& grp, size_t extra_doubles, int* steps_out, double* last_corr,
+           double* times, Prep&& prep, Emit&& emit, Fetch&& fetch)
+{
+	const int k = (int)grp.size() / 2;
+	if (steps_out) *steps_out = 0;
+	CovFront fr;
+	{
+		// the residual needs the row-sorted list of S's blocks whatever product the context's CG is set to (lsfm_set_spmv_variant)
+		struct Keep { lsfm_context* c; int v; ~Keep() { c->pcg.spmv_variant = v; } } keep{ ctx, ctx->pcg.spmv_variant };
+		ctx->pcg.spmv_variant = 2;
+		cov_front(ctx, map, mono, fr);
+	}
+	const SolveIO& io = fr.io;
+	const SchurSystem& sy = fr.sy;
+	hipStream_t s = ctx->stream;
+	LSFM_CHECK_HIP(hipGetLastError());
+	const int floored = cov_front_status(ctx, fr);
+	if (floored > 0) return floored; // the factor is of a perturbed S: nothing is written
+	if (!sy.gent) LSFM_FAIL(LSFM_ERR_INTERNAL, "the camera system has no row-sorted block list");
+	const int M = fr.ch.M;
+	const int kc = std::min(k, FC_KC), Rmax = 3 * kc;
+	{
+		const size_t need = (3 * (size_t)M * 6 * Rmax + extra_doubles) * sizeof(double);
+		size_t free_b = 0, total_b = 0;
+		if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b)
+			throw Error{ LSFM_ERR_OOM, "out of device memory: the columns of " + std::to_string(kc) + " features or pairs need " + std::to_string(need) + " bytes, " + std::to_string(free_b) + " are free" };
+	}
+	CcWork wk;
+	wk.alloc(M, Rmax);
+	DevBuf bG;
+	int* dgrp = bG.get<int>(2 * (size_t)k);
+	h2d(ctx, dgrp, grp.data(), 2 * (size_t)k * sizeof(int));
+	prep();
+	hipEvent_t ev[3] = { ctx->pool_event(), ctx->pool_event(), ctx->pool_event() };
+	int most_steps = 0;
+	bool undone = false;
+	double t_solve = 0.0, t_emit = 0.0;
+	for (int c0 = 0; c0 < k; c0 += kc)
+	{
+		const int kcur = std::min(kc, k - c0), R = 3 * kcur;
+		const size_t cells = (size_t)M * 6 * R;
+		const int* g = dgrp + 2 * (size_t)c0;
+		LSFM_CHECK_HIP(hipEventRecord(ev[0], s));
+		const CcOutcome oc = cc_solve_refine(ctx, fr, R, wk, [&](double* B) {
+			dev_zero(ctx, B, cells * sizeof(double));
+			hipLaunchKernelGGL(k_fc_rhs, dim3(kcur), dim3(LSFM_WAVE), 0, s, R, g, io.fptr, io.photo, io.W, sy.IV, io.d_fixed, B);
+		});
+		most_steps = std::max(most_steps, oc.steps);
+		undone = undone || oc.undone;
+		if (last_corr)
+			for (int a = 0; a < kcur; a++) last_corr[c0 + a] = *std::max_element(wk.ratio.begin() + 3 * a, wk.ratio.begin() + 3 * a + 3);
+		LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
+		emit(c0, kcur, R, g, fr, wk);
+		LSFM_CHECK_HIP(hipEventRecord(ev[2], s));
+		LSFM_CHECK_HIP(hipGetLastError());
+		fetch(c0, kcur, R, wk);
+		LSFM_CHECK_HIP(hipStreamSynchronize(s));
+		float ms = 0.0f;
+		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); t_solve += ms;
+		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[1], ev[2])); t_emit += ms;
+	}
+	if (steps_out) *steps_out = most_steps;
+	if (times)
+	{
+		float ms = 0.0f;
+		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, fr.ev[0], fr.ev[1])); times[0] = ms;
+		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, fr.ev[1], fr.ev[2])); times[1] = ms;
+		times[2] = t_solve; times[3] = t_emit;
+	}
+	return undone ? LSFM_NOT_CONVERGED : LSFM_OK;
+}
+
+} // namespace
+
+
+int map_covariance_feature_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* feats, int k, double* pose_cols, double* feat_cols,
+                                   double* joint, int* steps_out, double* last_corr, double* times)
+{
+	const int m = map->m, n = map->n;
+	std::vector<int> grp(2 * (size_t)k);
+	{
+		std::vector<char> seen(std::max(n, 1), 0);
+		for (int a = 0; a < k; a++)
+		{
+			if (feats[a] < 0 || feats[a] >= n) LSFM_FAIL(LSFM_ERR_ARG, "requested feature " + std::to_string(feats[a]) + " is not one of the map's " + std::to_string(n));
+			if (seen[feats[a]]) LSFM_FAIL(LSFM_ERR_ARG, "feature " + std::to_string(feats[a]) + " is requested twice");
+			seen[feats[a]] = 1;
+			grp[2 * a] = feats[a];
+			grp[2 * a + 1] = -1;
+		}
+	}
+	const int kc = std::min(k, FC_KC);
+	const size_t nF = feat_cols ? (size_t)n * 9 * kc : 0, nJ = joint ? (size_t)kc * k * 9 : 0;
+	DevBuf bF, bJ, bQ;
+	double *F = nullptr, *Jd = nullptr;
+	int* dq = nullptr;
+	std::vector<double> hj(nJ);
+	int steps = 0; // (> 0: the results were written)
+	if (steps_out) *steps_out = 0;
+	const int rc = fc_run(ctx, map, mono, grp, nF + nJ, &steps, last_corr, times,
+		[&]() {
+			if (feat_cols) F = bF.get<double>(nF);
+			if (!joint) return;
+			Jd = bJ.get<double>(nJ);
+			dq = bQ.get<int>(k);
+			h2d(ctx, dq, feats, (size_t)k * sizeof(int));
+		},
+		[&](int c0, int kcur, int R, const int* g, const CovFront& fr, CcWork& wk) {
+			if (pose_cols) cc_pose_out(ctx, 3, m, R, wk.Xo, wk.Y);
+			if (feat_cols) cc_feat(ctx, 3, fr, R, nullptr, n, g, wk.Xo, F);
+			if (joint) cc_feat(ctx, 3, fr, R, dq, k, g, wk.Xo, Jd); // the rows of the k requested features alone
+		},
+		[&](int c0, int kcur, int R, CcWork& wk) {
+			if (pose_cols) d2h(ctx, pose_cols + (size_t)c0 * m * 18, wk.Y, (size_t)m * 6 * R * sizeof(double));
+			if (feat_cols) d2h(ctx, feat_cols + (size_t)c0 * n * 9, F, (size_t)kcur * n * 9 * sizeof(double));
+			if (!joint) return;
+			d2h(ctx, hj.data(), Jd, (size_t)kcur * k * 9 * sizeof(double));
+			for (int a = 0; a < kcur; a++)
+				for (int b = 0; b < k; b++)
+					for (int i = 0; i < 3; i++) memcpy(&joint[((size_t)3 * b + i) * 3 * k + 3 * (size_t)(c0 + a)], &hj[((size_t)a * k + b) * 9 + 3 * i], 3 * sizeof(double));
+		});
+	if (steps_out) *steps_out = steps;
+	if (joint && steps > 0)
+	{
+		// exactly symmetric by lsfm_map_covariance_columns' rule: block (a, b), a < b, from column b and mirrored; a diagonal block (X + X^T) / 2
+		const size_t n3 = (size_t)k * 3;
+		for (size_t i = 0; i < n3; i++)
+			for (size_t j = i; j < n3; j++)
+			{
+				const double v = i / 3 == j / 3 ? 0.5 * (joint[i * n3 + j] + joint[j * n3 + i]) : joint[i * n3 + j];
+				joint[i * n3 + j] = joint[j * n3 + i] = v;
+			}
+	}
+	return rc;
+}
+
+int map_feature_pair_gate(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* pairs, int K, double* d2, double* cov_diff, int* steps_out,
+                          double* last_corr, double* times)
+{
+	const int m = map->m, n = map->n;
+	std::vector<int> grp(pairs, pairs + 2 * (size_t)K);
+	std::vector<double> dx(3 * (size_t)K);
+	for (int a = 0; a < K; a++)
+	{
+		const int f = grp[2 * a], g = grp[2 * a + 1];
+		if (f < 0 || f >= n || g < 0 || g >= n) LSFM_FAIL(LSFM_ERR_ARG, "pair " + std::to_string(a) + " (" + std::to_string(f) + ", " + std::to_string(g) + ") names a feature that is not one of the map's " + std::to_string(n));
+		if (f == g) LSFM_FAIL(LSFM_ERR_ARG, "pair " + std::to_string(a) + " names feature " + std::to_string(f) + " twice");
+		for (int i = 0; i < 3; i++) dx[3 * (size_t)a + i] = map->stVal[(size_t)6 * m + 3 * (size_t)f + i] - map->stVal[(size_t)6 * m + 3 * (size_t)g + i];
+	}
+	const int kc = std::min(K, FC_KC);
+	DevBuf bX, bD, bC;
+	double *ddx = nullptr, *dd2 = nullptr, *dcov = nullptr;
+	const int rc = fc_run(ctx, map, mono, grp, 13 * (size_t)K, steps_out, last_corr, times,
+		[&]() {
+			ddx = bX.get<double>(3 * (size_t)K);
+			h2d(ctx, ddx, dx.data(), 3 * (size_t)K * sizeof(double));
+			if (d2) dd2 = bD.get<double>(kc);
+			if (cov_diff) dcov = bC.get<double>(9 * (size_t)kc);
+		},
+		[&](int c0, int kcur, int R, const int* g, const CovFront& fr, CcWork& wk) {
+			hipLaunchKernelGGL(k_fc_gate, dim3(kcur), dim3(LSFM_WAVE), 0, ctx->stream, R, g, fr.io.fptr, fr.io.photo, fr.io.W, fr.sy.IV, wk.Xo, ddx + 3 * (size_t)c0, dd2, dcov);
+		},
+		[&](int c0, int kcur, int R, CcWork&) {
+			if (d2) d2h(ctx, d2 + c0, dd2, (size_t)kcur * sizeof(double));
+			if (cov_diff) d2h(ctx, cov_diff + 9 * (size_t)c0, dcov, 9 * (size_t)kcur * sizeof(double));
+		});
+	return rc;
+}
+
+} // namespace lsfm

@@ -564,6 +564,13 @@ int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* po
 // lsfm_map_covariance_columns).  times (may be null): [4] ms of reduce + analyse, factorisation, all sweeps and products, the feature part
 int map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* poses, int k, double* pose_cols, double* feat_cols, double* joint,
                            int* steps, double* last_corr, double* times);
+// whole columns of Sigma for the features feats[k] and the gate d^2 = dx^T Var(x_f - x_g)^-1 dx of the K feature pairs pairs[2 K], three
+// columns per feature or pair through the same sweeps and refinement (lsfm_featcols.hip; C ABI: lsfm_map_covariance_feature_columns,
+// lsfm_map_feature_pair_gate).  times (may be null): [4] ms of reduce + analyse, factorisation, all sweeps and products, the feature part / the gate kernel
+int map_covariance_feature_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* feats, int k, double* pose_cols, double* feat_cols,
+                                   double* joint, int* steps, double* last_corr, double* times);
+int map_feature_pair_gate(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* pairs, int K, double* d2, double* cov_diff, int* steps,
+                          double* last_corr, double* times);
 // the two feature-side pieces of the solve on their own (lsfm_solve.hip; C ABI: lsfm_inverse_v / lsfm_solve_features); host pointers,
 // arguments checked by the caller
 int inverse_v(lsfm_context* ctx, double* V, int n);

@@ -596,4 +596,53 @@ int lsfm_read_cov_columns(const char* path, int* ids_q, int* ids_p, double* bloc
 	return rc;
 }
 
+// the -gateout file (lsfm_map_feature_pair_gate): one line per pair in the order given, "id_f id_g d2" and the six upper entries of
+// Sigma_d row by row at %.17g
+int lsfm_save_pair_gate(const char* path, const int* ids, int K, const double* d2, const double* cov_diff)
+{
+	if (!path || !ids || K < 1 || !d2 || !cov_diff) return LSFM_ERR_ARG;
+	const std::string tmp = std::string(path) + ".tmp";
+	FILE* fp = fopen(tmp.c_str(), "w");
+	if (!fp) return LSFM_ERR_IO;
+	for (int a = 0; a < K; a++)
+	{
+		const double* b = cov_diff + (size_t)a * 9;
+		fprintf(fp, "%d %d %.17g", ids[2 * a], ids[2 * a + 1], d2[a]);
+		for (int r = 0; r < 3; r++)
+			for (int c = r; c < 3; c++) fprintf(fp, " %.17g", b[r * 3 + c]);
+		fprintf(fp, "\n");
+	}
+	const bool bad = ferror(fp) != 0;
+	if (fclose(fp) != 0 || bad || rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); return LSFM_ERR_IO; }
+	return LSFM_OK;
+}
+
+// a -gateout file back: ids_f, ids_g, d2 [cap], full symmetric blocks cov_diff[9 cap]; *count = lines read
+int lsfm_read_pair_gate(const char* path, int* ids_f, int* ids_g, double* d2, double* cov_diff, int cap, int* count)
+{
+	if (!path || cap < 0 || !count || (cap && (!ids_f || !ids_g || !d2 || !cov_diff))) return LSFM_ERR_ARG;
+	FILE* fp = fopen(path, "r");
+	if (!fp) return LSFM_ERR_IO;
+	int cnt = 0, f = 0, g = 0, rc = LSFM_OK;
+	while (rc == LSFM_OK && fscanf(fp, "%d", &f) == 1)
+	{
+		double v = 0.0;
+		if (fscanf(fp, "%d", &g) != 1 || fscanf(fp, "%lf", &v) != 1) { rc = LSFM_ERR_IO; break; }
+		if (cnt >= cap) { rc = LSFM_ERR_ARG; break; }
+		double* b = cov_diff + (size_t)cnt * 9;
+		for (int r = 0; r < 3 && rc == LSFM_OK; r++)
+			for (int c = r; c < 3; c++)
+			{
+				double e;
+				if (fscanf(fp, "%lf", &e) != 1) { rc = LSFM_ERR_IO; break; }
+				b[r * 3 + c] = b[c * 3 + r] = e;
+			}
+		if (rc == LSFM_OK) { ids_f[cnt] = f; ids_g[cnt] = g; d2[cnt] = v; cnt++; }
+	}
+	if (rc == LSFM_OK && !feof(fp)) rc = LSFM_ERR_IO;
+	fclose(fp);
+	*count = cnt;
+	return rc;
+}
+
 } // extern "C"
