@@ -358,6 +358,48 @@ int lsfm_map_covariance_feature_columns_timed(lsfm_context* ctx, const lsfm_map*
 int lsfm_map_feature_pair_gate_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, double* d2, double* cov_diff, int* steps,
                                      double* last_corr, double* times);
 
+/* ---- merging feature pairs of a map, with their joint compatibility D^2 (NO reference counterpart) ----
+ * out = `map` with x_f = x_g declared for the K pairs (f, g) = (pairs[2 a], pairs[2 a + 1]), indices into the map's feature order, f != g.
+ * The pairs partition the features into classes, the connected components of the pair graph (a pair given twice, in either order,
+ * or a pair that closes a cycle is fine); a class's representative is its member with the smallest index; output feature c is the
+ * c-th representative in ascending order (an untouched feature is a class of one).  With T the expansion x = T y the constrained
+ * Gaussian is exact and again a map, because V is block diagonal:
+ *     U' = U;   V'_c = sum_{h in c} V_h, members ascending;   W'_{p,c} = sum_{h in c} sum_{blocks (p,h)} W, one block per (pose, class),
+ *     ascending pose, its sources added by (member, position in the input);   y^ = argmin_y (x^ - T y)^T I (x^ - T y)
+ * (Mono: the gauge scalars of lsfm_solve_mono held at x^'s values).  y^ = y0 + I'^-1 T^T I (x^ - T y0), y0 = x^ with every class at its
+ * representative's estimate, through the camera system of the MERGED map: one right-hand side for lsfm_map_covariance_columns' sweeps
+ * and refinement, then a back-substitution.  The same solve gives the joint compatibility of all pairs
+ *     D^2 = sum_g r_g^T V_g r_g - eta^T delta        (r_g = x^_g - x^_rep over the merged-away features, eta = T^T I r, delta = y^ - y0)
+ * = d^T (A Sigma A^T)^-1 d with *dof = 3 (n - n') degrees of freedom; for one pair it is lsfm_map_feature_pair_gate's d^2.
+ * out (library-allocated, lsfm_map_release): m, the poses' labels, pose_origin, Ref, FRef, ScaP, Fix, Sign, FScaP, FFix and U / Ui / Uj are
+ * the input's, bit for bit; stVal = y^ (a gauge scalar: bit for bit the input's); an output feature has its representative's label;
+ * a class of one keeps V and its W run bit for bit (repeated (pose, feature) blocks stay, as in lsfm_map_marginalise), a larger class has
+ * one W block per pose.  rep[n] (may be NULL): the output feature of every input feature.  d2, dof, steps, last_corr[1] may be NULL.
+ * Bit-reproducible from call to call: the structure, U' V' W', the right-hand side, and D^2 GIVEN the solved delta.  NOT: delta itself
+ * (the sweeps add with atomics), and so y^ and the last bits of D^2; the refinement leaves the difference at rounding level.
+ * Always fp64 and always the sparse factorisation (lsfm_set_precision / lsfm_set_small_solve do not apply).  The merged map goes
+ * through the host between the merging passes and the factorisation in this version.
+ * Returns exactly as lsfm_map_covariance_columns: LSFM_OK; LSFM_NOT_CONVERGED (results written); LSFM_ERR_NOT_SPD, and > 0 = floored
+ * pivots (out untouched, *steps = 0); LSFM_ERR_OOM; LSFM_ERR_ARG for K < 1, an index out of range, f == g, out == NULL, and whatever
+ * lsfm_map_covariance refuses.  Lifetime: works in the context's arenas like lsfm_map_covariance. */
+int lsfm_map_merge_features(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, lsfm_map* out, double* d2, int* dof, int* rep,
+                            int* steps, double* last_corr);
+/* measurement entry: the same, and times[5] (may be NULL) = HIP-event ms of upload + W' / V' passes + the merged map's download | its
+ * upload + reduction + analysis + factorisation | right-hand side + sweeps + refinement | back-substitution + D^2 | download */
+int lsfm_map_merge_features_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, lsfm_map* out, double* d2, int* dof,
+                                  int* rep, int* steps, double* last_corr, double* times);
+/* Test entry, NO device needed: the structure of lsfm_map_merge_features from the map's index arrays and the pairs alone (no value is
+ * read).  Outputs, each optional:
+ *   rep[n]          the output feature of every input feature
+ *   photo, feature[cap_w], FBlock[n']   the output's W index arrays
+ *   sptr[cap_w + 1], sidx[cap_w]        per output W block its sources (input W blocks) as a CSR, by (member feature, position in the input)
+ *   info[8]         { n', nW', classes of more than one, features removed, output blocks with more than one source, 0, 0, 0 }
+ *   why[why_cap]    what is wrong, when LSFM_ERR_ARG is returned
+ * Call it once with info alone for the sizes (cap_w >= nW' for photo / feature / sptr, >= the input's nW for sidx).  LSFM_ERR_ARG for
+ * K < 1, an index out of range, f == g, W not sorted by feature, a cap that is too small. */
+int lsfm_merge_structure(const lsfm_map* map, const int* pairs, int K, int* rep, int* photo, int* feature, int* FBlock, int* sptr, int* sidx, int cap_w,
+                         int* info, char* why, int why_cap);
+
 /* ---- marginalising features out of a map (NO reference counterpart: the reference keeps every feature to the end) ----
  * out = `map` with every feature f that has drop[f] != 0 (drop[n], one flag per feature in the map's order) marginalised out:
  *     U' = U - sum_{f dropped} W_f V_f^-1 W_f^T
@@ -647,6 +689,13 @@ int lsfm_save_pair_gate(const char* path, const int* ids, int K, const double* d
 /* ... and back: ids_f[cap], ids_g[cap], d2[cap], the full symmetric blocks cov_diff[9 cap]; *count = lines read.  LSFM_ERR_IO for a
  * line cut short, LSFM_ERR_ARG when cap is too small */
 int lsfm_read_pair_gate(const char* path, int* ids_f, int* ids_g, double* d2, double* cov_diff, int cap, int* count);
+/* The -mergeout file (lsfm_map_merge_features): line 1 "K features_removed dof D2" (D2 at %.17g), then one line per pair in the order
+ * given, "id_f id_g id_kept" = ids[3 a .. 3 a + 3): the labels of the pair's features and of the feature both became.  Written through
+ * a temporary file that is renamed into place. */
+int lsfm_save_merge_report(const char* path, int K, int removed, int dof, double d2, const int* ids);
+/* ... and back: the head and ids[3 cap].  LSFM_ERR_IO for a line cut short and for a file with fewer or more lines than its head
+ * says, LSFM_ERR_ARG when cap < K */
+int lsfm_read_merge_report(const char* path, int* K, int* removed, int* dof, double* d2, int* ids, int cap);
 int lsfm_save_state(const char* path, const double* st, const int* stno, int n);
 /* the same state vector as raw doubles (parity tooling): int32 n, int32 0, stno[n] (+ 4 bytes of padding when n is odd),
  * st[n] float64 */

@@ -135,6 +135,11 @@ def lib():
         L.lsfm_map_covariance_feature_columns_timed.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, dp, ip, dp, dp]
         L.lsfm_map_feature_pair_gate.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, ip, dp]
         L.lsfm_map_feature_pair_gate_timed.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, ip, dp, dp]
+        L.lsfm_map_merge_features.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, P(LsfmMap), dp, ip, ip, ip, dp]
+        L.lsfm_map_merge_features_timed.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, P(LsfmMap), dp, ip, ip, ip, dp, dp]
+        L.lsfm_merge_structure.argtypes = [P(LsfmMap), ip, C.c_int, ip, ip, ip, ip, ip, ip, C.c_int, ip, C.c_char_p, C.c_int]
+        L.lsfm_save_merge_report.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, ip]
+        L.lsfm_read_merge_report.argtypes = [C.c_char_p, ip, ip, ip, dp, ip, C.c_int]
         L.lsfm_save_cov_columns.argtypes = [C.c_char_p, ip, C.c_int, ip, C.c_int, dp]
         L.lsfm_read_cov_columns.argtypes = [C.c_char_p, ip, ip, dp, C.c_int, ip]
         L.lsfm_save_pair_gate.argtypes = [C.c_char_p, ip, C.c_int, dp, dp]
@@ -173,6 +178,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_save_covariances", "lsfm_read_covariances",
            "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns",
            "lsfm_map_covariance_feature_columns", "lsfm_map_covariance_feature_columns_timed", "lsfm_map_feature_pair_gate", "lsfm_map_feature_pair_gate_timed", "lsfm_save_pair_gate", "lsfm_read_pair_gate",
+           "lsfm_map_merge_features", "lsfm_map_merge_features_timed", "lsfm_merge_structure", "lsfm_save_merge_report", "lsfm_read_merge_report",
            "lsfm_map_marginalise", "lsfm_map_marginalise_timed", "lsfm_tree_export_reduced_size", "lsfm_tree_export_reduced_dev",
            "lsfm_tree_export_reduced_dev_timed", "lsfm_map_marginalise_poses", "lsfm_map_marginalise_poses_timed", "lsfm_marg_pose_structure", "lsfm_gn_structure"]
 
@@ -711,6 +717,34 @@ class Context:
             raise LsfmError(f"lsfm_map_feature_pair_gate: {rc} pivot(s) floored -- the information matrix is too close to singular")
         return {"d2": dd, "cov_diff": cv, "steps": steps, "last_corr": corr, "converged": rc == 0}
 
+    def merge_features_raw(self, d, mono, pairs, times=False):
+        """lsfm_map_merge_features(_timed) as it is: (rc, map dict or None, d2, dof, rep [n], steps, last_corr, times[5] or None) for pairs
+        [K, 2] of feature indices.  rc is returned, not raised; the map is None where the call wrote none."""
+        h = HostMap(d)
+        pr = _c(pairs, np.int32)
+        K = len(pr) // 2
+        out = LsfmMap()
+        d2, corr = C.c_double(0.0), C.c_double(0.0)
+        dof, steps = C.c_int(0), C.c_int(0)
+        rep = np.zeros(max(h.c.n, 1), np.int32)
+        t = np.zeros(5) if times else None
+        rc = lib().lsfm_map_merge_features_timed(self._h, C.byref(h.c), int(mono), _ptr(pr, C.c_int) if K else None, K, C.byref(out), C.byref(d2),
+                                                 C.byref(dof), _ptr(rep, C.c_int), C.byref(steps), C.byref(corr), _ptr(t, C.c_double) if times else None)
+        g = map_to_dict(out) if bool(out.stno) else None
+        return rc, g, d2.value, dof.value, rep[:h.c.n], steps.value, corr.value, t
+
+    def merge_features(self, d, mono, pairs):
+        """lsfm_map_merge_features: map dict d with x_f = x_g declared for every pair (f, g) of pairs [K, 2] (indices into d's feature
+        order) -- the exact constrained Gaussian, again a map (U unchanged, V' and W' the classes' sums, the state re-estimated through the
+        merged map's camera system) -- and the joint compatibility D^2 of all pairs with dof = 3 (features removed).  No reference
+        counterpart.  Returns dict(map, d2, dof, rep [n] (output feature of every input feature), steps, last_corr, converged).  Errors
+        and statuses as covariance_columns."""
+        rc, g, d2, dof, rep, steps, corr, _ = self.merge_features_raw(d, mono, pairs)
+        self._check(rc, "lsfm_map_merge_features")
+        if rc > 0 and steps == 0:
+            raise LsfmError(f"lsfm_map_merge_features: {rc} pivot(s) floored -- the merged information matrix is too close to singular")
+        return dict(map=g, d2=d2, dof=dof, rep=rep, steps=steps, last_corr=corr, converged=rc == 0)
+
     def marginalise(self, d, drop, times=False):
         """lsfm_map_marginalise: the map dict d with every feature f that has drop[f] != 0 marginalised out (U' = U - sum W_f V_f^-1
         W_f^T over the dropped features), in canonical form: kept features in their order with V / W / photo unchanged, one U block
@@ -940,6 +974,34 @@ def marg_pose_structure(d, mono, keep_pose, drop_feat=None):
                 Ui=Ui[:int(info[3])].copy(), Uj=Uj[:int(info[3])].copy(), info=info)
 
 
+MERGE_STRUCTURE_INFO = ("n", "nW", "classes", "removed", "summed_blocks")
+
+
+def merge_structure(d, pairs):
+    """Host-only (lsfm_merge_structure): what lsfm_map_merge_features makes of the index arrays of map dict d and the pairs [K, 2], without
+    a device.  Returns dict(rep [n], photo / feature [nW'], FBlock [n'], sptr [nW' + 1] / sidx [nW] (the sources of every output W block),
+    info (by MERGE_STRUCTURE_INFO)).  Raises LsfmError with the library's reason."""
+    h = HostMap(d)
+    pr = _c(pairs, np.int32)
+    K = len(pr) // 2
+    info = np.zeros(8, np.int32)
+    why = C.create_string_buffer(512)
+    p = lambda a: _ptr(a, C.c_int)
+    head = (C.byref(h.c), p(pr) if K else None, K)
+    rc = lib().lsfm_merge_structure(*head, None, None, None, None, None, None, 0, p(info), why, len(why))
+    if rc:
+        raise LsfmError(f"lsfm_merge_structure failed (rc={rc}): {why.value.decode()}")
+    v = dict(zip(MERGE_STRUCTURE_INFO, (int(i) for i in info)))
+    n, nW = h.c.n, h.c.nW
+    cap = max(nW, 1)
+    rep, photo, feature, FBlock = np.zeros(max(n, 1), np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(max(n, 1), np.int32)
+    sptr, sidx = np.zeros(cap + 1, np.int32), np.zeros(cap, np.int32)
+    rc = lib().lsfm_merge_structure(*head, p(rep), p(photo), p(feature), p(FBlock), p(sptr), p(sidx), cap, p(info), why, len(why))
+    if rc:
+        raise LsfmError(f"lsfm_merge_structure failed (rc={rc}): {why.value.decode()}")
+    return dict(rep=rep[:n], photo=photo[:v["nW"]], feature=feature[:v["nW"]], FBlock=FBlock[:v["n"]], sptr=sptr[:v["nW"] + 1], sidx=sidx[:nW], info=v)
+
+
 GN_STRUCTURE_INFO = ("M", "NFG", "P", "FI", "NUJ", "NWJ", "nU", "nW", "slots", "contributors")
 
 
@@ -1108,3 +1170,27 @@ def read_pair_gate(path, cap=None):
         raise LsfmError(f"lsfm_read_pair_gate({path}) failed (rc={rc})")
     k = cnt.value
     return np.stack([jf[:k], jg[:k]], axis=1), dd[:k].copy(), cv[:k].copy()
+
+
+def save_merge_report(path, ids, removed, dof, d2):
+    """lsfm_save_merge_report: the -mergeout file for ids [K, 3] (the labels of each pair's two features and of the feature both became),
+    the number of features removed, dof and D^2 as merge_features gives them."""
+    i = _c(ids, np.int32)
+    if len(i) % 3 or not len(i):
+        raise LsfmError(f"save_merge_report: {len(i)} ids are not K > 0 triples")
+    rc = lib().lsfm_save_merge_report(path.encode(), len(i) // 3, int(removed), int(dof), float(d2), _ptr(i, C.c_int))
+    if rc != 0:
+        raise LsfmError(f"lsfm_save_merge_report failed (rc={rc})")
+
+
+def read_merge_report(path, cap=None):
+    """lsfm_read_merge_report: a -mergeout file as dict(K, removed, dof, d2, ids [K, 3])."""
+    if cap is None:
+        with open(path) as f:
+            cap = sum(1 for line in f if line.strip())
+    ids = np.zeros((max(cap, 1), 3), np.int32)
+    K, rem, dof, d2 = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0)
+    rc = lib().lsfm_read_merge_report(path.encode(), C.byref(K), C.byref(rem), C.byref(dof), C.byref(d2), _ptr(ids, C.c_int), int(cap))
+    if rc != 0:
+        raise LsfmError(f"lsfm_read_merge_report({path}) failed (rc={rc})")
+    return dict(K=K.value, removed=rem.value, dof=dof.value, d2=d2.value, ids=ids[:K.value].copy())

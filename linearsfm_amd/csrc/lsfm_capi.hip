@@ -616,6 +616,20 @@ int lsfm_map_feature_pair_gate(lsfm_context* ctx, const lsfm_map* map, int mono,
 	return lsfm_map_feature_pair_gate_timed(ctx, map, mono, pairs, K, d2, cov_diff, steps, last_corr, nullptr);
 }
 
+int lsfm_map_merge_features_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, lsfm_map* out, double* d2, int* dof, int* rep,
+                                  int* steps, double* last_corr, double* times)
+{
+	if (steps) *steps = 0;
+	if (!feature_map_ok(map, mono, true) || !map->stno || !pairs || K < 1 || !out) return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() { return map_merge_features(ctx, map, mono == 1, pairs, K, out, d2, dof, rep, steps, last_corr, times); });
+}
+
+int lsfm_map_merge_features(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, lsfm_map* out, double* d2, int* dof, int* rep,
+                            int* steps, double* last_corr)
+{
+	return lsfm_map_merge_features_timed(ctx, map, mono, pairs, K, out, d2, dof, rep, steps, last_corr, nullptr);
+}
+
 int lsfm_inverse_v(lsfm_context* ctx, double* V, int m, int n)
 {
 	(void)m;

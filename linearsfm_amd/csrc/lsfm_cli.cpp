@@ -17,6 +17,12 @@
 // lsfm_map_feature_pair_gate; written after -covcols and before -chi2 through a temporary file renamed into place; the two flags go together;
 // an unreadable file, an odd count, a pair naming one id twice or an id the final map does not have end the run non-zero with no file
 // written; with -keepf / -keepp / -relin the ids are resolved in the map the other covariance files describe; no reference counterpart),
+// -merge <pairs file> [-mergeout <file>] (declare the feature pairs of the file -- the -gate format, the same refusals -- one point each:
+// after -gn / -relin and BEFORE -keepf / -keepp and before any file is written the final map is replaced by the merged map of
+// lsfm_map_merge_features, so -st, -p, -f, -full, -fullbin, -info, -cov, -covf, -covcols and -gate describe the merged map, and a -gate id that
+// was merged away is "no feature"; -mergeout: line 1 "K features_removed dof D2", then "id_f id_g id_kept" per pair at %.17g, written after
+// -gateout through a temporary file renamed into place; not together with -chi2 / -chi2f -- the local maps still hold the merged-away ids --:
+// that ends the run non-zero before any file is written; a numerical failure ends the run as -gate's does; no reference counterpart),
 // -robust huber|cauchy <c> (-gn uses lsfm_gn_polish_robust: whole local maps down-weighted by an M-estimator on chi2_k / dof_k),
 // -chi2 <file> (per local map, in input order, "index dof chi2 weight" at the final state: lsfm_map_chi2; no reference counterpart),
 // -robustf huber|cauchy <c> (-gn uses lsfm_gn_polish_robust_features: single features of single local maps down-weighted by an M-estimator on
@@ -67,16 +73,17 @@ static void print_help()
 	printf("-relin 1		Information Matrix (-info, -cov, -covf, -covcols) Of The Local Maps Linearised At The Final State\n");
 	printf("-keepf <file>		Keep Only The Features Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
 	printf("-gate <file> -gateout <file>	Gate Candidate Feature Pairs (Two Ids Each): id_f id_g d2 And The Upper Triangle Of Var(x_f - x_g)\n");
+	printf("-merge <file> [-mergeout <file>]	Merge Feature Pairs (Two Ids Each) Into One Point Each; Report: K removed dof D2, Then id_f id_g id_kept\n");
 	printf("-keepp <file>		Keep Only The Poses Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
 	printf("\n");
 }
 
 int main(int argc, char** argv)
 {
-	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf, keepp, chi2ff, gate, gateout;
+	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf, keepp, chi2ff, gate, gateout, merge, mergeout;
 	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0, relin = 0, robustf = 0;
 	double robust_c = 0.0, robustf_c = 0.0;
-	bool has_path = false, has_num = false, has_keepf = false, has_keepp = false, has_gate = false, has_gateout = false;
+	bool has_path = false, has_num = false, has_keepf = false, has_keepp = false, has_gate = false, has_gateout = false, has_merge = false, has_mergeout = false;
 	double tol = 0;
 	for (int i = 1; i < argc; i++)
 	{
@@ -120,6 +127,8 @@ int main(int argc, char** argv)
 		else if (name == "chi2f") chi2ff = next();
 		else if (name == "gate") { gate = next(); has_gate = true; }
 		else if (name == "gateout") { gateout = next(); has_gateout = true; }
+		else if (name == "merge") { merge = next(); has_merge = true; }
+		else if (name == "mergeout") { mergeout = next(); has_mergeout = true; }
 		else if (name == "robust" || name == "robustf")
 		{
 			const std::string k = next(), v = next();
@@ -163,19 +172,28 @@ int main(int argc, char** argv)
 	if (has_keepf && !read_ids("-keepf", "feature", keepf, keepids)) return 1;
 	if (has_keepp && !read_ids("-keepp", "pose", keepp, keeppids)) return 1;
 	// -gate: the candidate pairs by label, in input order; a file that cannot be a list of pairs ends the run before anything is computed
-	std::vector<int> gateids;
-	if (has_gate != has_gateout || (has_gate && (gate.empty() || gateout.empty()))) { fprintf(stderr, "LinearSFM: -gate <pairs file> and -gateout <file> go together\n"); return 1; }
-	if (has_gate)
-	{
-		FILE* f = fopen(gate.c_str(), "r");
-		if (!f) { fprintf(stderr, "LinearSFM: -gate: cannot read %s\n", gate.c_str()); return 1; }
+	std::vector<int> gateids, mergeids;
+	auto read_pairs = [](const char* flag, const std::string& fn, std::vector<int>& ids) {
+		FILE* f = fopen(fn.c_str(), "r");
+		if (!f) { fprintf(stderr, "LinearSFM: %s: cannot read %s\n", flag, fn.c_str()); return false; }
 		int v = 0, got = 0;
-		while ((got = fscanf(f, "%d", &v)) == 1) gateids.push_back(v);
+		while ((got = fscanf(f, "%d", &v)) == 1) ids.push_back(v);
 		fclose(f);
-		if (got != EOF || gateids.empty() || gateids.size() % 2) { fprintf(stderr, "LinearSFM: -gate: %s is not a list of feature id pairs\n", gate.c_str()); return 1; }
-		for (size_t a = 0; a < gateids.size(); a += 2)
-			if (gateids[a] == gateids[a + 1]) { fprintf(stderr, "LinearSFM: -gate: a pair names feature %d twice\n", gateids[a]); return 1; }
+		if (got != EOF || ids.empty() || ids.size() % 2) { fprintf(stderr, "LinearSFM: %s: %s is not a list of feature id pairs\n", flag, fn.c_str()); return false; }
+		for (size_t a = 0; a < ids.size(); a += 2)
+			if (ids[a] == ids[a + 1]) { fprintf(stderr, "LinearSFM: %s: a pair names feature %d twice\n", flag, ids[a]); return false; }
+		return true;
+	};
+	if (has_gate != has_gateout || (has_gate && (gate.empty() || gateout.empty()))) { fprintf(stderr, "LinearSFM: -gate <pairs file> and -gateout <file> go together\n"); return 1; }
+	if (has_gate && !read_pairs("-gate", gate, gateids)) return 1;
+	// -merge: the pairs to merge, the same format and refusals
+	if ((has_mergeout && !has_merge) || (has_merge && merge.empty()) || (has_mergeout && mergeout.empty())) { fprintf(stderr, "LinearSFM: -mergeout <file> needs -merge <pairs file>\n"); return 1; }
+	if (has_merge && (!chi2f.empty() || !chi2ff.empty()))
+	{
+		fprintf(stderr, "LinearSFM: -merge does not go together with -chi2 / -chi2f: the local maps still hold the merged-away ids\n");
+		return 1;
 	}
+	if (has_merge && !read_pairs("-merge", merge, mergeids)) return 1;
 	if (robust && gn <= 0) { fprintf(stderr, "LinearSFM: -robust applies to -gn <steps>: give -gn too\n"); return 1; }
 	if (robustf && gn <= 0) { fprintf(stderr, "LinearSFM: -robustf applies to -gn <steps>: give -gn too\n"); return 1; }
 	if (robustf && robust) { fprintf(stderr, "LinearSFM: -robustf and -robust do not go together: the map and the feature estimator are not combined\n"); return 1; }
@@ -344,6 +362,37 @@ int main(int argc, char** argv)
 		lsfm_map_release(&out);
 		out = H;
 	}
+	std::vector<int> mergekept; // -merge: per pair the label of the feature both became
+	int merge_removed = 0, merge_dof = 0;
+	double merge_d2 = 0.0;
+	if (has_merge)
+	{
+		// the final map with the pairs of -merge declared one point each (lsfm_map_merge_features): what follows describes the merged map
+		std::vector<int> mp;
+		for (int id : mergeids)
+		{
+			int at = -1;
+			for (int f = 0; f < out.n; f++) if (out.stno[6 * out.m + 3 * f] == id) at = f; // (the last state entry of an id, as the feature file)
+			if (at < 0) { fprintf(stderr, "LinearSFM: -merge: the final map has no feature %d\n", id); return 3; }
+			mp.push_back(at);
+		}
+		const int K = (int)mp.size() / 2;
+		std::vector<int> rep(out.n > 0 ? out.n : 1);
+		lsfm_map M;
+		int steps = 0;
+		const int mrc = lsfm_map_merge_features(ctx, &out, type, mp.data(), K, &M, &merge_d2, &merge_dof, rep.data(), &steps, nullptr);
+		if (mrc < 0 || (mrc > 0 && steps == 0))
+		{
+			fprintf(stderr, "LinearSFM: merge: %s\n", mrc < 0 ? lsfm_last_error(ctx) : "pivots had to be floored (the merged information matrix is too close to singular)");
+			return 3;
+		}
+		if (mrc > 0) fprintf(stderr, "LinearSFM: merge: the refinement took all %d steps and its last correction is still above the tolerance\n", steps);
+		merge_removed = out.n - M.n;
+		for (int a = 0; a < K; a++) mergekept.push_back(M.stno[6 * M.m + 3 * rep[mp[2 * a]]]);
+		if (!quiet) printf("Merged %d Feature Pairs: %d Features Removed, D2 %.9e With %d Degrees Of Freedom\n\n", K, merge_removed, merge_d2, merge_dof);
+		lsfm_map_release(&out);
+		out = M;
+	}
 	std::vector<int> chi2dof; // -keepf with -chi2: filled before the reduction
 	if (has_keepf || has_keepp)
 	{
@@ -458,6 +507,13 @@ int main(int argc, char** argv)
 		}
 		if (grc > 0) fprintf(stderr, "LinearSFM: gate: the refinement took all %d steps and its last correction is still above the tolerance\n", steps);
 		if (lsfm_save_pair_gate(gateout.c_str(), gateids.data(), K, d2.data(), cd.data())) fprintf(stderr, "LinearSFM: cannot write %s\n", gateout.c_str());
+	}
+	if (has_mergeout)
+	{
+		const int K = (int)mergeids.size() / 2;
+		std::vector<int> ids;
+		for (int a = 0; a < K; a++) { ids.push_back(mergeids[2 * a]); ids.push_back(mergeids[2 * a + 1]); ids.push_back(mergekept[a]); }
+		if (lsfm_save_merge_report(mergeout.c_str(), K, merge_removed, merge_dof, merge_d2, ids.data())) fprintf(stderr, "LinearSFM: cannot write %s\n", mergeout.c_str());
 	}
 	if (!json.empty())
 	{

@@ -5,34 +5,12 @@
 #include <algorithm>
 #include <chrono>
 
+#include "lsfm_coalesce.hpp"
 #include "lsfm_device.hpp"
 #include "lsfm_gn.hpp"
 
 namespace lsfm {
 
-// ---- the joint system as a map like any other (lsfm_gn_linearise) ----
-// UJ / WJ hold the solver's working form: entries with equal coordinates are repeated and add up.  Output block o is the sum of its
-// sources sidx[sptr[o] .. sptr[o + 1]) in that order (map order: the structure pass sorts stably).  One lane per output block,
-// consecutive lanes on consecutive output blocks; the sources of neighbouring output blocks lie in the same feature's run of WJ.  The
-// sum is held in registers and stored once.  No atomics: given UJ / WJ the result is the same bits every time.  HBM-bound: NWJ * 144 B
-// in, nW' * 144 B out (U: 288 B a block), no products.
-template <int N>
-__global__ void __launch_bounds__(256)
-k_gn_coalesce(int no, const int* __restrict__ sptr, const int* __restrict__ sidx, const double* __restrict__ src, double* __restrict__ dst)
-{
-	const int o = blockIdx.x * blockDim.x + threadIdx.x;
-	if (o >= no) return;
-	double acc[N], v[N];
-	const int q0 = sptr[o], q1 = sptr[o + 1];
-	ld<N>(acc, src + (size_t)sidx[q0] * N);
-	for (int q = q0 + 1; q < q1; q++)
-	{
-		ld<N>(v, src + (size_t)sidx[q] * N);
-#pragma unroll
-		for (int i = 0; i < N; i++) acc[i] += v[i];
-	}
-	st<N>(dst + (size_t)o * N, acc);
-}
 
 // largest |v| over the scalars that are not fixed, as the bits of a non-negative double (they order like the numbers)
 __global__ void k_gn_maxabs(size_t n, const double* __restrict__ v, const unsigned char* __restrict__ fixed, unsigned long long* out)
@@ -356,7 +334,9 @@ int gn_polish_features(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono
 }
 
 // The joint system of the N local maps linearised at x, as a map like any other (C ABI: lsfm_gn_linearise).  One assembly at x with the
-// maps' weights, then every block of UJ / WJ summed once into its place (k_gn_coalesce<36> / <18>), then the download into arrays of the
+// maps' weights, then every block of UJ / WJ summed once into its place (UJ / WJ hold the solver's working form: entries with equal
+// coordinates are repeated and add up; k_gn_coalesce<36> / <18>, lsfm_coalesce.hpp, sums the sources of an output block in map order -- the
+// structure pass sorts stably; HBM-bound: NWJ * 144 B in, nW' * 144 B out, U: 288 B a block), then the download into arrays of the
 // library's own allocator (lsfm_map_release frees them).  x is read only.  The assembly sums with atomics: two calls agree to rounding,
 // not bit for bit; the structure of `out` depends on the labels alone.
 // times (may be null): [3] HIP-event ms of the assembly, k_gn_coalesce<18> (W), k_gn_coalesce<36> (U); counts (may be null): [4] NWJ, nW', NUJ, nU'.

@@ -571,6 +571,11 @@ int map_covariance_feature_columns(lsfm_context* ctx, const lsfm_map* map, bool 
                                    double* joint, int* steps, double* last_corr, double* times);
 int map_feature_pair_gate(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* pairs, int K, double* d2, double* cov_diff, int* steps,
                           double* last_corr, double* times);
+// the map with the K feature pairs pairs[2 K] declared equal, and the joint compatibility D^2 of all of them (lsfm_merge.hip, structure
+// lsfm_merge_structure.cpp; C ABI: lsfm_map_merge_features).  times (may be null): [5] ms of upload + W' / V' passes + the merged map's way
+// to the host, its upload + reduction + analysis + factorisation, right-hand side + sweeps + refinement, back-substitution + D^2, download
+int map_merge_features(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* pairs, int K, lsfm_map* out, double* d2, int* dof, int* rep,
+                       int* steps, double* last_corr, double* times);
 // the two feature-side pieces of the solve on their own (lsfm_solve.hip; C ABI: lsfm_inverse_v / lsfm_solve_features); host pointers,
 // arguments checked by the caller
 int inverse_v(lsfm_context* ctx, double* V, int n);

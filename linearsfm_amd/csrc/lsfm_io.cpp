@@ -645,4 +645,35 @@ int lsfm_read_pair_gate(const char* path, int* ids_f, int* ids_g, double* d2, do
 	return rc;
 }
 
+// the -mergeout file (lsfm_map_merge_features): "K features_removed dof D2", then one line per pair in the order given, "id_f id_g id_kept"
+int lsfm_save_merge_report(const char* path, int K, int removed, int dof, double d2, const int* ids)
+{
+	if (!path || K < 1 || !ids) return LSFM_ERR_ARG;
+	const std::string tmp = std::string(path) + ".tmp";
+	FILE* fp = fopen(tmp.c_str(), "w");
+	if (!fp) return LSFM_ERR_IO;
+	fprintf(fp, "%d %d %d %.17g\n", K, removed, dof, d2);
+	for (int a = 0; a < K; a++) fprintf(fp, "%d %d %d\n", ids[3 * a], ids[3 * a + 1], ids[3 * a + 2]);
+	const bool bad = ferror(fp) != 0;
+	if (fclose(fp) != 0 || bad || rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); return LSFM_ERR_IO; }
+	return LSFM_OK;
+}
+
+// a -mergeout file back: the head, and ids[3 cap] = (id_f, id_g, id_kept) per pair; a file with fewer or more lines than its head says is refused
+int lsfm_read_merge_report(const char* path, int* K, int* removed, int* dof, double* d2, int* ids, int cap)
+{
+	if (!path || !K || !removed || !dof || !d2 || cap < 0 || (cap && !ids)) return LSFM_ERR_ARG;
+	FILE* fp = fopen(path, "r");
+	if (!fp) return LSFM_ERR_IO;
+	int rc = LSFM_OK;
+	if (fscanf(fp, "%d %d %d %lf", K, removed, dof, d2) != 4 || *K < 1) rc = LSFM_ERR_IO;
+	else if (*K > cap) rc = LSFM_ERR_ARG;
+	for (int a = 0; rc == LSFM_OK && a < *K; a++)
+		if (fscanf(fp, "%d %d %d", &ids[3 * a], &ids[3 * a + 1], &ids[3 * a + 2]) != 3) rc = LSFM_ERR_IO;
+	int extra = 0;
+	if (rc == LSFM_OK && (fscanf(fp, "%d", &extra) == 1 || !feof(fp))) rc = LSFM_ERR_IO;
+	fclose(fp);
+	return rc;
+}
+
 } // extern "C"

@@ -12,7 +12,14 @@ usage: python tools/cov_bench.py <config> [maps] [reps]  -> one JSON object on s
   --gate K[,K...]      instead: lsfm_map_feature_pair_gate_timed for K seeded pairs each: HIP-event ms of the sweeps and of the gate
                        kernel, and the call's wall time (profiles/feature_gate_<config>.json)
   --gate-parent-route K[,K...]   instead: Sigma_d of the same pairs through covariance_columns(joint=True) of the union of the pairs' poses
-                       and the host formula -- the only route before the gate (existing API only: runs on older commits too)"""
+                       and the host formula -- the only route before the gate (existing API only: runs on older commits too)
+  --merge K[,K...]     instead: lsfm_map_merge_features_timed on the tree of the set with K features split in two (the rule of
+                       tests/merge_reference.split_set, seed 3) for the K split pairs: HIP-event ms of the five parts, the call's wall
+                       time, nW -> nW' and the bytes the W' pass moves; and two cross-checks of D^2 and the state on the same map: the
+                       residual form (x^ - T y)^T I (x^ - T y) in long double, and the columns route below (profiles/merge_<config>.json)
+  --merge-parent-route K[,K...]   instead: the same merged state and D^2 by the only route before lsfm_map_merge_features --
+                       covariance_feature_columns(the 2K features, poses, features, joint) and the host formula x^ - Sigma A^T C^-1 d,
+                       D^2 = d^T C^-1 d (existing API only: runs on older commits too; profiles/merge_parent_<config>.json)"""
 import json
 import os
 import sys
@@ -39,7 +46,7 @@ if "--parent-route" in args:
     parent_route = True
     args.remove("--parent-route")
 modes = {}
-for flag in ("--feature-columns", "--gate", "--gate-parent-route"):
+for flag in ("--feature-columns", "--gate", "--gate-parent-route", "--merge", "--merge-parent-route"):
     if flag in args:
         i = args.index(flag)
         modes[flag] = [int(v) for v in args[i + 1].split(",")]
@@ -51,6 +58,140 @@ typ, maps = synth.make_config(cfg, nmaps)
 mono = typ == "Monocular"
 d = [m.__dict__ for m in maps]
 ctx = api.Context(0)
+
+SPLIT_OFFSET = 100000
+
+
+def split_tree(K, seed=3):
+    """The tree's map of the set with K features split in two and the K split pairs: candidates are the features held by >= 2 local
+    maps, sorted by id; default_rng(seed).choice picks K without replacement; from the middle holder on a chosen feature carries the
+    label id + SPLIT_OFFSET (the rule of tests/merge_reference.split_set, stated here so that the tool runs on older commits)."""
+    holders = {}
+    for k, lm in enumerate(d):
+        for i in np.asarray(lm["stno"])[6 * int(lm["m"])::3]:
+            holders.setdefault(int(i), []).append(k)
+    cands = sorted(i for i, hs in holders.items() if len(hs) >= 2)
+    chosen = sorted(int(i) for i in np.random.default_rng(seed).choice(cands, size=K, replace=False))
+    sd = [dict(lm, stno=np.array(lm["stno"], np.int32, copy=True)) for lm in d]
+    for i in chosen:
+        hs = holders[i]
+        for k in hs[len(hs) // 2:]:
+            st, mk = sd[k]["stno"], int(sd[k]["m"])
+            st[6 * mk:][st[6 * mk:] == i] = i + SPLIT_OFFSET
+    Gs, _, src = ctx.divide_conquer(sd, mono)
+    if src != 0:
+        sys.exit(f"the tree of the split set ended with status {src}")
+    at = {int(l): f for f, l in enumerate(np.asarray(Gs["stno"])[6 * int(Gs["m"])::3])}
+    return Gs, np.array([(at[i], at[i + SPLIT_OFFSET]) for i in chosen], np.int32)
+
+
+def residual_form(Gs, Ty):
+    """(x^ - T y)^T I (x^ - T y) in long double, block by block: a statement of D^2 that owes nothing to either route.  D^2 is the
+    MINIMUM of this form over y, so an error of y enters in second order only, and the form's own cancellation (1e3 .. 1e6 of the
+    terms on the Mono sets) is far inside the 64-bit mantissa."""
+    ld = np.longdouble
+    ms = int(Gs["m"])
+    e = np.asarray(Gs["stVal"], np.float64).astype(ld) - np.asarray(Ty, np.float64).astype(ld)
+    ep, ef = e[: 6 * ms].reshape(-1, 6), e[6 * ms:].reshape(-1, 3)
+    U = np.asarray(Gs["U"], np.float64).reshape(-1, 6, 6).astype(ld)
+    Ui, Uj = np.asarray(Gs["Ui"]), np.asarray(Gs["Uj"])
+    qu = np.einsum("bi,bij,bj->b", ep[Ui], U, ep[Uj])
+    tot = (qu * np.where(Ui == Uj, 1, 2)).sum()
+    ph, fe = np.asarray(Gs["photo"]), np.asarray(Gs["feature"])
+    for lo in range(0, len(ph), 1 << 20):  # (in slices: the long-double copy of W is 16 bytes a number)
+        hi = min(lo + (1 << 20), len(ph))
+        W = np.asarray(Gs["W"], np.float64).reshape(-1, 6, 3)[lo:hi].astype(ld)
+        tot += 2 * np.einsum("bi,bij,bj->b", ep[ph[lo:hi]], W, ef[fe[lo:hi]]).sum()
+    V = np.asarray(Gs["V"], np.float64).reshape(-1, 3, 3).astype(ld)
+    tot += np.einsum("bi,bij,bj->b", ef, V, ef).sum()
+    return float(tot)
+
+
+def columns_route(Gs, pairs):
+    """The merged state and D^2 without lsfm_map_merge_features: covariance_feature_columns(poses, features, joint) of the 2K features
+    and the host formula y = x - Sigma A^T C^-1 d, D^2 = d^T C^-1 d.  Returns (y in x's numbering, D^2, C, the call's dict, the time
+    the call returned)."""
+    K = len(pairs)
+    ms, ns = int(Gs["m"]), int(Gs["n"])
+    x = np.asarray(Gs["stVal"], np.float64)
+    feats = pairs.reshape(-1)  # f0 g0 f1 g1 ...: distinct, every split feature is in one pair
+    fc = ctx.covariance_feature_columns(Gs, mono, feats, poses=True, features=True, joint=True)
+    t1 = time.perf_counter()
+    cols = np.concatenate([fc["pose"].reshape(2 * K, 6 * ms, 3), fc["feature"].reshape(2 * K, 3 * ns, 3)], axis=1)  # Sigma_{., feature}
+    SA = np.concatenate([cols[2 * a + 1] - cols[2 * a] for a in range(K)], axis=1)                                   # Sigma A^T, A x = x_g - x_f
+    Am = np.zeros((3 * K, 6 * K))
+    for a in range(K):
+        Am[3 * a: 3 * a + 3, 6 * a + 3: 6 * a + 6] = np.eye(3)
+        Am[3 * a: 3 * a + 3, 6 * a: 6 * a + 3] = -np.eye(3)
+    Cm = Am @ fc["joint"] @ Am.T
+    xf = x[6 * ms:].reshape(-1, 3)
+    dv = (xf[pairs[:, 1]] - xf[pairs[:, 0]]).reshape(-1)
+    sol = np.linalg.solve(Cm, dv)
+    return x - SA @ sol, float(dv @ sol), Cm, fc, t1
+
+
+if "--merge" in modes:
+    legs = []
+    for K in modes["--merge"]:
+        Gs, pairs = split_tree(K)
+        walls, parts = [], []
+        for rep in range(reps + 1):  # (the first call is a warm-up)
+            t0 = time.perf_counter()
+            mrc, g, d2, dof, rp, steps, corr, t = ctx.merge_features_raw(Gs, mono, pairs, times=True)
+            wall = 1e3 * (time.perf_counter() - t0)
+            if mrc < 0 or g is None:
+                sys.exit(f"lsfm_map_merge_features: status {mrc}: {api.lib().lsfm_last_error(ctx._h).decode()}")
+            if rep:
+                walls.append(wall)
+                parts.append(t.tolist())
+        med = np.median(np.array(parts), axis=0)
+        nW, nWo = len(Gs["photo"]), int(g["nW"])
+        ms_ = int(Gs["m"])
+        yv = np.asarray(g["stVal"], np.float64)
+        d2_res = residual_form(Gs, np.concatenate([yv[: 6 * ms_], yv[6 * ms_:].reshape(-1, 3)[rp].reshape(-1)]))
+        yc, d2_cols, _, _, _ = columns_route(Gs, pairs)  # the other route on the SAME map (a tree is not bit-reproducible from process to process)
+        sig = np.sqrt(np.concatenate([np.einsum("kii->ki", v).reshape(-1) for v in (lambda c: (c["pose"], c["feature"]))(ctx.covariance(Gs, mono))]))
+        kept = np.concatenate([np.arange(6 * ms_), (6 * ms_ + 3 * np.unique(rp, return_index=True)[1][:, None] + np.arange(3)).reshape(-1)])
+        on = sig[kept] > 0
+        dy = float(np.max(np.abs(yv - yc[kept])[on] / (sig[kept][on] * max(1.0, np.sqrt(d2_cols)))))
+        ws = {f"mode{md}_ms": ctx.wstream_bench(nW, md, 20) for md in (0, 2)} if hasattr(ctx, "wstream_bench") else {}
+        legs.append({"leg": "merge", "K": K, "status": mrc, "steps": steps, "last_corr": corr, "d2": d2, "d2_residual_form_long_double": d2_res, "d2_rel_diff": abs(d2 - d2_res) / d2_res,
+                     "d2_columns_route_same_map": d2_cols, "d2_rel_diff_columns_route": abs(d2 - d2_cols) / d2_cols, "state_diff_columns_route": dy, "dof": dof, "poses": int(Gs["m"]), "features": int(Gs["n"]),
+                     "nW": nW, "nW_merged": nWo, "w_pass_bytes": (nW + nWo) * 144,
+                     "ms_median": {"upload_merge_passes": med[0], "reduce_analyse_factor": med[1], "rhs_sweeps_refinement": med[2], "backsub_d2": med[3], "download": med[4]},
+                     "call_wall_ms_median": float(np.median(walls)), "call_wall_ms": walls, "wstream_same_blocks": ws})
+    print(json.dumps({"config": cfg, "type": typ, "maps": len(maps), "legs": legs,
+                      "note": "HIP events on the context's stream; upload_merge_passes covers the upload of W / V, the W' and V' passes and the merged map's "
+                              "download (the W' pass alone is not bracketed: its bytes are given, beside lsfm_wstream_bench on as many blocks); "
+                              "reduce_analyse_factor includes cov_front's upload of the merged map; split pairs by default_rng(3); d2_rel_diff: against the long-double "
+                              "residual form at the call's own state; *_columns_route: against covariance_feature_columns + the host formula on the same map, "
+                              "the state in units of sigma_i max(1, sqrt(D2))"}, indent=1))
+    ctx.close()
+    sys.exit(0)
+if "--merge-parent-route" in modes:
+    legs = []
+    for K in modes["--merge-parent-route"]:
+        Gs, pairs = split_tree(K)
+        ms = int(Gs["m"])
+        walls, hosts = [], []
+        for rep in range(reps + 1):  # (the first round is a warm-up)
+            t0 = time.perf_counter()
+            y, d2, Cm, fc, t1 = columns_route(Gs, pairs)
+            t2 = time.perf_counter()
+            if rep:
+                walls.append(1e3 * (t2 - t0))
+                hosts.append(1e3 * (t2 - t1))
+        Ty = y.copy()  # the route's state with both halves of a pair at the first one's value: T y
+        Ty[6 * ms:].reshape(-1, 3)[pairs[:, 1]] = Ty[6 * ms:].reshape(-1, 3)[pairs[:, 0]]
+        d2_res = residual_form(Gs, Ty)
+        legs.append({"leg": "merge-parent-route", "K": K, "columns": 6 * K, "d2": d2, "d2_residual_form_long_double": d2_res, "d2_rel_diff": abs(d2 - d2_res) / d2_res,
+                     "cond_C": float(np.linalg.cond(Cm)), "steps": fc["steps"], "wall_ms": walls,
+                     "wall_ms_median": float(np.median(walls)), "host_formula_ms_median": float(np.median(hosts))})
+    print(json.dumps({"config": cfg, "type": typ, "maps": len(maps), "legs": legs,
+                      "note": "wall time of the merged state and D^2 of the same split pairs through covariance_feature_columns(poses, features, joint) of "
+                              "the 2K features and the host formula y = x - Sigma A^T C^-1 d, D^2 = d^T C^-1 d; host_formula_ms: the part outside that call"}, indent=1))
+    ctx.close()
+    sys.exit(0)
 G, stats, rc = ctx.divide_conquer(d, mono)
 m_, n_ = int(G["m"]), int(G["n"])
 
