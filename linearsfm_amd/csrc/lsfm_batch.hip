@@ -361,21 +361,19 @@ unsigned long long batch_structure_digest(lsfm_context* ctx, const DevBatch& b)
 	return h;
 }
 
-void batch_download_map(lsfm_context* ctx, const DevBatch& b, int k, bool mono, lsfm_map* g)
+// On a throw *out is zeroed and nothing of the map is held.
+void batch_download_map(lsfm_context* ctx, const DevBatch& b, int k, bool mono, lsfm_map* out)
 {
-	memset(g, 0, sizeof *g);
+	memset(out, 0, sizeof *out);
 	int po = b.pose_off[k], fo = b.feat_off[k];
 	int m = b.pose_off[k + 1] - po, n = b.feat_off[k + 1] - fo;
 	// u_off / w_off of the batch are kept on the host by every stage
 	int uo = b.u_off[k], wo = b.w_off[k], nU = b.u_off[k + 1] - uo, nW = b.w_off[k + 1] - wo;
-	g->m = m; g->n = n; g->nU = nU; g->nW = nW; g->Ref = b.Ref[k]; g->FRef = b.FRef[k];
+	MapOut G;
+	map_new(G.g, nullptr, m, n, nU, nW, true);
+	lsfm_map* g = &G.g;
+	g->Ref = b.Ref[k]; g->FRef = b.FRef[k];
 	if (mono) { g->ScaP = b.ScaP[k]; g->Fix = b.Fix[k]; g->Sign = b.Sign[k]; g->FScaP = b.FScaP[k]; g->FFix = b.FFix[k]; }
-	int r = 6 * m + 3 * n;
-	g->stno = host_alloc<int>(r); g->stVal = host_alloc<double>(r);
-	g->U = host_alloc<double>((size_t)nU * 36); g->Ui = host_alloc<int>(nU); g->Uj = host_alloc<int>(nU);
-	g->W = host_alloc<double>((size_t)nW * 18); g->photo = host_alloc<int>(nW); g->feature = host_alloc<int>(nW);
-	g->V = host_alloc<double>((size_t)n * 9); g->FBlock = host_alloc<int>(n);
-	g->pose_origin = host_alloc<int>(m);
 	if (b.pose_origin) d2h(ctx, g->pose_origin, b.pose_origin + po, m * sizeof(int));
 	else for (int i = 0; i < m; i++) g->pose_origin[i] = k;
 	std::vector<int> pid(m), fid(n), fptr(n + 1);
@@ -394,6 +392,7 @@ void batch_download_map(lsfm_context* ctx, const DevBatch& b, int k, bool mono, 
 	d2h(ctx, g->V, b.V + (size_t)fo * 9, (size_t)n * 9 * sizeof(double));
 	d2h(ctx, fptr.data(), b.fptr + fo, (n + 1) * sizeof(int));
 	for (int i = 0; i < n; i++) g->FBlock[i] = fptr[i] - wo;
+	G.give(out);
 }
 
 // ---- measurement: the W access patterns against the stream copy (lsfm_wstream_bench) ------------------------------
@@ -450,11 +449,3 @@ int wstream_bench(lsfm_context* ctx, long long nblocks, int mode, int reps, doub
 }
 
 } // namespace lsfm
-
-extern "C" void lsfm_map_release(lsfm_map* g)
-{
-	if (!g) return;
-	free(g->stno); free(g->stVal); free(g->U); free(g->Ui); free(g->Uj); free(g->W); free(g->photo); free(g->feature);
-	free(g->V); free(g->FBlock); free(g->pose_origin);
-	memset(g, 0, sizeof *g);
-}

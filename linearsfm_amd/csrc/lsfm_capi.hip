@@ -526,12 +526,23 @@ int lsfm_gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, int type, 
 	return lsfm_gn_linearise_timed(ctx, maps, N, type, x, weight, out, obj, b, nullptr, nullptr);
 }
 
+// What the single-map calls ask of their map before anything runs: mono is 0 or 1, at least one pose, no negative size, no null array
+// that its sizes say is read, the labels (stno) of a Mono map -- its gauge is found by them -- and what `need` adds.
+enum MapNeeds : unsigned {
+	MAP_STVAL = 1u << 0, // the estimates
+	MAP_STNO  = 1u << 1, // the labels whatever mono is
+};
+static bool map_ok(const lsfm_map* map, int mono, unsigned need)
+{
+	if (!map || (mono != 0 && mono != 1) || map->m <= 0 || map->n < 0 || map->nU < 0 || map->nW < 0) return false;
+	if ((map->nU && (!map->U || !map->Ui || !map->Uj)) || (map->nW && (!map->W || !map->photo || !map->feature)) || (map->n && !map->V)) return false;
+	return !(((mono || (need & MAP_STNO)) && !map->stno) || ((need & MAP_STVAL) && !map->stVal));
+}
+
 int lsfm_map_covariance_timed(lsfm_context* ctx, const lsfm_map* map, int mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb,
                               double* times)
 {
-	if (!map || (mono != 0 && mono != 1) || map->m <= 0 || map->n < 0 || map->nU < 0 || map->nW < 0 || (pair_cov && (cap_blocks < 0 || !nnzb))) return LSFM_ERR_ARG;
-	if ((map->nU && (!map->U || !map->Ui || !map->Uj)) || (map->nW && (!map->W || !map->photo || !map->feature)) || (map->n && !map->V) || (mono && !map->stno))
-		return LSFM_ERR_ARG;
+	if (!map_ok(map, mono, 0) || (pair_cov && (cap_blocks < 0 || !nnzb))) return LSFM_ERR_ARG;
 	int cnt = 0;
 	const int rc = guarded(ctx, [&]() { return map_covariance(ctx, map, mono == 1, pose_cov, feat_cov, pair_cov, cap_blocks, &cnt, times); });
 	if (nnzb) *nnzb = cnt;
@@ -557,8 +568,7 @@ int lsfm_map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned 
 int lsfm_map_marginalise_poses_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const unsigned char* keep_pose, const unsigned char* drop_feat, lsfm_map* out,
                                      double* times, int* info)
 {
-	if (!map || !keep_pose || !out || (mono != 0 && mono != 1) || map->m <= 0 || map->n < 0 || map->nU < 0 || map->nW < 0 || !map->stno || !map->stVal) return LSFM_ERR_ARG;
-	if ((map->nU && (!map->U || !map->Ui || !map->Uj)) || (map->nW && (!map->W || !map->photo || !map->feature)) || (map->n && !map->V)) return LSFM_ERR_ARG;
+	if (!map_ok(map, mono, MAP_STNO | MAP_STVAL) || !keep_pose || !out) return LSFM_ERR_ARG;
 	return guarded(ctx, [&]() { return map_marginalise_poses(ctx, map, mono == 1, keep_pose, drop_feat, out, times, info); });
 }
 
@@ -570,10 +580,7 @@ int lsfm_map_marginalise_poses(lsfm_context* ctx, const lsfm_map* map, int mono,
 int lsfm_map_covariance_columns_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* poses, int k, double* pose_cols, double* feat_cols,
                                       double* joint, int* steps, double* last_corr, double* times)
 {
-	if (!map || (mono != 0 && mono != 1) || map->m <= 0 || map->n < 0 || map->nU < 0 || map->nW < 0 || !poses || k < 1 || (!pose_cols && !feat_cols && !joint))
-		return LSFM_ERR_ARG;
-	if ((map->nU && (!map->U || !map->Ui || !map->Uj)) || (map->nW && (!map->W || !map->photo || !map->feature)) || (map->n && !map->V) || (mono && !map->stno))
-		return LSFM_ERR_ARG;
+	if (!map_ok(map, mono, 0) || !poses || k < 1 || (!pose_cols && !feat_cols && !joint)) return LSFM_ERR_ARG;
 	return guarded(ctx, [&]() { return map_covariance_columns(ctx, map, mono == 1, poses, k, pose_cols, feat_cols, joint, steps, last_corr, times); });
 }
 
@@ -583,17 +590,10 @@ int lsfm_map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, int mono
 	return lsfm_map_covariance_columns_timed(ctx, map, mono, poses, k, pose_cols, feat_cols, joint, steps, last_corr, nullptr);
 }
 
-// what lsfm_map_covariance_columns asks of its map; need_state: and the estimates (the gate's x_f - x_g)
-static bool feature_map_ok(const lsfm_map* map, int mono, bool need_state)
-{
-	if (!map || (mono != 0 && mono != 1) || map->m <= 0 || map->n < 0 || map->nU < 0 || map->nW < 0 || (need_state && !map->stVal)) return false;
-	return !((map->nU && (!map->U || !map->Ui || !map->Uj)) || (map->nW && (!map->W || !map->photo || !map->feature)) || (map->n && !map->V) || (mono && !map->stno));
-}
-
 int lsfm_map_covariance_feature_columns_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* feats, int k, double* pose_cols, double* feat_cols,
                                               double* joint, int* steps, double* last_corr, double* times)
 {
-	if (!feature_map_ok(map, mono, false) || !feats || k < 1 || (!pose_cols && !feat_cols && !joint)) return LSFM_ERR_ARG;
+	if (!map_ok(map, mono, 0) || !feats || k < 1 || (!pose_cols && !feat_cols && !joint)) return LSFM_ERR_ARG;
 	return guarded(ctx, [&]() { return map_covariance_feature_columns(ctx, map, mono == 1, feats, k, pose_cols, feat_cols, joint, steps, last_corr, times); });
 }
 
@@ -606,7 +606,7 @@ int lsfm_map_covariance_feature_columns(lsfm_context* ctx, const lsfm_map* map, 
 int lsfm_map_feature_pair_gate_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, double* d2, double* cov_diff, int* steps,
                                      double* last_corr, double* times)
 {
-	if (!feature_map_ok(map, mono, true) || !pairs || K < 1 || (!d2 && !cov_diff)) return LSFM_ERR_ARG;
+	if (!map_ok(map, mono, MAP_STVAL) || !pairs || K < 1 || (!d2 && !cov_diff)) return LSFM_ERR_ARG; // (the estimates: the gate's x_f - x_g)
 	return guarded(ctx, [&]() { return map_feature_pair_gate(ctx, map, mono == 1, pairs, K, d2, cov_diff, steps, last_corr, times); });
 }
 
@@ -620,7 +620,7 @@ int lsfm_map_merge_features_timed(lsfm_context* ctx, const lsfm_map* map, int mo
                                   int* steps, double* last_corr, double* times)
 {
 	if (steps) *steps = 0;
-	if (!feature_map_ok(map, mono, true) || !map->stno || !pairs || K < 1 || !out) return LSFM_ERR_ARG;
+	if (!map_ok(map, mono, MAP_STNO | MAP_STVAL) || !pairs || K < 1 || !out) return LSFM_ERR_ARG;
 	return guarded(ctx, [&]() { return map_merge_features(ctx, map, mono == 1, pairs, K, out, d2, dof, rep, steps, last_corr, times); });
 }
 

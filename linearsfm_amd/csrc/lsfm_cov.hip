@@ -13,8 +13,9 @@
 // at a time).  Every sum runs in a fixed order in one lane: the result is the same bits on every call.
 // Sigma = P^T D^-1/2 Z D^-1/2 P on S's upper pattern (k_cov_pairs), then per feature (k_cov_feat, one wave per feature)
 //     Sigma_ff = V_f^-1 + V_f^-1 (sum_{a,b} W_af^T Sigma_{p_a p_b} W_bf) V_f^-1.
-// The front end -- argument checks and upload (lsfm_system.hpp), reduction, factorisation -- is cov_front (lsfm_cov.hpp), shared with the
-// covariance columns of chosen poses (lsfm_covcols.hip).
+// The front end -- argument checks and upload (lsfm_system.hpp), reduction, factorisation -- is cov_front (lsfm_cov.hpp), shared with
+// lsfm_map_marginalise_poses and, as cov_front_rowsorted (with the row-sorted block list and the status read), with the columns calls
+// (lsfm_covcols.hip, lsfm_featcols.hip) and the merge (lsfm_merge.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -271,10 +272,8 @@ void cov_front(lsfm_context* ctx, const lsfm_map* map, bool mono, CovFront& fr)
 {
 	const int m = map->m;
 	// ---- arguments (host) ----
-	HostSystem h;
-	h.m = m; h.n = map->n; h.nU = map->nU; h.nW = map->nW;
-	h.Ui = map->Ui; h.Uj = map->Uj; h.photo = map->photo; h.feature = map->feature;
-	h.U = map->U; h.W = map->W; h.V = map->V; h.pose_origin = map->pose_origin;
+	HostSystem h = host_system_of(*map, true);
+	h.pose_origin = map->pose_origin;
 	const std::vector<int> fptr = system_fptr(h);
 	std::vector<unsigned char> fx;
 	if (mono)
@@ -327,6 +326,20 @@ int cov_front_status(lsfm_context* ctx, const CovFront& fr)
 	d2h(ctx, &rs, fr.d_run, sizeof rs);
 	if (chol_err) LSFM_FAIL(LSFM_ERR_NOT_SPD, "the camera system is not positive definite (block column " + std::to_string(chol_err - 1) + " of the factor)");
 	return rs.floored;
+}
+
+int cov_front_rowsorted(lsfm_context* ctx, const lsfm_map* map, bool mono, CovFront& fr)
+{
+	{
+		// the residual needs the row-sorted list of S's blocks whatever product the context's CG is set to (lsfm_set_spmv_variant)
+		struct Keep { lsfm_context* c; int v; ~Keep() { c->pcg.spmv_variant = v; } } keep{ ctx, ctx->pcg.spmv_variant };
+		ctx->pcg.spmv_variant = 2;
+		cov_front(ctx, map, mono, fr);
+	}
+	LSFM_CHECK_HIP(hipGetLastError());
+	const int floored = cov_front_status(ctx, fr);
+	if (floored == 0 && !fr.sy.gent) LSFM_FAIL(LSFM_ERR_INTERNAL, "the camera system has no row-sorted block list");
+	return floored;
 }
 
 int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb_out,
@@ -382,14 +395,7 @@ int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* po
 	int ferr = 0;
 	d2h(ctx, &ferr, d_ferr, sizeof(int));
 	if (times)
-	{
-		for (int k = 0; k < 4; k++)
-		{
-			float ms = 0.0f;
-			LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-			times[k] = ms;
-		}
-	}
+		for (int k = 0; k < 4; k++) times[k] = event_ms(ev[k], ev[k + 1]);
 	const int floored = cov_front_status(ctx, fr);
 	if (floored > 0) return floored; // the factor is of a perturbed S: nothing is written
 	if (ferr) LSFM_FAIL(LSFM_ERR_INTERNAL, ferr == 2 ? "a block of the selected inversion is not on the factor's pattern" : "a feature's pose pair is not in the camera system's pattern");

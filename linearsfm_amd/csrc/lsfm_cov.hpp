@@ -1,5 +1,9 @@
-// What the two covariance entry points share (lsfm_cov.hip: lsfm_map_covariance, lsfm_covcols.hip: lsfm_map_covariance_columns): the
-// front end that checks a map, uploads it, reduces it to the camera system and factors that, and the device memory of one call.
+// What the single-map calls on a factored camera system share: the front end that checks a map, uploads it, reduces it to the camera
+// system and factors that (lsfm_cov.hip: lsfm_map_covariance, lsfm_map_marginalise_poses and, with the row-sorted block list, the
+// columns calls and the merge), the device memory of one call, the refined side-by-side solve of a chunk of columns and the one
+// driver that walks a list of requested items chunk by chunk (lsfm_covcols.hip: lsfm_map_covariance_columns; lsfm_featcols.hip:
+// lsfm_map_covariance_feature_columns, lsfm_map_feature_pair_gate).  lsfm_map_merge_features (lsfm_merge.hip) has one column and a
+// body of its own.
 #pragma once
 #include <algorithm>
 #include <functional>
@@ -44,6 +48,10 @@ struct CovFront {
 void cov_front(lsfm_context* ctx, const lsfm_map* map, bool mono, CovFront& fr);
 // the numerical status of the factorisation, read once: throws LSFM_ERR_NOT_SPD, returns the number of floored pivots
 int cov_front_status(lsfm_context* ctx, const CovFront& fr);
+// the front of a columns call: cov_front with the row-sorted list of S's blocks (fr.sy.gent / goth, which cc_solve_refine's residual
+// reads) whatever lsfm_set_spmv_variant says -- the context's setting is put back --, then cov_front_status.  Returns the number of
+// floored pivots: 0 = the factor is usable, > 0 = it is of a perturbed S and the caller writes nothing.
+int cov_front_rowsorted(lsfm_context* ctx, const lsfm_map* map, bool mono, CovFront& fr);
 
 // The side-by-side triangular sweeps of lsfm_covcols.hip against the factor `ch` (whole in ch.L / ch.Dinv), in place on a slab
 // V[6 ch.M][R] in elimination order, R <= 6 CC_KC = 192: V <- L^-1 V, and V <- L^-T V.  lsfm_map_covariance_columns runs one after the
@@ -76,5 +84,31 @@ void cc_pose_out(lsfm_context* ctx, int width, int M, int R, const double* Xo, d
 // may be null): [2 per column group] the features (f, +1), (g, -1 or none: g < 0) the group's columns belong to, whose own rows
 // receive +- V^-1 as well
 void cc_feat(lsfm_context* ctx, int width, const CovFront& fr, int R, const int* rows, int nrows, const int* grp, const double* Xo, double* out);
+
+// ---- the driver of a columns call: the factored front, then the k requested items in chunks of `chunk`, each R = width kcur columns ----
+struct CcCall {
+	int k;                // requested items
+	int width;            // columns of one item: 6 (a pose) or 3 (a feature, or a pair of features)
+	int chunk;            // most items of a chunk: CC_KC poses, 2 CC_KC features or pairs -- 192 columns either way
+	size_t extra_doubles; // the caller's own device outputs, for the refusal of a call that does not fit the free device memory
+	const char* noun;     // what the items are called in that refusal
+};
+// The callables, c0 = the chunk's first item, kcur its items:
+//   prep    once the factor stands: allocates (and uploads) what the caller's own kernels need on the device
+//   rhs     the chunk's right-hand sides, as CcRhs
+//   layout  (may be empty) the solved chunk into the caller's layouts, counted with the solve: times[2]
+//   emit    the caller's kernels behind the solve: times[3]
+//   fetch   downloads what layout and emit wrote; the stream is synchronised after it
+// steps_out / last_corr / times as the C ABI's entries have them (lsfm.h; all may be null).  Returns as lsfm_map_covariance_columns: > 0
+// floored pivots (nothing was run, *steps_out = 0), LSFM_NOT_CONVERGED, LSFM_OK.
+using CcPrep = std::function<void(const CovFront& fr)>;
+using CcChunkRhs = std::function<void(int c0, int kcur, int R, const CovFront& fr, double* B)>;
+using CcStep = std::function<void(int c0, int kcur, int R, const CovFront& fr, CcWork& wk)>;
+using CcFetch = std::function<void(int c0, int kcur, int R, CcWork& wk)>;
+int cc_run(lsfm_context* ctx, const lsfm_map* map, bool mono, const CcCall& call, int* steps_out, double* last_corr, double* times, const CcPrep& prep,
+           const CcChunkRhs& rhs, const CcStep& layout, const CcStep& emit, const CcFetch& fetch);
+// joint[k width][k width], its chunks' columns in place, made exactly symmetric: block (a, b), a < b, from column b and mirrored; a
+// diagonal block (X + X^T) / 2
+void symmetrise_joint(double* joint, int k, int width);
 
 } // namespace lsfm

@@ -26,6 +26,10 @@
 //
 // Not bit-reproducible: the rows of a column's ancestors collect their updates by fp64 atomics from whichever work-group comes
 // first.  The refinement takes the difference (a few ulps of the unrefined solve) far below what is asked of the result.
+//
+// The host side is one driver for every columns call (cc_run, lsfm_cov.hpp): the factored front, the chunks, the refined solve of
+// each, the two event brackets and the read-backs; lsfm_map_covariance_columns at the end of this file and the two entries of
+// lsfm_featcols.hip are its callers, each a right-hand side, a layout / emit step and the downloads.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -657,6 +661,70 @@ void cc_feat(lsfm_context* ctx, int width, const CovFront& fr, int R, const int*
 	else hipLaunchKernelGGL(k_cc_feat<3>, grid, block, 0, ctx->stream, nrows, rows, grp, io.fptr, io.photo, io.W, fr.sy.IV, R, Xo, out);
 }
 
+int cc_run(lsfm_context* ctx, const lsfm_map* map, bool mono, const CcCall& call, int* steps_out, double* last_corr, double* times, const CcPrep& prep,
+           const CcChunkRhs& rhs, const CcStep& layout, const CcStep& emit, const CcFetch& fetch)
+{
+	const int k = call.k, w = call.width;
+	if (steps_out) *steps_out = 0;
+	CovFront fr;
+	const int floored = cov_front_rowsorted(ctx, map, mono, fr);
+	if (floored > 0) return floored; // the factor is of a perturbed S: nothing is written
+	hipStream_t s = ctx->stream;
+	const int M = fr.ch.M;
+	const int kc = std::min(k, call.chunk), Rmax = w * kc;
+	{
+		const size_t need = (3 * (size_t)M * 6 * Rmax + call.extra_doubles) * sizeof(double);
+		size_t free_b = 0, total_b = 0;
+		if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b)
+			throw Error{ LSFM_ERR_OOM, "out of device memory: the columns of " + std::to_string(kc) + " " + call.noun + " need " + std::to_string(need) + " bytes, " + std::to_string(free_b) + " are free" };
+	}
+	CcWork wk;
+	wk.alloc(M, Rmax);
+	prep(fr);
+	hipEvent_t ev[3] = { ctx->pool_event(), ctx->pool_event(), ctx->pool_event() };
+	int most_steps = 0;
+	bool undone = false;
+	double t_solve = 0.0, t_emit = 0.0;
+	for (int c0 = 0; c0 < k; c0 += kc)
+	{
+		const int kcur = std::min(kc, k - c0), R = w * kcur;
+		LSFM_CHECK_HIP(hipEventRecord(ev[0], s));
+		const CcOutcome oc = cc_solve_refine(ctx, fr, R, wk, [&](double* B) { rhs(c0, kcur, R, fr, B); });
+		most_steps = std::max(most_steps, oc.steps);
+		undone = undone || oc.undone;
+		if (last_corr)
+			for (int a = 0; a < kcur; a++) last_corr[c0 + a] = *std::max_element(wk.ratio.begin() + w * a, wk.ratio.begin() + w * a + w);
+		if (layout) layout(c0, kcur, R, fr, wk);
+		LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
+		emit(c0, kcur, R, fr, wk);
+		LSFM_CHECK_HIP(hipEventRecord(ev[2], s));
+		LSFM_CHECK_HIP(hipGetLastError());
+		fetch(c0, kcur, R, wk);
+		LSFM_CHECK_HIP(hipStreamSynchronize(s));
+		t_solve += event_ms(ev[0], ev[1]);
+		t_emit += event_ms(ev[1], ev[2]);
+	}
+	if (steps_out) *steps_out = most_steps;
+	if (times)
+	{
+		times[0] = event_ms(fr.ev[0], fr.ev[1]);
+		times[1] = event_ms(fr.ev[1], fr.ev[2]);
+		times[2] = t_solve; times[3] = t_emit;
+	}
+	return undone ? LSFM_NOT_CONVERGED : LSFM_OK;
+}
+
+void symmetrise_joint(double* joint, int k, int width)
+{
+	const size_t w = (size_t)width, N = (size_t)k * w;
+	for (size_t i = 0; i < N; i++)
+		for (size_t j = i; j < N; j++)
+		{
+			const double v = i / w == j / w ? 0.5 * (joint[i * N + j] + joint[j * N + i]) : joint[i * N + j];
+			joint[i * N + j] = joint[j * N + i] = v;
+		}
+}
+
 int map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* poses, int k, double* pose_cols, double* feat_cols, double* joint,
                            int* steps_out, double* last_corr, double* times)
 {
@@ -670,99 +738,42 @@ int map_covariance_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, co
 			seen[poses[a]] = 1;
 		}
 	}
-	if (steps_out) *steps_out = 0;
-	CovFront fr;
-	{
-		// the residual needs the row-sorted list of S's blocks whatever product the context's CG is set to (lsfm_set_spmv_variant)
-		struct Keep { lsfm_context* c; int v; ~Keep() { c->pcg.spmv_variant = v; } } keep{ ctx, ctx->pcg.spmv_variant };
-		ctx->pcg.spmv_variant = 2;
-		cov_front(ctx, map, mono, fr);
-	}
-	const SolveIO& io = fr.io;
-	const SchurSystem& sy = fr.sy;
-	const CholDev& ch = fr.ch;
 	hipStream_t s = ctx->stream;
-	LSFM_CHECK_HIP(hipGetLastError());
-	const int floored = cov_front_status(ctx, fr);
-	if (floored > 0) return floored; // the factor is of a perturbed S: nothing is written
-	if (!sy.gent) LSFM_FAIL(LSFM_ERR_INTERNAL, "the camera system has no row-sorted block list");
-	const int M = ch.M;
-	const int kc = std::min(k, CC_KC), Rmax = 6 * kc;
-	// ---- memory of the call ----
-	const size_t slab = (size_t)M * 6 * Rmax;
+	const int kc = std::min(k, CC_KC);
 	const bool want_feat = feat_cols && n;
-	{
-		const size_t need = (3 * slab + (want_feat ? (size_t)n * 18 * kc : 0) + (joint ? (size_t)k * 6 * Rmax : 0)) * sizeof(double);
-		size_t free_b = 0, total_b = 0;
-		if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b)
-			throw Error{ LSFM_ERR_OOM, "out of device memory: the columns of " + std::to_string(kc) + " poses need " + std::to_string(need) + " bytes, " + std::to_string(free_b) + " are free" };
-	}
-	CcWork wk;
-	wk.alloc(M, Rmax);
-	double *Xo = wk.Xo, *Y = wk.Y; // Sigma_{.,Q} of the chunk, [6 m][R] | at the end the chunk of pose_cols
+	const size_t nF = want_feat ? (size_t)n * 18 * kc : 0, nJ = joint ? (size_t)k * 36 * kc : 0;
 	DevBuf bF, bJ, bQ;
-	double* F = want_feat ? bF.get<double>((size_t)n * 18 * kc) : nullptr;
-	double* Jd = joint ? bJ.get<double>((size_t)k * 6 * Rmax) : nullptr;
-	int* dq = bQ.get<int>(k);
-	h2d(ctx, dq, poses, (size_t)k * sizeof(int));
-	hipEvent_t ev[3] = { ctx->pool_event(), ctx->pool_event(), ctx->pool_event() };
-	std::vector<double> hj(joint ? (size_t)k * 6 * Rmax : 0);
-	int most_steps = 0;
-	bool undone = false;
-	double t_solve = 0.0, t_feat = 0.0;
-	for (int c0 = 0; c0 < k; c0 += kc)
-	{
-		const int kcur = std::min(kc, k - c0), R = 6 * kcur;
-		const size_t cells = (size_t)M * 6 * R;
-		const int* qpose = dq + c0;
-		LSFM_CHECK_HIP(hipEventRecord(ev[0], s));
-		const CcOutcome oc = cc_solve_refine(ctx, fr, R, wk, [&](double* B) {
-			hipLaunchKernelGGL(k_cc_unit, dim3(blocks_of(cells, 256)), dim3(256), 0, s, M, R, io.d_fixed, qpose, B);
-		});
-		const std::vector<double>& ratio = wk.ratio;
-		most_steps = std::max(most_steps, oc.steps);
-		undone = undone || oc.undone;
-		if (last_corr)
-			for (int a = 0; a < kcur; a++) last_corr[c0 + a] = *std::max_element(ratio.begin() + 6 * a, ratio.begin() + 6 * a + 6);
-		// ---- the caller's layouts ----
-		if (pose_cols) cc_pose_out(ctx, 6, M, R, Xo, Y);
-		if (joint) hipLaunchKernelGGL(k_cc_rows, dim3(blocks_of((size_t)k * 6 * R, 256)), dim3(256), 0, s, k, R, dq, Xo, Jd);
-		LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
-		if (want_feat) cc_feat(ctx, 6, fr, R, nullptr, n, nullptr, Xo, F);
-		LSFM_CHECK_HIP(hipEventRecord(ev[2], s));
-		LSFM_CHECK_HIP(hipGetLastError());
-		if (pose_cols) d2h(ctx, pose_cols + (size_t)c0 * m * 36, Y, cells * sizeof(double));
-		if (want_feat) d2h(ctx, feat_cols + (size_t)c0 * n * 18, F, (size_t)kcur * n * 18 * sizeof(double));
-		if (joint)
-		{
+	double *F = nullptr, *Jd = nullptr; // feat_cols of a chunk | the rows of the k requested poses in a chunk's columns
+	int* dq = nullptr;
+	std::vector<double> hj(nJ);
+	int own_steps = 0;
+	int& steps = steps_out ? *steps_out : own_steps; // (> 0: the results were written)
+	const int rc = cc_run(ctx, map, mono, CcCall{ k, 6, CC_KC, nF + nJ, "poses" }, &steps, last_corr, times,
+		[&](const CovFront&) {
+			if (want_feat) F = bF.get<double>(nF);
+			if (joint) Jd = bJ.get<double>(nJ);
+			dq = bQ.get<int>(k);
+			h2d(ctx, dq, poses, (size_t)k * sizeof(int));
+		},
+		[&](int c0, int, int R, const CovFront& fr, double* B) {
+			hipLaunchKernelGGL(k_cc_unit, dim3(blocks_of((size_t)m * 6 * R, 256)), dim3(256), 0, s, m, R, fr.io.d_fixed, dq + c0, B);
+		},
+		[&](int, int, int R, const CovFront&, CcWork& wk) { // (wk.Y is free once the chunk is solved: the chunk of pose_cols)
+			if (pose_cols) cc_pose_out(ctx, 6, m, R, wk.Xo, wk.Y);
+			if (joint) hipLaunchKernelGGL(k_cc_rows, dim3(blocks_of((size_t)k * 6 * R, 256)), dim3(256), 0, s, k, R, dq, wk.Xo, Jd);
+		},
+		[&](int, int, int R, const CovFront& fr, CcWork& wk) {
+			if (want_feat) cc_feat(ctx, 6, fr, R, nullptr, n, nullptr, wk.Xo, F);
+		},
+		[&](int c0, int kcur, int R, CcWork& wk) {
+			if (pose_cols) d2h(ctx, pose_cols + (size_t)c0 * m * 36, wk.Y, (size_t)m * 6 * R * sizeof(double));
+			if (want_feat) d2h(ctx, feat_cols + (size_t)c0 * n * 18, F, (size_t)kcur * n * 18 * sizeof(double));
+			if (!joint) return;
 			d2h(ctx, hj.data(), Jd, (size_t)k * 6 * R * sizeof(double));
 			for (int row = 0; row < 6 * k; row++) memcpy(&joint[(size_t)row * 6 * k + 6 * c0], &hj[(size_t)row * R], (size_t)R * sizeof(double));
-		}
-		LSFM_CHECK_HIP(hipStreamSynchronize(s));
-		float ms = 0.0f;
-		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); t_solve += ms;
-		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[1], ev[2])); t_feat += ms;
-	}
-	if (joint)
-	{
-		// the chunks' columns are in place; exactly symmetric: block (a, b), a < b, from column b and mirrored; the diagonal blocks (X + X^T) / 2
-		const size_t n6 = (size_t)k * 6;
-		for (size_t i = 0; i < n6; i++)
-			for (size_t j = i; j < n6; j++)
-			{
-				const double v = i / 6 == j / 6 ? 0.5 * (joint[i * n6 + j] + joint[j * n6 + i]) : joint[i * n6 + j];
-				joint[i * n6 + j] = joint[j * n6 + i] = v;
-			}
-	}
-	if (steps_out) *steps_out = most_steps;
-	if (times)
-	{
-		float ms = 0.0f;
-		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, fr.ev[0], fr.ev[1])); times[0] = ms;
-		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, fr.ev[1], fr.ev[2])); times[1] = ms;
-		times[2] = t_solve; times[3] = t_feat;
-	}
-	return undone ? LSFM_NOT_CONVERGED : LSFM_OK;
+		});
+	if (joint && steps > 0) symmetrise_joint(joint, k, 6);
+	return rc;
 }
 
 } // namespace lsfm

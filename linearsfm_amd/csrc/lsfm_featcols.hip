@@ -11,7 +11,9 @@
 // 6 |P(f) u P(g)| columns and end in a cancelling sum of large marginals.  Here a pair costs 3 columns, nothing cancels, and the
 // refinement's relative criterion acts on the scale of the difference.
 //
-// A chunk is 64 groups = 192 columns: the slabs and launch shapes of a full chunk of lsfm_map_covariance_columns.
+// A chunk is 64 groups = 192 columns: the slabs and launch shapes of a full chunk of lsfm_map_covariance_columns.  The chunk loop
+// is that call's too (cc_run, lsfm_cov.hpp, at width 3): the two entries below are its callables -- the right-hand sides k_fc_rhs, the
+// kernels behind a chunk's solve and the downloads.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -131,81 +133,25 @@ __global__ void __launch_bounds__(LSFM_WAVE) k_fc_gate(int R, const int* __restr
 	d2[a] = res;
 }
 
-// What the two entries share: the factor of the camera system, then per chunk of FC_KC groups the right-hand sides, the refined solve
-// and the caller's part -- prep() allocates the call's own outputs on the device once the factor stands, emit(c0, kcur, R, dgrp, fr, wk)
-// enqueues the caller's kernels behind the solve of a chunk, fetch(c0, kcur, R, wk) downloads what they wrote.
-template <class Prep, class Emit, class Fetch>
-int fc_run(lsfm_context* ctx, const lsfm_map* map, bool mono, const std::vector<int>& grp, size_t extra_doubles, int* steps_out, double* last_corr,
-           double* times, Prep&& prep, Emit&& emit, Fetch&& fetch)
-{
-	const int k = (int)grp.size() / 2;
-	if (steps_out) *steps_out = 0;
-	CovFront fr;
+// The column groups of a call on the device, and what both entries hand cc_run (lsfm_cov.hpp) as the right-hand sides of a chunk.
+struct FcGroups {
+	DevBuf buf;
+	int* d = nullptr; // [2 k]
+	void upload(lsfm_context* ctx, const std::vector<int>& grp)
 	{
-		// the residual needs the row-sorted list of S's blocks whatever product the context's CG is set to (lsfm_set_spmv_variant)
-		struct Keep { lsfm_context* c; int v; ~Keep() { c->pcg.spmv_variant = v; } } keep{ ctx, ctx->pcg.spmv_variant };
-		ctx->pcg.spmv_variant = 2;
-		cov_front(ctx, map, mono, fr);
+		d = buf.get<int>(grp.size());
+		h2d(ctx, d, grp.data(), grp.size() * sizeof(int));
 	}
-	const SolveIO& io = fr.io;
-	const SchurSystem& sy = fr.sy;
-	hipStream_t s = ctx->stream;
-	LSFM_CHECK_HIP(hipGetLastError());
-	const int floored = cov_front_status(ctx, fr);
-	if (floored > 0) return floored; // the factor is of a perturbed S: nothing is written
-	if (!sy.gent) LSFM_FAIL(LSFM_ERR_INTERNAL, "the camera system has no row-sorted block list");
-	const int M = fr.ch.M;
-	const int kc = std::min(k, FC_KC), Rmax = 3 * kc;
+	const int* of(int c0) const { return d + 2 * (size_t)c0; }
+	CcChunkRhs rhs(lsfm_context* ctx) const
 	{
-		const size_t need = (3 * (size_t)M * 6 * Rmax + extra_doubles) * sizeof(double);
-		size_t free_b = 0, total_b = 0;
-		if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b)
-			throw Error{ LSFM_ERR_OOM, "out of device memory: the columns of " + std::to_string(kc) + " features or pairs need " + std::to_string(need) + " bytes, " + std::to_string(free_b) + " are free" };
+		return [this, ctx](int c0, int kcur, int R, const CovFront& fr, double* B) {
+			const SolveIO& io = fr.io;
+			dev_zero(ctx, B, (size_t)fr.ch.M * 6 * R * sizeof(double));
+			hipLaunchKernelGGL(k_fc_rhs, dim3(kcur), dim3(LSFM_WAVE), 0, ctx->stream, R, of(c0), io.fptr, io.photo, io.W, fr.sy.IV, io.d_fixed, B);
+		};
 	}
-	CcWork wk;
-	wk.alloc(M, Rmax);
-	DevBuf bG;
-	int* dgrp = bG.get<int>(2 * (size_t)k);
-	h2d(ctx, dgrp, grp.data(), 2 * (size_t)k * sizeof(int));
-	prep();
-	hipEvent_t ev[3] = { ctx->pool_event(), ctx->pool_event(), ctx->pool_event() };
-	int most_steps = 0;
-	bool undone = false;
-	double t_solve = 0.0, t_emit = 0.0;
-	for (int c0 = 0; c0 < k; c0 += kc)
-	{
-		const int kcur = std::min(kc, k - c0), R = 3 * kcur;
-		const size_t cells = (size_t)M * 6 * R;
-		const int* g = dgrp + 2 * (size_t)c0;
-		LSFM_CHECK_HIP(hipEventRecord(ev[0], s));
-		const CcOutcome oc = cc_solve_refine(ctx, fr, R, wk, [&](double* B) {
-			dev_zero(ctx, B, cells * sizeof(double));
-			hipLaunchKernelGGL(k_fc_rhs, dim3(kcur), dim3(LSFM_WAVE), 0, s, R, g, io.fptr, io.photo, io.W, sy.IV, io.d_fixed, B);
-		});
-		most_steps = std::max(most_steps, oc.steps);
-		undone = undone || oc.undone;
-		if (last_corr)
-			for (int a = 0; a < kcur; a++) last_corr[c0 + a] = *std::max_element(wk.ratio.begin() + 3 * a, wk.ratio.begin() + 3 * a + 3);
-		LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
-		emit(c0, kcur, R, g, fr, wk);
-		LSFM_CHECK_HIP(hipEventRecord(ev[2], s));
-		LSFM_CHECK_HIP(hipGetLastError());
-		fetch(c0, kcur, R, wk);
-		LSFM_CHECK_HIP(hipStreamSynchronize(s));
-		float ms = 0.0f;
-		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); t_solve += ms;
-		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[1], ev[2])); t_emit += ms;
-	}
-	if (steps_out) *steps_out = most_steps;
-	if (times)
-	{
-		float ms = 0.0f;
-		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, fr.ev[0], fr.ev[1])); times[0] = ms;
-		LSFM_CHECK_HIP(hipEventElapsedTime(&ms, fr.ev[1], fr.ev[2])); times[1] = ms;
-		times[2] = t_solve; times[3] = t_emit;
-	}
-	return undone ? LSFM_NOT_CONVERGED : LSFM_OK;
-}
+};
 
 } // namespace
 
@@ -228,24 +174,27 @@ int map_covariance_feature_columns(lsfm_context* ctx, const lsfm_map* map, bool 
 	}
 	const int kc = std::min(k, FC_KC);
 	const size_t nF = feat_cols ? (size_t)n * 9 * kc : 0, nJ = joint ? (size_t)kc * k * 9 : 0;
+	FcGroups dg;
 	DevBuf bF, bJ, bQ;
 	double *F = nullptr, *Jd = nullptr;
 	int* dq = nullptr;
 	std::vector<double> hj(nJ);
-	int steps = 0; // (> 0: the results were written)
-	if (steps_out) *steps_out = 0;
-	const int rc = fc_run(ctx, map, mono, grp, nF + nJ, &steps, last_corr, times,
-		[&]() {
+	int own_steps = 0;
+	int& steps = steps_out ? *steps_out : own_steps; // (> 0: the results were written)
+	const int rc = cc_run(ctx, map, mono, CcCall{ k, 3, FC_KC, nF + nJ, "features or pairs" }, &steps, last_corr, times,
+		[&](const CovFront&) {
+			dg.upload(ctx, grp);
 			if (feat_cols) F = bF.get<double>(nF);
 			if (!joint) return;
 			Jd = bJ.get<double>(nJ);
 			dq = bQ.get<int>(k);
 			h2d(ctx, dq, feats, (size_t)k * sizeof(int));
 		},
-		[&](int c0, int kcur, int R, const int* g, const CovFront& fr, CcWork& wk) {
+		dg.rhs(ctx), nullptr,
+		[&](int c0, int kcur, int R, const CovFront& fr, CcWork& wk) {
 			if (pose_cols) cc_pose_out(ctx, 3, m, R, wk.Xo, wk.Y);
-			if (feat_cols) cc_feat(ctx, 3, fr, R, nullptr, n, g, wk.Xo, F);
-			if (joint) cc_feat(ctx, 3, fr, R, dq, k, g, wk.Xo, Jd); // the rows of the k requested features alone
+			if (feat_cols) cc_feat(ctx, 3, fr, R, nullptr, n, dg.of(c0), wk.Xo, F);
+			if (joint) cc_feat(ctx, 3, fr, R, dq, k, dg.of(c0), wk.Xo, Jd); // the rows of the k requested features alone
 		},
 		[&](int c0, int kcur, int R, CcWork& wk) {
 			if (pose_cols) d2h(ctx, pose_cols + (size_t)c0 * m * 18, wk.Y, (size_t)m * 6 * R * sizeof(double));
@@ -256,18 +205,7 @@ int map_covariance_feature_columns(lsfm_context* ctx, const lsfm_map* map, bool 
 				for (int b = 0; b < k; b++)
 					for (int i = 0; i < 3; i++) memcpy(&joint[((size_t)3 * b + i) * 3 * k + 3 * (size_t)(c0 + a)], &hj[((size_t)a * k + b) * 9 + 3 * i], 3 * sizeof(double));
 		});
-	if (steps_out) *steps_out = steps;
-	if (joint && steps > 0)
-	{
-		// exactly symmetric by lsfm_map_covariance_columns' rule: block (a, b), a < b, from column b and mirrored; a diagonal block (X + X^T) / 2
-		const size_t n3 = (size_t)k * 3;
-		for (size_t i = 0; i < n3; i++)
-			for (size_t j = i; j < n3; j++)
-			{
-				const double v = i / 3 == j / 3 ? 0.5 * (joint[i * n3 + j] + joint[j * n3 + i]) : joint[i * n3 + j];
-				joint[i * n3 + j] = joint[j * n3 + i] = v;
-			}
-	}
+	if (joint && steps > 0) symmetrise_joint(joint, k, 3);
 	return rc;
 }
 
@@ -285,23 +223,25 @@ int map_feature_pair_gate(lsfm_context* ctx, const lsfm_map* map, bool mono, con
 		for (int i = 0; i < 3; i++) dx[3 * (size_t)a + i] = map->stVal[(size_t)6 * m + 3 * (size_t)f + i] - map->stVal[(size_t)6 * m + 3 * (size_t)g + i];
 	}
 	const int kc = std::min(K, FC_KC);
+	FcGroups dg;
 	DevBuf bX, bD, bC;
 	double *ddx = nullptr, *dd2 = nullptr, *dcov = nullptr;
-	const int rc = fc_run(ctx, map, mono, grp, 13 * (size_t)K, steps_out, last_corr, times,
-		[&]() {
+	return cc_run(ctx, map, mono, CcCall{ K, 3, FC_KC, 13 * (size_t)K, "features or pairs" }, steps_out, last_corr, times,
+		[&](const CovFront&) {
+			dg.upload(ctx, grp);
 			ddx = bX.get<double>(3 * (size_t)K);
 			h2d(ctx, ddx, dx.data(), 3 * (size_t)K * sizeof(double));
 			if (d2) dd2 = bD.get<double>(kc);
 			if (cov_diff) dcov = bC.get<double>(9 * (size_t)kc);
 		},
-		[&](int c0, int kcur, int R, const int* g, const CovFront& fr, CcWork& wk) {
-			hipLaunchKernelGGL(k_fc_gate, dim3(kcur), dim3(LSFM_WAVE), 0, ctx->stream, R, g, fr.io.fptr, fr.io.photo, fr.io.W, fr.sy.IV, wk.Xo, ddx + 3 * (size_t)c0, dd2, dcov);
+		dg.rhs(ctx), nullptr,
+		[&](int c0, int kcur, int R, const CovFront& fr, CcWork& wk) {
+			hipLaunchKernelGGL(k_fc_gate, dim3(kcur), dim3(LSFM_WAVE), 0, ctx->stream, R, dg.of(c0), fr.io.fptr, fr.io.photo, fr.io.W, fr.sy.IV, wk.Xo, ddx + 3 * (size_t)c0, dd2, dcov);
 		},
 		[&](int c0, int kcur, int R, CcWork&) {
 			if (d2) d2h(ctx, d2 + c0, dd2, (size_t)kcur * sizeof(double));
 			if (cov_diff) d2h(ctx, cov_diff + 9 * (size_t)c0, dcov, 9 * (size_t)kcur * sizeof(double));
 		});
-	return rc;
 }
 
 } // namespace lsfm

@@ -189,10 +189,8 @@ int gn_run(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, lsfm_map* 
 		if (feat && n_asm == 0) gn_feature_check(ctx, maps, c); // (V does not change during the call)
 		if (robust && timing)
 		{
-			float ms = 0.0f;
-			LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev.chi2[0], ev.chi2[1]));
-			t_chi2 += ms;
-			if (feat) { LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev.fill[0], ev.fill[1])); t_fill += ms; }
+			t_chi2 += event_ms(ev.chi2[0], ev.chi2[1]);
+			if (feat) t_fill += event_ms(ev.fill[0], ev.fill[1]);
 		}
 		t_asm += gn_wall() - ta; n_asm++;
 		return F;
@@ -364,53 +362,30 @@ int gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, cons
 	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[3], s));
 	if (timing) LSFM_CHECK_HIP(hipStreamSynchronize(s));
 	const double tw2 = gn_wall();
-	lsfm_map g;
-	memset(&g, 0, sizeof g);
-	g.m = M; g.n = NFG; g.nU = co.nUo; g.nW = co.nWo;
-	g.Ref = x->Ref; g.FRef = x->FRef; g.ScaP = x->ScaP; g.Fix = x->Fix; g.Sign = x->Sign; g.FScaP = x->FScaP; g.FFix = x->FFix;
-	g.stno = host_alloc<int>(c.RS); g.stVal = host_alloc<double>(c.RS);
-	g.U = host_alloc<double>((size_t)g.nU * 36); g.Ui = host_alloc<int>(g.nU); g.Uj = host_alloc<int>(g.nU);
-	g.W = host_alloc<double>((size_t)g.nW * 18); g.photo = host_alloc<int>(g.nW); g.feature = host_alloc<int>(g.nW);
-	g.V = host_alloc<double>((size_t)NFG * 9); g.FBlock = host_alloc<int>(NFG);
-	g.pose_origin = host_alloc<int>(M);
-	if (!g.stno || !g.stVal || !g.U || !g.Ui || !g.Uj || !g.W || !g.photo || !g.feature || !g.V || !g.FBlock || !g.pose_origin)
+	MapOut G;
+	map_new(G.g, x, M, NFG, co.nUo, co.nWo, true);
+	lsfm_map& g = G.g;
+	std::copy(x->stno, x->stno + c.RS, g.stno); std::copy(x->stVal, x->stVal + c.RS, g.stVal);
+	std::copy(co.Ui.begin(), co.Ui.end(), g.Ui); std::copy(co.Uj.begin(), co.Uj.end(), g.Uj);
+	std::copy(co.photo.begin(), co.photo.end(), g.photo); std::copy(co.feature.begin(), co.feature.end(), g.feature);
+	std::copy(co.FBlock.begin(), co.FBlock.end(), g.FBlock); std::copy(st.origin.begin(), st.origin.end(), g.pose_origin);
+	if (g.nU) d2h(ctx, g.U, c.co.Uo, (size_t)g.nU * 36 * sizeof(double));
+	if (g.nW) d2h(ctx, g.W, c.co.Wo, (size_t)g.nW * 18 * sizeof(double));
+	if (NFG) d2h(ctx, g.V, c.VJ, (size_t)NFG * 9 * sizeof(double));
+	if (obj) d2h(ctx, obj, c.Fsum, sizeof(double));
+	if (b)
 	{
-		lsfm_map_release(&g);
-		LSFM_FAIL(LSFM_ERR_OOM, "gn linearise: out of host memory for the map");
+		d2h(ctx, b, c.ea, (size_t)M * 6 * sizeof(double));
+		if (NFG) d2h(ctx, b + (size_t)M * 6, c.eb, (size_t)NFG * 3 * sizeof(double));
 	}
-	try
-	{
-		std::copy(x->stno, x->stno + c.RS, g.stno); std::copy(x->stVal, x->stVal + c.RS, g.stVal);
-		std::copy(co.Ui.begin(), co.Ui.end(), g.Ui); std::copy(co.Uj.begin(), co.Uj.end(), g.Uj);
-		std::copy(co.photo.begin(), co.photo.end(), g.photo); std::copy(co.feature.begin(), co.feature.end(), g.feature);
-		std::copy(co.FBlock.begin(), co.FBlock.end(), g.FBlock); std::copy(st.origin.begin(), st.origin.end(), g.pose_origin);
-		if (g.nU) d2h(ctx, g.U, c.co.Uo, (size_t)g.nU * 36 * sizeof(double));
-		if (g.nW) d2h(ctx, g.W, c.co.Wo, (size_t)g.nW * 18 * sizeof(double));
-		if (NFG) d2h(ctx, g.V, c.VJ, (size_t)NFG * 9 * sizeof(double));
-		if (obj) d2h(ctx, obj, c.Fsum, sizeof(double));
-		if (b)
-		{
-			d2h(ctx, b, c.ea, (size_t)M * 6 * sizeof(double));
-			if (NFG) d2h(ctx, b + (size_t)M * 6, c.eb, (size_t)NFG * 3 * sizeof(double));
-		}
-		LSFM_CHECK_HIP(hipStreamSynchronize(s));
-		if (times)
-		{
-			float ms[3] = { 0.0f, 0.0f, 0.0f };
-			for (int i = 0; i < 3; i++) LSFM_CHECK_HIP(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
-			for (int i = 0; i < 3; i++) times[i] = ms[i];
-		}
-	}
-	catch (...)
-	{
-		lsfm_map_release(&g);
-		throw;
-	}
+	LSFM_CHECK_HIP(hipStreamSynchronize(s));
+	if (times)
+		for (int i = 0; i < 3; i++) times[i] = event_ms(ev[i], ev[i + 1]);
 	if (counts) { counts[0] = c.NWJ; counts[1] = co.nWo; counts[2] = c.NUJ; counts[3] = co.nUo; }
 	if (timing)
 		fprintf(stderr, "lsfm_gn_linearise: %d maps, %d poses, %d features, W %d -> %d blocks, U %d -> %d blocks; structure + upload %.2f ms, assembly + coalescing "
 		                "%.2f ms, download %.2f ms, call %.2f ms\n", N, M, NFG, c.NWJ, co.nWo, c.NUJ, co.nUo, tw1 - tw0, tw2 - tw1, gn_wall() - tw2, gn_wall() - tw0);
-	*out = g;
+	G.give(out);
 	return LSFM_OK;
 }
 

@@ -286,13 +286,10 @@ extern "C" int lsfm_gn_structure(const lsfm_map* maps, int N, int type, const ls
 	for (int k = 0; k < N; k++)
 	{
 		// (the device calls hand gn_structure maps that batch_upload has checked; here the same checks come from system_check)
-		HostSystem h;
-		h.m = maps[k].m; h.n = maps[k].n; h.nU = maps[k].nU; h.nW = maps[k].nW;
-		h.Ui = maps[k].Ui; h.Uj = maps[k].Uj; h.photo = maps[k].photo; h.feature = maps[k].feature;
 		std::vector<int> fptr;
 		const char* bad = nullptr;
-		if (system_check(h, false, fptr, &bad) != LSFM_OK) return fail(bad ? bad : "malformed map");
-		if ((h.m || h.n) && !maps[k].stno) return fail("null index array");
+		if (system_check(host_system_of(maps[k], false), false, fptr, &bad) != LSFM_OK) return fail(bad ? bad : "malformed map");
+		if ((maps[k].m || maps[k].n) && !maps[k].stno) return fail("null index array");
 	}
 	GnStructure st;
 	std::string msg;

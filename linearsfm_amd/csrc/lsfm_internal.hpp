@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/lsfm.h"
+#include "lsfm_map.hpp"
 
 namespace lsfm {
 
@@ -36,6 +37,13 @@ struct EarlyPattern; // an early pattern build in flight (lsfm_pattern.hip)
 			throw ::lsfm::Error{ LSFM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__) + " at " + __FILE__ + ":" + std::to_string(__LINE__) }; \
 	} while (0)
 #define LSFM_FAIL(code, m) throw ::lsfm::Error{ (code), std::string(m) + " at " + __FILE__ + ":" + std::to_string(__LINE__) }
+// the milliseconds between two recorded events, both complete
+inline double event_ms(hipEvent_t a, hipEvent_t b)
+{
+	float ms = 0.0f;
+	LSFM_CHECK_HIP(hipEventElapsedTime(&ms, a, b));
+	return ms;
+}
 
 // bump allocator over one hipMalloc'ed slab: maps and work space of a level are carved out without any
 // hipMalloc/hipFree (both synchronise) inside the timed region.
@@ -424,8 +432,11 @@ void fill_async(hipStream_t s, void* d, int byte, size_t bytes); // (a kernel of
 // ---- batches (lsfm_batch.hip) -------------------------------------------------------------------------------
 void batch_upload(lsfm_context* ctx, Arena& ar, const lsfm_map* maps, int N, bool mono, DevBatch& out);
 void batch_download_map(lsfm_context* ctx, const DevBatch& b, int k, bool mono, lsfm_map* out);
-// the allocator of every map the library hands out (lsfm_map_release frees with free())
-template <class T> inline T* host_alloc(size_t n) { return static_cast<T*>(malloc((n ? n : 1) * sizeof(T))); }
+// map_alloc (lsfm_map.hpp: the allocator of every map the library hands out) for an entry point: the map, or an Error (LSFM_ERR_OOM)
+inline void map_new(lsfm_map& g, const lsfm_map* like, int m, int n, int nU, int nW, bool pose_origin)
+{
+	if (map_alloc(g, like, m, n, nU, nW, pose_origin) != LSFM_OK) throw Error{ LSFM_ERR_OOM, "out of host memory for the merged map" };
+}
 struct CopyBatch;
 // uploads pose_off / feat_off, fills pose_map / feat_map (cb != null: the uploads join the caller's batch, which then calls batch_fill_maps)
 void batch_set_offsets(lsfm_context* ctx, Arena& ar, DevBatch& b, CopyBatch* cb = nullptr);

@@ -209,10 +209,7 @@ int map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned char*
 {
 	const int m = map->m, n = map->n;
 	// ---- arguments (host) ----
-	HostSystem h;
-	h.m = m; h.n = n; h.nU = map->nU; h.nW = map->nW;
-	h.Ui = map->Ui; h.Uj = map->Uj; h.photo = map->photo; h.feature = map->feature;
-	h.U = map->U; h.W = map->W; h.V = map->V;
+	const HostSystem h = host_system_of(*map, true);
 	const std::vector<int> fptr = system_fptr(h);
 	std::vector<int> hdrop(n + 1, 0);
 	int nkeep = 0, nWkeep = 0;
@@ -246,35 +243,21 @@ int map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned char*
 	d2h(ctx, &err, d_err, sizeof(int));
 	if (err) LSFM_FAIL(LSFM_ERR_NOT_SPD, "the V block of a feature to be marginalised out is not positive definite");
 	// ---- the map (library-allocated) ----
-	lsfm_map g;
-	memset(&g, 0, sizeof g);
-	g.Ref = map->Ref; g.FRef = map->FRef; g.m = m; g.n = nkeep; g.nU = nnzb; g.nW = nWkeep;
-	g.ScaP = map->ScaP; g.Fix = map->Fix; g.Sign = map->Sign; g.FScaP = map->FScaP; g.FFix = map->FFix;
-	const size_t r = (size_t)6 * m + (size_t)3 * nkeep;
-	g.stno = host_alloc<int>(r); g.stVal = host_alloc<double>(r);
-	g.U = host_alloc<double>((size_t)nnzb * 36); g.Ui = host_alloc<int>(nnzb); g.Uj = host_alloc<int>(nnzb);
-	g.W = host_alloc<double>((size_t)nWkeep * 18); g.photo = host_alloc<int>(nWkeep); g.feature = host_alloc<int>(nWkeep);
-	g.V = host_alloc<double>((size_t)nkeep * 9); g.FBlock = host_alloc<int>(nkeep);
-	if (map->pose_origin) { g.pose_origin = host_alloc<int>(m); memcpy(g.pose_origin, map->pose_origin, (size_t)m * sizeof(int)); }
-	try
+	MapOut G;
+	map_new(G.g, map, m, nkeep, nnzb, nWkeep, map->pose_origin != nullptr);
+	lsfm_map& g = G.g;
+	if (map->pose_origin) memcpy(g.pose_origin, map->pose_origin, (size_t)m * sizeof(int));
+	d2h(ctx, g.U, oU, (size_t)nnzb * 36 * sizeof(double));
+	d2h(ctx, g.Ui, oUi, (size_t)nnzb * sizeof(int));
+	d2h(ctx, g.Uj, oUj, (size_t)nnzb * sizeof(int));
+	LSFM_CHECK_HIP(hipEventRecord(ev[4], s));
+	LSFM_CHECK_HIP(hipEventSynchronize(ev[4]));
+	if (times)
 	{
-		d2h(ctx, g.U, oU, (size_t)nnzb * 36 * sizeof(double));
-		d2h(ctx, g.Ui, oUi, (size_t)nnzb * sizeof(int));
-		d2h(ctx, g.Uj, oUj, (size_t)nnzb * sizeof(int));
-		LSFM_CHECK_HIP(hipEventRecord(ev[4], s));
-		LSFM_CHECK_HIP(hipEventSynchronize(ev[4]));
-		if (times)
-		{
-			const int from[3] = { 0, 2, 3 }, to[3] = { 2, 3, 4 };
-			for (int k = 0; k < 3; k++)
-			{
-				float ms = 0.0f;
-				LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[from[k]], ev[to[k]]));
-				times[k] = ms;
-			}
-		}
+		times[0] = event_ms(ev[0], ev[2]);
+		times[1] = event_ms(ev[2], ev[3]);
+		times[2] = event_ms(ev[3], ev[4]);
 	}
-	catch (...) { lsfm_map_release(&g); throw; }
 	memcpy(g.stno, map->stno, (size_t)6 * m * sizeof(int));
 	memcpy(g.stVal, map->stVal, (size_t)6 * m * sizeof(double));
 	int p = 0, q = 0;
@@ -291,7 +274,7 @@ int map_marginalise(lsfm_context* ctx, const lsfm_map* map, const unsigned char*
 		g.FBlock[p] = q;
 		p++; q += len;
 	}
-	*out = g;
+	G.give(out);
 	return LSFM_OK;
 }
 
@@ -344,12 +327,7 @@ void marg_export_reduced(lsfm_context* ctx, const DevBatch& b, bool mono, Arena&
 	int err = 0;
 	d2h(ctx, &err, d_err, sizeof(int)); // (synchronises: the caller hands dst to another library / stream next)
 	if (times)
-		for (int k = 0; k < 5; k++)
-		{
-			float ms = 0.0f;
-			LSFM_CHECK_HIP(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-			times[k] = ms;
-		}
+		for (int k = 0; k < 5; k++) times[k] = event_ms(ev[k], ev[k + 1]);
 	if (err) LSFM_FAIL(LSFM_ERR_NOT_SPD, "the V block of a feature to be marginalised out is not positive definite");
 }
 

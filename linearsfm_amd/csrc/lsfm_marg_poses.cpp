@@ -172,12 +172,9 @@ extern "C" int lsfm_marg_pose_structure(const lsfm_map* map, int mono, const uns
 	std::vector<unsigned char> dr;
 	std::string msg;
 	if (pose_marg_flags(map, mono == 1, keep_pose, drop_feat, dr, msg) != LSFM_OK) return fail(msg);
-	HostSystem h;
-	h.m = map->m; h.n = map->n; h.nU = map->nU; h.nW = map->nW;
-	h.Ui = map->Ui; h.Uj = map->Uj; h.photo = map->photo; h.feature = map->feature;
 	std::vector<int> fptr;
 	const char* bad = nullptr;
-	if (system_check(h, false, fptr, &bad) != LSFM_OK) return fail(bad ? bad : "malformed map");
+	if (system_check(host_system_of(*map, false), false, fptr, &bad) != LSFM_OK) return fail(bad ? bad : "malformed map");
 	const std::vector<unsigned long long> keys = marg_pattern_host(map, fptr, dr.data());
 	std::vector<int> ui(keys.size()), uj(keys.size());
 	for (size_t k = 0; k < keys.size(); k++) { ui[k] = (int)(keys[k] >> 32); uj[k] = (int)(keys[k] & 0xffffffffull); }

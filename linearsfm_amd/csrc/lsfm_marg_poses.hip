@@ -177,14 +177,13 @@ int map_marginalise_poses(lsfm_context* ctx, const lsfm_map* map, bool mono, con
 	hipEvent_t ev[4] = { ctx->pool_event(), ctx->pool_event(), ctx->pool_event(), ctx->pool_event() }; // start | stage A on the host | sweeps done | downloaded
 	LSFM_CHECK_HIP(hipEventRecord(ev[0], s));
 	// ---- stage A: the features go, through the host ----
-	struct Hold { lsfm_map g; Hold() { memset(&g, 0, sizeof g); } ~Hold() { lsfm_map_release(&g); } } A;
+	MapOut A;
 	{
 		const int rc = map_marginalise(ctx, map, drop.data(), &A.g, nullptr);
 		if (rc != LSFM_OK) return rc;
 	}
 	const lsfm_map& a = A.g;
 	LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
-	auto ms_between = [&](hipEvent_t x, hipEvent_t y) { float ms = 0.0f; LSFM_CHECK_HIP(hipEventElapsedTime(&ms, x, y)); return (double)ms; };
 	// ---- structure ----
 	PoseMargStructure st;
 	pose_marg_structure(m, a.nU, a.Ui, a.Uj, keep_pose, st);
@@ -195,13 +194,12 @@ int map_marginalise_poses(lsfm_context* ctx, const lsfm_map* map, bool mono, con
 	{
 		// nothing to eliminate: stage A's map is the result
 		LSFM_CHECK_HIP(hipEventSynchronize(ev[1]));
-		if (times) times[0] = ms_between(ev[0], ev[1]);
+		if (times) times[0] = event_ms(ev[0], ev[1]);
 		for (int e = 0; e < a.nU; e++) // the diagonal blocks from their upper triangle, as k_pm_emit writes them
 			if (a.Ui[e] == a.Uj[e])
 				for (int r = 1; r < 6; r++)
 					for (int c = 0; c < r; c++) A.g.U[(size_t)e * 36 + r * 6 + c] = a.U[(size_t)e * 36 + c * 6 + r];
-		*out = A.g;
-		memset(&A.g, 0, sizeof A.g);
+		A.give(out);
 		return LSFM_OK;
 	}
 	// the pose-only sub-map of D (no gauge scalar is in D: mono = false)
@@ -319,32 +317,21 @@ int map_marginalise_poses(lsfm_context* ctx, const lsfm_map* map, bool mono, con
 	                   dI + 4 * (size_t)nout, dI + 5 * (size_t)nout, dU1, T, dO);
 	LSFM_CHECK_HIP(hipGetLastError());
 	// ---- the map (library-allocated) ----
-	lsfm_map g;
-	memset(&g, 0, sizeof g);
 	const int n = a.n, nW = a.nW;
-	g.Ref = map->Ref; g.FRef = map->FRef; g.m = nK; g.n = n; g.nU = nout; g.nW = nW;
-	g.ScaP = map->ScaP; g.Fix = map->Fix; g.Sign = map->Sign; g.FScaP = map->FScaP; g.FFix = map->FFix;
-	const size_t r = (size_t)6 * nK + (size_t)3 * n;
-	g.stno = host_alloc<int>(r); g.stVal = host_alloc<double>(r);
-	g.U = host_alloc<double>((size_t)nout * 36); g.Ui = host_alloc<int>(nout); g.Uj = host_alloc<int>(nout);
-	g.W = host_alloc<double>((size_t)nW * 18); g.photo = host_alloc<int>(nW); g.feature = host_alloc<int>(nW);
-	g.V = host_alloc<double>((size_t)n * 9); g.FBlock = host_alloc<int>(n);
-	if (map->pose_origin) g.pose_origin = host_alloc<int>(nK);
-	try
+	MapOut G;
+	map_new(G.g, map, nK, n, nout, nW, map->pose_origin != nullptr);
+	lsfm_map& g = G.g;
+	d2h(ctx, g.U, dO, (size_t)nout * 36 * sizeof(double));
+	LSFM_CHECK_HIP(hipEventRecord(ev[3], s));
+	LSFM_CHECK_HIP(hipEventSynchronize(ev[3]));
+	if (times)
 	{
-		d2h(ctx, g.U, dO, (size_t)nout * 36 * sizeof(double));
-		LSFM_CHECK_HIP(hipEventRecord(ev[3], s));
-		LSFM_CHECK_HIP(hipEventSynchronize(ev[3]));
-		if (times)
-		{
-			times[0] = ms_between(ev[0], ev[1]);
-			times[1] = ms_between(ev[1], fr.ev[0]);
-			times[2] = ms_between(fr.ev[0], fr.ev[2]);
-			times[3] = ms_between(fr.ev[2], ev[2]);
-			times[4] = ms_between(ev[2], ev[3]);
-		}
+		times[0] = event_ms(ev[0], ev[1]);
+		times[1] = event_ms(ev[1], fr.ev[0]);
+		times[2] = event_ms(fr.ev[0], fr.ev[2]);
+		times[3] = event_ms(fr.ev[2], ev[2]);
+		times[4] = event_ms(ev[2], ev[3]);
 	}
-	catch (...) { lsfm_map_release(&g); throw; }
 	memcpy(g.Ui, st.oUi.data(), (size_t)nout * sizeof(int));
 	memcpy(g.Uj, st.oUj.data(), (size_t)nout * sizeof(int));
 	for (int k = 0; k < nK; k++)
@@ -361,7 +348,7 @@ int map_marginalise_poses(lsfm_context* ctx, const lsfm_map* map, bool mono, con
 	memcpy(g.feature, a.feature, (size_t)nW * sizeof(int));
 	memcpy(g.FBlock, a.FBlock, (size_t)n * sizeof(int));
 	for (int w = 0; w < nW; w++) g.photo[w] = st.local[a.photo[w]]; // (a kept feature is seen by kept poses alone)
-	*out = g;
+	G.give(out);
 	return LSFM_OK;
 }
 

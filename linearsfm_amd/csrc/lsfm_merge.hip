@@ -13,7 +13,7 @@
 //   k_gn_coalesce<18>      W': one lane per output block, its sources summed in registers in the structure's order, stored once
 //   k_merge_features       one lane per output feature: V' (members ascending; a class of one: a copy), the representative's label and
 //                          estimate, eta_c and sum_g r_g^T V_g r_g of a larger class
-//   -- the merged map goes through the host here: cov_front uploads it, reduces it and factors S' --
+//   -- the merged map goes through the host here (map_alloc / MapOut, lsfm_map.hpp): cov_front_rowsorted uploads it, reduces it and factors S' --
 //   k_merge_rhs            one work-group per class of more than one member and one COLUMN of two slabs per class (k_fc_rhs's shape): the
 //                          class's part of eta_p from the W runs of its merged-away members, and W'_c V'_c^-1 eta_c from its merged run
 //   k_merge_rowsum         a lane per pose scalar sums the columns in ascending order: eta_p and B.  No atomics: the same bits every time
@@ -199,13 +199,6 @@ template <class T> T* put(lsfm_context* ctx, DevBuf& b, const T* src, size_t cou
 	return d;
 }
 
-float ms_between(hipEvent_t a, hipEvent_t b)
-{
-	float ms = 0.0f;
-	LSFM_CHECK_HIP(hipEventElapsedTime(&ms, a, b));
-	return ms;
-}
-
 } // namespace
 
 int map_merge_features(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* pairs, int K, lsfm_map* out, double* d2, int* dof, int* rep,
@@ -215,11 +208,7 @@ int map_merge_features(lsfm_context* ctx, const lsfm_map* map, bool mono, const 
 	const int m = map->m, n = map->n, nW = map->nW;
 	if (!map->stno || !map->stVal) LSFM_FAIL(LSFM_ERR_ARG, "the map has no labels or no estimates");
 	// ---- arguments and structure (host) ----
-	HostSystem h;
-	h.m = m; h.n = n; h.nU = map->nU; h.nW = nW;
-	h.Ui = map->Ui; h.Uj = map->Uj; h.photo = map->photo; h.feature = map->feature;
-	h.U = map->U; h.W = map->W; h.V = map->V;
-	const std::vector<int> fptr = system_fptr(h);
+	const std::vector<int> fptr = system_fptr(host_system_of(*map, true));
 	if ((map->nU && !map->U) || (nW && !map->W) || (n && !map->V)) LSFM_FAIL(LSFM_ERR_ARG, "null value array");
 	MergeStructure st;
 	{
@@ -268,115 +257,94 @@ int map_merge_features(lsfm_context* ctx, const lsfm_map* map, bool mono, const 
 	if (no) hipLaunchKernelGGL(k_merge_features, grid(no), dim3(256), 0, s, no, dcp, dcm, dV, dX, dL, oV, oX, oL, eta, quad);
 	LSFM_CHECK_HIP(hipGetLastError());
 	// ---- the merged map (library-allocated), at y0 for now: this version hands it to cov_front through the host ----
-	lsfm_map g;
-	memset(&g, 0, sizeof g);
-	g.Ref = map->Ref; g.FRef = map->FRef; g.m = m; g.n = no; g.nU = map->nU; g.nW = nWo;
-	g.ScaP = map->ScaP; g.Fix = map->Fix; g.Sign = map->Sign; g.FScaP = map->FScaP; g.FFix = map->FFix;
-	try
+	MapOut G;
+	map_new(G.g, map, m, no, map->nU, nWo, map->pose_origin != nullptr);
+	lsfm_map& g = G.g;
+	if (map->pose_origin) memcpy(g.pose_origin, map->pose_origin, (size_t)m * sizeof(int));
+	memcpy(g.stno, map->stno, (size_t)6 * m * sizeof(int));
+	memcpy(g.stVal, map->stVal, (size_t)6 * m * sizeof(double));
+	memcpy(g.U, map->U, (size_t)map->nU * 36 * sizeof(double));
+	memcpy(g.Ui, map->Ui, (size_t)map->nU * sizeof(int));
+	memcpy(g.Uj, map->Uj, (size_t)map->nU * sizeof(int));
+	memcpy(g.photo, st.photo.data(), (size_t)nWo * sizeof(int));
+	memcpy(g.feature, st.feature.data(), (size_t)nWo * sizeof(int));
+	memcpy(g.FBlock, st.FBlock.data(), (size_t)no * sizeof(int));
+	d2h(ctx, g.W, oW, (size_t)nWo * 18 * sizeof(double));
+	d2h(ctx, g.V, oV, (size_t)no * 9 * sizeof(double));
+	d2h(ctx, g.stVal + (size_t)6 * m, oX, (size_t)no * 3 * sizeof(double));
+	d2h(ctx, g.stno + (size_t)6 * m, oL, (size_t)no * 3 * sizeof(int));
+	LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
+	LSFM_CHECK_HIP(hipStreamSynchronize(s)); // (the staged copies have left the host vectors before cov_front reuses the ring)
+	// ---- factor S' ----
+	CovFront fr;
+	const int floored = cov_front_rowsorted(ctx, &g, mono, fr);
+	if (floored > 0) return floored; // the factor is of a perturbed S': nothing is written, the staged map is released
+	const SolveIO& io = fr.io;
+	const int rows = 6 * m;
+	// ---- the right-hand side ----
+	DevBuf bBg, bAp, bAwp, bAph, bAW, bAr, bE, bT, bEp, bB, bXp, bYp, bYf, bPd, bFd, bD;
+	const int* dbigs = put(ctx, bBg, st.bigs.data(), (size_t)big);
+	const int* daptr = put(ctx, bAp, aptr.data(), aptr.size());
+	const int* dawptr = put(ctx, bAwp, awptr.data(), awptr.size());
+	const int* daphoto = put(ctx, bAph, aphoto.data(), aphoto.size());
+	const double* daW = put(ctx, bAW, aW.data(), aW.size());
+	const double* dar = put(ctx, bAr, ar.data(), ar.size());
+	const int cols = std::min(big, MG_COLS);
+	double* E = bE.get<double>((size_t)rows * cols);
+	double* T = bT.get<double>((size_t)rows * cols);
+	double* etaP = bEp.get<double>(rows);
+	double* B = bB.get<double>(rows);
+	const double* dxp = put(ctx, bXp, map->stVal, (size_t)rows);
+	double* yp = bYp.get<double>(rows);
+	double* yf = bYf.get<double>((size_t)no * 3);
+	double* pdot = bPd.get<double>(rows);
+	double* fdot = bFd.get<double>(no);
+	double* dd = bD.get<double>(3);
+	dev_zero(ctx, etaP, (size_t)rows * sizeof(double));
+	dev_zero(ctx, B, (size_t)rows * sizeof(double));
+	for (int k0 = 0; k0 < big; k0 += cols)
 	{
-		const size_t r = (size_t)6 * m + (size_t)3 * no;
-		g.stno = host_alloc<int>(r); g.stVal = host_alloc<double>(r);
-		g.U = host_alloc<double>((size_t)map->nU * 36); g.Ui = host_alloc<int>(map->nU); g.Uj = host_alloc<int>(map->nU);
-		g.W = host_alloc<double>((size_t)nWo * 18); g.photo = host_alloc<int>(nWo); g.feature = host_alloc<int>(nWo);
-		g.V = host_alloc<double>((size_t)no * 9); g.FBlock = host_alloc<int>(no);
-		if (map->pose_origin) g.pose_origin = host_alloc<int>(m);
-		if (!g.stno || !g.stVal || !g.U || !g.Ui || !g.Uj || !g.W || !g.photo || !g.feature || !g.V || !g.FBlock || (map->pose_origin && !g.pose_origin))
-			throw Error{ LSFM_ERR_OOM, "out of host memory for the merged map" };
-		if (map->pose_origin) memcpy(g.pose_origin, map->pose_origin, (size_t)m * sizeof(int));
-		memcpy(g.stno, map->stno, (size_t)6 * m * sizeof(int));
-		memcpy(g.stVal, map->stVal, (size_t)6 * m * sizeof(double));
-		memcpy(g.U, map->U, (size_t)map->nU * 36 * sizeof(double));
-		memcpy(g.Ui, map->Ui, (size_t)map->nU * sizeof(int));
-		memcpy(g.Uj, map->Uj, (size_t)map->nU * sizeof(int));
-		memcpy(g.photo, st.photo.data(), (size_t)nWo * sizeof(int));
-		memcpy(g.feature, st.feature.data(), (size_t)nWo * sizeof(int));
-		memcpy(g.FBlock, st.FBlock.data(), (size_t)no * sizeof(int));
-		d2h(ctx, g.W, oW, (size_t)nWo * 18 * sizeof(double));
-		d2h(ctx, g.V, oV, (size_t)no * 9 * sizeof(double));
-		d2h(ctx, g.stVal + (size_t)6 * m, oX, (size_t)no * 3 * sizeof(double));
-		d2h(ctx, g.stno + (size_t)6 * m, oL, (size_t)no * 3 * sizeof(int));
-		LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
-		LSFM_CHECK_HIP(hipStreamSynchronize(s)); // (the staged copies have left the host vectors before cov_front reuses the ring)
-		// ---- factor S' ----
-		CovFront fr;
-		{
-			// the residual needs the row-sorted list of S's blocks whatever product the context's CG is set to (lsfm_set_spmv_variant)
-			struct Keep { lsfm_context* c; int v; ~Keep() { c->pcg.spmv_variant = v; } } keep{ ctx, ctx->pcg.spmv_variant };
-			ctx->pcg.spmv_variant = 2;
-			cov_front(ctx, &g, mono, fr);
-		}
-		LSFM_CHECK_HIP(hipGetLastError());
-		const int floored = cov_front_status(ctx, fr);
-		if (floored > 0) { lsfm_map_release(&g); return floored; } // the factor is of a perturbed S': nothing is written
-		if (!fr.sy.gent) LSFM_FAIL(LSFM_ERR_INTERNAL, "the camera system has no row-sorted block list");
-		const SolveIO& io = fr.io;
-		const int rows = 6 * m;
-		// ---- the right-hand side ----
-		DevBuf bBg, bAp, bAwp, bAph, bAW, bAr, bE, bT, bEp, bB, bXp, bYp, bYf, bPd, bFd, bD;
-		const int* dbigs = put(ctx, bBg, st.bigs.data(), (size_t)big);
-		const int* daptr = put(ctx, bAp, aptr.data(), aptr.size());
-		const int* dawptr = put(ctx, bAwp, awptr.data(), awptr.size());
-		const int* daphoto = put(ctx, bAph, aphoto.data(), aphoto.size());
-		const double* daW = put(ctx, bAW, aW.data(), aW.size());
-		const double* dar = put(ctx, bAr, ar.data(), ar.size());
-		const int cols = std::min(big, MG_COLS);
-		double* E = bE.get<double>((size_t)rows * cols);
-		double* T = bT.get<double>((size_t)rows * cols);
-		double* etaP = bEp.get<double>(rows);
-		double* B = bB.get<double>(rows);
-		const double* dxp = put(ctx, bXp, map->stVal, (size_t)rows);
-		double* yp = bYp.get<double>(rows);
-		double* yf = bYf.get<double>((size_t)no * 3);
-		double* pdot = bPd.get<double>(rows);
-		double* fdot = bFd.get<double>(no);
-		double* dd = bD.get<double>(3);
-		dev_zero(ctx, etaP, (size_t)rows * sizeof(double));
-		dev_zero(ctx, B, (size_t)rows * sizeof(double));
-		for (int k0 = 0; k0 < big; k0 += cols)
-		{
-			const int kc = std::min(cols, big - k0);
-			dev_zero(ctx, E, (size_t)rows * kc * sizeof(double));
-			dev_zero(ctx, T, (size_t)rows * kc * sizeof(double));
-			hipLaunchKernelGGL(k_merge_rhs, dim3(kc), dim3(LSFM_WAVE), 0, s, k0, kc, dbigs, daptr, dawptr, daphoto, daW, dar, io.fptr, io.photo, io.W, fr.sy.IV, eta,
-			                   io.d_fixed, E, T);
-			hipLaunchKernelGGL(k_merge_rowsum, grid(rows), dim3(256), 0, s, rows, kc, E, T, etaP, B);
-		}
-		// ---- delta_p = S'^-1 B ----
-		CcWork wk;
-		wk.alloc(fr.ch.M, 1);
-		const CcOutcome oc = cc_solve_refine(ctx, fr, 1, wk, [&](double* dst) {
-			LSFM_CHECK_HIP(hipMemcpyAsync(dst, B, (size_t)rows * sizeof(double), hipMemcpyDeviceToDevice, s));
-		});
-		LSFM_CHECK_HIP(hipEventRecord(ev[2], s));
-		// ---- back-substitution and D^2 ----
-		if (no) hipLaunchKernelGGL(k_merge_backsub, grid(no), dim3(256), 0, s, no, io.fptr, io.photo, io.W, fr.sy.IV, eta, wk.Xo, oX, yf, fdot);
-		hipLaunchKernelGGL(k_merge_pose, grid(rows), dim3(256), 0, s, rows, dxp, wk.Xo, etaP, io.d_fixed, yp, pdot);
-		hipLaunchKernelGGL(k_merge_d2, dim3(1), dim3(MG_RED), 0, s, no, quad, fdot, rows, pdot, dd);
-		LSFM_CHECK_HIP(hipEventRecord(ev[3], s));
-		LSFM_CHECK_HIP(hipGetLastError());
-		double hd[3] = { 0.0, 0.0, 0.0 };
-		d2h(ctx, g.stVal, yp, (size_t)rows * sizeof(double));
-		d2h(ctx, g.stVal + (size_t)rows, yf, (size_t)no * 3 * sizeof(double));
-		d2h(ctx, hd, dd, sizeof hd);
-		LSFM_CHECK_HIP(hipEventRecord(ev[4], s));
-		LSFM_CHECK_HIP(hipEventSynchronize(ev[4]));
-		if (times)
-		{
-			times[0] = ms_between(ev[0], ev[1]);
-			times[1] = ms_between(ev[1], fr.ev[2]);
-			times[2] = ms_between(fr.ev[2], ev[2]);
-			times[3] = ms_between(ev[2], ev[3]);
-			times[4] = ms_between(ev[3], ev[4]);
-		}
-		if (d2) *d2 = hd[0];
-		if (dof) *dof = 3 * st.removed;
-		if (rep) memcpy(rep, st.rep.data(), (size_t)n * sizeof(int));
-		if (steps_out) *steps_out = oc.steps;
-		if (last_corr) last_corr[0] = wk.ratio[0];
-		*out = g;
-		return oc.undone ? LSFM_NOT_CONVERGED : LSFM_OK;
+		const int kc = std::min(cols, big - k0);
+		dev_zero(ctx, E, (size_t)rows * kc * sizeof(double));
+		dev_zero(ctx, T, (size_t)rows * kc * sizeof(double));
+		hipLaunchKernelGGL(k_merge_rhs, dim3(kc), dim3(LSFM_WAVE), 0, s, k0, kc, dbigs, daptr, dawptr, daphoto, daW, dar, io.fptr, io.photo, io.W, fr.sy.IV, eta,
+		                   io.d_fixed, E, T);
+		hipLaunchKernelGGL(k_merge_rowsum, grid(rows), dim3(256), 0, s, rows, kc, E, T, etaP, B);
 	}
-	catch (...) { lsfm_map_release(&g); throw; }
+	// ---- delta_p = S'^-1 B ----
+	CcWork wk;
+	wk.alloc(fr.ch.M, 1);
+	const CcOutcome oc = cc_solve_refine(ctx, fr, 1, wk, [&](double* dst) {
+		LSFM_CHECK_HIP(hipMemcpyAsync(dst, B, (size_t)rows * sizeof(double), hipMemcpyDeviceToDevice, s));
+	});
+	LSFM_CHECK_HIP(hipEventRecord(ev[2], s));
+	// ---- back-substitution and D^2 ----
+	if (no) hipLaunchKernelGGL(k_merge_backsub, grid(no), dim3(256), 0, s, no, io.fptr, io.photo, io.W, fr.sy.IV, eta, wk.Xo, oX, yf, fdot);
+	hipLaunchKernelGGL(k_merge_pose, grid(rows), dim3(256), 0, s, rows, dxp, wk.Xo, etaP, io.d_fixed, yp, pdot);
+	hipLaunchKernelGGL(k_merge_d2, dim3(1), dim3(MG_RED), 0, s, no, quad, fdot, rows, pdot, dd);
+	LSFM_CHECK_HIP(hipEventRecord(ev[3], s));
+	LSFM_CHECK_HIP(hipGetLastError());
+	double hd[3] = { 0.0, 0.0, 0.0 };
+	d2h(ctx, g.stVal, yp, (size_t)rows * sizeof(double));
+	d2h(ctx, g.stVal + (size_t)rows, yf, (size_t)no * 3 * sizeof(double));
+	d2h(ctx, hd, dd, sizeof hd);
+	LSFM_CHECK_HIP(hipEventRecord(ev[4], s));
+	LSFM_CHECK_HIP(hipEventSynchronize(ev[4]));
+	if (times)
+	{
+		times[0] = event_ms(ev[0], ev[1]);
+		times[1] = event_ms(ev[1], fr.ev[2]);
+		times[2] = event_ms(fr.ev[2], ev[2]);
+		times[3] = event_ms(ev[2], ev[3]);
+		times[4] = event_ms(ev[3], ev[4]);
+	}
+	if (d2) *d2 = hd[0];
+	if (dof) *dof = 3 * st.removed;
+	if (rep) memcpy(rep, st.rep.data(), (size_t)n * sizeof(int));
+	if (steps_out) *steps_out = oc.steps;
+	if (last_corr) last_corr[0] = wk.ratio[0];
+	G.give(out);
+	return oc.undone ? LSFM_NOT_CONVERGED : LSFM_OK;
 }
 
 } // namespace lsfm

@@ -109,12 +109,9 @@ extern "C" int lsfm_merge_structure(const lsfm_map* map, const int* pairs, int K
 	};
 	if (why && why_cap > 0) why[0] = 0;
 	if (!map) return fail("map is NULL");
-	HostSystem h;
-	h.m = map->m; h.n = map->n; h.nU = map->nU; h.nW = map->nW;
-	h.Ui = map->Ui; h.Uj = map->Uj; h.photo = map->photo; h.feature = map->feature;
 	std::vector<int> fptr;
 	const char* bad = nullptr;
-	if (system_check(h, false, fptr, &bad) != LSFM_OK) return fail(bad ? bad : "malformed map");
+	if (system_check(host_system_of(*map, false), false, fptr, &bad) != LSFM_OK) return fail(bad ? bad : "malformed map");
 	MergeStructure st;
 	std::string msg;
 	if (merge_structure(map->n, fptr, map->photo, pairs, K, st, msg) != LSFM_OK) return fail(msg);

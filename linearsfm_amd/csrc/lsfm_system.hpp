@@ -6,6 +6,8 @@
 #include <cstddef>
 #include <vector>
 
+#include "../../include/lsfm.h"
+
 struct lsfm_context;
 
 namespace lsfm {
@@ -20,6 +22,15 @@ struct HostSystem {
 	const double *ea = nullptr, *eb = nullptr, *x0 = nullptr; // [6 m] / [3 n] right-hand sides, [6 m] initial guess
 	const int* pose_origin = nullptr;                        // [m]
 };
+// the system of a map: its sizes and index arrays, and (values) U, W, V; the right-hand sides and pose_origin stay unset
+inline HostSystem host_system_of(const lsfm_map& g, bool values)
+{
+	HostSystem h;
+	h.m = g.m; h.n = g.n; h.nU = g.nU; h.nW = g.nW;
+	h.Ui = g.Ui; h.Uj = g.Uj; h.photo = g.photo; h.feature = g.feature;
+	if (values) { h.U = g.U; h.W = g.W; h.V = g.V; }
+	return h;
+}
 
 // ---- host only (lsfm_system.cpp) ----
 // fptr[n + 1]: the W run of every feature, from feature[] (W sorted by feature); 0 <= Ui <= Uj < m; 0 <= photo < m.

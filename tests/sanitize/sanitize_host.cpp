@@ -1,5 +1,6 @@
 // Sanitizer driver (CPU only, test infrastructure): the host-side code of the library that runs without a device --
-// lsfm_io.cpp (reader, writers), lsfm_symbolic.cpp (ordering + symbolic factorisation), lsfm_system.cpp (argument checks) -- and the oracle (oracle/lsfm_oracle.c,
+// lsfm_io.cpp (reader, writers), lsfm_symbolic.cpp (ordering + symbolic factorisation), lsfm_system.cpp (argument checks), lsfm_map.cpp
+// (lsfm_map_release) -- and the oracle (oracle/lsfm_oracle.c,
 // lsfm_chol.c), all compiled with -fsanitize=address,undefined by tests/test_sanitize_cpu.py and run over a small join tree:
 //   sanitize_host <dir> <N> <Monocular|Stereo>
 // reads <dir>/localmap_1..N.txt with the library's reader (one by one and as a threaded set) and with the oracle's, compares
@@ -19,14 +20,6 @@
 #include "../../linearsfm_amd/csrc/lsfm_system.hpp"
 extern "C" {
 #include "../../oracle/lsfm_oracle.h"
-}
-
-extern "C" void lsfm_map_release(lsfm_map* g) // (the library's lives in a .hip file; same body)
-{
-	if (!g) return;
-	free(g->stno); free(g->stVal); free(g->U); free(g->Ui); free(g->Uj); free(g->W); free(g->photo); free(g->feature);
-	free(g->V); free(g->FBlock); free(g->pose_origin);
-	memset(g, 0, sizeof *g);
 }
 
 #define CHECK(c) do { if (!(c)) { fprintf(stderr, "sanitize_host: check failed: %s (line %d)\n", #c, __LINE__); return 1; } } while (0)

@@ -1,6 +1,6 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer over the code that runs on the host: the library's reader / writers
 (linearsfm_amd/csrc/lsfm_io.cpp), its ordering + symbolic factorisation (lsfm_symbolic.cpp), its checks of a system from host arrays
-(lsfm_system.cpp) and the oracle (oracle/lsfm_oracle.c,
+(lsfm_system.cpp), the release of its maps (lsfm_map.cpp) and the oracle (oracle/lsfm_oracle.c,
 lsfm_chol.c), built with -fsanitize=address,undefined -fno-sanitize-recover=all into tests/sanitize/_build/sanitize_host and run over
 small join trees (tests/sanitize/sanitize_host.cpp says what it exercises).  GPU sanitizers are not available on the pool; the device
 code is covered by the parity tests instead."""
@@ -26,11 +26,11 @@ def san_exe():
     os.makedirs(OUT, exist_ok=True)
     exe = os.path.join(OUT, "sanitize_host")
     srcs = [SRC, os.path.join(ROOT, "linearsfm_amd", "csrc", "lsfm_io.cpp"), os.path.join(ROOT, "linearsfm_amd", "csrc", "lsfm_symbolic.cpp"),
-            os.path.join(ROOT, "linearsfm_amd", "csrc", "lsfm_system.cpp"),
+            os.path.join(ROOT, "linearsfm_amd", "csrc", "lsfm_system.cpp"), os.path.join(ROOT, "linearsfm_amd", "csrc", "lsfm_map.cpp"),
             os.path.join(ROOT, "oracle", "lsfm_oracle.c"), os.path.join(ROOT, "oracle", "lsfm_chol.c")]
     deps = srcs + [os.path.join(ROOT, "oracle", f) for f in ("lsfm_oracle.h", "lsfm_solve_num.inc", "lsfm_chol_num.inc")] + \
         [os.path.join(ROOT, "include", "lsfm.h"), os.path.join(ROOT, "linearsfm_amd", "csrc", "lsfm_symbolic.hpp"),
-         os.path.join(ROOT, "linearsfm_amd", "csrc", "lsfm_system.hpp")]
+         os.path.join(ROOT, "linearsfm_amd", "csrc", "lsfm_system.hpp"), os.path.join(ROOT, "linearsfm_amd", "csrc", "lsfm_map.hpp")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         objs = []
         for s in srcs:
