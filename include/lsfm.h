@@ -721,6 +721,12 @@ int lsfm_wstream_bench(lsfm_context* ctx, long long nblocks, int mode, int reps,
  * mismatch in lsfm_last_error. */
 int lsfm_selftest_prims(lsfm_context* ctx, int cases, unsigned seed);
 
+/* Test entry: the per-feature kernel of the level solve (K7) alone, with everything it leaves per feature.  V[9n], eb[3n] in;
+ * IV[9n] = V^-1 as lsfm_inverse_v returns it, LY[9n] = (l00 l10 l11 l20 l21 l22 | L^T eb) with V^-1 = L L^T, the record the Schur
+ * kernels read (l00 is NaN where V^-1 has no Cholesky factor).  skip: the feature range starts that many doubles into the device
+ * arrays (0 or 1: an odd value puts every array 8 bytes off a 16-byte boundary). */
+int lsfm_selftest_vinv(lsfm_context* ctx, const double* V, const double* eb, int n, int skip, double* IV, double* LY);
+
 /* Test entry: the device Cholesky factorisation of a camera system (the preconditioner of every level solve, the factor the
  * covariance calls invert; it stands for cholmod_analyze / factorize / solve, Imp.cpp:2380-2449 / 7043-7121) on a matrix of the
  * caller's, and UNREFINED applications of it.  Inside a level solve the refinement tests the true residual and goes on until it

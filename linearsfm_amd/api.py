@@ -117,6 +117,7 @@ def lib():
         L.lsfm_schur_pattern.argtypes = [vp, ip, ip, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, ip]
         L.lsfm_symbolic_analyse.argtypes = [C.c_int, ip, ip, ip, C.c_int, ip, ip, ip, C.c_int, ip, dp]
         L.lsfm_inverse_v.argtypes = [vp, dp, C.c_int, C.c_int]
+        L.lsfm_selftest_vinv.argtypes = [vp, dp, dp, C.c_int, C.c_int, dp, dp]
         L.lsfm_gn_polish.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), C.c_int, dp, dp, ip]
         L.lsfm_gn_polish_robust.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), C.c_int, C.c_int, C.c_double, dp, dp, ip, dp, dp]
         L.lsfm_map_chi2.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, ip]
@@ -173,7 +174,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_tree_upload_dev", "lsfm_tree_reload_dev", "lsfm_tree_set_comm", "lsfm_tree_set_comm_blocks", "lsfm_tree_export_slice_sizes", "lsfm_tree_export_slice_dev",
            "lsfm_tree_free", "lsfm_divide_conquer", "lsfm_read_localmap", "lsfm_read_localmaps", "lsfm_write_localmap", "lsfm_write_mapset", "lsfm_mapset_info", "lsfm_mapset_stamp", "lsfm_read_mapset", "lsfm_save_state_bin", "lsfm_save_state", "lsfm_save_poses", "lsfm_gn_polish",
            "lsfm_gn_polish_robust", "lsfm_map_chi2", "lsfm_map_feature_chi2", "lsfm_gn_polish_robust_features", "lsfm_gn_linearise", "lsfm_gn_linearise_timed",
-           "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_selftest_chol", "lsfm_selftest_transform", "lsfm_selftest_small", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_solve_features",
+           "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_selftest_chol", "lsfm_selftest_transform", "lsfm_selftest_small", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_selftest_vinv", "lsfm_solve_features",
            "lsfm_map_covariance", "lsfm_map_covariance_timed",
            "lsfm_save_covariances", "lsfm_read_covariances",
            "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns",
@@ -565,6 +566,18 @@ class Context:
         n = IV.size // 9
         self._check(lib().lsfm_inverse_v(self._h, _ptr(IV, C.c_double), 0, n), "lsfm_inverse_v")
         return IV.reshape(n, 9)
+
+    def selftest_vinv(self, V, eb, skip=0):
+        """lsfm_selftest_vinv: K7 (k_vinv) alone on V [n, 9], eb [n, 3]; skip = 1 puts the device arrays 8 bytes off a 16-byte
+        boundary.  Returns (IV [n, 9], LY [n, 9]: the factor of V^-1 and L^T eb, as the Schur kernels read them)."""
+        V = _c(np.asarray(V, np.float64).reshape(-1), np.float64); eb = _c(np.asarray(eb, np.float64).reshape(-1), np.float64)
+        n = V.size // 9
+        if V.size != 9 * n or eb.size != 3 * n:
+            raise LsfmError("selftest_vinv: V [n, 9] and eb [n, 3]")
+        IV = np.zeros(9 * n); LY = np.zeros(9 * n)
+        self._check(lib().lsfm_selftest_vinv(self._h, _ptr(V, C.c_double), _ptr(eb, C.c_double), n, int(skip), _ptr(IV, C.c_double), _ptr(LY, C.c_double)),
+                    "lsfm_selftest_vinv")
+        return IV.reshape(n, 9), LY.reshape(n, 9)
 
     def solve_features(self, j, IV, eb, dpa):
         """lsfm_solve_features (the reference's pba_solveFeatures, Imp.cpp:2980): the features' back-substitution for the given pose

@@ -637,6 +637,12 @@ int lsfm_inverse_v(lsfm_context* ctx, double* V, int m, int n)
 	return guarded(ctx, [&]() { return inverse_v(ctx, V, n); });
 }
 
+int lsfm_selftest_vinv(lsfm_context* ctx, const double* V, const double* eb, int n, int skip, double* IV, double* LY)
+{
+	if (n < 0 || skip < 0 || skip > 1 || (n && (!V || !eb || !IV || !LY))) return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() { return vinv_selftest(ctx, V, eb, n, skip, IV, LY); });
+}
+
 int lsfm_solve_features(lsfm_context* ctx, const double* W, const double* IV, const double* ea, const double* eb, const double* dpa, double* dpb,
                         int m, int n, const int* mapCor, const int* photo)
 {

@@ -232,6 +232,42 @@ __device__ __forceinline__ double block_sum_fixed(double v, double* part)
 	return sum;
 }
 
+// S values per lane summed over the wave, each sum left in ONE lane: at every step of the butterfly a lane keeps one half of its values
+// and hands the other half to its partner, so S values cost S + S/2 + ... ~ S exchanges instead of the 6 S of S wave_sum() calls (N = 36:
+// 38 against 216).  on: the lane's values count (the others add zeros).  The lane holds the sum of element wave_spread_index<S>(lane).
+template <int S, int OFF>
+__device__ __forceinline__ double wave_sum_spread(const double* v, bool on, int lane)
+{
+	if constexpr (OFF == 0) return on ? v[0] : 0.0;
+	else
+	{
+		constexpr int H = (S + 1) / 2;
+		const bool up = (lane & OFF) != 0;
+		double w[H];
+#pragma unroll
+		for (int i = 0; i < H; i++)
+		{
+			const double lo = on ? v[i] : 0.0, hi = (i + H < S && on) ? v[i + H < S ? i + H : 0] : 0.0;
+			w[i] = (up ? hi : lo) + __shfl_xor(up ? lo : hi, OFF, LSFM_WAVE);
+		}
+		return wave_sum_spread<H, OFF / 2>(w, true, lane);
+	}
+}
+// the element whose sum wave_sum_spread<S, 32> leaves in this lane; -1: none (64 lanes, S elements)
+template <int S>
+__device__ __forceinline__ int wave_spread_index(int lane)
+{
+	int off = 0, len = S, s = S;
+#pragma unroll
+	for (int o = LSFM_WAVE / 2; o; o >>= 1)
+	{
+		const int h = (s + 1) / 2;
+		if (lane & o) { off += h; len -= h; } else len = min(len, h);
+		s = h;
+	}
+	return len >= 1 ? off : -1;
+}
+
 __device__ __forceinline__ void atomic_add_f64(double* p, double v)
 {
 	// hardware global_atomic_add_f64 (built with -munsafe-fp-atomics), agent scope, no return value used
@@ -274,6 +310,7 @@ __device__ __forceinline__ void to_fixed2(double v, int sh, long long& hi, long 
 // other (a wave that straddles a map boundary has two; until round 6 any second target sent ALL 64 lanes to N single-lane atomics
 // each on the same few addresses -- at the lowest levels of a monocular tree, whose maps hold ~200 features, most waves straddle:
 // k_tr_feat_post<2> took 4.7 ms at level 1 of a synth-16k tree against 1.3 at level 0); what is left after four adds lane by lane.
+// (The transform's per-map sums have since moved on to tile_wave_add below, which collects them per work-group first.)
 // Must be called by all 64 lanes (convergent).
 template <int N>
 __device__ __forceinline__ void wave_scatter_add(double* dst, const double* vals, bool valid)
@@ -394,6 +431,47 @@ __device__ __forceinline__ void tile_scatter_add_rot(int* keys, double* vals, in
 		if (sl >= 0) lds_add_f64(vals + sl * N + i, v); else atomic_add_f64(gdst + i, v);
 	}
 }
+// The same, for sums that have FEW keys and many lanes each (the per-map sums of the transform: features and poses lie map by map, so
+// a work-group meets a handful of maps, and far up a tree every wave of a launch adds to the same one or two).  Every distinct key of
+// the wave shared by several lanes is taken in turn, as wave_scatter_add takes its targets (four at the most): the lanes of the key are
+// summed across the wave (wave_sum_spread: each of the N sums ends in a lane of its own), and the N sums go to the key's row of the
+// table as ONE LDS instruction over N distinct addresses.  A key that finds no slot leaves the wave as wave_scatter_add's sums do: one
+// instruction of N global atomics on gbase + key*N.  Lanes that are alone with their key, and what is left after four keys, add lane
+// by lane -- to the table where their key has a slot.  With tile_flush() a row leaves the work-group once, not once per wave.  Must
+// be called by all 64 lanes.
+template <int N>
+__device__ __forceinline__ void tile_wave_add(int* keys, double* vals, int cap, int key, double* gbase, const double* x, bool valid)
+{
+	static_assert(N <= LSFM_WAVE, "one lane per value");
+	unsigned long long todo = __ballot(valid), alone = 0ull;
+	if (todo == 0ull) return;
+	const int lane = threadIdx.x & (LSFM_WAVE - 1), mine = wave_spread_index<N>(lane); // (the element whose sum this lane gets)
+#pragma unroll 1
+	for (int round = 0; round < 4 && todo; round++)
+	{
+		const int leader = __ffsll((long long)todo) - 1;
+		const int first = __shfl(key, leader, LSFM_WAVE);
+		const bool same = valid && key == first;
+		const unsigned long long grp = __ballot(same);
+		if (__popcll(grp) > 1)
+		{
+			const double keep = wave_sum_spread<N, LSFM_WAVE / 2>(x, same, lane);
+			int sl = -1;
+			if (lane == leader) sl = lds_slot(keys, cap, first);
+			sl = __shfl(sl, leader, LSFM_WAVE);
+			if (mine >= 0) { if (sl >= 0) lds_add_f64(vals + sl * N + mine, keep); else atomic_add_f64(gbase + (size_t)first * N + mine, keep); }
+		}
+		else alone |= grp;
+		todo &= ~grp;
+	}
+	alone |= todo;
+	if (valid && ((alone >> lane) & 1ull))
+	{
+		const int sl = lds_slot(keys, cap, key);
+#pragma unroll
+		for (int i = 0; i < N; i++) { if (sl >= 0) lds_add_f64(vals + sl * N + i, x[i]); else atomic_add_f64(gbase + (size_t)key * N + i, x[i]); }
+	}
+}
 // the empty table; a __syncthreads() before its first use
 template <int N>
 __device__ __forceinline__ void tile_clear(int* keys, double* vals, int cap)
@@ -410,6 +488,48 @@ __device__ __forceinline__ void tile_flush(const int* keys, const double* vals, 
 		const int k = keys[i / N];
 		if (k >= 0) atomic_add_f64(gbase + (size_t)k * N + i % N, vals[i]);
 	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// records of N doubles, one per lane, through LDS
+// ---------------------------------------------------------------------------------------------------------
+// A lane that loads or stores its own record of N doubles moves 8-byte pieces at a lane stride of 8 N bytes: every wave instruction
+// touches 64 pieces spread over 512 N bytes.  Here the work-group moves the contiguous range of its records instead: consecutive lanes
+// take consecutive 16-byte pieces (one 8-byte piece before the first 16-byte boundary of the range and one after the last, where there
+// is one), and record r lies in the LDS tile at r * N doubles.  N is odd (the records of 9 and of 3 doubles): the tile is the range as
+// it lies in memory, and the lanes of a wave reading their own records at that odd stride fall on different banks.  All threads of
+// the work-group must call these; a __syncthreads() between tile_records_load and the lanes' reads, and between the lanes' writes and
+// tile_records_store.  g: the first record of the range; nrec <= 0 moves nothing.
+template <int N>
+__device__ __forceinline__ void tile_records_load(double* tile, const double* __restrict__ g, int nrec)
+{
+	static_assert(N % 2 == 1, "an even record length needs a padded stride in the tile");
+	const int len = nrec * N, head = (int)(((size_t)g >> 3) & 1);
+	if (len <= 0) return;
+	if (threadIdx.x == 0 && head) tile[0] = g[0];
+	const int pairs = (len - head) >> 1;
+	for (int p = threadIdx.x; p < pairs; p += blockDim.x)
+	{
+		const int j = head + 2 * p;
+		const double2 v = *reinterpret_cast<const double2*>(g + j);
+		tile[j] = v.x; tile[j + 1] = v.y;
+	}
+	if (threadIdx.x == 0 && ((len - head) & 1)) tile[len - 1] = g[len - 1];
+}
+template <int N>
+__device__ __forceinline__ void tile_records_store(const double* tile, double* __restrict__ g, int nrec)
+{
+	static_assert(N % 2 == 1, "an even record length needs a padded stride in the tile");
+	const int len = nrec * N, head = (int)(((size_t)g >> 3) & 1);
+	if (len <= 0) return;
+	if (threadIdx.x == 0 && head) g[0] = tile[0];
+	const int pairs = (len - head) >> 1;
+	for (int p = threadIdx.x; p < pairs; p += blockDim.x)
+	{
+		const int j = head + 2 * p;
+		*reinterpret_cast<double2*>(g + j) = make_double2(tile[j], tile[j + 1]);
+	}
+	if (threadIdx.x == 0 && ((len - head) & 1)) g[len - 1] = tile[len - 1];
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -590,6 +590,7 @@ int map_merge_features(lsfm_context* ctx, const lsfm_map* map, bool mono, const 
 // the two feature-side pieces of the solve on their own (lsfm_solve.hip; C ABI: lsfm_inverse_v / lsfm_solve_features); host pointers,
 // arguments checked by the caller
 int inverse_v(lsfm_context* ctx, double* V, int n);
+int vinv_selftest(lsfm_context* ctx, const double* V, const double* eb, int n, int skip, double* IV, double* LY); // C ABI: lsfm_selftest_vinv
 int solve_features(lsfm_context* ctx, const double* W, const double* IV, const double* eb, const double* dpa, double* dpb, int m, int n, const int* mapCor,
                    const int* photo);
 bool no_timing_events(); // (LSFM_NO_TIMING_EVENTS=1: the phase brackets are not recorded -- the stage times of lsfm_stats stay zero)

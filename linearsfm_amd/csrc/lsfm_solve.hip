@@ -28,16 +28,23 @@ __global__ void __launch_bounds__(256) k_vinv(int NF, const double* __restrict__
                                                double* __restrict__ ymax, RhsFused rhs, double* __restrict__ uu)
 {
 	__shared__ double wmax[4];
-	int f = blockIdx.x * blockDim.x + threadIdx.x;
+	// V, eb in and V^-1, (L, y) out as the work-group's contiguous ranges (tile_records_*): one tile for the 9-double records in turn
+	__shared__ double sRec[256 * 9], sEb[256 * 3];
+	const int f0 = blockIdx.x * 256, nrec = min(256, NF - f0);
+	int f = f0 + threadIdx.x;
+	tile_records_load<9>(sRec, V + (size_t)f0 * 9, nrec);
+	tile_records_load<3>(sEb, eb + (size_t)f0 * 3, nrec);
+	__syncthreads();
 	double y2 = 0.0;
+	double* rec = sRec + threadIdx.x * 9;
+	double l[9];
 	if (f < NF)
 	{
 	double a[9], o[9];
-	ld<9>(a, V + (size_t)f * 9);
+	ld<9>(a, rec);
 	inv3_sym(a, o);
-	st<9>(IV + (size_t)f * 9, o);
-	const double* e = eb + (size_t)f * 3;
-	double l[9];
+	st<9>(rec, o);
+	const double* e = sEb + threadIdx.x * 3;
 	const double d0 = o[0];
 	l[0] = sqrt(d0);
 	l[1] = o[3] / l[0];
@@ -51,7 +58,6 @@ __global__ void __launch_bounds__(256) k_vinv(int NF, const double* __restrict__
 	l[7] = l[2] * e[1] + l[4] * e[2];
 	l[8] = l[5] * e[2];
 	if (!(d0 > 0.0) || !(d1 > 0.0) || !(d2 > 0.0)) l[0] = __builtin_nan("");
-	st<9>(LY + (size_t)f * 9, l);
 	y2 = l[6] * l[6] + l[7] * l[7] + l[8] * l[8];
 	if (uu)
 	{
@@ -73,6 +79,12 @@ __global__ void __launch_bounds__(256) k_vinv(int NF, const double* __restrict__
 	}
 	if (!(y2 == y2)) y2 = 0.0; // (a feature without a factor goes to k_schur_w, which checks its own sums)
 	}
+	__syncthreads();
+	tile_records_store<9>(sRec, IV + (size_t)f0 * 9, nrec);
+	__syncthreads();
+	if (f < NF) st<9>(rec, l);
+	__syncthreads();
+	tile_records_store<9>(sRec, LY + (size_t)f0 * 9, nrec);
 	if (!ymax) return;
 #pragma unroll
 	for (int off = 32; off > 0; off >>= 1) y2 = fmax(y2, __shfl_xor(y2, off, LSFM_WAVE));
@@ -847,6 +859,25 @@ int inverse_v(lsfm_context* ctx, double* V, int n)
 		LSFM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
 	}
 	d2h(ctx, V, dIV, (size_t)n * 9 * sizeof(double));
+	return LSFM_OK;
+}
+// C ABI: lsfm_selftest_vinv -- k_vinv alone with both of its records back; skip doubles in front of every device array
+int vinv_selftest(lsfm_context* ctx, const double* V, const double* eb, int n, int skip, double* IV, double* LY)
+{
+	ctx->ensure_arenas((size_t)n * 400 + ((size_t)64 << 20));
+	ctx->arena[0].reset(); ctx->scratch.reset();
+	Arena& ar = ctx->arena[0];
+	double* dV = ar.alloc<double>((size_t)n * 9 + skip) + skip;
+	double* deb = ar.alloc<double>((size_t)n * 3 + skip) + skip;
+	double* dIV = ar.alloc<double>((size_t)n * 9 + skip) + skip;
+	double* dLY = ar.alloc<double>((size_t)n * 9 + skip) + skip;
+	if (!n) return LSFM_OK;
+	h2d(ctx, dV, V, (size_t)n * 9 * sizeof(double));
+	h2d(ctx, deb, eb, (size_t)n * 3 * sizeof(double));
+	hipLaunchKernelGGL(k_vinv, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, dV, deb, dIV, dLY, (double*)nullptr, RhsFused(), (double*)nullptr);
+	LSFM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+	d2h(ctx, IV, dIV, (size_t)n * 9 * sizeof(double));
+	d2h(ctx, LY, dLY, (size_t)n * 9 * sizeof(double));
 	return LSFM_OK;
 }
 int solve_features(lsfm_context* ctx, const double* W, const double* IV, const double* eb, const double* dpa, double* dpb, int m, int n, const int* mapCor,

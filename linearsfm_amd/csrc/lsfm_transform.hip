@@ -348,6 +348,7 @@ __global__ void k_tr_gather_counts(const int* __restrict__ KU, const int* __rest
 #define TRE_TILE 128 /* features per work-group: the LDS pose table is flushed once per tile */
 #define TRE_ROUND 256 /* W blocks per round = threads */
 #define TRE_MAPS 4 /* Stereo: records of the tile's first maps kept in LDS by k_tr_entries (a lane of a later map reads global memory) */
+#define TR_PCAP(NH) ((NH) == 1 ? 4 : 16) /* rows of the LDS table of per-map sums in k_tr_feat_post / k_tr_poseslots: a map has one row (Mono: three) */
 #define TR_REC 39 /* R, dRA, dRB, dRG, t of a map: what the Stereo Jacobians of its features are made from */
 static_assert(offsetof(TMap, dRA) == offsetof(TMap, R) + 72 && offsetof(TMap, dRB) == offsetof(TMap, R) + 144 && offsetof(TMap, dRG) == offsetof(TMap, R) + 216 &&
               offsetof(TMap, t) == offsetof(TMap, R) + 288, "R, dRA, dRB, dRG, t of TMap are read as one run of TR_REC doubles");
@@ -362,24 +363,19 @@ __device__ __forceinline__ void stereo_tf(const double* rec, const double* xn, d
 	for (int r = 0; r < 3; r++) { Tf[3 * r] = tmp1[r]; Tf[3 * r + 1] = tmp2[r]; Tf[3 * r + 2] = tmp3[r]; }
 }
 
+// feature f of k_tr_feat_pre; x, v: its value and its V in the work-group's LDS tiles, replaced by x' and V'
 template <int NH>
-__global__ void __launch_bounds__(256)
-k_tr_feat_pre(int NF, const TMap* __restrict__ tm, const int* __restrict__ feat_map, const double* __restrict__ feat, const int* __restrict__ fptr,
-              const double* __restrict__ Vold, const int* __restrict__ KW, double* __restrict__ nfeat, int* __restrict__ nfptr,
-              double* __restrict__ Vn, double* __restrict__ FD, int4* __restrict__ finfo, int* __restrict__ hubJ)
+__device__ __forceinline__ void feat_pre_lane(int f, const TMap* __restrict__ tm, const int* __restrict__ feat_map, const int* __restrict__ fptr,
+                                              const int* __restrict__ KW, int* __restrict__ nfptr, double* __restrict__ FD, int4* __restrict__ finfo,
+                                              int* __restrict__ hubJ, double* x, double* v)
 {
-	const int f = blockIdx.x * blockDim.x + threadIdx.x;
-	if (f >= NF) return;
 #pragma unroll
 	for (int sidx = 0; sidx < NH; sidx++) hubJ[(size_t)f * NH + sidx] = -1; // (no old block to a hub pose seen yet: k_tr_entries records them)
 	const TMap* t = &tm[feat_map[f]];
 	const int j0 = fptr[f];
-	const double* x = feat + (size_t)f * 3;
 	if (!(t->active > 0 && t->nh == NH))
 	{
-		// pass-through map: plain copy at the new offsets
-		nfeat[3 * (size_t)f] = x[0]; nfeat[3 * (size_t)f + 1] = x[1]; nfeat[3 * (size_t)f + 2] = x[2];
-		for (int i = 0; i < 9; i++) Vn[(size_t)f * 9 + i] = Vold[(size_t)f * 9 + i];
+		// pass-through map: x and V leave as they came, at the new offsets
 		nfptr[f] = t->W0n + (j0 - t->W0);
 		finfo[f] = make_int4(0, -1, NH == 2 ? -1 : feat_map[f], -j0); // new place of block j: (start of the feature's new run) + w + j
 		return;
@@ -393,7 +389,7 @@ k_tr_feat_pre(int NF, const TMap* __restrict__ tm, const int* __restrict__ feat_
 	double d[3] = { x[0] - t->t1[0], x[1] - t->t1[1], x[2] - t->t1[2] };
 	mv3(t->R1, d, xn);
 	if (NH == 2) { xn[0] = xn[0] / t->scale1; xn[1] = xn[1] / t->scale1; xn[2] = xn[2] / t->scale1; }
-	nfeat[3 * (size_t)f] = xn[0]; nfeat[3 * (size_t)f + 1] = xn[1]; nfeat[3 * (size_t)f + 2] = xn[2];
+	x[0] = xn[0]; x[1] = xn[1]; x[2] = xn[2];
 	// D_f, C_f: Imp.cpp:638-680 / 3587-3684
 	if constexpr (NH == 1)
 	{
@@ -421,10 +417,10 @@ k_tr_feat_pre(int NF, const TMap* __restrict__ tm, const int* __restrict__ feat_
 	}
 	// V' = D_f^T V D_f
 	double V[9], T[9], Vnew[9];
-	ld<9>(V, Vold + (size_t)f * 9);
+	ld<9>(V, v);
 	mtm<3, 3, 3, false>(Df, V, T);
 	mm<3, 3, 3, false>(T, Df, Vnew);
-	st<9>(Vn + (size_t)f * 9, Vnew);
+	st<9>(v, Vnew);
 	if constexpr (NH == 2)
 	{
 		double* fd = FD + (size_t)f * (9 + 18 * NH);
@@ -432,6 +428,24 @@ k_tr_feat_pre(int NF, const TMap* __restrict__ tm, const int* __restrict__ feat_
 #pragma unroll
 		for (int s = 0; s < NH; s++) st<18>(fd + 9 + 18 * s, Cf[s]);
 	}
+}
+
+// V and x in, V' and x' out as the work-group's contiguous ranges (tile_records_*), each lane on its own records in between
+template <int NH>
+__global__ void __launch_bounds__(256)
+k_tr_feat_pre(int NF, const TMap* __restrict__ tm, const int* __restrict__ feat_map, const double* __restrict__ feat, const int* __restrict__ fptr,
+              const double* __restrict__ Vold, const int* __restrict__ KW, double* __restrict__ nfeat, int* __restrict__ nfptr,
+              double* __restrict__ Vn, double* __restrict__ FD, int4* __restrict__ finfo, int* __restrict__ hubJ)
+{
+	__shared__ double sV[256 * 9], sX[256 * 3];
+	const int f0 = blockIdx.x * 256, nrec = min(256, NF - f0), f = f0 + threadIdx.x;
+	tile_records_load<9>(sV, Vold + (size_t)f0 * 9, nrec);
+	tile_records_load<3>(sX, feat + (size_t)f0 * 3, nrec);
+	__syncthreads();
+	if (f < NF) feat_pre_lane<NH>(f, tm, feat_map, fptr, KW, nfptr, FD, finfo, hubJ, sX + threadIdx.x * 3, sV + threadIdx.x * 9);
+	__syncthreads();
+	tile_records_store<9>(sV, Vn + (size_t)f0 * 9, nrec);
+	tile_records_store<3>(sX, nfeat + (size_t)f0 * 3, nrec);
 }
 
 // Profiling aid (make K9_TIMING=1; tools/tr_phase_times.py): lane 0 of every work-group adds up the shader clocks it spends
@@ -782,6 +796,12 @@ k_tr_feat_post(int NF, int M, const TMap* __restrict__ tm, const int* __restrict
 {
 	// FD: Mono's records (null for Stereo, which makes D_f and C_f from the map's record t and the feature's new value in xnew)
 	constexpr int TW = 18 * NH;
+	// the per-map sums C_s^T G_t of the work-group: the features lie map by map, so its 256 features belong to a handful of maps; a
+	// map without a slot adds to PP directly
+	__shared__ int pkeys[TR_PCAP(NH)];
+	__shared__ double pvals[TR_PCAP(NH) * 36];
+	tile_clear<36>(pkeys, pvals, TR_PCAP(NH));
+	__syncthreads();
 	const int f = blockIdx.x * blockDim.x + threadIdx.x;
 	const bool inb = f < NF;
 	const TMap* t = inb ? &tm[feat_map[f]] : nullptr;
@@ -873,8 +893,10 @@ k_tr_feat_post(int NF, int M, const TMap* __restrict__ tm, const int* __restrict
 			if (act) mtm<3, 6, 6, false>(Cf[s], G[s2], P);
 			const int idx = (s == 0 ? s2 : 2);
 			const int mp = act ? feat_map[f] : 0;
-			wave_scatter_add<36>(PP + ((size_t)mp * 3 + idx) * 36, P, act);
+			tile_wave_add<36>(pkeys, pvals, TR_PCAP(NH), mp * 3 + idx, PP, P, act);
 		}
+	__syncthreads();
+	tile_flush<36>(pkeys, pvals, TR_PCAP(NH), PP);
 }
 
 template <int NH>
@@ -974,6 +996,10 @@ k_tr_poseslots(int M, const TMap* __restrict__ tm, const int* __restrict__ pose_
                                const double* __restrict__ Cp, const double* __restrict__ Gpose, double* __restrict__ Un, int* __restrict__ nUi,
                                int* __restrict__ nUj, double* __restrict__ PP)
 {
+	__shared__ int pkeys[TR_PCAP(NH)]; // the per-map sums of the work-group, as in k_tr_feat_post
+	__shared__ double pvals[TR_PCAP(NH) * 36];
+	tile_clear<36>(pkeys, pvals, TR_PCAP(NH));
+	__syncthreads();
 	const int k0 = blockIdx.x * blockDim.x + threadIdx.x;
 	const bool inb = k0 < M;
 	const int k = inb ? k0 : 0;
@@ -1021,15 +1047,18 @@ k_tr_poseslots(int M, const TMap* __restrict__ tm, const int* __restrict__ pose_
 		}
 		// sum_a C_a^T G_a
 #pragma unroll
-		for (int s0 = 0; s0 <= s; s0++)
+		for (int s0 = 0; s0 < NH; s0++)
 		{
+			if (s0 > s) continue; // (a trip count that hangs on s is not unrolled around the per-map sums)
 			double C[36], P[36];
 			ld<36>(C, Cp + (size_t)s0 * M * 36 + (size_t)k * 36);
 			mtm<6, 6, 6, false>(C, G, P);
 			const int idx = (s0 == 0 ? s : 2);
-			wave_scatter_add<36>(PP + ((size_t)mp * 3 + idx) * 36, P, act);
+			tile_wave_add<36>(pkeys, pvals, TR_PCAP(NH), mp * 3 + idx, PP, P, act);
 		}
 	}
+	__syncthreads();
+	tile_flush<36>(pkeys, pvals, TR_PCAP(NH), PP);
 }
 
 template <int NH>
