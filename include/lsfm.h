@@ -400,6 +400,37 @@ int lsfm_map_merge_features_timed(lsfm_context* ctx, const lsfm_map* map, int mo
 int lsfm_merge_structure(const lsfm_map* map, const int* pairs, int K, int* rep, int* photo, int* feature, int* FBlock, int* sptr, int* sidx, int cap_w,
                          int* info, char* why, int why_cap);
 
+/* ---- candidate feature pairs for the gate: a cell search with a sure bound (NO reference counterpart) ----
+ * The first stage in front of lsfm_map_feature_pair_gate / lsfm_map_merge_features: from the map alone, every pair f < g of indices into
+ * the map's feature order with, d = x_f - x_g from map->stVal,
+ *   1. dx^2 + dy^2 + dz^2 <= radius^2 in fp64 (the products and sums rounded one by one, left to right); radius finite and > 0: a
+ *      metric cap the caller always gives;
+ *   2. only when feat_cov != NULL:  q_fg = 1/2 d^T (Sigma_ff + Sigma_gg)^-1 d <= tau, tau finite and > 0.  feat_cov[9 n] is what
+ *      lsfm_map_covariance writes (the upper triangle is read); the sum is factored by a 3x3 LDL^T in registers; a pair whose sum has a
+ *      pivot that is not > 0 (NaN included) is KEPT, with q = NaN: the call never drops what it cannot bound.
+ * For any joint covariance Var(x_f - x_g) + Var(x_f + x_g) = 2 (Sigma_ff + Sigma_gg), hence Var(x_f - x_g) <= 2 (Sigma_ff + Sigma_gg) and
+ * q_fg <= d^2_fg, the gate's distance: a pair dropped by 2. is one the gate rejects at tau (under the Mono gauge too: a conditioned
+ * covariance is a covariance).  Pairs within 4 ulp of radius^2 or 1e-12 relative of tau may fall on either side.
+ * Outputs: pairs[2 cap] sorted by (f, g) ascending; dist2[cap] and q[cap] (each may be NULL; q without feat_cov: LSFM_ERR_ARG); *count =
+ * the number found, set even when cap is too small -- the call then returns LSFM_ERR_ARG and writes nothing else (lsfm_map_covariance's
+ * nnzb convention); pairs == NULL with cap == 0 is the sizing call (LSFM_OK, *count alone).  n < 2: *count = 0.
+ * Bit-reproducible: the same input gives the same pairs in the same order and the same bits of dist2 and q; no value is summed by
+ * atomics and a final sort on the unique key (f << 32) | g fixes the order.
+ * A uniform grid of cells of edge radius (1 + 2^-20) (21 bits of cell index per axis), a stable radix sort of the features by cell, then
+ * one wave per (cell, 64 of its records) against the half neighbourhood, counting and then filling.  The call does no
+ * factorisation and reads neither U, W nor V, and needs no `mono`.
+ * Returns LSFM_OK; LSFM_ERR_ARG (lsfm_last_error says which; the context stays usable) for radius or tau out of range, a feature
+ * coordinate that is not finite (the feature is named), more than 2^21 cells along an axis ("radius too small for the map's extent"),
+ * more than 2^31 - 1 candidates ("reduce the radius"), more than 2^25 features, a cap that is too small; LSFM_ERR_OOM when the output does not fit the arenas.
+ * Lifetime: works in the context's arenas like lsfm_map_covariance -- a tree's result must be downloaded first. */
+int lsfm_map_feature_pair_candidates(lsfm_context* ctx, const lsfm_map* map, const double* feat_cov, double radius, double tau, int* pairs, double* dist2,
+                                     double* q, long long cap, long long* count);
+/* measurement entry: the same, and times[4] (may be NULL) = HIP-event ms of upload + cell keys | the sort, the records in cell order and
+ * the cell table | the counting pass and its scan | the fill pass, the final sort and the download; info[4] (may be NULL) = { occupied
+ * cells, features in the fullest cell, pair tests made, candidates } */
+int lsfm_map_feature_pair_candidates_timed(lsfm_context* ctx, const lsfm_map* map, const double* feat_cov, double radius, double tau, int* pairs,
+                                           double* dist2, double* q, long long cap, long long* count, double* times, long long* info);
+
 /* ---- marginalising features out of a map (NO reference counterpart: the reference keeps every feature to the end) ----
  * out = `map` with every feature f that has drop[f] != 0 (drop[n], one flag per feature in the map's order) marginalised out:
  *     U' = U - sum_{f dropped} W_f V_f^-1 W_f^T
@@ -696,6 +727,13 @@ int lsfm_save_merge_report(const char* path, int K, int removed, int dof, double
 /* ... and back: the head and ids[3 cap].  LSFM_ERR_IO for a line cut short and for a file with fewer or more lines than its head
  * says, LSFM_ERR_ARG when cap < K */
 int lsfm_read_merge_report(const char* path, int* K, int* removed, int* dof, double* d2, int* ids, int cap);
+/* A pair list, the input format of -gate and -merge and the output of -cand: one line "id_f id_g" per pair, ids[2 K] the labels of the
+ * pairs' features, K >= 0.  Written through a temporary file that is renamed into place. */
+int lsfm_save_pair_list(const char* path, const int* ids, long long K);
+/* ... and back: ids[2 cap]; *count = pairs in the file, set also when cap is too small (LSFM_ERR_ARG; call with cap = 0 for the size).
+ * Read as -gate and -merge read it: whitespace-separated ids, two per pair.  LSFM_ERR_IO for an odd number of ids (a line cut short)
+ * and for anything that is not an id */
+int lsfm_read_pair_list(const char* path, int* ids, long long cap, long long* count);
 int lsfm_save_state(const char* path, const double* st, const int* stno, int n);
 /* the same state vector as raw doubles (parity tooling): int32 n, int32 0, stno[n] (+ 4 bytes of padding when n is odd),
  * st[n] float64 */

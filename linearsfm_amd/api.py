@@ -139,6 +139,11 @@ def lib():
         L.lsfm_map_merge_features.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, P(LsfmMap), dp, ip, ip, ip, dp]
         L.lsfm_map_merge_features_timed.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, P(LsfmMap), dp, ip, ip, ip, dp, dp]
         L.lsfm_merge_structure.argtypes = [P(LsfmMap), ip, C.c_int, ip, ip, ip, ip, ip, ip, C.c_int, ip, C.c_char_p, C.c_int]
+        llp = P(C.c_longlong)
+        L.lsfm_map_feature_pair_candidates.argtypes = [vp, P(LsfmMap), dp, C.c_double, C.c_double, ip, dp, dp, C.c_longlong, llp]
+        L.lsfm_map_feature_pair_candidates_timed.argtypes = [vp, P(LsfmMap), dp, C.c_double, C.c_double, ip, dp, dp, C.c_longlong, llp, dp, llp]
+        L.lsfm_save_pair_list.argtypes = [C.c_char_p, ip, C.c_longlong]
+        L.lsfm_read_pair_list.argtypes = [C.c_char_p, ip, C.c_longlong, llp]
         L.lsfm_save_merge_report.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, ip]
         L.lsfm_read_merge_report.argtypes = [C.c_char_p, ip, ip, ip, dp, ip, C.c_int]
         L.lsfm_save_cov_columns.argtypes = [C.c_char_p, ip, C.c_int, ip, C.c_int, dp]
@@ -180,6 +185,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns",
            "lsfm_map_covariance_feature_columns", "lsfm_map_covariance_feature_columns_timed", "lsfm_map_feature_pair_gate", "lsfm_map_feature_pair_gate_timed", "lsfm_save_pair_gate", "lsfm_read_pair_gate",
            "lsfm_map_merge_features", "lsfm_map_merge_features_timed", "lsfm_merge_structure", "lsfm_save_merge_report", "lsfm_read_merge_report",
+           "lsfm_map_feature_pair_candidates", "lsfm_map_feature_pair_candidates_timed", "lsfm_save_pair_list", "lsfm_read_pair_list",
            "lsfm_map_marginalise", "lsfm_map_marginalise_timed", "lsfm_tree_export_reduced_size", "lsfm_tree_export_reduced_dev",
            "lsfm_tree_export_reduced_dev_timed", "lsfm_map_marginalise_poses", "lsfm_map_marginalise_poses_timed", "lsfm_marg_pose_structure", "lsfm_gn_structure"]
 
@@ -758,6 +764,49 @@ class Context:
             raise LsfmError(f"lsfm_map_merge_features: {rc} pivot(s) floored -- the merged information matrix is too close to singular")
         return dict(map=g, d2=d2, dof=dof, rep=rep, steps=steps, last_corr=corr, converged=rc == 0)
 
+    def feature_pair_candidates_raw(self, d, radius, feat_cov=None, tau=None, cap=None, dist2=True, q=None, times=False):
+        """lsfm_map_feature_pair_candidates(_timed) as it is: (rc, count, pairs [min(count, cap), 2] or None, dist2 or None, q or None,
+        times[4] or None, info[4] or None).  cap None: the sizing call (pairs NULL, cap 0).  q None: asked for exactly when feat_cov is
+        given.  rc is returned, not raised; the arrays come back whole up to cap where the call refused, so a test sees what was
+        written."""
+        h = HostMap(d)
+        fc = None
+        if feat_cov is not None:
+            fc = _c(feat_cov, np.float64)
+            if len(fc) != 9 * h.c.n:
+                raise LsfmError(f"feature_pair_candidates: {len(fc)} covariance entries for {h.c.n} features")
+        if q is None:
+            q = fc is not None
+        sizing = cap is None
+        cap = 0 if sizing else int(cap)
+        pr = None if sizing else np.full((max(cap, 1), 2), -1, np.int32)
+        dd = np.full(max(cap, 1), -1.0) if (dist2 and not sizing) else None
+        qq = np.full(max(cap, 1), -1.0) if (q and not sizing) else None
+        cnt = C.c_longlong(0)
+        t = np.zeros(4) if times else None
+        inf = np.zeros(4, np.int64) if times else None
+        rc = lib().lsfm_map_feature_pair_candidates_timed(self._h, C.byref(h.c), _ptr(fc, C.c_double) if fc is not None else None, float(radius),
+                                                          float(tau) if tau is not None else 0.0, _ptr(pr, C.c_int) if pr is not None else None,
+                                                          _ptr(dd, C.c_double) if dd is not None else None, _ptr(qq, C.c_double) if qq is not None else None,
+                                                          cap, C.byref(cnt), _ptr(t, C.c_double) if times else None,
+                                                          _ptr(inf, C.c_longlong) if times else None)
+        k = min(cnt.value, cap) if rc == 0 else cap
+        return (rc, cnt.value, pr[:k] if pr is not None else None, dd[:k] if dd is not None else None, qq[:k] if qq is not None else None, t, inf)
+
+    def feature_pair_candidates(self, d, radius, feat_cov=None, tau=None):
+        """lsfm_map_feature_pair_candidates: every pair f < g of map dict d's features (indices into its feature order) that lie within
+        `radius` of each other and, with feat_cov [n, 3, 3] (covariance(d, mono)["feature"]) and tau, whose bound q = 1/2 d^T (Sigma_ff +
+        Sigma_gg)^-1 d is <= tau.  q never exceeds the gate's d^2, so no pair feature_pair_gate would accept at tau is lost; a pair whose
+        sum of blocks is not positive definite is kept with q = NaN.  Sizes, then fills: two calls.  No reference counterpart.  Returns
+        dict(pairs [K, 2] int32 sorted by (f, g), dist2 [K], q [K] or None)."""
+        if (feat_cov is None) != (tau is None):
+            raise LsfmError("feature_pair_candidates: feat_cov and tau go together")
+        rc, count, _, _, _, _, _ = self.feature_pair_candidates_raw(d, radius, feat_cov, tau)
+        self._check(rc, "lsfm_map_feature_pair_candidates")
+        rc, count, pr, dd, qq, _, _ = self.feature_pair_candidates_raw(d, radius, feat_cov, tau, cap=count)
+        self._check(rc, "lsfm_map_feature_pair_candidates")
+        return dict(pairs=pr[:count], dist2=dd[:count], q=qq[:count] if qq is not None else None)
+
     def marginalise(self, d, drop, times=False):
         """lsfm_map_marginalise: the map dict d with every feature f that has drop[f] != 0 marginalised out (U' = U - sum W_f V_f^-1
         W_f^T over the dropped features), in canonical form: kept features in their order with V / W / photo unchanged, one U block
@@ -1183,6 +1232,31 @@ def read_pair_gate(path, cap=None):
         raise LsfmError(f"lsfm_read_pair_gate({path}) failed (rc={rc})")
     k = cnt.value
     return np.stack([jf[:k], jg[:k]], axis=1), dd[:k].copy(), cv[:k].copy()
+
+
+def save_pair_list(path, ids):
+    """lsfm_save_pair_list: a pair list -- the input of -gate and -merge, the output of -cand -- for the feature labels ids [K, 2]."""
+    i = _c(ids, np.int32)
+    if len(i) % 2:
+        raise LsfmError(f"save_pair_list: {len(i)} ids are not pairs")
+    rc = lib().lsfm_save_pair_list(path.encode(), _ptr(i, C.c_int) if len(i) else None, len(i) // 2)
+    if rc != 0:
+        raise LsfmError(f"lsfm_save_pair_list failed (rc={rc})")
+
+
+def read_pair_list(path, cap=None):
+    """lsfm_read_pair_list: a pair list as ids [count, 2] int32; cap None: sized by a first call."""
+    cnt = C.c_longlong(0)
+    if cap is None:
+        rc = lib().lsfm_read_pair_list(path.encode(), None, 0, C.byref(cnt))
+        if rc != 0 and not (rc == -1 and cnt.value > 0):
+            raise LsfmError(f"lsfm_read_pair_list({path}) failed (rc={rc})")
+        cap = cnt.value
+    ids = np.zeros((max(int(cap), 1), 2), np.int32)
+    rc = lib().lsfm_read_pair_list(path.encode(), _ptr(ids, C.c_int), int(cap), C.byref(cnt))
+    if rc != 0:
+        raise LsfmError(f"lsfm_read_pair_list({path}) failed (rc={rc})")
+    return ids[:cnt.value].copy()
 
 
 def save_merge_report(path, ids, removed, dof, d2):

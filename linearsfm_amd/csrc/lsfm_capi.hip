@@ -630,6 +630,23 @@ int lsfm_map_merge_features(lsfm_context* ctx, const lsfm_map* map, int mono, co
 	return lsfm_map_merge_features_timed(ctx, map, mono, pairs, K, out, d2, dof, rep, steps, last_corr, nullptr);
 }
 
+int lsfm_map_feature_pair_candidates_timed(lsfm_context* ctx, const lsfm_map* map, const double* feat_cov, double radius, double tau, int* pairs,
+                                           double* dist2, double* q, long long cap, long long* count, double* times, long long* info)
+{
+	// (neither U, W nor V is read: the map needs its sizes and, where it has features, its estimates)
+	if (!map || map->m < 0 || map->n < 0 || (map->n && !map->stVal) || !count) return LSFM_ERR_ARG;
+	long long cnt = 0; // (set even where the call throws: a cap that is too small)
+	const int rc = guarded(ctx, [&]() { return map_feature_pair_candidates(ctx, map, feat_cov, radius, tau, pairs, dist2, q, cap, &cnt, times, info); });
+	*count = cnt;
+	return rc;
+}
+
+int lsfm_map_feature_pair_candidates(lsfm_context* ctx, const lsfm_map* map, const double* feat_cov, double radius, double tau, int* pairs, double* dist2,
+                                     double* q, long long cap, long long* count)
+{
+	return lsfm_map_feature_pair_candidates_timed(ctx, map, feat_cov, radius, tau, pairs, dist2, q, cap, count, nullptr, nullptr);
+}
+
 int lsfm_inverse_v(lsfm_context* ctx, double* V, int m, int n)
 {
 	(void)m;

@@ -23,6 +23,14 @@
 // was merged away is "no feature"; -mergeout: line 1 "K features_removed dof D2", then "id_f id_g id_kept" per pair at %.17g, written after
 // -gateout through a temporary file renamed into place; not together with -chi2 / -chi2f -- the local maps still hold the merged-away ids --:
 // that ends the run non-zero before any file is written; a numerical failure ends the run as -gate's does; no reference counterpart),
+// -cand <file> -candr <radius> [-candtau <tau>] (the candidate pairs for -gate / -merge from the final map alone -- the map -gate resolves its
+// ids in: after -gn, -relin, -merge, -keepf and -keepp: every pair of features within <radius> of each other and, with -candtau, whose bound
+// q = 1/2 d^T (Sigma_ff + Sigma_gg)^-1 d is <= tau -- never above the gate's d2, so no pair the gate accepts at tau is lost:
+// lsfm_map_feature_pair_candidates; with -candtau the feature covariances are lsfm_map_covariance's, computed once and shared with -cov / -covf;
+// the file is a pair list of the features' ids in the call's order, the format -gate and -merge read, written after -mergeout and before
+// -chi2 through a temporary file renamed into place; -cand without -candr, -candr or -candtau without -cand, a value that is not a positive
+// number or a refusal of the library end the run non-zero before any file is written; feeding the file to -gate in the same run is not
+// offered: -gate validates its file before anything is computed; no reference counterpart),
 // -robust huber|cauchy <c> (-gn uses lsfm_gn_polish_robust: whole local maps down-weighted by an M-estimator on chi2_k / dof_k),
 // -chi2 <file> (per local map, in input order, "index dof chi2 weight" at the final state: lsfm_map_chi2; no reference counterpart),
 // -robustf huber|cauchy <c> (-gn uses lsfm_gn_polish_robust_features: single features of single local maps down-weighted by an M-estimator on
@@ -74,16 +82,17 @@ static void print_help()
 	printf("-keepf <file>		Keep Only The Features Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
 	printf("-gate <file> -gateout <file>	Gate Candidate Feature Pairs (Two Ids Each): id_f id_g d2 And The Upper Triangle Of Var(x_f - x_g)\n");
 	printf("-merge <file> [-mergeout <file>]	Merge Feature Pairs (Two Ids Each) Into One Point Each; Report: K removed dof D2, Then id_f id_g id_kept\n");
+	printf("-cand <file> -candr <radius> [-candtau <tau>]	Save The Candidate Feature Pairs For -gate / -merge: Within <radius>, And With -candtau Bound q <= tau\n");
 	printf("-keepp <file>		Keep Only The Poses Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
 	printf("\n");
 }
 
 int main(int argc, char** argv)
 {
-	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf, keepp, chi2ff, gate, gateout, merge, mergeout;
+	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf, keepp, chi2ff, gate, gateout, merge, mergeout, cand, candr, candtau;
 	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0, relin = 0, robustf = 0;
 	double robust_c = 0.0, robustf_c = 0.0;
-	bool has_path = false, has_num = false, has_keepf = false, has_keepp = false, has_gate = false, has_gateout = false, has_merge = false, has_mergeout = false;
+	bool has_path = false, has_num = false, has_keepf = false, has_keepp = false, has_gate = false, has_gateout = false, has_merge = false, has_mergeout = false, has_cand = false, has_candr = false, has_candtau = false;
 	double tol = 0;
 	for (int i = 1; i < argc; i++)
 	{
@@ -129,6 +138,9 @@ int main(int argc, char** argv)
 		else if (name == "gateout") { gateout = next(); has_gateout = true; }
 		else if (name == "merge") { merge = next(); has_merge = true; }
 		else if (name == "mergeout") { mergeout = next(); has_mergeout = true; }
+		else if (name == "cand") { cand = next(); has_cand = true; }
+		else if (name == "candr") { candr = next(); has_candr = true; }
+		else if (name == "candtau") { candtau = next(); has_candtau = true; }
 		else if (name == "robust" || name == "robustf")
 		{
 			const std::string k = next(), v = next();
@@ -194,6 +206,18 @@ int main(int argc, char** argv)
 		return 1;
 	}
 	if (has_merge && !read_pairs("-merge", merge, mergeids)) return 1;
+	// -cand: the flags go together and their values are positive numbers, before anything is computed
+	double cand_radius = 0.0, cand_tau = 0.0;
+	if (has_cand && (!has_candr || cand.empty())) { fprintf(stderr, "LinearSFM: -cand <file> needs -candr <radius>\n"); return 1; }
+	if ((has_candr || has_candtau) && !has_cand) { fprintf(stderr, "LinearSFM: -candr <radius> and -candtau <tau> need -cand <file>\n"); return 1; }
+	auto positive = [](const char* flag, const std::string& v, double& x) {
+		char* end = nullptr;
+		x = strtod(v.c_str(), &end);
+		if (v.empty() || *end || !std::isfinite(x) || x <= 0) { fprintf(stderr, "LinearSFM: %s: '%s' is not a positive number\n", flag, v.c_str()); return false; }
+		return true;
+	};
+	if (has_candr && !positive("-candr", candr, cand_radius)) return 1;
+	if (has_candtau && !positive("-candtau", candtau, cand_tau)) return 1;
 	if (robust && gn <= 0) { fprintf(stderr, "LinearSFM: -robust applies to -gn <steps>: give -gn too\n"); return 1; }
 	if (robustf && gn <= 0) { fprintf(stderr, "LinearSFM: -robustf applies to -gn <steps>: give -gn too\n"); return 1; }
 	if (robustf && robust) { fprintf(stderr, "LinearSFM: -robustf and -robust do not go together: the map and the feature estimator are not combined\n"); return 1; }
@@ -456,6 +480,33 @@ int main(int argc, char** argv)
 		if (at < 0) { fprintf(stderr, "LinearSFM: -gate: the final map has no feature %d\n", id); return 3; }
 		gatepairs.push_back(at);
 	}
+	// marginal covariances of the final map (after -gn its information matrix is still the tree's, unless -relin 1): once, for -cov / -covf
+	// and for -candtau
+	std::vector<double> pc, fc;
+	auto covariances = [&]() {
+		if (!pc.empty()) return true;
+		pc.resize((size_t)out.m * 36 + 1); fc.resize((size_t)out.n * 9 + 1);
+		const int crc = lsfm_map_covariance(ctx, &out, type, pc.data(), fc.data(), nullptr, 0, nullptr);
+		if (crc != LSFM_OK)
+			fprintf(stderr, "LinearSFM: covariance: %s\n", crc < 0 ? lsfm_last_error(ctx) : "pivots had to be floored (the information matrix is too close to singular)");
+		return crc == LSFM_OK;
+	};
+	// -cand: the candidate pairs of the final map, before any file is written (a refusal: nothing is written)
+	std::vector<int> candids;
+	long long ncand = 0;
+	if (has_cand)
+	{
+		if (has_candtau && !covariances()) return 3;
+		const double* sig = has_candtau ? fc.data() : nullptr;
+		int crc = lsfm_map_feature_pair_candidates(ctx, &out, sig, cand_radius, cand_tau, nullptr, nullptr, nullptr, 0, &ncand);
+		if (crc == LSFM_OK && ncand > 0)
+		{
+			candids.resize(2 * (size_t)ncand);
+			crc = lsfm_map_feature_pair_candidates(ctx, &out, sig, cand_radius, cand_tau, candids.data(), nullptr, nullptr, ncand, &ncand);
+		}
+		if (crc != LSFM_OK) { fprintf(stderr, "LinearSFM: -cand: %s\n", lsfm_last_error(ctx)); return 3; }
+		for (int& f : candids) f = out.stno[6 * out.m + 3 * f]; // indices to labels
+	}
 	const int r = 6 * out.m + 3 * out.n;
 	if (!st.empty()) lsfm_save_state(st.c_str(), out.stVal, out.stno, r);
 	if (!pose.empty() && !fea.empty()) lsfm_save_poses(pose.c_str(), fea.c_str(), out.stno, out.stVal, r); // only together (Imp.cpp:2078)
@@ -468,14 +519,8 @@ int main(int argc, char** argv)
 	if (!fullbin.empty() && lsfm_save_state_bin(fullbin.c_str(), out.stVal, out.stno, r)) fprintf(stderr, "LinearSFM: cannot write %s\n", fullbin.c_str());
 	if (!cov.empty() || !covf.empty())
 	{
-		// marginal covariances of the map the files above hold (after -gn its information matrix is still the tree's, unless -relin 1)
-		std::vector<double> pc((size_t)out.m * 36), fc((size_t)out.n * 9);
-		const int crc = lsfm_map_covariance(ctx, &out, type, pc.data(), fc.data(), nullptr, 0, nullptr);
-		if (crc != LSFM_OK)
-		{
-			fprintf(stderr, "LinearSFM: covariance: %s\n", crc < 0 ? lsfm_last_error(ctx) : "pivots had to be floored (the information matrix is too close to singular)");
-			return 3;
-		}
+		// of the map the files above hold
+		if (!covariances()) return 3;
 		if (lsfm_save_covariances(cov.empty() ? nullptr : cov.c_str(), covf.empty() ? nullptr : covf.c_str(), out.stno, out.m, out.n, pc.data(), fc.data()))
 			fprintf(stderr, "LinearSFM: cannot write the covariance files\n");
 	}
@@ -515,18 +560,20 @@ int main(int argc, char** argv)
 		for (int a = 0; a < K; a++) { ids.push_back(mergeids[2 * a]); ids.push_back(mergeids[2 * a + 1]); ids.push_back(mergekept[a]); }
 		if (lsfm_save_merge_report(mergeout.c_str(), K, merge_removed, merge_dof, merge_d2, ids.data())) fprintf(stderr, "LinearSFM: cannot write %s\n", mergeout.c_str());
 	}
+	if (has_cand && lsfm_save_pair_list(cand.c_str(), candids.data(), ncand)) fprintf(stderr, "LinearSFM: cannot write %s\n", cand.c_str());
 	if (!json.empty())
 	{
+		const std::string cand_json = has_cand ? ", \"candidates\": " + std::to_string(ncand) : "";
 		FILE* f = fopen(json.c_str(), "w");
 		if (f)
 		{
 			fprintf(f, "{\"maps\": %d, \"type\": \"%s\", \"from_cache\": %s, \"poses\": %d, \"features\": %d, \"rc\": %d, \"t_total_ms\": %.6f, \"t_transform_ms\": %.6f, "
 			           "\"t_join_ms\": %.6f, \"t_schur_ms\": %.6f, \"t_pcg_ms\": %.6f, \"t_backsub_ms\": %.6f, \"levels\": %d, \"joins\": %d, \"transforms\": %d, "
-			           "\"pcg_iterations\": %ld, \"max_rel_residual\": %.6e, \"not_converged\": %d, \"attempts\": %d, "
+			           "\"pcg_iterations\": %ld, \"max_rel_residual\": %.6e, \"not_converged\": %d, \"attempts\": %d%s, "
 			           "\"phases_s\": {\"read\": %.6f, \"context\": %.6f, \"upload\": %.6f, \"join_tree\": %.6f, \"download\": %.6f, \"write\": %.6f}}\n",
 			        num, type ? "Monocular" : "Stereo", from_cache ? "true" : "false", out.m, out.n, rc, stats.t_total_ms, stats.t_transform_ms, stats.t_join_ms,
 			        stats.t_schur_ms, stats.t_pcg_ms, stats.t_backsub_ms, stats.levels, stats.joins, stats.transforms, (long)stats.pcg_iterations,
-			        stats.max_rel_residual, stats.not_converged, stats.attempts, w1 - w0, w2 - w1, w3 - w2, w4 - w3, w5 - w4, now() - w5);
+			        stats.max_rel_residual, stats.not_converged, stats.attempts, cand_json.c_str(), w1 - w0, w2 - w1, w3 - w2, w4 - w3, w5 - w4, now() - w5);
 			fclose(f);
 		}
 		else fprintf(stderr, "LinearSFM: cannot write %s\n", json.c_str());

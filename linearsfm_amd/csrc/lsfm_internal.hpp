@@ -587,6 +587,12 @@ int map_feature_pair_gate(lsfm_context* ctx, const lsfm_map* map, bool mono, con
 // to the host, its upload + reduction + analysis + factorisation, right-hand side + sweeps + refinement, back-substitution + D^2, download
 int map_merge_features(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* pairs, int K, lsfm_map* out, double* d2, int* dof, int* rep,
                        int* steps, double* last_corr, double* times);
+// every feature pair within `radius` whose bound q = 1/2 d^T (Sigma_ff + Sigma_gg)^-1 d <= tau (feat_cov may be null: the radius alone), by a
+// cell search (lsfm_candidates.hip; C ABI: lsfm_map_feature_pair_candidates).  *count is set before a cap that is too small is refused.
+// times (may be null): [4] ms of upload + keys, sort + cell table, count + scan, fill + sort + download; info (may be null): [4] cells,
+// fullest cell, pair tests, candidates
+int map_feature_pair_candidates(lsfm_context* ctx, const lsfm_map* map, const double* feat_cov, double radius, double tau, int* pairs, double* dist2, double* q,
+                                long long cap, long long* count, double* times, long long* info);
 // the two feature-side pieces of the solve on their own (lsfm_solve.hip; C ABI: lsfm_inverse_v / lsfm_solve_features); host pointers,
 // arguments checked by the caller
 int inverse_v(lsfm_context* ctx, double* V, int n);

@@ -676,4 +676,40 @@ int lsfm_read_merge_report(const char* path, int* K, int* removed, int* dof, dou
 	return rc;
 }
 
+// a pair list (what -gate and -merge read, what -cand writes): one line "id_f id_g" per pair
+int lsfm_save_pair_list(const char* path, const int* ids, long long K)
+{
+	if (!path || K < 0 || (K && !ids)) return LSFM_ERR_ARG;
+	const std::string tmp = std::string(path) + ".tmp";
+	FILE* fp = fopen(tmp.c_str(), "w");
+	if (!fp) return LSFM_ERR_IO;
+	for (long long a = 0; a < K; a++) fprintf(fp, "%d %d\n", ids[2 * a], ids[2 * a + 1]);
+	const bool bad = ferror(fp) != 0;
+	if (fclose(fp) != 0 || bad || rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); return LSFM_ERR_IO; }
+	return LSFM_OK;
+}
+
+// a pair list back, read as -gate and -merge read it (whitespace-separated ids, two per pair): ids[2 cap]; *count = the pairs in the file,
+// also when cap is too small.  An odd number of ids -- a last line cut short -- or anything that is not an id is LSFM_ERR_IO
+int lsfm_read_pair_list(const char* path, int* ids, long long cap, long long* count)
+{
+	if (!path || cap < 0 || !count || (cap && !ids)) return LSFM_ERR_ARG;
+	*count = 0;
+	FILE* fp = fopen(path, "r");
+	if (!fp) return LSFM_ERR_IO;
+	long long cnt = 0;
+	int f = 0, g = 0, got = 0, rc = LSFM_OK;
+	while ((got = fscanf(fp, "%d", &f)) == 1)
+	{
+		if ((got = fscanf(fp, "%d", &g)) != 1) { rc = LSFM_ERR_IO; break; }
+		if (cnt < cap) { ids[2 * cnt] = f; ids[2 * cnt + 1] = g; }
+		cnt++;
+	}
+	if (rc == LSFM_OK && got != EOF) rc = LSFM_ERR_IO;
+	fclose(fp);
+	*count = cnt;
+	if (rc == LSFM_OK && cnt > cap) rc = LSFM_ERR_ARG;
+	return rc;
+}
+
 } // extern "C"

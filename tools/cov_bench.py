@@ -19,7 +19,13 @@ usage: python tools/cov_bench.py <config> [maps] [reps]  -> one JSON object on s
                        residual form (x^ - T y)^T I (x^ - T y) in long double, and the columns route below (profiles/merge_<config>.json)
   --merge-parent-route K[,K...]   instead: the same merged state and D^2 by the only route before lsfm_map_merge_features --
                        covariance_feature_columns(the 2K features, poses, features, joint) and the host formula x^ - Sigma A^T C^-1 d,
-                       D^2 = d^T C^-1 d (existing API only: runs on older commits too; profiles/merge_parent_<config>.json)"""
+                       D^2 = d^T C^-1 d (existing API only: runs on older commits too; profiles/merge_parent_<config>.json)
+  --candidates R[,R...] [--tau t] [--split K]   instead: lsfm_map_feature_pair_candidates_timed at every radius R on the tree of the set with
+                       K features split in two (default 32; --merge's rule), with --tau on lsfm_map_covariance's feature blocks: HIP-event ms
+                       of the four parts, info, pair tests per second of the counting pass, how many of the K split pairs are among the
+                       candidates, and the wall time of the sizing + filling calls beside the only route without the entry point --
+                       scipy.spatial.cKDTree.query_pairs(R) on the host and the q filter in numpy; the two lists are compared
+                       (profiles/candidates_<config>.json)"""
 import json
 import os
 import sys
@@ -51,6 +57,19 @@ for flag in ("--feature-columns", "--gate", "--gate-parent-route", "--merge", "-
         i = args.index(flag)
         modes[flag] = [int(v) for v in args[i + 1].split(",")]
         del args[i: i + 2]
+cand_radii, cand_tau, cand_split = None, None, 32
+if "--candidates" in args:
+    i = args.index("--candidates")
+    cand_radii = [float(v) for v in args[i + 1].split(",")]
+    del args[i: i + 2]
+if "--tau" in args:
+    i = args.index("--tau")
+    cand_tau = float(args[i + 1])
+    del args[i: i + 2]
+if "--split" in args:
+    i = args.index("--split")
+    cand_split = int(args[i + 1])
+    del args[i: i + 2]
 cfg = args[0]
 nmaps = int(args[1]) if len(args) > 1 and int(args[1]) > 0 else None
 reps = int(args[2]) if len(args) > 2 else 3
@@ -130,6 +149,69 @@ def columns_route(Gs, pairs):
     return x - SA @ sol, float(dv @ sol), Cm, fc, t1
 
 
+def host_candidates(x, R, fcov, tau):
+    """The route without the entry point: a k-d tree on the host for the radius, then q = 1/2 d^T (Sigma_ff + Sigma_gg)^-1 d in numpy.  Returns
+    (pairs sorted by (f, g), seconds of the tree + query, seconds of the filter + sort)."""
+    from scipy.spatial import cKDTree
+    t0 = time.perf_counter()
+    pr = cKDTree(x).query_pairs(R, output_type="ndarray")
+    t1 = time.perf_counter()
+    if fcov is not None and len(pr):
+        dv = x[pr[:, 0]] - x[pr[:, 1]]
+        M = fcov[pr[:, 0]] + fcov[pr[:, 1]]
+        with np.errstate(all="ignore"):
+            qv = 0.5 * np.einsum("ki,ki->k", dv, np.linalg.solve(M, dv[:, :, None])[:, :, 0])
+        pr = pr[~(qv > tau)]
+    pr = pr[np.lexsort((pr[:, 1], pr[:, 0]))] if len(pr) else pr.reshape(0, 2)
+    return pr.astype(np.int32), t1 - t0, time.perf_counter() - t1
+
+
+if cand_radii is not None:
+    Gs, split = split_tree(cand_split)
+    ms, ns = int(Gs["m"]), int(Gs["n"])
+    x = np.ascontiguousarray(np.asarray(Gs["stVal"], np.float64)[6 * ms:].reshape(-1, 3))
+    fcov = np.ascontiguousarray(ctx.covariance(Gs, mono)["feature"]) if cand_tau is not None else None
+    splitset = {tuple(sorted(map(int, p))) for p in split}
+    legs = []
+    for R in cand_radii:
+        walls, parts = [], []
+        try:
+            for rep in range(reps + 1):  # (the first round is a warm-up)
+                t0 = time.perf_counter()
+                out = ctx.feature_pair_candidates(Gs, R, fcov, cand_tau)
+                wall = 1e3 * (time.perf_counter() - t0)
+                if rep:
+                    walls.append(wall)
+        except api.LsfmError as e:  # (a refusal -- too many cells, too many candidates, no room -- is a row too)
+            legs.append({"leg": "candidates", "radius": R, "tau": cand_tau, "refused": str(e)})
+            continue
+        for rep in range(reps):  # the parts, from filling calls of their own
+            crc, count, pr, _, _, t, info = ctx.feature_pair_candidates_raw(Gs, R, fcov, cand_tau, cap=len(out["pairs"]), times=True)
+            if crc != 0:
+                sys.exit(f"lsfm_map_feature_pair_candidates: {api.lib().lsfm_last_error(ctx._h).decode()}")
+            parts.append(t.tolist())
+        med = np.median(np.array(parts), axis=0)
+        hw, hq, hf = [], [], []
+        for rep in range(max(1, min(reps, 2))):
+            t0 = time.perf_counter()
+            hp, tq, tf = host_candidates(x, R, fcov, cand_tau)
+            hw.append(1e3 * (time.perf_counter() - t0)); hq.append(1e3 * tq); hf.append(1e3 * tf)
+        have = {tuple(p) for p in out["pairs"].tolist()} if len(out["pairs"]) <= 5_000_000 else None
+        legs.append({"leg": "candidates", "radius": R, "tau": cand_tau, "split_pairs": len(splitset),
+                     "split_pairs_among_candidates": len(splitset & have) if have is not None else None,
+                     "info": {"cells": int(info[0]), "fullest_cell": int(info[1]), "pair_tests": int(info[2]), "candidates": int(info[3])},
+                     "ms_median": {"upload_keys": med[0], "sort_cell_table": med[1], "count_scan": med[2], "fill_sort_download": med[3]},
+                     "pair_tests_per_s_count_pass": float(info[2]) / (med[2] * 1e-3) if med[2] > 0 else None,
+                     "call_wall_ms_median": float(np.median(walls)), "call_wall_ms": walls,
+                     "host_route_wall_ms_median": float(np.median(hw)), "host_route_wall_ms": hw, "host_kdtree_ms_median": float(np.median(hq)),
+                     "host_filter_sort_ms_median": float(np.median(hf)), "host_route_pairs": int(len(hp)),
+                     "same_pairs_as_host_route": bool(np.array_equal(hp, out["pairs"]))})
+    print(json.dumps({"config": cfg, "type": typ, "maps": len(maps), "poses": ms, "features": ns, "split": cand_split, "legs": legs,
+                      "note": "HIP events on the context's stream; call wall: Context.feature_pair_candidates, the sizing and the filling call with the "
+                              "upload of the estimates (and blocks) and the downloads, the covariance call not included on either route; host route: "
+                              "scipy.spatial.cKDTree(x).query_pairs(R) and the q filter in numpy on the same arrays; split pairs by default_rng(3)"}, indent=1))
+    ctx.close()
+    sys.exit(0)
 if "--merge" in modes:
     legs = []
     for K in modes["--merge"]:
