@@ -431,6 +431,48 @@ int lsfm_map_feature_pair_candidates(lsfm_context* ctx, const lsfm_map* map, con
 int lsfm_map_feature_pair_candidates_timed(lsfm_context* ctx, const lsfm_map* map, const double* feat_cov, double radius, double tau, int* pairs,
                                            double* dist2, double* q, long long cap, long long* count, double* times, long long* info);
 
+/* ---- joint compatibility of gated feature pairs: sequential selection (NO reference counterpart) ----
+ * Between lsfm_map_feature_pair_gate, which judges each pair alone, and lsfm_map_merge_features, which reports the joint D^2 of all the
+ * pairs it is given: which of the K pairs (f_b, g_b) = (pairs[2 b], pairs[2 b + 1]) are compatible TOGETHER.  With A the 3K x (6m + 3n)
+ * matrix of rows e_f - e_g, C = A Sigma A^T and d = A x^ (map->stVal): block C_ba = Sigma_{f_b,a} - Sigma_{g_b,a} from the feature rows of
+ * the gate's column group a -- the 3 K columns the gate solves, no others (chunks of 64 groups, lsfm_map_covariance_columns' sweeps and
+ * refinement); a diagonal block is the gate's Sigma_d, d2[K] the gate's individual d^2 (NaN as there); C is made exactly symmetric by the
+ * rule of `joint` above.  joint_C[(3K)^2] (may be NULL): C, row-major, pairs in input order.
+ * order[K] (may be NULL): the processing order, a permutation of 0..K-1.  NULL: ascending d2, ties by input index, NaN last -- a function
+ * of the bits of d2 alone.
+ * Selection, for b in that order, with Acc the list of the pairs accepted so far:
+ *   - f_b and g_b already connected in the graph whose edges are the accepted pairs (a pair given twice, in either order; the side that
+ *     closes a cycle): status 2 (implied), delta = 0, nothing is factored.  The test is structural and exact: C_AccAcc is singular exactly
+ *     when the rows of A are dependent, i.e. when a pair closes a cycle, so no pivot threshold exists.
+ *   - otherwise S = C_bb - C_bAcc C_AccAcc^-1 C_Accb, e = d_b - C_bAcc C_AccAcc^-1 d_Acc, delta = e^T S^-1 e by a 3x3 Cholesky; a pivot that is
+ *     not > 0 (NaN included) or a NaN d2: status 0, delta = NaN; status 1 (accepted) iff delta <= tau, else status 0.
+ *   *D2 = the sum of delta over the accepted pairs in processing order = d_Acc^T C_AccAcc^-1 d_Acc, with 3 *accepted degrees of freedom:
+ *   what lsfm_map_merge_features reports for exactly those pairs.  tau > 0, +inf allowed (every independent pair is accepted).
+ * A delta within 1e-6 relative of tau may fall on either side (the sweeps behind C are not bit-reproducible); what follows is then the
+ * selection after that decision.  GIVEN the bits of C, d, the order and tau the selection is bit-reproducible: a right-looking blocked
+ * Cholesky with rejection on the device, panels of 16 pairs, the trailing update on v_mfma_f64_16x16x4_f64 with one wave per output tile,
+ * no floating-point atomics.
+ * Outputs: status[K], delta[K] in input order; *accepted, *implied the counts; *steps, last_corr[K] as the gate's; d2, joint_C, last_corr
+ * may be NULL.  1 <= K <= LSFM_JOINT_GATE_MAX.
+ * Returns as lsfm_map_feature_pair_gate: LSFM_OK; LSFM_NOT_CONVERGED (results written); LSFM_ERR_NOT_SPD, and > 0 = floored pivots (nothing
+ * written, *steps = 0); LSFM_ERR_OOM; LSFM_ERR_ARG for K out of range, an index out of range, f == g, an order that is no permutation, tau
+ * NaN or <= 0, a required output NULL, and whatever lsfm_map_covariance refuses.  Lifetime: the context's arenas, as the gate. */
+#define LSFM_JOINT_GATE_MAX 2048
+int lsfm_map_feature_pair_joint_gate(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, const int* order, double tau, int* status,
+                                     double* delta, double* d2, double* joint_C, int* accepted, int* implied, double* D2, int* steps, double* last_corr);
+/* measurement entry: the same, and times[6] (may be NULL) = HIP-event ms of reduction + analysis | factorisation | sweeps + refinement | the
+ * blocks of C | the selection: its kernels, k_jc_permute to the last panel, and nothing else | the downloads (d2, status, delta, joint_C) together
+ * with what the host does between them: the order, the endpoint numbering, the selection's device allocations and uploads */
+int lsfm_map_feature_pair_joint_gate_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, const int* order, double tau,
+                                           int* status, double* delta, double* d2, double* joint_C, int* accepted, int* implied, double* D2, int* steps,
+                                           double* last_corr, double* times);
+/* Test entry: the selection alone on the caller's matrix.  C[(3K)^2] row-major and symmetric (either triangle of a block pair may be the one read), d[3K], ends[2K] the two
+ * endpoints of every pair (any int labels; equal labels are one vertex; ends[2 b] != ends[2 b + 1]), order[K] or NULL (then the individual
+ * d^2 = d_b^T C_bb^-1 d_b is taken on the host, NaN where C_bb has a pivot that is not > 0), tau as above.  status[K], delta[K], *D2,
+ * *accepted, *implied as above.  Host plumbing around the kernels of the call above; nothing is solved. */
+int lsfm_selftest_pair_select(lsfm_context* ctx, int K, const double* C, const double* d, const int* ends, const int* order, double tau, int* status,
+                              double* delta, double* D2, int* accepted, int* implied);
+
 /* ---- marginalising features out of a map (NO reference counterpart: the reference keeps every feature to the end) ----
  * out = `map` with every feature f that has drop[f] != 0 (drop[n], one flag per feature in the map's order) marginalised out:
  *     U' = U - sum_{f dropped} W_f V_f^-1 W_f^T
@@ -727,6 +769,15 @@ int lsfm_save_merge_report(const char* path, int K, int removed, int dof, double
 /* ... and back: the head and ids[3 cap].  LSFM_ERR_IO for a line cut short and for a file with fewer or more lines than its head
  * says, LSFM_ERR_ARG when cap < K */
 int lsfm_read_merge_report(const char* path, int* K, int* removed, int* dof, double* d2, int* ids, int cap);
+/* The -jgateout file (lsfm_map_feature_pair_joint_gate): line 1 "K accepted implied dof D2" with dof = 3 accepted; then per pair, in the
+ * order given, "id_f id_g status d2 delta" at %.17g (NaN is written "nan"); ids[2 K] the labels of the pairs' features.  Written through a
+ * temporary file that is renamed into place. */
+int lsfm_save_joint_gate(const char* path, const int* ids, int K, const int* status, const double* d2, const double* delta, int accepted, int implied,
+                         double D2);
+/* ... and back: head[4] = { K, accepted, implied, dof }, *D2, ids[2 cap], status / d2 / delta [cap].  LSFM_ERR_IO for a line cut short, fewer
+ * or more lines than the head says, a status outside 0..2, counts in the head that are not those of the lines, dof != 3 accepted;
+ * LSFM_ERR_ARG when cap < K (the head is set: call with cap = 0 for the size) */
+int lsfm_read_joint_gate(const char* path, int* ids, int* status, double* d2, double* delta, int cap, int* head, double* D2);
 /* A pair list, the input format of -gate and -merge and the output of -cand: one line "id_f id_g" per pair, ids[2 K] the labels of the
  * pairs' features, K >= 0.  Written through a temporary file that is renamed into place. */
 int lsfm_save_pair_list(const char* path, const int* ids, long long K);

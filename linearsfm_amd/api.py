@@ -50,6 +50,8 @@ class LsfmError(RuntimeError):
 # include/lsfm.h lsfm_allreduce_fn: (user, offset_bytes, count, dtype, hip_stream) -> 0 on success
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p)
 LSFM_DTYPE_F64, LSFM_DTYPE_I64 = 0, 1
+JOINT_GATE_MAX = 2048                   # include/lsfm.h LSFM_JOINT_GATE_MAX
+JOINT_GATE_TAU = 11.344866730144373     # chi^2_3 at 0.99: the default tau of feature_pair_joint_gate and -jgate
 
 
 def lib():
@@ -138,6 +140,11 @@ def lib():
         L.lsfm_map_feature_pair_gate_timed.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, dp, dp, ip, dp, dp]
         L.lsfm_map_merge_features.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, P(LsfmMap), dp, ip, ip, ip, dp]
         L.lsfm_map_merge_features_timed.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, P(LsfmMap), dp, ip, ip, ip, dp, dp]
+        L.lsfm_map_feature_pair_joint_gate.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, ip, C.c_double, ip, dp, dp, dp, ip, ip, dp, ip, dp]
+        L.lsfm_map_feature_pair_joint_gate_timed.argtypes = [vp, P(LsfmMap), C.c_int, ip, C.c_int, ip, C.c_double, ip, dp, dp, dp, ip, ip, dp, ip, dp, dp]
+        L.lsfm_selftest_pair_select.argtypes = [vp, C.c_int, dp, dp, ip, ip, C.c_double, ip, dp, dp, ip, ip]
+        L.lsfm_save_joint_gate.argtypes = [C.c_char_p, ip, C.c_int, ip, dp, dp, C.c_int, C.c_int, C.c_double]
+        L.lsfm_read_joint_gate.argtypes = [C.c_char_p, ip, ip, dp, dp, C.c_int, ip, dp]
         L.lsfm_merge_structure.argtypes = [P(LsfmMap), ip, C.c_int, ip, ip, ip, ip, ip, ip, C.c_int, ip, C.c_char_p, C.c_int]
         llp = P(C.c_longlong)
         L.lsfm_map_feature_pair_candidates.argtypes = [vp, P(LsfmMap), dp, C.c_double, C.c_double, ip, dp, dp, C.c_longlong, llp]
@@ -186,6 +193,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_map_covariance_feature_columns", "lsfm_map_covariance_feature_columns_timed", "lsfm_map_feature_pair_gate", "lsfm_map_feature_pair_gate_timed", "lsfm_save_pair_gate", "lsfm_read_pair_gate",
            "lsfm_map_merge_features", "lsfm_map_merge_features_timed", "lsfm_merge_structure", "lsfm_save_merge_report", "lsfm_read_merge_report",
            "lsfm_map_feature_pair_candidates", "lsfm_map_feature_pair_candidates_timed", "lsfm_save_pair_list", "lsfm_read_pair_list",
+           "lsfm_map_feature_pair_joint_gate", "lsfm_map_feature_pair_joint_gate_timed", "lsfm_selftest_pair_select", "lsfm_save_joint_gate", "lsfm_read_joint_gate",
            "lsfm_map_marginalise", "lsfm_map_marginalise_timed", "lsfm_tree_export_reduced_size", "lsfm_tree_export_reduced_dev",
            "lsfm_tree_export_reduced_dev_timed", "lsfm_map_marginalise_poses", "lsfm_map_marginalise_poses_timed", "lsfm_marg_pose_structure", "lsfm_gn_structure"]
 
@@ -807,6 +815,66 @@ class Context:
         self._check(rc, "lsfm_map_feature_pair_candidates")
         return dict(pairs=pr[:count], dist2=dd[:count], q=qq[:count] if qq is not None else None)
 
+    def feature_pair_joint_gate_raw(self, d, mono, pairs, tau=None, order=None, want_C=False, times=False):
+        """lsfm_map_feature_pair_joint_gate(_timed) as it is: (rc, dict(status [K], delta [K], d2 [K], C [3K,3K] or None, accepted, implied,
+        D2, steps, last_corr [K]), times[6] or None) for pairs [K, 2] of feature indices.  rc is returned, not raised."""
+        h = HostMap(d)
+        pr = _c(pairs, np.int32)
+        K = len(pr) // 2
+        k1 = max(K, 1)
+        od = _c(order, np.int32) if order is not None else None
+        if od is not None and len(od) != K:
+            raise LsfmError(f"feature_pair_joint_gate: an order of {len(od)} entries for {K} pairs")
+        st, dl, dd, corr = np.zeros(k1, np.int32), np.zeros(k1), np.zeros(k1), np.zeros(k1)
+        Cm = np.zeros((3 * K, 3 * K)) if (want_C and 1 <= K <= JOINT_GATE_MAX) else None
+        acc, imp, steps, D2 = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0)
+        t = np.zeros(6) if times else None
+        rc = lib().lsfm_map_feature_pair_joint_gate_timed(self._h, C.byref(h.c), int(mono), _ptr(pr, C.c_int) if K else None, K,
+                                                          _ptr(od, C.c_int) if od is not None and K else None, float(JOINT_GATE_TAU if tau is None else tau),
+                                                          _ptr(st, C.c_int), _ptr(dl, C.c_double), _ptr(dd, C.c_double),
+                                                          _ptr(Cm, C.c_double) if Cm is not None else None, C.byref(acc), C.byref(imp), C.byref(D2),
+                                                          C.byref(steps), _ptr(corr, C.c_double), _ptr(t, C.c_double) if times else None)
+        return rc, dict(status=st[:K], delta=dl[:K], d2=dd[:K], C=Cm, accepted=acc.value, implied=imp.value, D2=D2.value, steps=steps.value,
+                        last_corr=corr[:K]), t
+
+    def feature_pair_joint_gate(self, d, mono, pairs, tau=None, order=None, want_C=False):
+        """lsfm_map_feature_pair_joint_gate: which of the pairs [K, 2] (indices into map dict d's feature order) are compatible TOGETHER.  In
+        `order` (a permutation of 0..K-1; None: ascending individual d2) a pair already connected by the accepted pairs is implied (status
+        2, delta 0); otherwise delta = its d^2 conditioned on the accepted pairs, accepted (status 1) iff delta <= tau (None: chi^2_3 at
+        0.99; inf accepts every independent pair), else status 0.  D2 = the sum of delta over the accepted pairs = their joint compatibility
+        with 3 accepted degrees of freedom, what merge_features reports for exactly those pairs.  No reference counterpart.  Returns
+        dict(status, delta, d2, C (the joint matrix A Sigma A^T, with want_C), accepted, implied, D2, dof, steps, last_corr, converged).
+        Errors and statuses as feature_pair_gate."""
+        rc, out, _ = self.feature_pair_joint_gate_raw(d, mono, pairs, tau, order, want_C)
+        self._check(rc, "lsfm_map_feature_pair_joint_gate")
+        if rc > 0 and out["steps"] == 0:
+            raise LsfmError(f"lsfm_map_feature_pair_joint_gate: {rc} pivot(s) floored -- the information matrix is too close to singular")
+        out["dof"] = 3 * out["accepted"]
+        out["converged"] = rc == 0
+        return out
+
+    def selftest_pair_select(self, Cm, d, ends, tau, order=None, raw=False):
+        """lsfm_selftest_pair_select: the selection of feature_pair_joint_gate alone on the caller's symmetric matrix Cm [3K, 3K], d [3K]
+        and the pairs' endpoints ends [K, 2] (any labels).  Returns dict(status, delta, D2, accepted, implied); raw: (rc, dict)."""
+        en = _c(ends, np.int32)
+        K = len(en) // 2
+        cm, dv = _c(Cm, np.float64), _c(d, np.float64)
+        if len(cm) != 9 * K * K or len(dv) != 3 * K:
+            raise LsfmError(f"selftest_pair_select: {len(cm)} matrix and {len(dv)} vector entries for {K} pairs")
+        od = _c(order, np.int32) if order is not None else None
+        if od is not None and len(od) != K:
+            raise LsfmError(f"selftest_pair_select: an order of {len(od)} entries for {K} pairs")
+        st, dl = np.zeros(max(K, 1), np.int32), np.zeros(max(K, 1))
+        acc, imp, D2 = C.c_int(0), C.c_int(0), C.c_double(0.0)
+        rc = lib().lsfm_selftest_pair_select(self._h, K, _ptr(cm, C.c_double), _ptr(dv, C.c_double), _ptr(en, C.c_int),
+                                             _ptr(od, C.c_int) if od is not None else None, float(tau), _ptr(st, C.c_int), _ptr(dl, C.c_double),
+                                             C.byref(D2), C.byref(acc), C.byref(imp))
+        out = dict(status=st[:K], delta=dl[:K], D2=D2.value, accepted=acc.value, implied=imp.value)
+        if raw:
+            return rc, out
+        self._check(rc, "lsfm_selftest_pair_select")
+        return out
+
     def marginalise(self, d, drop, times=False):
         """lsfm_map_marginalise: the map dict d with every feature f that has drop[f] != 0 marginalised out (U' = U - sum W_f V_f^-1
         W_f^T over the dropped features), in canonical form: kept features in their order with V / W / photo unchanged, one U block
@@ -1281,3 +1349,35 @@ def read_merge_report(path, cap=None):
     if rc != 0:
         raise LsfmError(f"lsfm_read_merge_report({path}) failed (rc={rc})")
     return dict(K=K.value, removed=rem.value, dof=dof.value, d2=d2.value, ids=ids[:K.value].copy())
+
+
+def save_joint_gate(path, ids, status, d2, delta, D2):
+    """lsfm_save_joint_gate: the -jgateout file for the pairs' feature labels ids [K, 2] and status / d2 / delta [K], D2 as
+    feature_pair_joint_gate gives them (the counts of the head are taken from status)."""
+    i, st = _c(ids, np.int32), _c(status, np.int32)
+    dd, dl = _c(d2, np.float64), _c(delta, np.float64)
+    K = len(st)
+    if K < 1 or len(i) != 2 * K or len(dd) != K or len(dl) != K:
+        raise LsfmError(f"save_joint_gate: {len(i)} ids, {K} statuses, {len(dd)} d2 and {len(dl)} delta do not belong together")
+    rc = lib().lsfm_save_joint_gate(path.encode(), _ptr(i, C.c_int), K, _ptr(st, C.c_int), _ptr(dd, C.c_double), _ptr(dl, C.c_double),
+                                    int(np.sum(st == 1)), int(np.sum(st == 2)), float(D2))
+    if rc != 0:
+        raise LsfmError(f"lsfm_save_joint_gate failed (rc={rc})")
+
+
+def read_joint_gate(path, cap=None):
+    """lsfm_read_joint_gate: a -jgateout file as dict(K, accepted, implied, dof, D2, ids [K, 2], status, d2, delta [K])."""
+    if cap is None:
+        with open(path) as f:
+            cap = sum(1 for line in f if line.strip())
+    k1 = max(cap, 1)
+    ids, st, dd, dl = np.zeros((k1, 2), np.int32), np.zeros(k1, np.int32), np.zeros(k1), np.zeros(k1)
+    head = np.zeros(4, np.int32)
+    D2 = C.c_double(0.0)
+    rc = lib().lsfm_read_joint_gate(path.encode(), _ptr(ids, C.c_int), _ptr(st, C.c_int), _ptr(dd, C.c_double), _ptr(dl, C.c_double), int(cap),
+                                    _ptr(head, C.c_int), C.byref(D2))
+    if rc != 0:
+        raise LsfmError(f"lsfm_read_joint_gate({path}) failed (rc={rc})")
+    K = int(head[0])
+    return dict(K=K, accepted=int(head[1]), implied=int(head[2]), dof=int(head[3]), D2=D2.value, ids=ids[:K].copy(), status=st[:K].copy(),
+                d2=dd[:K].copy(), delta=dl[:K].copy())

@@ -616,6 +616,30 @@ int lsfm_map_feature_pair_gate(lsfm_context* ctx, const lsfm_map* map, int mono,
 	return lsfm_map_feature_pair_gate_timed(ctx, map, mono, pairs, K, d2, cov_diff, steps, last_corr, nullptr);
 }
 
+int lsfm_map_feature_pair_joint_gate_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, const int* order, double tau,
+                                           int* status, double* delta, double* d2, double* joint_C, int* accepted, int* implied, double* D2, int* steps,
+                                           double* last_corr, double* times)
+{
+	if (steps) *steps = 0;
+	if (!map_ok(map, mono, MAP_STVAL) || !pairs || K < 1 || !status || !delta || !accepted || !implied || !D2) return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() {
+		return map_feature_pair_joint_gate(ctx, map, mono == 1, pairs, K, order, tau, status, delta, d2, joint_C, accepted, implied, D2, steps, last_corr, times);
+	});
+}
+
+int lsfm_map_feature_pair_joint_gate(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, const int* order, double tau, int* status,
+                                     double* delta, double* d2, double* joint_C, int* accepted, int* implied, double* D2, int* steps, double* last_corr)
+{
+	return lsfm_map_feature_pair_joint_gate_timed(ctx, map, mono, pairs, K, order, tau, status, delta, d2, joint_C, accepted, implied, D2, steps, last_corr, nullptr);
+}
+
+int lsfm_selftest_pair_select(lsfm_context* ctx, int K, const double* Cm, const double* d, const int* ends, const int* order, double tau, int* status,
+                              double* delta, double* D2, int* accepted, int* implied)
+{
+	if (K < 1 || !Cm || !d || !ends || !status || !delta || !D2 || !accepted || !implied) return LSFM_ERR_ARG;
+	return guarded(ctx, [&]() { return pair_select_selftest(ctx, K, Cm, d, ends, order, tau, status, delta, D2, accepted, implied); });
+}
+
 int lsfm_map_merge_features_timed(lsfm_context* ctx, const lsfm_map* map, int mono, const int* pairs, int K, lsfm_map* out, double* d2, int* dof, int* rep,
                                   int* steps, double* last_corr, double* times)
 {

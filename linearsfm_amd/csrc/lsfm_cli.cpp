@@ -31,6 +31,14 @@
 // -chi2 through a temporary file renamed into place; -cand without -candr, -candr or -candtau without -cand, a value that is not a positive
 // number or a refusal of the library end the run non-zero before any file is written; feeding the file to -gate in the same run is not
 // offered: -gate validates its file before anything is computed; no reference counterpart),
+// -jgate <pairs file> -jgateout <file> [-jgatetau <tau>] [-jgatepairs <file>] (which of the candidate pairs are compatible TOGETHER: the sequential
+// joint-compatibility selection of lsfm_map_feature_pair_joint_gate in ascending order of the individual d2, tau = chi^2_3 at 0.99 unless
+// -jgatetau gives a positive number or inf; the pairs file is -gate's format with -gate's refusals and the ids are resolved in the map -gate
+// resolves them in; -jgateout: line 1 "K accepted implied dof D2", then per pair in input order "id_f id_g status d2 delta" at %.17g, status 1
+// accepted, 2 implied by the accepted pairs, 0 rejected; -jgatepairs: the accepted pairs as a pair list -- exactly what -merge reads in a later
+// run; everything is computed before any file is written, the files follow -gateout and precede -mergeout, each through a temporary file
+// renamed into place; -jgate without -jgateout or the reverse, -jgatetau / -jgatepairs without -jgate, more than 2048 pairs or a refusal of the
+// library end the run non-zero with nothing written; no reference counterpart),
 // -robust huber|cauchy <c> (-gn uses lsfm_gn_polish_robust: whole local maps down-weighted by an M-estimator on chi2_k / dof_k),
 // -chi2 <file> (per local map, in input order, "index dof chi2 weight" at the final state: lsfm_map_chi2; no reference counterpart),
 // -robustf huber|cauchy <c> (-gn uses lsfm_gn_polish_robust_features: single features of single local maps down-weighted by an M-estimator on
@@ -83,16 +91,18 @@ static void print_help()
 	printf("-gate <file> -gateout <file>	Gate Candidate Feature Pairs (Two Ids Each): id_f id_g d2 And The Upper Triangle Of Var(x_f - x_g)\n");
 	printf("-merge <file> [-mergeout <file>]	Merge Feature Pairs (Two Ids Each) Into One Point Each; Report: K removed dof D2, Then id_f id_g id_kept\n");
 	printf("-cand <file> -candr <radius> [-candtau <tau>]	Save The Candidate Feature Pairs For -gate / -merge: Within <radius>, And With -candtau Bound q <= tau\n");
+	printf("-jgate <file> -jgateout <file> [-jgatetau <tau>] [-jgatepairs <file>]	Select The Jointly Compatible Feature Pairs: K accepted implied dof D2, Then id_f id_g status d2 delta\n");
 	printf("-keepp <file>		Keep Only The Poses Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
 	printf("\n");
 }
 
 int main(int argc, char** argv)
 {
-	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf, keepp, chi2ff, gate, gateout, merge, mergeout, cand, candr, candtau;
+	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf, keepp, chi2ff, gate, gateout, merge, mergeout, cand, candr, candtau, jgate, jgateout, jgatetau, jgatepairs;
 	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0, relin = 0, robustf = 0;
 	double robust_c = 0.0, robustf_c = 0.0;
 	bool has_path = false, has_num = false, has_keepf = false, has_keepp = false, has_gate = false, has_gateout = false, has_merge = false, has_mergeout = false, has_cand = false, has_candr = false, has_candtau = false;
+	bool has_jgate = false, has_jgateout = false, has_jgatetau = false, has_jgatepairs = false;
 	double tol = 0;
 	for (int i = 1; i < argc; i++)
 	{
@@ -141,6 +151,10 @@ int main(int argc, char** argv)
 		else if (name == "cand") { cand = next(); has_cand = true; }
 		else if (name == "candr") { candr = next(); has_candr = true; }
 		else if (name == "candtau") { candtau = next(); has_candtau = true; }
+		else if (name == "jgate") { jgate = next(); has_jgate = true; }
+		else if (name == "jgateout") { jgateout = next(); has_jgateout = true; }
+		else if (name == "jgatetau") { jgatetau = next(); has_jgatetau = true; }
+		else if (name == "jgatepairs") { jgatepairs = next(); has_jgatepairs = true; }
 		else if (name == "robust" || name == "robustf")
 		{
 			const std::string k = next(), v = next();
@@ -218,6 +232,20 @@ int main(int argc, char** argv)
 	};
 	if (has_candr && !positive("-candr", candr, cand_radius)) return 1;
 	if (has_candtau && !positive("-candtau", candtau, cand_tau)) return 1;
+	// -jgate: the flags go together, the file is a list of pairs and tau a positive number (inf allowed), before anything is computed
+	std::vector<int> jgateids;
+	double jgate_tau = 11.344866730144373; // chi^2_3 at 0.99
+	if (has_jgate != has_jgateout || (has_jgate && (jgate.empty() || jgateout.empty()))) { fprintf(stderr, "LinearSFM: -jgate <pairs file> and -jgateout <file> go together\n"); return 1; }
+	if ((has_jgatetau || has_jgatepairs) && !has_jgate) { fprintf(stderr, "LinearSFM: -jgatetau <tau> and -jgatepairs <file> need -jgate <pairs file>\n"); return 1; }
+	if (has_jgatepairs && jgatepairs.empty()) { fprintf(stderr, "LinearSFM: -jgatepairs needs a file name\n"); return 1; }
+	if (has_jgatetau)
+	{
+		char* end = nullptr;
+		jgate_tau = strtod(jgatetau.c_str(), &end);
+		if (jgatetau.empty() || *end || !(jgate_tau > 0)) { fprintf(stderr, "LinearSFM: -jgatetau: '%s' is not a positive number\n", jgatetau.c_str()); return 1; }
+	}
+	if (has_jgate && !read_pairs("-jgate", jgate, jgateids)) return 1;
+	if (jgateids.size() / 2 > LSFM_JOINT_GATE_MAX) { fprintf(stderr, "LinearSFM: -jgate: %zu pairs, at most %d\n", jgateids.size() / 2, LSFM_JOINT_GATE_MAX); return 1; }
 	if (robust && gn <= 0) { fprintf(stderr, "LinearSFM: -robust applies to -gn <steps>: give -gn too\n"); return 1; }
 	if (robustf && gn <= 0) { fprintf(stderr, "LinearSFM: -robustf applies to -gn <steps>: give -gn too\n"); return 1; }
 	if (robustf && robust) { fprintf(stderr, "LinearSFM: -robustf and -robust do not go together: the map and the feature estimator are not combined\n"); return 1; }
@@ -480,6 +508,14 @@ int main(int argc, char** argv)
 		if (at < 0) { fprintf(stderr, "LinearSFM: -gate: the final map has no feature %d\n", id); return 3; }
 		gatepairs.push_back(at);
 	}
+	std::vector<int> jgatefeat;
+	for (int id : jgateids)
+	{
+		int at = -1;
+		for (int f = 0; f < out.n; f++) if (out.stno[6 * out.m + 3 * f] == id) at = f;
+		if (at < 0) { fprintf(stderr, "LinearSFM: -jgate: the final map has no feature %d\n", id); return 3; }
+		jgatefeat.push_back(at);
+	}
 	// marginal covariances of the final map (after -gn its information matrix is still the tree's, unless -relin 1): once, for -cov / -covf
 	// and for -candtau
 	std::vector<double> pc, fc;
@@ -506,6 +542,25 @@ int main(int argc, char** argv)
 		}
 		if (crc != LSFM_OK) { fprintf(stderr, "LinearSFM: -cand: %s\n", lsfm_last_error(ctx)); return 3; }
 		for (int& f : candids) f = out.stno[6 * out.m + 3 * f]; // indices to labels
+	}
+	// -jgate: the selection among the candidate pairs, before any file is written (a refusal or a numerical failure: nothing is written)
+	std::vector<int> jstatus;
+	std::vector<double> jdelta, jd2;
+	int jacc = 0, jimp = 0;
+	double jD2 = 0.0;
+	if (has_jgate)
+	{
+		const int K = (int)jgatefeat.size() / 2;
+		jstatus.resize(K); jdelta.resize(K); jd2.resize(K);
+		int steps = 0;
+		const int jrc = lsfm_map_feature_pair_joint_gate(ctx, &out, type, jgatefeat.data(), K, nullptr, jgate_tau, jstatus.data(), jdelta.data(), jd2.data(), nullptr,
+		                                                 &jacc, &jimp, &jD2, &steps, nullptr);
+		if (jrc < 0 || (jrc > 0 && steps == 0))
+		{
+			fprintf(stderr, "LinearSFM: -jgate: %s\n", jrc < 0 ? lsfm_last_error(ctx) : "pivots had to be floored (the information matrix is too close to singular)");
+			return 3;
+		}
+		if (jrc > 0) fprintf(stderr, "LinearSFM: -jgate: the refinement took all %d steps and its last correction is still above the tolerance\n", steps);
 	}
 	const int r = 6 * out.m + 3 * out.n;
 	if (!st.empty()) lsfm_save_state(st.c_str(), out.stVal, out.stno, r);
@@ -553,6 +608,18 @@ int main(int argc, char** argv)
 		if (grc > 0) fprintf(stderr, "LinearSFM: gate: the refinement took all %d steps and its last correction is still above the tolerance\n", steps);
 		if (lsfm_save_pair_gate(gateout.c_str(), gateids.data(), K, d2.data(), cd.data())) fprintf(stderr, "LinearSFM: cannot write %s\n", gateout.c_str());
 	}
+	if (has_jgate)
+	{
+		const int K = (int)jgateids.size() / 2;
+		if (lsfm_save_joint_gate(jgateout.c_str(), jgateids.data(), K, jstatus.data(), jd2.data(), jdelta.data(), jacc, jimp, jD2)) fprintf(stderr, "LinearSFM: cannot write %s\n", jgateout.c_str());
+		if (has_jgatepairs)
+		{
+			std::vector<int> ids;
+			for (int a = 0; a < K; a++)
+				if (jstatus[a] == 1) { ids.push_back(jgateids[2 * a]); ids.push_back(jgateids[2 * a + 1]); }
+			if (lsfm_save_pair_list(jgatepairs.c_str(), ids.data(), (long long)ids.size() / 2)) fprintf(stderr, "LinearSFM: cannot write %s\n", jgatepairs.c_str());
+		}
+	}
 	if (has_mergeout)
 	{
 		const int K = (int)mergeids.size() / 2;
@@ -563,7 +630,13 @@ int main(int argc, char** argv)
 	if (has_cand && lsfm_save_pair_list(cand.c_str(), candids.data(), ncand)) fprintf(stderr, "LinearSFM: cannot write %s\n", cand.c_str());
 	if (!json.empty())
 	{
-		const std::string cand_json = has_cand ? ", \"candidates\": " + std::to_string(ncand) : "";
+		std::string cand_json = has_cand ? ", \"candidates\": " + std::to_string(ncand) : "";
+		if (has_jgate)
+		{
+			char buf[160];
+			snprintf(buf, sizeof buf, ", \"joint_gate\": {\"accepted\": %d, \"implied\": %d, \"D2\": %.17g}", jacc, jimp, jD2);
+			cand_json += buf;
+		}
 		FILE* f = fopen(json.c_str(), "w");
 		if (f)
 		{

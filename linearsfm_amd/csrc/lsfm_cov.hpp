@@ -107,6 +107,20 @@ using CcStep = std::function<void(int c0, int kcur, int R, const CovFront& fr, C
 using CcFetch = std::function<void(int c0, int kcur, int R, CcWork& wk)>;
 int cc_run(lsfm_context* ctx, const lsfm_map* map, bool mono, const CcCall& call, int* steps_out, double* last_corr, double* times, const CcPrep& prep,
            const CcChunkRhs& rhs, const CcStep& layout, const CcStep& emit, const CcFetch& fetch);
+// ---- what lsfm_featcols.hip shares with lsfm_jointgate.hip: the column groups of signed features and the gate of a chunk ----
+// The column groups of a call on the device, [2 k]: group a = the signed features (f, +1)[, (g, -1); g < 0: none]; rhs() is what the group
+// calls hand cc_run as the right-hand sides of a chunk (B = -sum s W V^-1, k_fc_rhs).
+struct FcGroups {
+	DevBuf buf;
+	int* d = nullptr; // [2 k]
+	void upload(lsfm_context* ctx, const std::vector<int>& grp);
+	const int* of(int c0) const { return d + 2 * (size_t)c0; }
+	CcChunkRhs rhs(lsfm_context* ctx) const;
+};
+// the gate of the chunk's kcur pairs grp[2 kcur] from the solved columns Xo[6 m][R] (k_fc_gate, a wave per pair): d2[kcur] (may be null) =
+// dx^T Sigma_d^-1 dx, NaN at a pivot that is not > 0; cov[9 kcur] (may be null) = Sigma_d, exactly symmetric
+void fc_gate(lsfm_context* ctx, const CovFront& fr, int R, int kcur, const int* grp, const double* Xo, const double* dx, double* d2, double* cov);
+
 // joint[k width][k width], its chunks' columns in place, made exactly symmetric: block (a, b), a < b, from column b and mirrored; a
 // diagonal block (X + X^T) / 2
 void symmetrise_joint(double* joint, int k, int width);

@@ -13,7 +13,8 @@
 //
 // A chunk is 64 groups = 192 columns: the slabs and launch shapes of a full chunk of lsfm_map_covariance_columns.  The chunk loop
 // is that call's too (cc_run, lsfm_cov.hpp, at width 3): the two entries below are its callables -- the right-hand sides k_fc_rhs, the
-// kernels behind a chunk's solve and the downloads.
+// kernels behind a chunk's solve and the downloads.  The column groups (FcGroups) and the gate of a chunk (fc_gate) are declared in
+// lsfm_cov.hpp: lsfm_jointgate.hip solves the same columns.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -133,27 +134,26 @@ __global__ void __launch_bounds__(LSFM_WAVE) k_fc_gate(int R, const int* __restr
 	d2[a] = res;
 }
 
-// The column groups of a call on the device, and what both entries hand cc_run (lsfm_cov.hpp) as the right-hand sides of a chunk.
-struct FcGroups {
-	DevBuf buf;
-	int* d = nullptr; // [2 k]
-	void upload(lsfm_context* ctx, const std::vector<int>& grp)
-	{
-		d = buf.get<int>(grp.size());
-		h2d(ctx, d, grp.data(), grp.size() * sizeof(int));
-	}
-	const int* of(int c0) const { return d + 2 * (size_t)c0; }
-	CcChunkRhs rhs(lsfm_context* ctx) const
-	{
-		return [this, ctx](int c0, int kcur, int R, const CovFront& fr, double* B) {
-			const SolveIO& io = fr.io;
-			dev_zero(ctx, B, (size_t)fr.ch.M * 6 * R * sizeof(double));
-			hipLaunchKernelGGL(k_fc_rhs, dim3(kcur), dim3(LSFM_WAVE), 0, ctx->stream, R, of(c0), io.fptr, io.photo, io.W, fr.sy.IV, io.d_fixed, B);
-		};
-	}
-};
-
 } // namespace
+
+// The column groups of a call on the device, and what the group calls hand cc_run (lsfm_cov.hpp) as the right-hand sides of a chunk.
+void FcGroups::upload(lsfm_context* ctx, const std::vector<int>& grp)
+{
+	d = buf.get<int>(grp.size());
+	h2d(ctx, d, grp.data(), grp.size() * sizeof(int));
+}
+CcChunkRhs FcGroups::rhs(lsfm_context* ctx) const
+{
+	return [this, ctx](int c0, int kcur, int R, const CovFront& fr, double* B) {
+		const SolveIO& io = fr.io;
+		dev_zero(ctx, B, (size_t)fr.ch.M * 6 * R * sizeof(double));
+		hipLaunchKernelGGL(k_fc_rhs, dim3(kcur), dim3(LSFM_WAVE), 0, ctx->stream, R, of(c0), io.fptr, io.photo, io.W, fr.sy.IV, io.d_fixed, B);
+	};
+}
+void fc_gate(lsfm_context* ctx, const CovFront& fr, int R, int kcur, const int* grp, const double* Xo, const double* dx, double* d2, double* cov)
+{
+	hipLaunchKernelGGL(k_fc_gate, dim3(kcur), dim3(LSFM_WAVE), 0, ctx->stream, R, grp, fr.io.fptr, fr.io.photo, fr.io.W, fr.sy.IV, Xo, dx, d2, cov);
+}
 
 
 int map_covariance_feature_columns(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* feats, int k, double* pose_cols, double* feat_cols,
@@ -236,7 +236,7 @@ int map_feature_pair_gate(lsfm_context* ctx, const lsfm_map* map, bool mono, con
 		},
 		dg.rhs(ctx), nullptr,
 		[&](int c0, int kcur, int R, const CovFront& fr, CcWork& wk) {
-			hipLaunchKernelGGL(k_fc_gate, dim3(kcur), dim3(LSFM_WAVE), 0, ctx->stream, R, dg.of(c0), fr.io.fptr, fr.io.photo, fr.io.W, fr.sy.IV, wk.Xo, ddx + 3 * (size_t)c0, dd2, dcov);
+			fc_gate(ctx, fr, R, kcur, dg.of(c0), wk.Xo, ddx + 3 * (size_t)c0, dd2, dcov);
 		},
 		[&](int c0, int kcur, int R, CcWork&) {
 			if (d2) d2h(ctx, d2 + c0, dd2, (size_t)kcur * sizeof(double));

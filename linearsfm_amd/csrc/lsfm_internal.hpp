@@ -582,6 +582,13 @@ int map_covariance_feature_columns(lsfm_context* ctx, const lsfm_map* map, bool 
                                    double* joint, int* steps, double* last_corr, double* times);
 int map_feature_pair_gate(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* pairs, int K, double* d2, double* cov_diff, int* steps,
                           double* last_corr, double* times);
+// the sequential joint-compatibility selection among the K feature pairs pairs[2 K] (lsfm_jointgate.hip; C ABI:
+// lsfm_map_feature_pair_joint_gate, lsfm_selftest_pair_select).  times (may be null): [6] ms of reduce + analyse, factorisation, sweeps +
+// refinement, the blocks of C, the selection's kernels, the downloads with the selection's host preparation and allocations
+int map_feature_pair_joint_gate(lsfm_context* ctx, const lsfm_map* map, bool mono, const int* pairs, int K, const int* order, double tau, int* status,
+                                double* delta, double* d2, double* joint_C, int* accepted, int* implied, double* D2, int* steps, double* last_corr, double* times);
+int pair_select_selftest(lsfm_context* ctx, int K, const double* C, const double* d, const int* ends, const int* order, double tau, int* status, double* delta,
+                         double* D2, int* accepted, int* implied);
 // the map with the K feature pairs pairs[2 K] declared equal, and the joint compatibility D^2 of all of them (lsfm_merge.hip, structure
 // lsfm_merge_structure.cpp; C ABI: lsfm_map_merge_features).  times (may be null): [5] ms of upload + W' / V' passes + the merged map's way
 // to the host, its upload + reduction + analysis + factorisation, right-hand side + sweeps + refinement, back-substitution + D^2, download

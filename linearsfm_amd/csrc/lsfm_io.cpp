@@ -676,6 +676,44 @@ int lsfm_read_merge_report(const char* path, int* K, int* removed, int* dof, dou
 	return rc;
 }
 
+// the -jgateout file (lsfm_map_feature_pair_joint_gate): the head "K accepted implied dof D2", dof = 3 accepted, then one line per pair in the
+// order given, "id_f id_g status d2 delta" at %.17g (a NaN is written "nan")
+int lsfm_save_joint_gate(const char* path, const int* ids, int K, const int* status, const double* d2, const double* delta, int accepted, int implied, double D2)
+{
+	if (!path || K < 1 || !ids || !status || !d2 || !delta) return LSFM_ERR_ARG;
+	const std::string tmp = std::string(path) + ".tmp";
+	FILE* fp = fopen(tmp.c_str(), "w");
+	if (!fp) return LSFM_ERR_IO;
+	fprintf(fp, "%d %d %d %d %.17g\n", K, accepted, implied, 3 * accepted, D2);
+	for (int a = 0; a < K; a++) fprintf(fp, "%d %d %d %.17g %.17g\n", ids[2 * a], ids[2 * a + 1], status[a], d2[a], delta[a]);
+	const bool bad = ferror(fp) != 0;
+	if (fclose(fp) != 0 || bad || rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); return LSFM_ERR_IO; }
+	return LSFM_OK;
+}
+
+// a -jgateout file back: head[4] = K, accepted, implied, dof; ids[2 cap], status, d2, delta [cap].  Refused (LSFM_ERR_IO): a line cut short, fewer
+// or more lines than the head says, a status outside 0..2, a head whose counts are not those of the lines or whose dof is not 3 accepted
+int lsfm_read_joint_gate(const char* path, int* ids, int* status, double* d2, double* delta, int cap, int* head, double* D2)
+{
+	if (!path || !head || !D2 || cap < 0 || (cap && (!ids || !status || !d2 || !delta))) return LSFM_ERR_ARG;
+	FILE* fp = fopen(path, "r");
+	if (!fp) return LSFM_ERR_IO;
+	int rc = LSFM_OK;
+	if (fscanf(fp, "%d %d %d %d %lf", &head[0], &head[1], &head[2], &head[3], D2) != 5 || head[0] < 1 || head[3] != 3 * head[1]) rc = LSFM_ERR_IO;
+	else if (head[0] > cap) rc = LSFM_ERR_ARG;
+	int na = 0, ni = 0;
+	for (int a = 0; rc == LSFM_OK && a < head[0]; a++)
+	{
+		if (fscanf(fp, "%d %d %d %lf %lf", &ids[2 * a], &ids[2 * a + 1], &status[a], &d2[a], &delta[a]) != 5 || status[a] < 0 || status[a] > 2) rc = LSFM_ERR_IO;
+		else { na += status[a] == 1; ni += status[a] == 2; }
+	}
+	if (rc == LSFM_OK && (na != head[1] || ni != head[2])) rc = LSFM_ERR_IO;
+	char extra[2];
+	if (rc == LSFM_OK && (fscanf(fp, "%1s", extra) == 1 || !feof(fp))) rc = LSFM_ERR_IO;
+	fclose(fp);
+	return rc;
+}
+
 // a pair list (what -gate and -merge read, what -cand writes): one line "id_f id_g" per pair
 int lsfm_save_pair_list(const char* path, const int* ids, long long K)
 {

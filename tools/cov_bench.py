@@ -25,7 +25,16 @@ usage: python tools/cov_bench.py <config> [maps] [reps]  -> one JSON object on s
                        of the four parts, info, pair tests per second of the counting pass, how many of the K split pairs are among the
                        candidates, and the wall time of the sizing + filling calls beside the only route without the entry point --
                        scipy.spatial.cKDTree.query_pairs(R) on the host and the q filter in numpy; the two lists are compared
-                       (profiles/candidates_<config>.json)"""
+                       (profiles/candidates_<config>.json)
+  --joint-gate K[,K...] [--split S] [--radius R]   instead: lsfm_map_feature_pair_joint_gate_timed on the tree of the set with S features split in
+                       two (default 32) for a list of K pairs -- the --candidates list of that tree (radius R, default 0.5; tau = chi^2_3 at 0.99
+                       on lsfm_map_covariance's blocks), the split pairs first, then by ascending q, cut or padded with seeded pairs
+                       (default_rng(1)) to K: HIP-event ms of
+                       the six parts, the call's wall time, the selection kernels' GFLOP/s on (3K)^3 / 3 (profiles/joint_gate_<config>.json)
+  --joint-gate-parent-route K[,K...]   instead: the same selection by the only route before the entry point -- covariance_feature_columns(
+                       joint=True) of the distinct endpoints (6 columns per pair where no endpoint repeats), C = A J A^T and the sequential
+                       selection in numpy / LAPACK on the host, whose share is reported separately (existing API only: runs on a build of
+                       an older commit too; profiles/joint_gate_parent_<config>.json)"""
 import json
 import os
 import sys
@@ -52,7 +61,7 @@ if "--parent-route" in args:
     parent_route = True
     args.remove("--parent-route")
 modes = {}
-for flag in ("--feature-columns", "--gate", "--gate-parent-route", "--merge", "--merge-parent-route"):
+for flag in ("--feature-columns", "--gate", "--gate-parent-route", "--merge", "--merge-parent-route", "--joint-gate", "--joint-gate-parent-route"):
     if flag in args:
         i = args.index(flag)
         modes[flag] = [int(v) for v in args[i + 1].split(",")]
@@ -69,6 +78,11 @@ if "--tau" in args:
 if "--split" in args:
     i = args.index("--split")
     cand_split = int(args[i + 1])
+    del args[i: i + 2]
+jg_radius = 0.5
+if "--radius" in args:
+    i = args.index("--radius")
+    jg_radius = float(args[i + 1])
     del args[i: i + 2]
 cfg = args[0]
 nmaps = int(args[1]) if len(args) > 1 and int(args[1]) > 0 else None
@@ -210,6 +224,138 @@ if cand_radii is not None:
                       "note": "HIP events on the context's stream; call wall: Context.feature_pair_candidates, the sizing and the filling call with the "
                               "upload of the estimates (and blocks) and the downloads, the covariance call not included on either route; host route: "
                               "scipy.spatial.cKDTree(x).query_pairs(R) and the q filter in numpy on the same arrays; split pairs by default_rng(3)"}, indent=1))
+    ctx.close()
+    sys.exit(0)
+JG_TAU = 11.344866730144373  # chi^2_3 at 0.99
+
+
+def joint_gate_list(Gs, split, K):
+    """K pairs for the joint gate: the candidates of the split tree at --radius (default 0.5, the first radius of profiles/candidates_*.json)
+    and tau -- the split pairs among them first, then the others by ascending bound q --, cut to K, or padded with seeded pairs that are
+    not yet in the list."""
+    ms, ns = int(Gs["m"]), int(Gs["n"])
+    radius = jg_radius
+    fcov = np.ascontiguousarray(ctx.covariance(Gs, mono)["feature"])
+    out = ctx.feature_pair_candidates(Gs, radius, fcov, JG_TAU)
+    cand = out["pairs"]
+    true = {tuple(sorted(map(int, p))) for p in split}
+    is_split = np.array([tuple(p) in true for p in cand.tolist()], bool) if len(cand) <= 5_000_000 else np.zeros(len(cand), bool)
+    rank = np.lexsort((np.nan_to_num(out["q"], nan=np.inf), ~is_split))
+    pairs = [tuple(p) for p in cand[rank[:K]].tolist()]
+    have = {tuple(sorted(p)) for p in pairs}
+    rng = np.random.default_rng(1)
+    while len(pairs) < K:
+        f, g = (int(v) for v in rng.choice(ns, size=2, replace=False))
+        if tuple(sorted((f, g))) not in have:
+            have.add(tuple(sorted((f, g))))
+            pairs.append((f, g))
+    return np.array(pairs, np.int32), len(cand), radius
+
+
+def host_select(Cm, dv, ends, tau):
+    """The sequential selection of lsfm_map_feature_pair_joint_gate on the host, float64: ascending individual d2, a growing Cholesky factor of
+    the accepted block, union-find for the implied pairs.  Returns (status, delta, D2)."""
+    import scipy.linalg as sla
+    K = len(ends)
+    blk = lambda a, b: Cm[3 * a: 3 * a + 3, 3 * b: 3 * b + 3]
+    d2 = np.full(K, np.nan)
+    for b in range(K):
+        try:
+            y = sla.solve_triangular(np.linalg.cholesky(blk(b, b)), dv[3 * b: 3 * b + 3], lower=True)
+            d2[b] = y @ y
+        except np.linalg.LinAlgError:
+            pass
+    order = sorted(range(K), key=lambda b: (bool(np.isnan(d2[b])), 0.0 if np.isnan(d2[b]) else d2[b], b))
+    parent = {}
+
+    def find(v):
+        parent.setdefault(v, v)
+        while parent[v] != v:
+            parent[v] = parent[parent[v]]
+            v = parent[v]
+        return v
+    status, delta = np.zeros(K, np.int32), np.full(K, np.nan)
+    L, yv, rows, n = np.zeros((3 * K, 3 * K)), np.zeros(3 * K), np.zeros(3 * K, np.int64), 0
+    for b in order:
+        if np.isnan(d2[b]):
+            continue
+        f, g = find(int(ends[b, 0])), find(int(ends[b, 1]))
+        if f == g:
+            status[b], delta[b] = 2, 0.0
+            continue
+        cb = np.arange(3 * b, 3 * b + 3)
+        Wt = sla.solve_triangular(L[:n, :n], Cm[np.ix_(rows[:n], cb)], lower=True, check_finite=False) if n else np.zeros((0, 3))
+        S = blk(b, b) - Wt.T @ Wt
+        e = dv[cb] - Wt.T @ yv[:n]
+        try:
+            L3 = np.linalg.cholesky(S)
+        except np.linalg.LinAlgError:
+            continue
+        y3 = sla.solve_triangular(L3, e, lower=True)
+        delta[b] = y3 @ y3
+        if delta[b] <= tau:
+            status[b] = 1
+            parent[max(f, g)] = min(f, g)
+            L[n: n + 3, :n], L[n: n + 3, n: n + 3], yv[n: n + 3], rows[n: n + 3] = Wt.T, L3, y3, cb
+            n += 3
+    return status, delta, float(np.sum(delta[status == 1]))
+
+
+if "--joint-gate" in modes or "--joint-gate-parent-route" in modes:
+    parent_leg = "--joint-gate-parent-route" in modes
+    Gs, split = split_tree(cand_split)
+    ms, ns = int(Gs["m"]), int(Gs["n"])
+    splitset = {tuple(sorted(map(int, p))) for p in split}
+    legs = []
+    for K in modes["--joint-gate-parent-route" if parent_leg else "--joint-gate"]:
+        pairs, ncand, radius = joint_gate_list(Gs, split, K)
+        row = {"K": K, "candidates": ncand, "radius": radius, "distinct_endpoints": int(len(np.unique(pairs)))}
+        walls, parts, hosts = [], [], []
+        for rep in range(reps + 1):  # (the first call is a warm-up)
+            t0 = time.perf_counter()
+            if parent_leg:
+                feats = np.unique(pairs)
+                fc = ctx.covariance_feature_columns(Gs, mono, feats, poses=False, features=False, joint=True)
+                t1 = time.perf_counter()
+                at = np.searchsorted(feats, pairs)
+                idx = lambda col: (3 * at[:, col][:, None] + np.arange(3)[None, :]).ravel()
+                R = fc["joint"][idx(0), :] - fc["joint"][idx(1), :]
+                Cm = R[:, idx(0)] - R[:, idx(1)]
+                xf = np.asarray(Gs["stVal"], np.float64)[6 * ms:].reshape(-1, 3)
+                status, delta, D2 = host_select(Cm, (xf[pairs[:, 0]] - xf[pairs[:, 1]]).ravel(), pairs, JG_TAU)
+                t2 = time.perf_counter()
+                steps = fc["steps"]
+                if rep:
+                    hosts.append(1e3 * (t2 - t1))
+            else:
+                jrc, out, t = ctx.feature_pair_joint_gate_raw(Gs, mono, pairs, times=True)
+                if jrc < 0 or (jrc > 0 and out["steps"] == 0):
+                    sys.exit(f"lsfm_map_feature_pair_joint_gate: status {jrc}: {api.lib().lsfm_last_error(ctx._h).decode()}")
+                status, delta, D2, steps = out["status"], out["delta"], out["D2"], out["steps"]
+                if rep:
+                    parts.append(t.tolist())
+            if rep:
+                walls.append(1e3 * (time.perf_counter() - t0))
+            if parent_leg and K >= 1024 and rep:
+                break  # (one warm call at this size: the host loop takes seconds)
+        acc = {tuple(sorted(map(int, pairs[b]))) for b in np.nonzero(status == 1)[0]}
+        row.update({"accepted": int(np.sum(status == 1)), "implied": int(np.sum(status == 2)), "split_pairs_among_accepted": len(splitset & acc),
+                    "split_pairs_in_list": len(splitset & {tuple(sorted(map(int, p))) for p in pairs}), "D2": D2, "steps": int(steps),
+                    "call_wall_ms_median": float(np.median(walls)), "call_wall_ms": walls, "calls_measured": len(walls), "warm_up_calls": 1})
+        if parent_leg:
+            row.update({"leg": "joint_gate_parent_route", "columns_solved": 3 * int(len(np.unique(pairs))), "host_ms_median": float(np.median(hosts)),
+                        "columns_call_ms_median": float(np.median(walls) - np.median(hosts))})
+        else:
+            med = np.median(np.array(parts), axis=0)
+            row.update({"leg": "joint_gate", "columns_solved": 3 * K,
+                        "ms_median": {"reduce_analyse": med[0], "factor": med[1], "sweeps_refine": med[2], "C_blocks": med[3], "selection_kernels": med[4], "downloads_host_prep_alloc": med[5]},
+                        "selection_gflops": (3.0 * K) ** 3 / 3.0 / (med[4] * 1e-3) / 1e9 if med[4] > 0 else None})
+        legs.append(row)
+    print(json.dumps({"config": cfg, "type": typ, "maps": len(maps), "poses": ms, "features": ns, "split": cand_split, "tau": JG_TAU, "legs": legs,
+                      "note": "HIP events on the context's stream; call wall: the upload of the map and every download included, the candidate search and "
+                              "its covariance call not included on either route; selection_kernels: events around k_jc_permute .. the last panel alone; "
+                              "downloads_host_prep_alloc: d2 / status / delta down, the order and endpoint numbering on the host, the selection's "
+                              "hipMallocs and uploads; parent route: host = C = A J A^T and the numpy / LAPACK selection loop"}, indent=1))
     ctx.close()
     sys.exit(0)
 if "--merge" in modes:
