@@ -845,6 +845,32 @@ int lsfm_selftest_chol(lsfm_context* ctx, int m, const int* rowptr, const int* c
                        const int* pose_seg, int nseg, const double* r, int nrhs, int mode, double* z, double* dot, int* perm, int* colptr, int* rowidx,
                        double* L, double* Dinv, double* dscale, int cap_blocks, int* info);
 
+/* Test entry: the side-by-side triangular sweeps of the columns calls (lsfm_map_covariance_columns, lsfm_map_covariance_feature_columns,
+ * lsfm_map_feature_pair_gate, lsfm_map_feature_pair_joint_gate, the first step of lsfm_map_merge_features; the forward half alone:
+ * lsfm_map_marginalise_poses) on a matrix of the caller's, UNREFINED, and one launch of their residual product.  In those calls the
+ * sweeps are the preconditioner of a refinement against S itself, so a wrong block of a sweep only costs steps there; here nothing
+ * corrects it.  The call runs the library's own steps and nothing else: ordering + symbolic analysis, scatter, fp64 factorisation
+ * (no fused forward substitution), the group columns merged into the one array of the factor -- as the columns calls' front does --,
+ * then  B -> elimination order, scaled -> forward sweep -> [fwd] -> backward sweep -> caller's numbering, scaled -> x.
+ *   m, rowptr, colidx, val, origin, fixed   as lsfm_selftest_chol, with the same checks (LSFM_ERR_ARG)
+ *   B[6 m][R]       right-hand sides in the caller's numbering, unscaled, the R values of a scalar row contiguous; 1 <= R <= 192,
+ *                   need not be a multiple of 6 or 3
+ *   X[6 m][R]       (may be NULL) input of the residual product; zero in fixed rows.  Needs y (LSFM_ERR_ARG), and y needs X
+ * Outputs, each optional: x[6 m][R] = P^T D (L L^T)^-1 D P B (0 in fixed rows); fwd[6 m][R] = L^-1 D P B, the slab after the forward
+ * sweep alone, in elimination order and scaled (what lsfm_map_marginalise_poses consumes); perm[m] (new -> old), dscale[6 m] (the
+ * diagonal of D, new numbering, powers of two); y[6 m][R] = B - S X by one launch of the columns calls' residual kernel on the
+ * row-sorted list of S's blocks (built whatever lsfm_set_spmv_variant says; the setting is put back); a fixed row of y is B's.
+ * The panel version is the context's (lsfm_set_covcols_panel).
+ * info[LSFM_SELFTEST_CC_SWEEPS_INFO] = { leaf tasks, supernode groups, group levels, most rows below a group, mask of the run widths
+ * that occur among the groups (bit s - 1: a group of s block columns), launches of the leaf-task forward kernel, of the group forward
+ * kernel, of the forward panel kernel, of the backward panel kernel, the panel version that ran (1 plain, 2 MFMA), the
+ * factorisation's error word, pivots held at their lower bound, 0 ... }.
+ * Returns LSFM_ERR_NOT_SPD for a non-positive pivot (info is complete, nothing else is written). */
+#define LSFM_SELFTEST_CC_SWEEPS_INFO 16
+int lsfm_selftest_cc_sweeps(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin,
+                            const unsigned char* fixed, const double* B, int R, const double* X, double* x, double* fwd, int* perm, double* dscale,
+                            double* y, int* info);
+
 /* Test entry: the batched coordinate transform (lsfm_transform.hip) on a batch of the caller's, as a tree level calls it -- several
  * maps in one set of launches, each with a target of its own -- where lsfm_transform_stereo / lsfm_transform_mono hand it one map.  The
  * N maps are uploaded as one batch, transformed once, and every map of the result is downloaded; no plans, no hook, no communicator.

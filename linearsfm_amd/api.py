@@ -173,6 +173,7 @@ def lib():
         L.lsfm_selftest_prims.argtypes = [vp, C.c_int, C.c_uint]
         L.lsfm_selftest_chol.argtypes = [vp, C.c_int, ip, ip, dp, ip, P(C.c_ubyte), ip, C.c_int, dp, C.c_int, C.c_int, dp, dp, ip, ip, ip, dp, dp, dp,
                                          C.c_int, ip]
+        L.lsfm_selftest_cc_sweeps.argtypes = [vp, C.c_int, ip, ip, dp, ip, P(C.c_ubyte), dp, C.c_int, dp, dp, dp, ip, dp, dp, ip]
         L.lsfm_selftest_transform.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, ip, ip, ip, C.c_int, P(LsfmMap)]
         L.lsfm_selftest_small.argtypes = [vp, C.c_int, ip, ip, ip, ub, dp, ip, ip, dp, ip, ip, C.c_int, dp, dp, dp, dp, ub, C.c_int, dp, dp, ip, dp]
         _LIB = L
@@ -186,7 +187,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_tree_upload_dev", "lsfm_tree_reload_dev", "lsfm_tree_set_comm", "lsfm_tree_set_comm_blocks", "lsfm_tree_export_slice_sizes", "lsfm_tree_export_slice_dev",
            "lsfm_tree_free", "lsfm_divide_conquer", "lsfm_read_localmap", "lsfm_read_localmaps", "lsfm_write_localmap", "lsfm_write_mapset", "lsfm_mapset_info", "lsfm_mapset_stamp", "lsfm_read_mapset", "lsfm_save_state_bin", "lsfm_save_state", "lsfm_save_poses", "lsfm_gn_polish",
            "lsfm_gn_polish_robust", "lsfm_map_chi2", "lsfm_map_feature_chi2", "lsfm_gn_polish_robust_features", "lsfm_gn_linearise", "lsfm_gn_linearise_timed",
-           "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_selftest_chol", "lsfm_selftest_transform", "lsfm_selftest_small", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_selftest_vinv", "lsfm_solve_features",
+           "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_selftest_chol", "lsfm_selftest_cc_sweeps", "lsfm_selftest_transform", "lsfm_selftest_small", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_selftest_vinv", "lsfm_solve_features",
            "lsfm_map_covariance", "lsfm_map_covariance_timed",
            "lsfm_save_covariances", "lsfm_read_covariances",
            "lsfm_map_covariance_columns", "lsfm_map_covariance_columns_timed", "lsfm_save_cov_columns", "lsfm_read_cov_columns",
@@ -988,6 +989,48 @@ def _selftest_chol(self, rowptr, colidx, val, r, origin=None, fixed=None, pose_s
 
 
 Context.selftest_chol = _selftest_chol
+
+SELFTEST_CC_SWEEPS_INFO = ("leaf_tasks", "groups", "group_levels", "max_rows_below", "width_mask", "fwd_task_launches", "fwd_group_launches",
+                           "fwd_panel_launches", "bwd_panel_launches", "panel", "d_err", "floored")
+
+
+def _selftest_cc_sweeps(self, rowptr, colidx, val, B, origin=None, fixed=None, X=None):
+    """lsfm_selftest_cc_sweeps: the columns calls' side-by-side sweeps, UNREFINED, against the device Cholesky factor of the block
+    matrix (rowptr, colidx, val: as selftest_chol) on the right-hand sides B[6 m, R] (caller's numbering, unscaled, 1 <= R <= 192),
+    with the panel version of set_covcols_panel.  X[6 m, R] (optional): y = B - S X by one launch of the residual kernel.  Returns
+    dict(x [6 m, R], fwd [6 m, R] (the slab after the forward sweep: elimination order, scaled), perm, dscale, y (None without X),
+    info: dict by SELFTEST_CC_SWEEPS_INFO)."""
+    rowptr = _c(rowptr, np.int32); colidx = _c(colidx, np.int32); val = _c(val, np.float64)
+    m = len(rowptr) - 1
+    if m < 1 or len(colidx) != rowptr[-1] or len(val) != 36 * len(colidx):
+        raise LsfmError("selftest_cc_sweeps: rowptr / colidx / val do not fit together")
+    B = np.ascontiguousarray(B, dtype=np.float64)
+    if B.ndim != 2 or B.shape[0] != 6 * m:
+        raise LsfmError("selftest_cc_sweeps: B is not [6 m, R]")
+    R = B.shape[1]
+    org = _c(origin, np.int32) if origin is not None else None
+    fx = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.uint8).reshape(-1) if fixed is not None else None
+    if (org is not None and len(org) != m) or (fx is not None and len(fx) != 6 * m):
+        raise LsfmError("selftest_cc_sweeps: origin / fixed do not fit m")
+    Xc = y = None
+    if X is not None:
+        Xc = np.ascontiguousarray(X, dtype=np.float64)
+        if Xc.shape != B.shape:
+            raise LsfmError("selftest_cc_sweeps: X is not shaped like B")
+        y = np.zeros_like(B)
+    x = np.zeros_like(B); fwd = np.zeros_like(B)
+    perm = np.zeros(m, np.int32); dscale = np.zeros(6 * m)
+    info = np.zeros(16, np.int32)
+    rc = lib().lsfm_selftest_cc_sweeps(self._h, m, _ptr(rowptr, C.c_int), _ptr(colidx, C.c_int), _ptr(val, C.c_double),
+                                       _ptr(org, C.c_int) if org is not None else None, _ptr(fx, C.c_ubyte) if fx is not None else None,
+                                       _ptr(B, C.c_double), R, _ptr(Xc, C.c_double) if Xc is not None else None, _ptr(x, C.c_double),
+                                       _ptr(fwd, C.c_double), _ptr(perm, C.c_int), _ptr(dscale, C.c_double),
+                                       _ptr(y, C.c_double) if y is not None else None, _ptr(info, C.c_int))
+    self._check(rc, "lsfm_selftest_cc_sweeps")
+    return dict(x=x, fwd=fwd, perm=perm, dscale=dscale, y=y, info=dict(zip(SELFTEST_CC_SWEEPS_INFO, (int(v) for v in info))))
+
+
+Context.selftest_cc_sweeps = _selftest_cc_sweeps
 
 
 def _selftest_transform(self, dicts, mono, targets, alias=False):

@@ -725,23 +725,41 @@ int lsfm_spmv_bench(lsfm_context* ctx, int m, const int* rowptr, const int* coli
 	});
 }
 
+// the matrix of the test entries on a caller's system: upper block CSR, every block row starting with its diagonal block, the
+// columns of a row ascending
+static bool block_csr_ok(int m, const int* rowptr, const int* colidx, const double* val)
+{
+	if (m <= 0 || !rowptr || !colidx || !val || rowptr[0] != 0) return false;
+	for (int p = 0; p < m; p++)
+	{
+		if (rowptr[p + 1] <= rowptr[p] || colidx[rowptr[p]] != p) return false;
+		for (int k = rowptr[p] + 1; k < rowptr[p + 1]; k++)
+			if (colidx[k] <= colidx[k - 1] || colidx[k] >= m) return false;
+	}
+	return true;
+}
+
 int lsfm_selftest_chol(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin, const unsigned char* fixed,
                        const int* pose_seg, int nseg, const double* r, int nrhs, int mode, double* z, double* dot, int* perm, int* colptr, int* rowidx,
                        double* L, double* Dinv, double* dscale, int cap_blocks, int* info)
 {
-	if (m <= 0 || !rowptr || !colidx || !val || !pose_seg || nseg <= 0 || !r || nrhs <= 0 || mode < 0 || mode > 3 || !z || !dot || !info || cap_blocks < 0 ||
-	    rowptr[0] != 0)
+	if (!block_csr_ok(m, rowptr, colidx, val) || !pose_seg || nseg <= 0 || !r || nrhs <= 0 || mode < 0 || mode > 3 || !z || !dot || !info || cap_blocks < 0)
 		return LSFM_ERR_ARG;
 	for (int p = 0; p < m; p++)
-	{
-		if (rowptr[p + 1] <= rowptr[p] || colidx[rowptr[p]] != p || pose_seg[p] < 0 || pose_seg[p] >= nseg) return LSFM_ERR_ARG; // every block row starts with its diagonal block
-		for (int k = rowptr[p] + 1; k < rowptr[p + 1]; k++)
-			if (colidx[k] <= colidx[k - 1] || colidx[k] >= m) return LSFM_ERR_ARG;
-	}
+		if (pose_seg[p] < 0 || pose_seg[p] >= nseg) return LSFM_ERR_ARG;
 	for (int i = 0; i < LSFM_SELFTEST_CHOL_INFO; i++) info[i] = 0;
 	return guarded(ctx, [&]() {
 		return chol_selftest(ctx, m, rowptr, colidx, val, origin, fixed, pose_seg, nseg, r, nrhs, mode, z, dot, perm, colptr, rowidx, L, Dinv, dscale, cap_blocks, info);
 	});
+}
+
+int lsfm_selftest_cc_sweeps(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin,
+                            const unsigned char* fixed, const double* B, int R, const double* X, double* x, double* fwd, int* perm, double* dscale,
+                            double* y, int* info)
+{
+	if (!block_csr_ok(m, rowptr, colidx, val) || !B || R < 1 || R > 192 /* 6 CC_KC: one chunk of columns */ || (X != nullptr) != (y != nullptr) || !info) return LSFM_ERR_ARG;
+	for (int i = 0; i < LSFM_SELFTEST_CC_SWEEPS_INFO; i++) info[i] = 0;
+	return guarded(ctx, [&]() { return cc_sweeps_selftest(ctx, m, rowptr, colidx, val, origin, fixed, B, R, X, x, fwd, perm, dscale, y, info); });
 }
 
 int lsfm_selftest_transform(lsfm_context* ctx, const lsfm_map* maps, int N, int mono, const int* tref, const int* tscap, const int* tfix,

@@ -1653,13 +1653,9 @@ void chol_apply(lsfm_context* ctx, const CholDev& ch, const double* r, double* v
 		hipLaunchKernelGGL(k_perm_out_dot, dim3((ch.M + 127) / 128), dim3(128), 0, s, ch.M, ch.pinv, v, r, fixed, ch.dscale, pose_seg, z, dot, dot_stride, (const int*)nullptr, 0);
 }
 
-// Test entry of the C ABI (lsfm_selftest_chol, include/lsfm.h has the arguments): the factor of a caller's matrix and UNREFINED
-// applications of it, by the host steps above and nothing else -- chol_analyse, chol_scatter, chol_factor, chol_round_to_float
-// (mode bit 1), chol_apply once per right-hand side in order, chol_merge_groups.  Inside a level solve the refinement corrects
-// whatever a wrong factor or sweep leaves (it only takes more steps); here nothing does.  The caller has checked the arguments.
-int chol_selftest(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin, const unsigned char* fixed,
-                  const int* pose_seg, int nseg, const double* r, int nrhs, int mode, double* z, double* dot, int* perm, int* colptr, int* rowidx,
-                  double* L, double* Dinv, double* dscale, int cap_blocks, int* info)
+// The front of the test entries on a caller's matrix (lsfm_chol.hpp): upload, chol_analyse, chol_scatter, chol_factor.
+void chol_selftest_front(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin, const unsigned char* fixed,
+                         size_t extra_bytes, int cap_blocks, int* nnzL_out, bool rowsorted, const double* ride_r, SelftestFront& fr)
 {
 	const int nnzb = rowptr[m];
 	const size_t ns = (size_t)m * 6;
@@ -1675,14 +1671,14 @@ int chol_selftest(lsfm_context* ctx, int m, const int* rowptr, const int* colidx
 		// (the size of the factor first, on the host: the arenas are made for it, and a caller whose arrays are too small learns it here)
 		CholSymbolic sym;
 		chol_symbolic(hin.keys.data(), nnzb, hin.origin.data(), m, sym);
-		info[0] = sym.nnzL;
-		if (cap_blocks < sym.nnzL) LSFM_FAIL(LSFM_ERR_ARG, "rowidx / L too small for the factor (" + std::to_string(sym.nnzL) + " blocks)");
-		// (L, Lg and their fp32 copies; S, keys; a dozen vectors and the right-hand sides)
-		ctx->ensure_arenas((size_t)sym.nnzL * 36 * 32 + (size_t)nnzb * 320 + ns * 8 * (16 + 2 * (size_t)nrhs) + ((size_t)64 << 20));
+		if (nnzL_out) *nnzL_out = sym.nnzL;
+		if (cap_blocks >= 0 && cap_blocks < sym.nnzL) LSFM_FAIL(LSFM_ERR_ARG, "rowidx / L too small for the factor (" + std::to_string(sym.nnzL) + " blocks)");
+		// (L, Lg and their fp32 copies; S, keys and the row-sorted list; a dozen vectors and what the caller adds)
+		ctx->ensure_arenas((size_t)sym.nnzL * 36 * 32 + (size_t)nnzb * (rowsorted ? 448 : 320) + ns * 8 * 16 + extra_bytes + ((size_t)64 << 20));
 	}
 	ctx->scratch.reset();
 	Arena& sc = ctx->scratch;
-	SchurSystem sy;
+	SchurSystem& sy = fr.sy;
 	sy.M = m; sy.nnzb = nnzb;
 	unsigned long long* dk = sc.alloc<unsigned long long>(nnzb + 1);
 	sy.S = sc.alloc<double>((size_t)nnzb * 36);
@@ -1691,35 +1687,60 @@ int chol_selftest(lsfm_context* ctx, int m, const int* rowptr, const int* colidx
 	h2d(ctx, sy.S, val, (size_t)nnzb * 36 * sizeof(double));
 	h2d(ctx, sy.rowptr, rowptr, (size_t)(m + 1) * sizeof(int));
 	sy.upper_keys = dk;
-	unsigned char* dfx = nullptr;
-	if (fixed) { dfx = sc.alloc<unsigned char>(ns); h2d(ctx, dfx, fixed, ns); }
+	if (rowsorted)
+	{
+		struct Keep { lsfm_context* c; int v; ~Keep() { c->pcg.spmv_variant = v; } } keep{ ctx, ctx->pcg.spmv_variant };
+		ctx->pcg.spmv_variant = 2;
+		build_spmv_index(ctx, sy, dk);
+	}
+	if (fixed) { fr.d_fixed = sc.alloc<unsigned char>(ns); h2d(ctx, fr.d_fixed, fixed, ns); }
+	CholDev& ch = fr.ch;
+	chol_analyse(ctx, sy, hin, ch);
+	// (the count of floored pivots goes to a record of this call's own, as in lsfm_cov.hip)
+	RunStatsDev* d_run = fr.d_run = sc.alloc<RunStatsDev>(1);
+	dev_zero(ctx, d_run, sizeof(RunStatsDev));
+	struct Swap { lsfm_context* c; RunStatsDev* keep; ~Swap() { c->d_run = keep; } } swap{ ctx, ctx->d_run };
+	ctx->d_run = d_run;
+	chol_scatter(ctx, sy, fr.d_fixed, ch);
+	if (ride_r)
+	{
+		double* dr = sc.alloc<double>(ns);
+		fr.fwd_v = sc.alloc<double>(ns);
+		h2d(ctx, dr, ride_r, ns * sizeof(double));
+		chol_perm_in(ctx, ch, dr, fr.d_fixed, fr.fwd_v);
+	}
+	chol_factor(ctx, sy, fr.d_fixed, ch, fr.fwd_v);
+}
+
+// Test entry of the C ABI (lsfm_selftest_chol, include/lsfm.h has the arguments): the factor of a caller's matrix and UNREFINED
+// applications of it, by the host steps above and nothing else -- chol_analyse, chol_scatter, chol_factor, chol_round_to_float
+// (mode bit 1), chol_apply once per right-hand side in order, chol_merge_groups.  Inside a level solve the refinement corrects
+// whatever a wrong factor or sweep leaves (it only takes more steps); here nothing does.  The caller has checked the arguments.
+int chol_selftest(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin, const unsigned char* fixed,
+                  const int* pose_seg, int nseg, const double* r, int nrhs, int mode, double* z, double* dot, int* perm, int* colptr, int* rowidx,
+                  double* L, double* Dinv, double* dscale, int cap_blocks, int* info)
+{
+	const size_t ns = (size_t)m * 6;
+	const bool fused = (mode & 1) != 0;
+	SelftestFront fr;
+	chol_selftest_front(ctx, m, rowptr, colidx, val, origin, fixed, ns * 8 * 2 * (size_t)nrhs, cap_blocks, &info[0], false, fused ? r : nullptr, fr);
+	Arena& sc = ctx->scratch;
+	CholDev& ch = fr.ch;
+	unsigned char* dfx = fr.d_fixed;
 	int* dseg = sc.alloc<int>(m);
 	h2d(ctx, dseg, pose_seg, (size_t)m * sizeof(int));
 	double* dr = sc.alloc<double>(ns * nrhs);
 	double* dz = sc.alloc<double>(ns * nrhs);
 	double* ddot = sc.alloc<double>((size_t)nseg * nrhs);
-	double* dv = sc.alloc<double>(ns);
+	double* dv = fused ? fr.fwd_v : sc.alloc<double>(ns);
 	h2d(ctx, dr, r, ns * nrhs * sizeof(double));
 	dev_zero(ctx, ddot, (size_t)nseg * nrhs * sizeof(double));
-	CholDev ch;
-	chol_analyse(ctx, sy, hin, ch);
-	// (the count of floored pivots goes to a record of this call's own, as in lsfm_cov.hip)
-	RunStatsDev* d_run = sc.alloc<RunStatsDev>(1);
-	dev_zero(ctx, d_run, sizeof(RunStatsDev));
-	const bool fused = (mode & 1) != 0;
-	{
-		struct Swap { lsfm_context* c; RunStatsDev* keep; ~Swap() { c->d_run = keep; } } swap{ ctx, ctx->d_run };
-		ctx->d_run = d_run;
-		chol_scatter(ctx, sy, dfx, ch);
-		if (fused) chol_perm_in(ctx, ch, dr, dfx, dv);
-		chol_factor(ctx, sy, dfx, ch, fused ? dv : nullptr);
-	}
 	if (mode & 2) chol_round_to_float(ctx, ch);
 	for (int k = 0; k < nrhs; k++) chol_apply(ctx, ch, dr + ns * k, dv, dz + ns * k, dfx, dseg, ddot + (size_t)nseg * k, 1, fused && k == 0);
 	chol_merge_groups(ctx, ch);
 	LSFM_CHECK_HIP(hipGetLastError());
 	RunStatsDev rs;
-	d2h(ctx, &rs, d_run, sizeof rs);
+	d2h(ctx, &rs, fr.d_run, sizeof rs);
 	const int chol_err = d2h_int(ctx, ch.d_err);
 	const int ngl = (int)ch.glevel_ptr.size() - 1;
 	info[1] = ch.ntask0; info[2] = ch.ncol0; info[3] = ch.task0_outer; info[4] = ch.ngroups; info[5] = std::max(ngl, 0);

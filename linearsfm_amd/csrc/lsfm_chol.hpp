@@ -107,4 +107,21 @@ bool chol_distributed(const lsfm_context* ctx, const CholDev& ch);
 void comm_sum_host(lsfm_context* ctx, long long* h, int n);
 // chol_selftest (test entry lsfm_selftest_chol: the factor of a caller's matrix and unrefined applications of it): lsfm_internal.hpp
 
+// The front the test entries on a caller's matrix share (lsfm_selftest_chol, lsfm_selftest_cc_sweeps): the upper block CSR as a
+// SchurSystem on the device and its factor, by chol_analyse -> chol_scatter -> chol_factor with a RunStatsDev of the call's own.
+// Resets the scratch arena; what the caller allocates there afterwards follows the factor.
+struct SelftestFront {
+	SchurSystem sy;                  // M, nnzb, S, rowptr, upper_keys (rowsorted: + the SpMV index with gent / goth)
+	CholDev ch;                      // factored; the group columns not merged into ch.L yet
+	unsigned char* d_fixed = nullptr; // the caller's fixed[6 m] on the device (null: none)
+	RunStatsDev* d_run = nullptr;    // floored pivots
+	double* fwd_v = nullptr;         // ride_r given: its forward substitution, as chol_apply's fwd_done expects it
+};
+// extra_bytes: what the caller will allocate in the scratch arena behind the factor.  *nnzL_out (may be null) = blocks of the factor,
+// written before cap_blocks (< 0: no bound) refuses a caller whose arrays are too small.  rowsorted: the row-sorted list of both
+// orientations of S's blocks is built whatever lsfm_set_spmv_variant says, as cov_front_rowsorted forces it; the context's setting
+// is put back.  ride_r[6 m] (host, may be null): a right-hand side whose forward substitution rides on the factorisation.
+void chol_selftest_front(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin, const unsigned char* fixed,
+                         size_t extra_bytes, int cap_blocks, int* nnzL_out, bool rowsorted, const double* ride_r, SelftestFront& fr);
+
 } // namespace lsfm

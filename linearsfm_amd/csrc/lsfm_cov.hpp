@@ -57,8 +57,10 @@ int cov_front_rowsorted(lsfm_context* ctx, const lsfm_map* map, bool mono, CovFr
 // V[6 ch.M][R] in elimination order, R <= 6 CC_KC = 192: V <- L^-1 V, and V <- L^-T V.  lsfm_map_covariance_columns runs one after the
 // other; lsfm_map_marginalise_poses the forward one alone.
 #define CC_KC 32 /* poses per chunk of columns (lsfm_covcols.hip) */
-void cc_sweep_forward(lsfm_context* ctx, const CholDev& ch, int R, double* V);
-void cc_sweep_backward(lsfm_context* ctx, const CholDev& ch, int R, double* V);
+// count (may be null): the launches of each kernel are added to it (what lsfm_selftest_cc_sweeps reports).
+struct CcLaunches { int fwd_tasks = 0, fwd_groups = 0, fwd_panel = 0, bwd_panel = 0, panel = 0; }; // panel: the version that ran, 1 plain, 2 MFMA
+void cc_sweep_forward(lsfm_context* ctx, const CholDev& ch, int R, double* V, CcLaunches* count = nullptr);
+void cc_sweep_backward(lsfm_context* ctx, const CholDev& ch, int R, double* V, CcLaunches* count = nullptr);
 
 // ---- what lsfm_covcols.hip shares with lsfm_featcols.hip: a chunk of R <= 192 columns X = S^-1 B, solved side by side and refined ----
 // the device memory of a columns call, whatever its right-hand sides are: three slabs [6 M][Rmax] and the norms of a refinement step

@@ -543,25 +543,34 @@ struct SweepShape {
 };
 } // namespace
 
-void cc_sweep_forward(lsfm_context* ctx, const CholDev& ch, int R, double* V)
+void cc_sweep_forward(lsfm_context* ctx, const CholDev& ch, int R, double* V, CcLaunches* count)
 {
 	hipStream_t s = ctx->stream;
 	const SweepShape sh(ctx, R);
 	const unsigned rp = sh.rp, nsl = sh.nsl, pt = sh.pt;
 	const bool plain = sh.plain;
 	const int ngl = (int)ch.glevel_ptr.size() - 1;
-	if (ch.ntask0) hipLaunchKernelGGL(k_cc_fwd<false>, dim3(ch.ntask0), dim3(rp, 1), 0, s, ch.task_ptr, ch.task_cols, ch.col_task, false, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
+	if (count) count->panel = plain ? 1 : 2;
+	if (ch.ntask0)
+	{
+		hipLaunchKernelGGL(k_cc_fwd<false>, dim3(ch.ntask0), dim3(rp, 1), 0, s, ch.task_ptr, ch.task_cols, ch.col_task, false, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
+		if (count) count->fwd_tasks++;
+	}
 	for (int l = 0; l < ngl; l++)
 	{
 		const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0, mnr = ch.glevel_maxnr[l];
 		if (!ng) continue;
 		hipLaunchKernelGGL(k_cc_fwd<true>, dim3(ng), dim3(rp, nsl), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, plain, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
+		if (count) count->fwd_groups++;
 		if (!plain && mnr > 0)
+		{
 			hipLaunchKernelGGL(k_cc_fwd_panel, dim3(ng, std::min(CC_GY, (6 * mnr + 15) / 16)), dim3(pt), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, R, ch.colptr, ch.rowidx, ch.L, V);
+			if (count) count->fwd_panel++;
+		}
 	}
 }
 
-void cc_sweep_backward(lsfm_context* ctx, const CholDev& ch, int R, double* V)
+void cc_sweep_backward(lsfm_context* ctx, const CholDev& ch, int R, double* V, CcLaunches* count)
 {
 	hipStream_t s = ctx->stream;
 	const SweepShape sh(ctx, R);
@@ -573,7 +582,10 @@ void cc_sweep_backward(lsfm_context* ctx, const CholDev& ch, int R, double* V)
 		const int g0 = ch.glevel_ptr[l], ng = ch.glevel_ptr[l + 1] - g0, mnr = ch.glevel_maxnr[l];
 		if (!ng) continue;
 		if (!plain && mnr > 0)
+		{
 			hipLaunchKernelGGL(k_cc_bwd_panel, dim3(ng, std::min(CC_GY, (6 * mnr + CC_GK - 1) / CC_GK)), dim3(pt), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, R, ch.colptr, ch.rowidx, ch.L, V);
+			if (count) count->bwd_panel++;
+		}
 		hipLaunchKernelGGL(k_cc_bwd<true>, dim3(ng), dim3(rp, nsl), 0, s, ch.grp_c0 + g0, ch.grp_s + g0, ch.grp_nr + g0, plain, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
 	}
 	if (ch.ntask0) hipLaunchKernelGGL(k_cc_bwd<false>, dim3(ch.ntask0), dim3(rp, 1), 0, s, ch.task_ptr, ch.task_cols, (const int*)nullptr, false, R, ch.colptr, ch.rowidx, ch.L, ch.Dinv, V);
@@ -643,6 +655,63 @@ CcOutcome cc_solve_refine(lsfm_context* ctx, const CovFront& fr, int R, CcWork& 
 		prev = worst;
 	}
 	return oc;
+}
+
+// Test entry of the C ABI (lsfm_selftest_cc_sweeps, include/lsfm.h has the arguments): the sweeps above on a caller's matrix with
+// nothing behind them -- the front of the Cholesky's own test entry (no fused forward substitution, fp64), chol_merge_groups as in
+// cov_front, then cc_solve_refine's unrefined solve with the slab copied out between its halves -- and k_cc_resid once, on the list
+// cov_front_rowsorted would have built.  The caller has checked the arguments.
+int cc_sweeps_selftest(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin, const unsigned char* fixed,
+                       const double* B, int R, const double* X, double* x, double* fwd, int* perm, double* dscale, double* y, int* info)
+{
+	if (R < 1 || R > 6 * CC_KC) LSFM_FAIL(LSFM_ERR_ARG, "a chunk has 1 .. " + std::to_string(6 * CC_KC) + " columns");
+	const size_t ns = (size_t)m * 6, cells = ns * R;
+	SelftestFront fr;
+	chol_selftest_front(ctx, m, rowptr, colidx, val, origin, fixed, 3 * cells * sizeof(double) + 4096, -1, nullptr, X != nullptr, nullptr, fr);
+	const CholDev& ch = fr.ch;
+	const SchurSystem& sy = fr.sy;
+	chol_merge_groups(ctx, ch);
+	hipStream_t s = ctx->stream;
+	Arena& sc = ctx->scratch;
+	double *Y = sc.alloc<double>(cells), *V = sc.alloc<double>(cells), *Xo = sc.alloc<double>(cells);
+	const unsigned rp = (unsigned)((R + LSFM_WAVE - 1) / LSFM_WAVE * LSFM_WAVE);
+	h2d(ctx, Y, B, cells * sizeof(double));
+	CcLaunches count;
+	hipLaunchKernelGGL(k_cc_perm_in, dim3(blocks_of(cells, 256)), dim3(256), 0, s, m, R, ch.perm, ch.dscale, fr.d_fixed, Y, V);
+	cc_sweep_forward(ctx, ch, R, V, &count);
+	LSFM_CHECK_HIP(hipGetLastError());
+	// the factorisation's status before anything is handed out: the sweeps of a factor that does not exist mean nothing
+	RunStatsDev rs;
+	d2h(ctx, &rs, fr.d_run, sizeof rs);
+	const int chol_err = d2h_int(ctx, ch.d_err);
+	if (fwd && !chol_err) d2h(ctx, fwd, V, cells * sizeof(double));
+	cc_sweep_backward(ctx, ch, R, V, &count);
+	hipLaunchKernelGGL(k_cc_perm_out, dim3(blocks_of(ns, CC_ROWS)), dim3(rp), 0, s, m, R, ch.pinv, ch.dscale, fr.d_fixed, V, Xo);
+	LSFM_CHECK_HIP(hipGetLastError());
+	std::vector<int> gs(ch.ngroups);
+	if (ch.ngroups) d2h_ints(ctx, ch.grp_s, gs.data(), gs.size());
+	int widths = 0;
+	for (int w : gs) widths |= 1 << (w - 1);
+	const int ngl = (int)ch.glevel_ptr.size() - 1;
+	info[0] = ch.ntask0; info[1] = ch.ngroups; info[2] = std::max(ngl, 0);
+	info[3] = ch.glevel_maxnr.empty() ? 0 : *std::max_element(ch.glevel_maxnr.begin(), ch.glevel_maxnr.end());
+	info[4] = widths;
+	info[5] = count.fwd_tasks; info[6] = count.fwd_groups; info[7] = count.fwd_panel; info[8] = count.bwd_panel; info[9] = count.panel;
+	info[10] = chol_err; info[11] = rs.floored;
+	if (chol_err) LSFM_FAIL(LSFM_ERR_NOT_SPD, "the matrix is not positive definite (block column " + std::to_string(chol_err - 1) + " of the factor)");
+	if (x) d2h(ctx, x, Xo, cells * sizeof(double));
+	if (perm) d2h(ctx, perm, ch.perm, (size_t)m * sizeof(int));
+	if (dscale) d2h(ctx, dscale, ch.dscale, ns * sizeof(double));
+	if (X)
+	{
+		// Y = B - S X as a refinement step forms it: Y holds B still (k_cc_perm_in only read it)
+		if (!sy.gent) LSFM_FAIL(LSFM_ERR_INTERNAL, "the matrix has no row-sorted block list");
+		h2d(ctx, Xo, X, cells * sizeof(double));
+		hipLaunchKernelGGL(k_cc_resid, dim3(blocks_of((size_t)2 * sy.nnzb, CC_EPW)), dim3(rp), 0, s, 2 * sy.nnzb, sy.gent, sy.goth, sy.S, fr.d_fixed, R, Xo, Y);
+		LSFM_CHECK_HIP(hipGetLastError());
+		d2h(ctx, y, Y, cells * sizeof(double));
+	}
+	return LSFM_OK;
 }
 
 void cc_pose_out(lsfm_context* ctx, int width, int M, int R, const double* Xo, double* out)

@@ -619,6 +619,10 @@ int spmv_external(lsfm_context* ctx, int m, const int* rowptr, const int* colidx
 int chol_selftest(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin, const unsigned char* fixed,
                   const int* pose_seg, int nseg, const double* r, int nrhs, int mode, double* z, double* dot, int* perm, int* colptr, int* rowidx,
                   double* L, double* Dinv, double* dscale, int cap_blocks, int* info);
+// the side-by-side sweeps of the columns calls on a caller's matrix, without refinement, and one residual product (lsfm_covcols.hip;
+// C ABI: lsfm_selftest_cc_sweeps); arguments checked by the caller
+int cc_sweeps_selftest(lsfm_context* ctx, int m, const int* rowptr, const int* colidx, const double* val, const int* origin, const unsigned char* fixed,
+                       const double* B, int R, const double* X, double* x, double* fwd, int* perm, double* dscale, double* y, int* info);
 
 int wstream_bench(lsfm_context* ctx, long long nblocks, int mode, int reps, double* avg_ms); // measurement: W access patterns vs stream copy
 // fills, word copies and CopyBatch against a host mirror (lsfm_prims.hip; C ABI: lsfm_selftest_prims)
