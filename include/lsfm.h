@@ -264,6 +264,27 @@ int lsfm_gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, int type, 
  * counts[4] (may be NULL) = blocks of the working form's W, of out's W, of the working form's U, of out's U */
 int lsfm_gn_linearise_timed(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, const double* weight,
                             lsfm_map* out, double* obj, double* b, double* times, int* counts);
+/* The same at given feature weights: the matrix, the quadratic value and the gradient of one step of lsfm_gn_polish_robust_features
+ * at fixed weights,
+ *     H = sum_k w_k J_k^T I_k(w_k.) J_k,   obj = sum_k w_k (pose_chi2_k + sum_f w_kf c_kf),   b = sum_k w_k J_k^T I_k(w_k.) r_k
+ * with I_k(w) as stated for lsfm_gn_polish_robust_features.  fweight[sum_k n_k] (not NULL): w_kf in map order and within a map in the
+ * map's feature order -- the order lsfm_gn_polish_robust_features returns.  Every entry must be finite and in [0, 1], else LSFM_ERR_ARG
+ * (lsfm_last_error names the map and the feature; the context stays usable): a weight above 1 would SUBTRACT a positive semi-definite
+ * term from the map's Schur complement U - sum_f W_f V_f^-1 W_f^T, and I_k(w) is positive semi-definite for every w in [0, 1] only.
+ * weight[N] (may be NULL) as for lsfm_gn_linearise; the two multiply.  Every other argument check is lsfm_gn_linearise's;
+ * LSFM_ERR_NOT_SPD: a V_f is not positive definite (the map and the feature are named, as by lsfm_map_feature_chi2).
+ * `out` is canonical exactly as lsfm_gn_linearise's, with one difference: U also holds a block for every pair of poses of a local map
+ * that see a common feature (the places the correction of U falls into), whether or not the map holds a U block there.  The structure
+ * depends on the labels alone, never on fweight: a block that exists only for the correction is exactly 0.0 when every weight of its
+ * features is 1, and a V block whose instances all have weight 0 is a zero block and stays.  W and V follow lsfm_gn_linearise's rules.
+ * The chi^2 pass of lsfm_map_feature_chi2 (reading the weights), the fill of the correction slots, the feature-robust step's assembly,
+ * then the two coalescing kernels; obj is summed in a fixed order. */
+int lsfm_gn_linearise_features(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, const double* weight,
+                               const double* fweight, lsfm_map* out, double* obj, double* b);
+/* measurement entry: times[4] (may be NULL) = HIP-event ms of the chi^2 pass + slot fill, of the rest of the assembly, of the W and of
+ * the U coalescing launch; counts[4] as lsfm_gn_linearise_timed */
+int lsfm_gn_linearise_features_timed(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, const double* weight,
+                                     const double* fweight, lsfm_map* out, double* obj, double* b, double* times, int* counts);
 
 /* ---- marginal covariances of a map (NO reference counterpart: the reference keeps the information matrix and never inverts it) ----
  * Sigma = I^-1 with I = [U W; W^T V] of `map` (any lsfm_map: a downloaded tree result, a checkpoint node, a local map).

@@ -127,6 +127,8 @@ def lib():
         L.lsfm_gn_polish_robust_features.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), C.c_int, C.c_int, C.c_double, dp, dp, ip, dp, dp]
         L.lsfm_gn_linearise.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, P(LsfmMap), dp, dp]
         L.lsfm_gn_linearise_timed.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, P(LsfmMap), dp, dp, dp, ip]
+        L.lsfm_gn_linearise_features.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, dp, P(LsfmMap), dp, dp]
+        L.lsfm_gn_linearise_features_timed.argtypes = [vp, P(LsfmMap), C.c_int, C.c_int, P(LsfmMap), dp, dp, P(LsfmMap), dp, dp, dp, ip]
         L.lsfm_solve_features.argtypes = [vp, dp, dp, dp, dp, dp, dp, C.c_int, C.c_int, ip, ip]
         L.lsfm_map_covariance.argtypes = [vp, P(LsfmMap), C.c_int, dp, dp, dp, C.c_int, ip]
         L.lsfm_map_covariance_timed.argtypes = [vp, P(LsfmMap), C.c_int, dp, dp, dp, C.c_int, ip, dp]
@@ -187,6 +189,7 @@ EXPORTS = ["lsfm_context_create", "lsfm_context_destroy", "lsfm_set_pcg", "lsfm_
            "lsfm_tree_upload_dev", "lsfm_tree_reload_dev", "lsfm_tree_set_comm", "lsfm_tree_set_comm_blocks", "lsfm_tree_export_slice_sizes", "lsfm_tree_export_slice_dev",
            "lsfm_tree_free", "lsfm_divide_conquer", "lsfm_read_localmap", "lsfm_read_localmaps", "lsfm_write_localmap", "lsfm_write_mapset", "lsfm_mapset_info", "lsfm_mapset_stamp", "lsfm_read_mapset", "lsfm_save_state_bin", "lsfm_save_state", "lsfm_save_poses", "lsfm_gn_polish",
            "lsfm_gn_polish_robust", "lsfm_map_chi2", "lsfm_map_feature_chi2", "lsfm_gn_polish_robust_features", "lsfm_gn_linearise", "lsfm_gn_linearise_timed",
+           "lsfm_gn_linearise_features", "lsfm_gn_linearise_features_timed",
            "lsfm_spmv_bench", "lsfm_wstream_bench", "lsfm_selftest_prims", "lsfm_selftest_chol", "lsfm_selftest_cc_sweeps", "lsfm_selftest_transform", "lsfm_selftest_small", "lsfm_schur_pattern", "lsfm_symbolic_analyse", "lsfm_inverse_v", "lsfm_selftest_vinv", "lsfm_solve_features",
            "lsfm_map_covariance", "lsfm_map_covariance_timed",
            "lsfm_save_covariances", "lsfm_read_covariances",
@@ -552,27 +555,49 @@ class Context:
         cut = np.cumsum(ns)[:-1]
         return st, obj, gn, hv[:iters], np.split(fchi2[:sum(ns)], cut), np.split(fw[:sum(ns)], cut), rc
 
-    def gn_linearise(self, maps, mono, G, weight=None, want_b=False, timed=False):
+    def gn_linearise(self, maps, mono, G, weight=None, want_b=False, timed=False, feature_weight=None):
         """lsfm_gn_linearise: the joint map of the local maps linearised at the global state G (as gn_polish takes it; read only) --
         H = sum_k w_k J_k^T I_k J_k as U / W / V with every block once, the matrix a step of gn_polish[_robust] solves with at G.
         weight [N] or None (all 1): e.g. what gn_polish_robust returned.  No reference counterpart.  Returns (map dict of the form
         tree_download returns, F = sum_k w_k chi2_k, b = sum_k w_k J_k^T I_k r_k or None); timed: also ({"assembly_ms",
-        "coalesce_w_ms", "coalesce_u_ms"} by HIP events, {"NWJ", "nW", "NUJ", "nU"}: blocks of the working form / of the map)."""
+        "coalesce_w_ms", "coalesce_u_ms"} by HIP events, {"NWJ", "nW", "NUJ", "nU"}: blocks of the working form / of the map).
+        feature_weight (None: the call above): lsfm_gn_linearise_features -- weights w_kf in [0, 1] of the features' conditional terms, a
+        list of per-map arrays as gn_polish_robust_features returns them or one flat array [sum n_k]; the maps are then I_k(w_k.), H
+        the matrix of a feature-robust step at those weights, F = sum_k w_k (pose_chi2_k + sum_f w_kf c_kf), U also holds the blocks of
+        poses that see a common feature, and timed gains "chi2_fill_ms" (the chi^2 pass + the correction of U) ahead of the others."""
         hms, arr, x, keep = _gn_args(maps, G)
         w = _c(weight, np.float64) if weight is not None else None
         if w is not None and len(w) != len(hms):
             raise LsfmError(f"gn_linearise: {len(w)} weights for {len(hms)} maps")
+        fw = None
+        if feature_weight is not None:
+            ns = [int(h.c.n) for h in hms]
+            if isinstance(feature_weight, (list, tuple)) and len(feature_weight) and np.ndim(feature_weight[0]) > 0:
+                if len(feature_weight) != len(hms) or any(np.size(a) != n for a, n in zip(feature_weight, ns)):
+                    raise LsfmError(f"gn_linearise: feature weights of sizes {[int(np.size(a)) for a in feature_weight]} for maps of {ns} features")
+                fw = _c(np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in feature_weight]), np.float64)
+            else:
+                fw = _c(feature_weight, np.float64)
+                if len(fw) != sum(ns):
+                    raise LsfmError(f"gn_linearise: {len(fw)} feature weights for {sum(ns)} feature instances")
+            if len(fw) == 0:
+                fw = np.zeros(1)  # (no feature at all: the pointer must still be one)
         out = LsfmMap()
         F = C.c_double(0.0)
         b = np.zeros(6 * x.m + 3 * x.n) if want_b else None
-        t, cnt = np.zeros(3), np.zeros(4, np.int32)
-        rc = lib().lsfm_gn_linearise_timed(self._h, arr, len(hms), int(mono), C.byref(x), _ptr(w, C.c_double) if w is not None else None,
-                                           C.byref(out), C.byref(F), _ptr(b, C.c_double) if want_b else None,
-                                           _ptr(t, C.c_double) if timed else None, _ptr(cnt, C.c_int) if timed else None)
-        self._check(rc, "lsfm_gn_linearise")
+        names = ("assembly_ms", "coalesce_w_ms", "coalesce_u_ms")
+        if fw is not None:
+            names = ("chi2_fill_ms",) + names
+        t, cnt = np.zeros(len(names)), np.zeros(4, np.int32)
+        head = (self._h, arr, len(hms), int(mono), C.byref(x), _ptr(w, C.c_double) if w is not None else None)
+        tail = (C.byref(out), C.byref(F), _ptr(b, C.c_double) if want_b else None, _ptr(t, C.c_double) if timed else None, _ptr(cnt, C.c_int) if timed else None)
+        if fw is None:
+            self._check(lib().lsfm_gn_linearise_timed(*head, *tail), "lsfm_gn_linearise")
+        else:
+            self._check(lib().lsfm_gn_linearise_features_timed(*head, _ptr(fw, C.c_double), *tail), "lsfm_gn_linearise_features")
         d = map_to_dict(out)
         if timed:
-            return d, F.value, b, dict(zip(("assembly_ms", "coalesce_w_ms", "coalesce_u_ms"), t.tolist())), dict(zip(("NWJ", "nW", "NUJ", "nU"), cnt.tolist()))
+            return d, F.value, b, dict(zip(names, t.tolist())), dict(zip(("NWJ", "nW", "NUJ", "nU"), cnt.tolist()))
         return d, F.value, b
 
     def inverse_v(self, V):

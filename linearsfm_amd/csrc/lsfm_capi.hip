@@ -517,7 +517,32 @@ int lsfm_gn_linearise_timed(lsfm_context* ctx, const lsfm_map* maps, int N, int 
 		for (int k = 0; k < N; k++)
 			if (!std::isfinite(weight[k]) || weight[k] < 0.0)
 				return guarded(ctx, [&]() -> int { LSFM_FAIL(LSFM_ERR_ARG, "gn linearise: weight " + std::to_string(k + 1) + " is negative or not finite"); });
-	return guarded(ctx, [&]() { return gn_linearise(ctx, maps, N, type == 1, x, weight, out, obj, b, times, counts); });
+	return guarded(ctx, [&]() { return gn_linearise(ctx, maps, N, type == 1, x, weight, nullptr, out, obj, b, times, counts); });
+}
+
+int lsfm_gn_linearise_features_timed(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, const double* weight,
+                                     const double* fweight, lsfm_map* out, double* obj, double* b, double* times, int* counts)
+{
+	if (!maps || N <= 0 || !x || !out || !fweight || (type != 0 && type != 1)) return LSFM_ERR_ARG;
+	if (weight)
+		for (int k = 0; k < N; k++)
+			if (!std::isfinite(weight[k]) || weight[k] < 0.0)
+				return guarded(ctx, [&]() -> int { LSFM_FAIL(LSFM_ERR_ARG, "gn linearise: weight " + std::to_string(k + 1) + " is negative or not finite"); });
+	// (a map with a negative size is refused by the upload, before a weight of it would be read)
+	size_t q = 0;
+	for (int k = 0; k < N && maps[k].n >= 0; q += (size_t)maps[k].n, k++)
+		for (int f = 0; f < maps[k].n; f++)
+			if (!(fweight[q + f] >= 0.0 && fweight[q + f] <= 1.0))
+				return guarded(ctx, [&]() -> int {
+					LSFM_FAIL(LSFM_ERR_ARG, "gn linearise: the weight of feature " + std::to_string(f + 1) + " of local map " + std::to_string(k + 1) + " is not in [0, 1]");
+				});
+	return guarded(ctx, [&]() { return gn_linearise(ctx, maps, N, type == 1, x, weight, fweight, out, obj, b, times, counts); });
+}
+
+int lsfm_gn_linearise_features(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, const double* weight, const double* fweight,
+                               lsfm_map* out, double* obj, double* b)
+{
+	return lsfm_gn_linearise_features_timed(ctx, maps, N, type, x, weight, fweight, out, obj, b, nullptr, nullptr);
 }
 
 int lsfm_gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, int type, const lsfm_map* x, const double* weight, lsfm_map* out, double* obj,

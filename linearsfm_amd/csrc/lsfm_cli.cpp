@@ -42,13 +42,17 @@
 // -robust huber|cauchy <c> (-gn uses lsfm_gn_polish_robust: whole local maps down-weighted by an M-estimator on chi2_k / dof_k),
 // -chi2 <file> (per local map, in input order, "index dof chi2 weight" at the final state: lsfm_map_chi2; no reference counterpart),
 // -robustf huber|cauchy <c> (-gn uses lsfm_gn_polish_robust_features: single features of single local maps down-weighted by an M-estimator on
-// their conditional chi2 c_kf / 3; not together with -robust or -relin: the two estimators are not combined, and linearising with feature
-// weights is not offered),
+// their conditional chi2 c_kf / 3; not together with -robust or -relin: the two estimators are not combined, and the linearisation with
+// the feature weights is a flag of its own, -relinf),
 // -chi2f <file> (per local map and feature, in input order, "map_index feature_id chi2 weight" at the final state: lsfm_map_feature_chi2, the
 // weight 1 without -robustf; written after -chi2 through a temporary file renamed into place; no reference counterpart),
 // -relin 1 (the final map's information matrix -- U / W / V and their index arrays -- is replaced by the local maps linearised at the final
 // state, after -gn if given and with the polish's weights under -robust: lsfm_gn_linearise; -info, -cov, -covf and -covcols then describe
 // the estimate the other files hold; no reference counterpart),
+// -relinf 1 (with -gn and -robustf, at the place -relin acts: the final map's U / W / V and their index arrays are replaced by the local
+// maps linearised at the polished state WITH the polish's feature weights, lsfm_gn_linearise_features -- the matrix the last feature-robust
+// step solved with; every later flag then describes that map; -st, -p, -f and -chi2f are what they are without it; without -robustf,
+// together with -relin or on a library error the run ends non-zero before any file is written; no reference counterpart),
 // -keepf <file> (whitespace-separated feature ids, unknown ones ignored: after -gn / -relin and before any file is written the final map is
 // replaced by its reduction to these features -- every other feature marginalised out, lsfm_map_marginalise; -st, -p, -f, -full, -fullbin,
 // -info, -cov, -covf and -covcols describe the reduced map, -chi2 is evaluated on the full state first; no reference counterpart),
@@ -84,9 +88,10 @@ static void print_help()
 	printf("			II : Stereo\n");
 	printf("-robust huber|cauchy <c>	With -gn: Down-Weight Inconsistent Local Maps (Threshold c On chi2 / dof)\n");
 	printf("-chi2 <file>		Save chi2 Of Every Local Map: index dof chi2 weight\n");
-	printf("-robustf huber|cauchy <c>	With -gn: Down-Weight Inconsistent Single Features (Threshold c On Their chi2 / 3); Not With -robust Or -relin\n");
+	printf("-robustf huber|cauchy <c>	With -gn: Down-Weight Inconsistent Single Features (Threshold c On Their chi2 / 3); Not With -robust Or -relin (See -relinf)\n");
 	printf("-chi2f <file>		Save chi2 Of Every Feature Of Every Local Map: map_index feature_id chi2 weight\n");
 	printf("-relin 1		Information Matrix (-info, -cov, -covf, -covcols) Of The Local Maps Linearised At The Final State\n");
+	printf("-relinf 1		With -gn And -robustf: The Same With The Polish's Feature Weights (The Matrix Of Its Last Step); Not With -relin\n");
 	printf("-keepf <file>		Keep Only The Features Whose Ids The File Lists: The Others Are Marginalised Out Of The Final Map\n");
 	printf("-gate <file> -gateout <file>	Gate Candidate Feature Pairs (Two Ids Each): id_f id_g d2 And The Upper Triangle Of Var(x_f - x_g)\n");
 	printf("-merge <file> [-mergeout <file>]	Merge Feature Pairs (Two Ids Each) Into One Point Each; Report: K removed dof D2, Then id_f id_g id_kept\n");
@@ -99,7 +104,7 @@ static void print_help()
 int main(int argc, char** argv)
 {
 	std::string path, st, pose, fea, full, info, nodes, cache, fullbin, json, cov, covf, chi2f, robust_err, covcols, covposes, keepf, keepp, chi2ff, gate, gateout, merge, mergeout, cand, candr, candtau, jgate, jgateout, jgatetau, jgatepairs;
-	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0, relin = 0, robustf = 0;
+	int num = 0, type = -1, gpu = 0, want_stats = 0, levels = 0, quiet = 0, gn = 0, robust = 0, relin = 0, robustf = 0, relinf = 0;
 	double robust_c = 0.0, robustf_c = 0.0;
 	bool has_path = false, has_num = false, has_keepf = false, has_keepp = false, has_gate = false, has_gateout = false, has_merge = false, has_mergeout = false, has_cand = false, has_candr = false, has_candtau = false;
 	bool has_jgate = false, has_jgateout = false, has_jgatetau = false, has_jgatepairs = false;
@@ -139,6 +144,7 @@ int main(int argc, char** argv)
 		else if (name == "covf") covf = next();
 		else if (name == "chi2") chi2f = next();
 		else if (name == "relin") relin = atoi(next());
+		else if (name == "relinf") relinf = atoi(next());
 		else if (name == "covcols") covcols = next();
 		else if (name == "covposes") covposes = next();
 		else if (name == "keepf") { keepf = next(); has_keepf = true; }
@@ -250,6 +256,8 @@ int main(int argc, char** argv)
 	if (robustf && gn <= 0) { fprintf(stderr, "LinearSFM: -robustf applies to -gn <steps>: give -gn too\n"); return 1; }
 	if (robustf && robust) { fprintf(stderr, "LinearSFM: -robustf and -robust do not go together: the map and the feature estimator are not combined\n"); return 1; }
 	if (robustf && relin) { fprintf(stderr, "LinearSFM: -robustf and -relin do not go together: linearising with feature weights is not offered\n"); return 1; }
+	if (relinf && relin) { fprintf(stderr, "LinearSFM: -relinf and -relin do not go together: the final map is one linearisation or the other\n"); return 1; }
+	if (relinf && !robustf) { fprintf(stderr, "LinearSFM: -relinf applies to -gn <steps> -robustf <kind> <c>: it linearises with that polish's feature weights\n"); return 1; }
 
 	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double w0 = now();
@@ -401,14 +409,17 @@ int main(int argc, char** argv)
 			printf("Gauss-Newton Used Time:  %lf  sec\n\n", now() - g0);
 		}
 	}
-	if (relin)
+	if (relin || relinf)
 	{
 		// -relin 1: the information matrix of the state the files hold -- the local maps linearised at it (under -robust with the weights the
-		// polish ended at) instead of the tree's, whose joins linearised at states the estimate has since left
+		// polish ended at) instead of the tree's, whose joins linearised at states the estimate has since left.  -relinf 1: the same with
+		// the feature weights -robustf ended at
 		lsfm_map H;
-		if (lsfm_gn_linearise(ctx, maps.data(), num, type, &out, weightv.empty() ? nullptr : weightv.data(), &H, nullptr, nullptr) != LSFM_OK)
+		const int lrc = relinf ? lsfm_gn_linearise_features(ctx, maps.data(), num, type, &out, nullptr, fweightv.data(), &H, nullptr, nullptr)
+		                       : lsfm_gn_linearise(ctx, maps.data(), num, type, &out, weightv.empty() ? nullptr : weightv.data(), &H, nullptr, nullptr);
+		if (lrc != LSFM_OK)
 		{
-			fprintf(stderr, "LinearSFM: relin: %s\n", lsfm_last_error(ctx));
+			fprintf(stderr, "LinearSFM: %s: %s\n", relinf ? "relinf" : "relin", lsfm_last_error(ctx));
 			return 3;
 		}
 		lsfm_map_release(&out);

@@ -58,6 +58,8 @@ size_t gn_arena_need(const lsfm_map* maps, int N, const lsfm_map* x, const GnWan
 			}
 		need += FI * 16 + (size_t)N * 64 + 4096;
 		if (w.slots) need += (nU + nc) * (288 + 800 + 8 + 288) + nc * (16 + 36) + nW * 8;
+		// (every slot is one more joint U block: one more source of the coalesced form and at most one more output block)
+		if (w.slots && w.coalesce) need += nc * (288 + 16);
 	}
 	return need;
 }
@@ -337,24 +339,35 @@ int gn_polish_features(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono
 // structure pass sorts stably; HBM-bound: NWJ * 144 B in, nW' * 144 B out, U: 288 B a block), then the download into arrays of the
 // library's own allocator (lsfm_map_release frees them).  x is read only.  The assembly sums with atomics: two calls agree to rounding,
 // not bit for bit; the structure of `out` depends on the labels alone.
-// times (may be null): [3] HIP-event ms of the assembly, k_gn_coalesce<18> (W), k_gn_coalesce<36> (U); counts (may be null): [4] NWJ, nW', NUJ, nU'.
-int gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, const double* weight, lsfm_map* out, double* obj,
-                 double* b, double* times, int* counts)
+// fweight (null: lsfm_gn_linearise, the launches above and no others; else lsfm_gn_linearise_features): [sum n_k] weights w_kf in [0, 1]
+// of the features' conditional terms (the caller has checked them).  The maps are then I_k(w_k.) of lsfm_gn_chi2.hip: the structure
+// carries the correction slots as well as the coalesced form, the assembly is the feature-robust step's with the weights given
+// (GnEstimator::given: chi^2 pass, slot fill, k_gn_ublocks over the extended list, k_gn_features<NH, true>), a map's weight w_k reaches
+// its slots as it reaches its own blocks (k_gn_ublocks scales every block of the list it reads), and the coalescing sums the slots'
+// joint blocks with the others.  obj is then sum_k w_k (pose_chi2_k + sum_f w_kf c_kf), summed without atomics.
+// times (may be null): [3] HIP-event ms of the assembly, k_gn_coalesce<18> (W), k_gn_coalesce<36> (U) -- with fweight [4]: the chi^2 pass
+// + slot fill first, then the rest of the assembly and the two; counts (may be null): [4] NWJ, nW', NUJ, nU'.
+int gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, const double* weight, const double* fweight,
+                 lsfm_map* out, double* obj, double* b, double* times, int* counts)
 {
 	hipStream_t s = ctx->stream;
-	const bool timing = gn_timing();
+	const bool timing = gn_timing(), given = fweight != nullptr;
 	const double tw0 = gn_wall();
 	GnStructure st;
 	GnCall c;
-	gn_begin(ctx, maps, N, mono, x, weight, GnWants::linearise(), st, c);
+	gn_begin(ctx, maps, N, mono, x, weight, given ? GnWants::linearise_features() : GnWants::linearise(), st, c);
 	const GnCoalesced& co = st.co;
 	const int M = c.M, NFG = c.NFG;
+	if (given && c.FI) h2d(ctx, c.feat.fw, fweight, (size_t)c.FI * sizeof(double));
 	if (timing) LSFM_CHECK_HIP(hipStreamSynchronize(s));
 	const double tw1 = gn_wall();
 	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr }; // around the assembly and the two coalescing launches
+	GnEvents gev;                                              // given: around the chi^2 pass and the slot fill inside the assembly
 	if (times) for (hipEvent_t& e : ev) e = ctx->pool_event();
+	if (times && given) { gev.chi2[0] = ctx->pool_event(); gev.chi2[1] = ctx->pool_event(); gev.fill[0] = ctx->pool_event(); gev.fill[1] = ctx->pool_event(); }
 	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[0], s));
-	gn_assemble(ctx, c, GnEstimator(), nullptr);
+	if (given) gn_assemble(ctx, c, GnEstimator{ GnEstimator::given, 0, 1.0 }, times ? &gev : nullptr);
+	else gn_assemble(ctx, c, GnEstimator(), nullptr);
 	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[1], s));
 	if (co.nWo) hipLaunchKernelGGL(k_gn_coalesce<18>, gn_grid(co.nWo, 256), dim3(256), 0, s, co.nWo, c.co.d_wsp, c.co.d_wsi, c.WJ, c.co.Wo);
 	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[2], s));
@@ -362,6 +375,7 @@ int gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, cons
 	if (times) LSFM_CHECK_HIP(hipEventRecord(ev[3], s));
 	if (timing) LSFM_CHECK_HIP(hipStreamSynchronize(s));
 	const double tw2 = gn_wall();
+	if (given) gn_feature_check(ctx, maps, c); // (before anything is allocated for the caller)
 	MapOut G;
 	map_new(G.g, x, M, NFG, co.nUo, co.nWo, true);
 	lsfm_map& g = G.g;
@@ -372,7 +386,7 @@ int gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, cons
 	if (g.nU) d2h(ctx, g.U, c.co.Uo, (size_t)g.nU * 36 * sizeof(double));
 	if (g.nW) d2h(ctx, g.W, c.co.Wo, (size_t)g.nW * 18 * sizeof(double));
 	if (NFG) d2h(ctx, g.V, c.VJ, (size_t)NFG * 9 * sizeof(double));
-	if (obj) d2h(ctx, obj, c.Fsum, sizeof(double));
+	if (obj) d2h(ctx, obj, given ? c.d_G : c.Fsum, sizeof(double));
 	if (b)
 	{
 		d2h(ctx, b, c.ea, (size_t)M * 6 * sizeof(double));
@@ -380,11 +394,15 @@ int gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, cons
 	}
 	LSFM_CHECK_HIP(hipStreamSynchronize(s));
 	if (times)
-		for (int i = 0; i < 3; i++) times[i] = event_ms(ev[i], ev[i + 1]);
+	{
+		double* t = times + (given ? 1 : 0);
+		for (int i = 0; i < 3; i++) t[i] = event_ms(ev[i], ev[i + 1]);
+		if (given) { times[0] = event_ms(gev.chi2[0], gev.fill[1]); t[0] -= times[0]; }
+	}
 	if (counts) { counts[0] = c.NWJ; counts[1] = co.nWo; counts[2] = c.NUJ; counts[3] = co.nUo; }
 	if (timing)
-		fprintf(stderr, "lsfm_gn_linearise: %d maps, %d poses, %d features, W %d -> %d blocks, U %d -> %d blocks; structure + upload %.2f ms, assembly + coalescing "
-		                "%.2f ms, download %.2f ms, call %.2f ms\n", N, M, NFG, c.NWJ, co.nWo, c.NUJ, co.nUo, tw1 - tw0, tw2 - tw1, gn_wall() - tw2, gn_wall() - tw0);
+		fprintf(stderr, "lsfm_gn_linearise%s: %d maps, %d poses, %d features, W %d -> %d blocks, U %d -> %d blocks; structure + upload %.2f ms, assembly + coalescing "
+		                "%.2f ms, download %.2f ms, call %.2f ms\n", given ? "_features" : "", N, M, NFG, c.NWJ, co.nWo, c.NUJ, co.nUo, tw1 - tw0, tw2 - tw1, gn_wall() - tw2, gn_wall() - tw0);
 	G.give(out);
 	return LSFM_OK;
 }

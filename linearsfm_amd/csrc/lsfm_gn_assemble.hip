@@ -223,8 +223,8 @@ k_gn_ublocks(int NU, int P, const int* __restrict__ Ui, const int* __restrict__ 
 }
 
 // one lane per local feature (see the header).  NH: 1 Stereo, 2 Mono (a Stereo map in the global frame has t.nh = 0: its C are zero
-// and it owns no hub blocks).  FW (lsfm_gn_polish_robust_features only): the instance's W and V blocks are weighted
-// by t.w * fw[f], the weight of the feature's conditional term (k_gn_chi2<true>); FW = false is the kernel of the plain and the map-robust polish, fw unused
+// and it owns no hub blocks).  FW (lsfm_gn_polish_robust_features and lsfm_gn_linearise_features only): the instance's W and V blocks are weighted
+// by t.w * fw[f], the weight of the feature's conditional term (k_gn_chi2<true>: computed; <true, true>: given); FW = false is the kernel of the plain and the map-robust polish, fw unused
 template <int NH, bool FW>
 __global__ void __launch_bounds__(256)
 k_gn_features(int NF, int P, const int* __restrict__ feat_map, const GnMap* __restrict__ gm, const int* __restrict__ gf, const double* __restrict__ xf,
@@ -465,13 +465,14 @@ void gn_assemble(lsfm_context* ctx, const GnCall& c, const GnEstimator& est, con
 	hipStream_t s = ctx->stream;
 	const DevBatch& X = c.X;
 	const int N = c.N, M = c.M, NFG = c.NFG, P = c.P;
-	const bool feat = est.on == GnEstimator::features;
+	const bool feat = est.on == GnEstimator::features || est.on == GnEstimator::given;
 	dev_zero(ctx, c.Gacc, ((size_t)P * GN_GW + (size_t)N * GN_HW + 2) * sizeof(double));
 	gn_frames(ctx, c);
 	if (est.on != GnEstimator::none)
 	{
 		if (ev) LSFM_CHECK_HIP(hipEventRecord(ev->chi2[0], s));
-		if (feat) gn_feature_chi2(ctx, c, est.kind, est.c);
+		if (est.on == GnEstimator::given) gn_feature_chi2_given(ctx, c);
+		else if (feat) gn_feature_chi2(ctx, c, est.kind, est.c);
 		else { gn_map_chi2(ctx, c); gn_map_weights(ctx, c, est.kind, est.c); }
 		if (ev) LSFM_CHECK_HIP(hipEventRecord(ev->chi2[1], s));
 	}

@@ -1,6 +1,6 @@
 // Gauss-Newton polish (lsfm_gn.hpp): chi^2 of the local maps and of their single features at the frames of k_gn_hubs and the pose
 // residuals of k_gn_poses, the M-estimators' weights and objectives, and the correction of U that the feature weights need
-// (lsfm_map_chi2, lsfm_gn_polish_robust, lsfm_map_feature_chi2, lsfm_gn_polish_robust_features).  No sum here uses an atomic: the same
+// (lsfm_map_chi2, lsfm_gn_polish_robust, lsfm_map_feature_chi2, lsfm_gn_polish_robust_features, lsfm_gn_linearise_features).  No sum here uses an atomic: the same
 // state gives the same bits.
 #include "lsfm_device.hpp"
 #include "lsfm_gn.hpp"
@@ -105,9 +105,10 @@ __device__ __forceinline__ double gn_feature_term(const GnMap& t, int f, const d
 // 1200-1882 over 600-941 features -- two to four features per lane.
 // FEAT = false: chi2_k into out[k].  FEAT = true: per feature c_kf and its weight w_kf = rho'(c_kf / 3) (gn_rho), per map chi2_k,
 // sum_f c_kf and sum_f rho(c_kf / 3) into out[3 k ..]; bad: the smallest feature instance whose V is not positive definite (an integer
-// minimum: the same for every order).
+// minimum: the same for every order).  GIVEN (with FEAT; lsfm_gn_linearise_features): no estimator -- fweight is read, not written, and
+// the third sum is sum_f w_kf c_kf; kind and c are unused.  The two earlier instantiations are what they were.
 #define GN_CHI2_LANES 256
-template <bool FEAT>
+template <bool FEAT, bool GIVEN = false>
 __global__ void __launch_bounds__(GN_CHI2_LANES)
 k_gn_chi2(int kind, double c, const GnMap* __restrict__ gm, const double* __restrict__ U, const int* __restrict__ Ui, const int* __restrict__ Uj,
           const double* __restrict__ rp, const int* __restrict__ gf, const double* __restrict__ xf, const double* __restrict__ fhat,
@@ -129,9 +130,10 @@ k_gn_chi2(int kind, double c, const GnMap* __restrict__ gm, const double* __rest
 			if (!gn_chol3(Vb, L)) atomicMin(bad, f);
 			gn_lsolve3(L, g, y);
 			const double cf = y[0] * y[0] + y[1] * y[1] + y[2] * y[2];
-			gn_rho(kind, c, cf / 3.0, w, rho);
+			if (GIVEN) { w = fweight[f]; rho = w * cf; }
+			else gn_rho(kind, c, cf / 3.0, w, rho);
 			fchi2[f] = cf;
-			fweight[f] = w;
+			if (!GIVEN) fweight[f] = w;
 			accc += cf; accr += rho;
 		}
 	}
@@ -178,6 +180,23 @@ k_gn_feature_objective(int N, const double* __restrict__ msum, double* __restric
 		const double p = msum[(size_t)3 * k] - msum[(size_t)3 * k + 1];
 		pose_chi2[k] = p;
 		acc += p + 3.0 * msum[(size_t)3 * k + 2];
+	}
+	acc = block_sum_fixed<GN_WEIGHT_LANES>(acc, part);
+	if (threadIdx.x == 0) *Gsum = acc;
+}
+
+// one work-group, the weights given (k_gn_chi2<true, true>): pose_chi2[k] = chi2_k - sum_f c_kf and
+// G = sum_k w_k (pose_chi2[k] + sum_f w_kf c_kf) in a fixed order, w_k the maps' weights of gn_upload
+__global__ void __launch_bounds__(GN_WEIGHT_LANES)
+k_gn_given_objective(int N, const GnMap* __restrict__ gm, const double* __restrict__ msum, double* __restrict__ pose_chi2, double* __restrict__ Gsum)
+{
+	__shared__ double part[GN_WEIGHT_LANES / LSFM_WAVE];
+	double acc = 0.0;
+	for (int k = threadIdx.x; k < N; k += GN_WEIGHT_LANES)
+	{
+		const double p = msum[(size_t)3 * k] - msum[(size_t)3 * k + 1];
+		pose_chi2[k] = p;
+		acc += gm[k].w * (p + msum[(size_t)3 * k + 2]);
 	}
 	acc = block_sum_fixed<GN_WEIGHT_LANES>(acc, part);
 	if (threadIdx.x == 0) *Gsum = acc;
@@ -259,10 +278,10 @@ k_gn_feature_ufill(int NS, const int* __restrict__ sptr, const int* __restrict__
 	if (lane == 0) st<36>(Ux + (size_t)sdst[s] * 36, acc);
 }
 
-template <bool FEAT>
+template <bool FEAT, bool GIVEN = false>
 static void gn_launch_chi2(lsfm_context* ctx, const GnCall& c, int kind, double cth, double* out)
 {
-	hipLaunchKernelGGL(k_gn_chi2<FEAT>, dim3(c.N), dim3(GN_CHI2_LANES), 0, ctx->stream, kind, cth, c.d_gm, c.u.U, c.u.Ui, c.u.Uj, c.rp, c.d_gf,
+	hipLaunchKernelGGL((k_gn_chi2<FEAT, GIVEN>), dim3(c.N), dim3(GN_CHI2_LANES), 0, ctx->stream, kind, cth, c.d_gm, c.u.U, c.u.Ui, c.u.Uj, c.rp, c.d_gf,
 	                   c.d_x + (size_t)c.M * 6, c.X.feat, c.X.fptr, c.X.photo, c.X.W, c.X.V, out, c.feat.fchi2, c.feat.fw, c.feat.d_bad);
 }
 void gn_map_chi2(lsfm_context* ctx, const GnCall& c) { gn_launch_chi2<false>(ctx, c, 0, 1.0, c.d_chi2); }
@@ -274,6 +293,11 @@ void gn_feature_chi2(lsfm_context* ctx, const GnCall& c, int kind, double cth)
 {
 	gn_launch_chi2<true>(ctx, c, kind, cth, c.feat.msum);
 	hipLaunchKernelGGL(k_gn_feature_objective, dim3(1), dim3(GN_WEIGHT_LANES), 0, ctx->stream, c.N, c.feat.msum, c.feat.pose_chi2, c.d_G);
+}
+void gn_feature_chi2_given(lsfm_context* ctx, const GnCall& c)
+{
+	gn_launch_chi2<true, true>(ctx, c, 0, 1.0, c.feat.msum);
+	hipLaunchKernelGGL(k_gn_given_objective, dim3(1), dim3(GN_WEIGHT_LANES), 0, ctx->stream, c.N, c.d_gm, c.feat.msum, c.feat.pose_chi2, c.d_G);
 }
 void gn_extend_u(lsfm_context* ctx, const GnCall& c, const int* d_ushift)
 {

@@ -563,10 +563,12 @@ int gn_polish_features(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono
                        int* halvings, double* fchi2, double* fweight);
 // per-map chi^2 of the map-joining objective at a global state (lsfm_gn.hip, kernel lsfm_gn_chi2.hip; C ABI: lsfm_map_chi2)
 int map_chi2(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, double* chi2, int* dof);
-// the joint system of the local maps linearised at x as a map of its own, every block once (lsfm_gn.hip; C ABI: lsfm_gn_linearise).
-// times (may be null): [3] ms of the assembly, the W and the U coalescing launch; counts (may be null): [4] NWJ, nW', NUJ, nU'
-int gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, const double* weight, lsfm_map* out, double* obj,
-                 double* b, double* times, int* counts);
+// the joint system of the local maps linearised at x as a map of its own, every block once (lsfm_gn.hip; C ABI: lsfm_gn_linearise;
+// with fweight, [sum n_k] weights in [0, 1] of the features' conditional terms: lsfm_gn_linearise_features).
+// times (may be null): [3] ms of the assembly, the W and the U coalescing launch -- with fweight [4], the chi^2 pass + slot fill ahead of
+// them; counts (may be null): [4] NWJ, nW', NUJ, nU'
+int gn_linearise(lsfm_context* ctx, const lsfm_map* maps, int N, bool mono, const lsfm_map* x, const double* weight, const double* fweight,
+                 lsfm_map* out, double* obj, double* b, double* times, int* counts);
 // marginal covariances of a map's information matrix (lsfm_cov.hip; C ABI: lsfm_map_covariance).  times (may be null): [4] ms of the
 // Schur reduction + analysis, the factorisation, the selected inversion + pose gather, the feature part
 int map_covariance(lsfm_context* ctx, const lsfm_map* map, bool mono, double* pose_cov, double* feat_cov, double* pair_cov, int cap_blocks, int* nnzb,

@@ -1,6 +1,6 @@
 """lsfm_gn_polish on a named stand-in set, from the device's own tree result: the objective / gradient trace and the wall clock of the
 call's parts (LSFM_GN_TIMING=1: structure + upload, per assembly (with the chi2 + weights kernels' HIP-event time when robust), per
-solve).  usage: python tools/gn_bench.py <config> [steps] [maps] [--robust huber|cauchy --c <c>] [--linearise]
+solve).  usage: python tools/gn_bench.py <config> [steps] [maps] [--robust huber|cauchy --c <c>] [--robust-features huber|cauchy --c <c>] [--linearise]
 -> one JSON object per call on stdout (profiles/r06_gn_polish_<config>.json).  --robust: lsfm_gn_polish_robust instead, and the same
 steps of the plain polish beside it (wall clock per step of each, the chi2 kernel's share of an assembly).  --linearise: after the
 polish, lsfm_gn_linearise at the polished state (profiles/gn_linearise_<config>.json), one warm-up and the medians of 3 calls: HIP-event ms
@@ -10,7 +10,11 @@ of lsfm_map_covariance on the result beside the same call on the tree's own map.
 lsfm_gn_polish_robust_features beside the plain and the map-robust polish (same kind and c), two calls of each and the warm one read
 (profiles/gn_robust_features_<config>.json): per assembly the HIP-event ms of the feature chi2 pass (k_gn_chi2<true> + the objective
 kernel) with its GB/s on the bytes it must read (every U, W and V block and feature estimate of the local maps once), beside
-k_gn_chi2<false> (+ weights kernel) on the same arrays, the HIP-event ms of the U correction kernel, and the wall ms per assembly and step."""
+k_gn_chi2<false> (+ weights kernel) on the same arrays, the HIP-event ms of the U correction kernel, and the wall ms per assembly and step.
+--linearise --robust-features huber|cauchy --c <c>: after `steps` of lsfm_gn_polish_robust_features, at its state, in one session and as
+medians of 3 calls after a warm-up each: plain lsfm_gn_linearise beside lsfm_gn_linearise_features with the polish's weights -- HIP-event
+ms per part (the chi2 pass + slot fill, the rest of the assembly, the two coalescing launches), NUJ -> nU' and NWJ -> nW' of each, and the
+library's wall split of each call (written to profiles/gn_linearise_features_<config>.json as well as printed)."""
 import json
 import os
 import re
@@ -31,13 +35,25 @@ if len(sys.argv) > 1 and sys.argv[1] != "--child":
     d = json.loads(line[0])
     d["library_timing"] = tim
     lin = [l for l in p.stderr.splitlines() if l.startswith("lsfm_gn_linearise:")]
-    if lin:
+    if lin and "linearise" in d:
         # the library's own split of the calls after the warm-up: medians
         pat = r"structure \+ upload ([0-9.]+) ms, assembly \+ coalescing ([0-9.]+) ms, download ([0-9.]+) ms, call ([0-9.]+) ms"
         rows = sorted(tuple(float(v) for v in re.search(pat, l).groups()) for l in lin[1:])
         up, dev, down, call = (sorted(r[i] for r in rows)[len(rows) // 2] for i in range(4))
         d["linearise"]["library_wall_ms"] = {"structure_upload": up, "device": dev, "download": down, "call": call,
                                              "upload_download_share": (up + down) / call}
+    if "linearise_features" in d:
+        pat = r"structure \+ upload ([0-9.]+) ms, assembly \+ coalescing ([0-9.]+) ms, download ([0-9.]+) ms, call ([0-9.]+) ms"
+        for key, head in (("plain", "lsfm_gn_linearise:"), ("feature_weighted", "lsfm_gn_linearise_features:")):
+            rows = [tuple(float(v) for v in re.search(pat, l).groups()) for l in p.stderr.splitlines() if l.startswith(head)][1:]
+            up, dev, down, call = (sorted(r[i] for r in rows)[len(rows) // 2] for i in range(4))
+            d["linearise_features"][key]["library_wall_ms"] = {"structure_upload": up, "device": dev, "download": down, "call": call}
+        out = os.path.join(ROOT, "profiles", "gn_linearise_features_%s.json" % d["config"])
+        with open(out, "w") as f:
+            json.dump(d, f, indent=1)
+            f.write("\n")
+        print(json.dumps(d, indent=1))
+        sys.exit(0)
     if "robust_features" in d and len(tim) >= 6:
         def parse(t):
             g = lambda pat: float(re.search(pat, t).group(1))
@@ -98,6 +114,30 @@ for rep in range(2):
     t0 = time.perf_counter()
     st, obj, gn, hv, rc2 = ctx.gn_polish(d, mono, G, steps)
     calls.append(1e3 * (time.perf_counter() - t0))
+if a.robust_features and a.linearise:
+    med = lambda v: float(np.median(v))
+    rst, robj, _, rhv, _, fw, rrc = ctx.gn_polish_robust_features(d, mono, G, steps, a.robust_features, a.c)
+    Gp = dict(G, stVal=rst)
+    res = {}
+    for name, kw in (("plain", {}), ("feature_weighted", {"feature_weight": fw})):
+        rows, walls = [], []
+        for rep in range(4):
+            t0 = time.perf_counter()
+            H, F, _, tm, cnt = ctx.gn_linearise(d, mono, Gp, timed=True, **kw)
+            walls.append(1e3 * (time.perf_counter() - t0))
+            rows.append(tm)
+        ev = {k: med([r[k] for r in rows[1:]]) for k in rows[0]}
+        res[name] = {"events_ms": ev, "device_ms": sum(ev.values()), "blocks": cnt, "python_call_wall_ms": med(walls[1:]), "objective": F}
+    w = np.concatenate(fw)
+    sys.stdout.flush()
+    print(json.dumps({"config": cfg, "type": typ, "maps": len(maps), "poses": int(G["m"]), "features": int(G["n"]), "steps": steps,
+                      "robust_features": a.robust_features, "c": a.c, "polish_rc": rrc, "weights_below_1": float(np.mean(w < 1.0)), "weight_min": float(np.min(w)),
+                      "linearise_features": dict(res, extra_device_ms=res["feature_weighted"]["device_ms"] - res["plain"]["device_ms"]),
+                      "note": "at the state lsfm_gn_polish_robust_features ended at; plain = lsfm_gn_linearise, feature_weighted = "
+                              "lsfm_gn_linearise_features with the polish's weights, one session, medians of 3 calls after one warm-up of each; events_ms: "
+                              "HIP events (chi2_fill_ms: k_gn_chi2<true, true> + k_gn_given_objective + k_gn_feature_ufill); blocks: NWJ -> nW, NUJ -> nU; "
+                              "python_call_wall_ms includes building the lsfm_map views and copying the result; library_wall_ms: the library's own clocks"}))
+    sys.exit(0)
 if a.robust_features:
     runs = {}
     for name, call in (("map_robust_run", lambda: ctx.gn_polish_robust(d, mono, G, steps, a.robust_features, a.c)),
